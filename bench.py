@@ -5,8 +5,8 @@ One "step" = one view: ``render()`` forward of the S-nyc-1M synthetic scene (1,0
 1920x1080) through the drop-in ``diff_gaussian_rasterization`` package (libgsraster.so,
 hand-written HIP) + one backward from a fixed dL/dC[3,H,W] down to .grad on all seven raw attribute tensors
 (59 attack-relevant floats per Gaussian), object channels off.  Inputs are resident in HBM before a timed region
-starts.  A timed region is EXACTLY --steps steps between barrier + synchronise on both sides; --regions of them are
-run back to back and the MEDIAN region is reported (every region's time is listed).
+starts.  A timed region is EXACTLY --steps steps between barrier + synchronise on both sides; --regions of them (default
+1, with --full 5) are run back to back and the MEDIAN region is reported (every region's time is listed).
 
 N = 1 (the BASELINE metric): `value` = independent views -- each with its own forward, its own dL/dC and its own 59
 attribute-gradient floats per Gaussian -- rendered several at a time through ONE launch chain on one HIP stream
@@ -23,13 +23,18 @@ passes into the rank's gradient bucket, ONE sum all-reduce of the bucket (59 flo
 projected-gradient step on all six attribute tensors -- strictly in that order, as a PGD loop needs it; `allreduce_ms`
 is the collective alone.  --independent-views restores round 2's behaviour (views pipelined across steps, no update).
 
-    python bench.py                       # N=1, defaults finish in ~2 minutes incl. the CPU baseline
+    python bench.py --gpus 1 --steps K --warmup W    # the headline alone: set-up, warm-up, K timed steps, one line
+    python bench.py --full                # N=1, everything below; defaults finish in about half a minute
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel stage against the 8 TB/s HBM peak with the
-algorithmic bytes of SURVEY.md section 8(d) and its live HIP-event duration over the timed region;
-`cpu_baseline` times oracle-R (pure PyTorch, CPU) on a bounded sample of the same scene.
+Rank 0 prints ONE JSON line.  A plain run measures the headline `value` / `ms_per_step` and nothing else; --full adds
+what takes runs of its own: the other regimes (`pipelined_streams`, `sequential`, `batched`, `dense`, N > 1
+`independent_views`), the per-stage pass (`stages`), `roofline` -- the dominant kernel stage priced against the 8 TB/s
+HBM peak with the algorithmic bytes of SURVEY.md section 8(d) and its live HIP-event duration over the timed region --,
+the untimed `extras` and `pgd` blocks, and `cpu_baseline` -- oracle-R (pure PyTorch, CPU) timed on a bounded sample of
+the same scene -- with the parity check against it.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32; fixed, seeded samples of pixels and Gaussians).
 """
 from __future__ import annotations
 
@@ -51,7 +56,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
-from benchparts.common import HBM_PEAK_GBS, log, sources_digest, stage_bytes  # noqa: E402
+from benchparts.common import HBM_PEAK_GBS, dump_outputs, log, sources_digest, stage_bytes  # noqa: E402
 from benchparts.cpu import cpu_baseline, parity_and_cfg1  # noqa: E402
 from benchparts.extras import extras_and_pgd, masked_streams  # noqa: E402
 from benchparts.fanout import fan_out  # noqa: E402
@@ -64,7 +69,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the other regimes, the per-stage pass and roofline, the "
+                         "dense point, the extras and PGD blocks, the CPU baseline and the parity check (--no-extras and "
+                         "--no-cpu-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (images, radii, screen-space and "
+                         "attribute gradients; seeded samples) as DIR/<name>.npy")
     ap.add_argument("--scene", default="nyc-1M")
     ap.add_argument("--P", type=int, default=None, help="override the Gaussian count (parity-size runs)")
     ap.add_argument("--width", type=int, default=None)
@@ -115,6 +128,8 @@ def main():
                     help="experiment: one CU mask per view stream, ';'-separated, each a ','-separated list of 32-bit hex "
                          "words (hipExtStreamCreateWithCUMask); replaces --streams")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(fan_out(args.gpus))              # before anything touches a GPU in this (parent) process
@@ -194,18 +209,27 @@ def main():
         args.streams = len(streams)
 
     def run_steps(n, use_streams=True):
+        # -> the last step's output (no step's output is kept while a later one runs)
         sts = streams if use_streams else None
+        last = None
         if sts is None:
-            for _ in range(n):
-                step()
-            return
+            for i in range(n):
+                if i < n - 1:
+                    step()
+                else:
+                    last = step()
+            return last
         for s_ in sts:
             s_.wait_stream(torch.cuda.current_stream(dev))
         for i in range(n):
             with torch.cuda.stream(sts[i % len(sts)]):
-                step()
+                if i < n - 1:
+                    step()
+                else:
+                    last = step()
         for s_ in sts:
             torch.cuda.current_stream(dev).wait_stream(s_)
+        return last
 
     # ---- N = 1 headline: independent views, several at a time through ONE launch chain --------------------------------
     # Every view keeps its own gradient: view v's 59 floats per Gaussian land in bucket v of a GradBucketSet, bit for bit
@@ -328,9 +352,9 @@ def main():
     out = None
     ar_events.clear()
     info = {}
-    # pair / visible counts of every camera of the ring (the roofline figures use their means)
+    # pair / visible counts of every camera of the ring (the roofline figures use their means; --full only)
     Ns, Vs, Es = [], [], []
-    if Bh and args.headline_only:
+    if args.full and Bh and args.headline_only:
         # (profiling runs: counted from forward-only GROUPS, so that every K6 launch of the process is a group launch)
         with torch.no_grad():
             pass
@@ -341,7 +365,7 @@ def main():
             Vs.extend([int(D.export_state(o_["render"], "dv")[1].item()) // Bh] * Bh)
             Es.extend([int(D.export_state(o_["render"], "n_contrib").to(torch.int64).sum().item()) // Bh] * Bh)
             del o_
-    for c_ in ([] if (Bh and args.headline_only) else (cams[:n_views] if not args.one_camera else [cam])):
+    for c_ in ([] if (not args.full or (Bh and args.headline_only)) else (cams[:n_views] if not args.one_camera else [cam])):
         o_ = render(c_, model, pipe, bg, scale_mod[0])
         Ns.append(D.last_num_rendered(o_["render"]))
         Vs.append(int(D.export_state(o_["render"], "dv")[1].item()))
@@ -349,23 +373,56 @@ def main():
         # contributor ("Flops (secondary)": E, measured here from the forward's n_contrib)
         Es.append(int(D.export_state(o_["render"], "n_contrib").to(torch.int64).sum().item()))
         del o_
-    info["N_per_camera"], info["V_per_camera"] = Ns, Vs
-    info["N"], info["V"] = int(round(sum(Ns) / len(Ns))), int(round(sum(Vs) / len(Vs)))
-    info["E"] = int(round(sum(Es) / len(Es)))
+    if Ns:
+        info["N_per_camera"], info["V_per_camera"] = Ns, Vs
+        info["N"], info["V"] = int(round(sum(Ns) / len(Ns))), int(round(sum(Vs) / len(Vs)))
+        info["E"] = int(round(sum(Es) / len(Es)))
     step_no[0] = 0
+    last_out = [None]                                      # the output of the last timed step (--dump-outputs)
 
-    def timed_regions(n_regions, use_streams=True, profile_stage=None, runner=None):
-        """n_regions x exactly --steps steps, each between barrier + synchronise; per-region seconds (max over ranks)."""
+    def dump_last_step(out_dir):
+        """What the caller of the timed path received from its last step: the images, radii and screen-space gradients of
+        the step's views and their attribute gradients (N > 1: the rank's reduced gradients and updated parameters)."""
+        torch.cuda.synchronize()
+        o = last_out[0]
+        views, per = {}, {}
+        if o is not None:
+            img = o["render"] if Bh else o["render"].unsqueeze(0)
+            views["render"] = img
+            if args.objects and not Bh:
+                views["render_object"] = o["render_object"].unsqueeze(0)
+            per["radii"] = o["radii"] if Bh else o["radii"].unsqueeze(0)
+            vs = o["viewspace_points"]
+            if vs is not None and vs.grad is not None:
+                per["viewspace_grad"] = vs.grad if Bh else vs.grad.unsqueeze(0)
+        if Bh:
+            grads = [bset_h.bucket(v).views() for v in range(Bh)]
+            per.update({"grad" + n_: [g_[n_] for g_ in grads] for n_ in grads[0]})
+        else:
+            for n_ in D.GradBucket.NAMES + ("_objects_dc",):
+                p_ = getattr(model, n_)
+                if p_.grad is not None:
+                    per["grad" + n_] = [p_.grad]
+                if pgd_loop:
+                    per["param" + n_] = [p_]
+        return dump_outputs(out_dir, views, per)
+
+    def timed_regions(n_regions, use_streams=True, profile_stage=None, runner=None, keep_last=False):
+        """n_regions x exactly --steps steps, each between barrier + synchronise; per-region seconds (max over ranks).
+        keep_last: the last step's output is left in last_out[0]."""
         secs = []
         for _ in range(n_regions):
+            last_out[0] = None                             # no live reference to an earlier region's output
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if runner is not None:
-                runner(args.steps)
+                res = runner(args.steps)
             else:
-                run_steps(args.steps, use_streams)
+                res = run_steps(args.steps, use_streams)
+            last_out[0] = res if keep_last else None
+            del res
             torch.cuda.synchronize()
             if world > 1:
                 dist.barrier()
@@ -379,31 +436,35 @@ def main():
             secs.append(dt)
         return secs
 
-    # Timed regions: only the dominant kernel (K7, the backward composite) is timed inside them, by two HIP events that
-    # hipExtLaunchKernelGGL stamps with the dispatch's own start and end on its launch stream.
+    # Timed regions: with --full the dominant kernel (K7, the backward composite) is timed inside them, by two HIP events
+    # that hipExtLaunchKernelGGL stamps with the dispatch's own start and end on its launch stream; nothing else is.
     DOMINANT = "render_bwd"
     pipelined = None
-    if Bh:
-        D.profile(True, stages=[DOMINANT])
-        secs = timed_regions(args.regions, runner=run_headline)
-        dom_calls = D.profile_read()[DOMINANT]
-        D.profile(False)
-        if not args.headline_only and streams is not None:
-            # rounds 2-5's headline regime beside it: one render() + backward per view, dealt over the streams
-            run_steps(2 * max(args.streams, 1))
-            torch.cuda.synchronize()
-            secs_p = timed_regions(args.regions)
-            mp_ = sorted(secs_p)[len(secs_p) // 2]
-            pipelined = {"value": round(args.steps / mp_, 2), "unit": "views/s", "ms_per_step": round(mp_ / args.steps * 1e3, 4),
-                         "regions_ms": [round(x * 1e3, 2) for x in secs_p], "streams": args.streams,
-                         "what": "the same independent views as one render() + backward per view dealt round-robin over "
-                                 "--streams HIP streams: the headline regime of rounds 2-5"}
-    else:
+    dom_calls = (0.0, 0)
+    if not Bh:
         run_steps(2 * max(args.streams, 1))                # untimed: lets every stream build its own workspace blocks
         torch.cuda.synchronize()
+    if args.full:
         D.profile(True, stages=[DOMINANT])
-        secs = timed_regions(args.regions)
+    secs = timed_regions(args.regions, runner=run_headline if Bh else None, keep_last=True)
+    if args.full:
         dom_calls = D.profile_read()[DOMINANT]
+        if Bh:
+            D.profile(False)
+    if args.dump_outputs and rank == 0:
+        dumped = dump_last_step(args.dump_outputs)
+        log(f"outputs of the last timed step in {args.dump_outputs}: {', '.join(dumped)}")
+    last_out[0] = None
+    if args.full and Bh and not args.headline_only and streams is not None:
+        # rounds 2-5's headline regime beside it: one render() + backward per view, dealt over the streams
+        run_steps(2 * max(args.streams, 1))
+        torch.cuda.synchronize()
+        secs_p = timed_regions(args.regions)
+        mp_ = sorted(secs_p)[len(secs_p) // 2]
+        pipelined = {"value": round(args.steps / mp_, 2), "unit": "views/s", "ms_per_step": round(mp_ / args.steps * 1e3, 4),
+                     "regions_ms": [round(x * 1e3, 2) for x in secs_p], "streams": args.streams,
+                     "what": "the same independent views as one render() + backward per view dealt round-robin over "
+                             "--streams HIP streams: the headline regime of rounds 2-5"}
     dom_ms_timed = dom_calls[0] / max(dom_calls[1], 1)
     # views one launch of the dominant kernel covers in the timed regions
     views_per_launch = Bh if Bh else (B if (pgd_loop and batch_views) else 1)
@@ -418,7 +479,7 @@ def main():
     # (forward + backward, no collective, no update) over its streams, exactly what the N = 1 line's `value` times on one
     # GPU; one region between barrier + synchronise, max over ranks
     indep = None
-    if pgd_loop:
+    if args.full and pgd_loop:
         def indep_steps(n):
             for s_ in (streams or []):
                 s_.wait_stream(torch.cuda.current_stream(dev))
@@ -439,7 +500,7 @@ def main():
                          "streams: N x what the N = 1 line's `value` measures; one region, max over ranks"}
     # the same views strictly one after another on one stream
     seq = None
-    if world == 1 and streams is not None and not args.headline_only:
+    if args.full and world == 1 and streams is not None and not args.headline_only:
         D.profile(False)
         secs1 = timed_regions(args.regions, use_streams=False)
         m1 = sorted(secs1)[len(secs1) // 2]
@@ -453,7 +514,8 @@ def main():
     # virtual scene -- one scan, one depth sort, one emission, one tile sort, one schedule, one forward and one backward
     # composite for all of them, every SH row read once, the 59 gradient floats per Gaussian written once.  ONE stream.
     batched = None
-    if world == 1 and args.batch >= 2 and not args.classic and not args.objects and not args.color_only and not args.headline_only:
+    if (args.full and world == 1 and args.batch >= 2 and not args.classic and not args.objects and not args.color_only
+            and not args.headline_only):
         Bb = min(args.batch, len(cams), D.MAX_BATCH)
         bcams = cams[:Bb]
         bucket_b = D.GradBucket(P, dev)
@@ -498,22 +560,24 @@ def main():
                            "every image bit for bit the single-view render (tests/test_gpu_batch.py)"}
         model.zero_grad()
     # Untimed extra pass with every stage bracketed: the per-stage breakdown reported under "stages".
-    D.profile(True)
-    nb = max(3, min(args.steps, 10))
-    if pgd_loop:
-        for _ in range(nb):
-            pgd_step()
-        nb_views = nb * B
-    elif Bh:
-        run_headline(3 * Bh)                               # the headline regime's stages (per view: / views)
-        nb_views = 3 * Bh
-    else:
-        for _ in range(nb):
-            step()
-        nb_views = nb
-    torch.cuda.synchronize()
-    stages = {k: (ms / max(nb_views, 1), calls) for k, (ms, calls) in D.profile_read().items()}
-    D.profile(False)
+    stages = None
+    if args.full:
+        D.profile(True)
+        nb = max(3, min(args.steps, 10))
+        if pgd_loop:
+            for _ in range(nb):
+                pgd_step()
+            nb_views = nb * B
+        elif Bh:
+            run_headline(3 * Bh)                           # the headline regime's stages (per view: / views)
+            nb_views = 3 * Bh
+        else:
+            for _ in range(nb):
+                step()
+            nb_views = nb
+        torch.cuda.synchronize()
+        stages = {k: (ms / max(nb_views, 1), calls) for k, (ms, calls) in D.profile_read().items()}
+        D.profile(False)
 
     ranks_seen = 1
     if world > 1:
@@ -524,62 +588,64 @@ def main():
         ranks_seen = int(one.item())
         assert ranks_seen == world, (ranks_seen, world)
     if rank == 0:
-        N, V, HW = info["N"], info["V"], H * W
-        sb = stage_bytes(P, V, N, HW)
-        per = {}
-        for name, (avg_ms, calls) in stages.items():
-            per[name] = {"avg_ms": round(avg_ms, 4),
-                         "GBps": round(sb[name] / (avg_ms * 1e-3) / 1e9, 1) if avg_ms > 0 and sb[name] else None}
-        dom = max(("render_fwd", "render_bwd", "preprocess", "preprocess_bwd", "tile_sort", "bin"),
-                  key=lambda n: per[n]["avg_ms"])
-        # (stage times are per VIEW; a launch of the dominant kernel covers views_per_launch views in the headline regime)
-        vpl = views_per_launch
-        dom_ms = round(per[dom]["avg_ms"] * vpl, 4)
-        if dom == DOMINANT:
-            dom_ms = round(dom_ms_timed, 4)      # the duration measured inside the timed regions themselves
-        achieved = sb[dom] * vpl / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        # HBM bytes of the dominant kernel from the committed PMC passes (profiles/collect_r03.sh: FETCH_SIZE and
-        # WRITE_SIZE in separate runs, FETCH doubled as MI355X_MICROARCH.md prescribes for gfx950) -- only when they
-        # were taken on this very workload
-        traffic = None
-        valu = None
-        traffic_note = None
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
-            if pmc.get("sources_sha256") != sources_digest():
-                traffic_note = (f"profiles/{PMC_FILE} was collected from other kernel sources than this build's (digest "
-                                "mismatch): not quoted; run profiles/collect_r06.sh again")
-                raise LookupError(traffic_note)
-            kern = {"render_bwd": "void gsr::k_render_bwd<false, 4, true>", "render_fwd": "void gsr::k_render_fwd<false, 2, 1>",
-                    "preprocess_bwd": "void gsr::k_pre_bwd<true, true, false>",
-                    "preprocess": "void gsr::k_pre_color<true>"}.get(dom)
-            if int(pmc.get("views_per_launch", 1)) != vpl:
-                traffic_note = (f"profiles/{PMC_FILE} counts launches of {pmc.get('views_per_launch', 1)} view(s), this run's "
-                                f"cover {vpl}: not quoted")
-                raise LookupError(traffic_note)
-            if (args.scene, args.P, args.width, args.height, args.objects) == ("nyc-1M", None, None, None, False):
-                traffic = round(pmc["per_kernel"][kern]["hbm_bytes_fetch_x2"])
-                n_valu = pmc["per_kernel"][kern].get("SQ_INSTS_VALU")
-                if n_valu:
-                    peak = 1024 * 2.4e9 / 2 / 1e9
-                    ach = n_valu / (per[dom]["avg_ms"] * vpl * 1e-3) / 1e9
-                    valu = {"bound": "fp32 VALU issue", "wave_instr_per_launch": round(n_valu),
-                            "achieved": round(ach, 1), "peak": round(peak, 1), "unit": "G wave-instr/s",
-                            "frac": round(ach / peak, 4), "launch_ms": round(per[dom]["avg_ms"] * vpl, 4)}
-                    if dom == "render_bwd":
-                        # what a kernel made of NOTHING but K7's strip-body instruction mix sustains on this chip at six
-                        # waves per SIMD (tests/ubench/valu_rate.hip `kmix`: 2 transcendentals, 1 min, 4 compares, 2 selects,
-                        # 23 mul / add / fma per strip evaluation; profiles/r06_valu_rate.txt)
-                        valu["mix_ceiling"] = 765.9
-                        valu["frac_of_mix_ceiling"] = round(ach / 765.9, 4)
-                        valu["mix_source"] = "profiles/r06_valu_rate.txt (K7 strip-body mix, 6 waves/SIMD)"
-        except Exception as e:                             # noqa: BLE001
+        HW = H * W
+        if args.full:
+            N, V = info["N"], info["V"]
+            sb = stage_bytes(P, V, N, HW)
+            per = {}
+            for name, (avg_ms, calls) in stages.items():
+                per[name] = {"avg_ms": round(avg_ms, 4),
+                             "GBps": round(sb[name] / (avg_ms * 1e-3) / 1e9, 1) if avg_ms > 0 and sb[name] else None}
+            dom = max(("render_fwd", "render_bwd", "preprocess", "preprocess_bwd", "tile_sort", "bin"),
+                      key=lambda n: per[n]["avg_ms"])
+            # (stage times are per VIEW; a launch of the dominant kernel covers views_per_launch views in the headline regime)
+            vpl = views_per_launch
+            dom_ms = round(per[dom]["avg_ms"] * vpl, 4)
+            if dom == DOMINANT:
+                dom_ms = round(dom_ms_timed, 4)      # the duration measured inside the timed regions themselves
+            achieved = sb[dom] * vpl / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            # HBM bytes of the dominant kernel from the committed PMC passes (profiles/collect_r03.sh: FETCH_SIZE and
+            # WRITE_SIZE in separate runs, FETCH doubled: gfx950 counts a 128-byte request as 64 bytes) -- only when they
+            # were taken on this very workload
             traffic = None
             valu = None
-            traffic_note = traffic_note or f"profiles/{PMC_FILE}: {type(e).__name__}"
-        B_total = 304 * P + 548 * V + 116 * N + 40 * HW
+            traffic_note = None
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
+                if pmc.get("sources_sha256") != sources_digest():
+                    traffic_note = (f"profiles/{PMC_FILE} was collected from other kernel sources than this build's (digest "
+                                    "mismatch): not quoted; run profiles/collect_r06.sh again")
+                    raise LookupError(traffic_note)
+                kern = {"render_bwd": "void gsr::k_render_bwd<false, 4, true>", "render_fwd": "void gsr::k_render_fwd<false, 2, 1>",
+                        "preprocess_bwd": "void gsr::k_pre_bwd<true, true, false>",
+                        "preprocess": "void gsr::k_pre_color<true>"}.get(dom)
+                if int(pmc.get("views_per_launch", 1)) != vpl:
+                    traffic_note = (f"profiles/{PMC_FILE} counts launches of {pmc.get('views_per_launch', 1)} view(s), this run's "
+                                    f"cover {vpl}: not quoted")
+                    raise LookupError(traffic_note)
+                if (args.scene, args.P, args.width, args.height, args.objects) == ("nyc-1M", None, None, None, False):
+                    traffic = round(pmc["per_kernel"][kern]["hbm_bytes_fetch_x2"])
+                    n_valu = pmc["per_kernel"][kern].get("SQ_INSTS_VALU")
+                    if n_valu:
+                        peak = 1024 * 2.4e9 / 2 / 1e9
+                        ach = n_valu / (per[dom]["avg_ms"] * vpl * 1e-3) / 1e9
+                        valu = {"bound": "fp32 VALU issue", "wave_instr_per_launch": round(n_valu),
+                                "achieved": round(ach, 1), "peak": round(peak, 1), "unit": "G wave-instr/s",
+                                "frac": round(ach / peak, 4), "launch_ms": round(per[dom]["avg_ms"] * vpl, 4)}
+                        if dom == "render_bwd":
+                            # what a kernel made of NOTHING but K7's strip-body instruction mix sustains on this chip at six
+                            # waves per SIMD (tests/ubench/valu_rate.hip `kmix`: 2 transcendentals, 1 min, 4 compares, 2 selects,
+                            # 23 mul / add / fma per strip evaluation; profiles/r06_valu_rate.txt)
+                            valu["mix_ceiling"] = 765.9
+                            valu["frac_of_mix_ceiling"] = round(ach / 765.9, 4)
+                            valu["mix_source"] = "profiles/r06_valu_rate.txt (K7 strip-body mix, 6 waves/SIMD)"
+            except Exception as e:                             # noqa: BLE001
+                traffic = None
+                valu = None
+                traffic_note = traffic_note or f"profiles/{PMC_FILE}: {type(e).__name__}"
+            B_total = 304 * P + 548 * V + 116 * N + 40 * HW
+            t_view = med / (args.steps * B)
         views_per_step = world * B
-        t_view = med / (args.steps * B)
         workload = (f"{spec.name}: {P} Gaussians (SH degree 3), {W}x{H}, "
                     + (f"one PGD iteration per step: {B} view(s) per GPU fwd+bwd into a gradient bucket, one all-reduce of "
                        "59 floats/Gaussian, fused L2 step on all six attribute tensors" if pgd_loop else
@@ -606,48 +672,51 @@ def main():
             "regions_ms": [round(x * 1e3, 2) for x in secs],
             "timing": f"median of {args.regions} regions of exactly {args.steps} steps, each between barrier + synchronise",
             "config": {"workload": workload,
-                       "P": P, "V_visible": V, "N_pairs": N, "width": W, "height": H,
+                       "P": P, "width": W, "height": H,
                        "loop": "pgd" if pgd_loop else "independent views",
                        "views_per_rank": B,
                        "views_per_launch_chain": views_per_launch,
                        "cameras": "one fixed camera" if args.one_camera else
-                                  f"the {n_views} ring cameras in turn (V and N are means over them)",
-                       "N_pairs_per_camera": info["N_per_camera"], "V_visible_per_camera": info["V_per_camera"],
+                                  f"the {n_views} ring cameras in turn" + (" (V and N are means over them)" if args.full else ""),
                        "streams": args.streams,
                        "parallelism": f"views sharded {B}/GPU, dp{world}"
                                       + (f", independent views {Bh} per launch chain on one HIP stream" if Bh else
                                          (f", independent views pipelined over {args.streams} HIP streams per GPU"
                                           if args.streams > 1 and not pgd_loop else ""))
                                       + (", RCCL all-reduce of 59 floats/Gaussian per step" if world > 1 else "")},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                         "traffic_source": traffic_note if traffic is None else
-                         f"profiles/{PMC_FILE}: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on "
-                         "this workload (not measured inside this run; FETCH_SIZE doubled per MI355X_MICROARCH.md)",
-                         "algorithmic_bytes_per_launch": sb[dom] * vpl, "views_per_launch": vpl, "avg_launch_ms": dom_ms,
-                         # the same kernel in the untimed per-stage pass (stage events around it)
-                         "avg_launch_ms_alone": round(per[dom]["avg_ms"] * vpl, 4),
-                         "note": "K6/K7 are bound by VALU instruction issue (256*N alpha evaluations), not by HBM; "
-                                 "HBM is the reporting roofline BASELINE.md section 3 prescribes"},
-            "pipeline": {"bytes_per_view": B_total, "achieved": round(B_total / t_view / 1e9, 1), "unit": "GB/s",
-                         "frac": round(B_total / t_view / 1e9 / HBM_PEAK_GBS, 5)},
-            "stages": per,
         }
-        if valu is not None:
-            result["roofline"]["valu"] = valu
-        # SURVEY.md section 8d's secondary figure: the (pixel, entry) alpha evaluations E of the reference's walk (sum over
-        # pixels of the last contributor's list position, mean over the cameras) against the compositors' own durations,
-        # priced at the survey's 14 FMA + exp forward / 45 FMA + exp backward per evaluation (29 / 91 flop) -- what the
-        # kernels deliver in the reference's own unit of work, whatever strips and lanes they evaluate to get there
-        k6, k7 = per["render_fwd"]["avg_ms"], per["render_bwd"]["avg_ms"]
-        if k6 > 0 and k7 > 0 and info.get("E"):
-            E = info["E"]
-            result["roofline"]["alpha_evaluations"] = {
-                "per_view": E, "per_pixel": round(E / HW, 1),
-                "fwd_Geval_per_s": round(E / (k6 * 1e-3) / 1e9, 1), "bwd_Geval_per_s": round(E / (k7 * 1e-3) / 1e9, 1),
-                "fwd_TFLOPs_equiv": round(29 * E / (k6 * 1e-3) / 1e12, 1), "bwd_TFLOPs_equiv": round(91 * E / (k7 * 1e-3) / 1e12, 1),
-                "fp32_vector_peak_TFLOPs": 157.3,
-                "note": "render_fwd includes the tile-schedule kernel; one-stream stage durations of the untimed pass"}
+        if args.full:
+            result["config"].update({"V_visible": V, "N_pairs": N, "N_pairs_per_camera": info["N_per_camera"],
+                                     "V_visible_per_camera": info["V_per_camera"]})
+            result["roofline"] = {
+                "bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                "traffic_source": traffic_note if traffic is None else
+                f"profiles/{PMC_FILE}: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on this "
+                "workload (not measured inside this run; FETCH_SIZE doubled: gfx950 counts a 128-byte request as 64 bytes)",
+                "algorithmic_bytes_per_launch": sb[dom] * vpl, "views_per_launch": vpl, "avg_launch_ms": dom_ms,
+                # the same kernel in the untimed per-stage pass (stage events around it)
+                "avg_launch_ms_alone": round(per[dom]["avg_ms"] * vpl, 4),
+                "note": "K6/K7 are bound by VALU instruction issue (256*N alpha evaluations), not by HBM; "
+                        "HBM is the reporting roofline BASELINE.md section 3 prescribes"}
+            result["pipeline"] = {"bytes_per_view": B_total, "achieved": round(B_total / t_view / 1e9, 1), "unit": "GB/s",
+                                  "frac": round(B_total / t_view / 1e9 / HBM_PEAK_GBS, 5)}
+            result["stages"] = per
+            if valu is not None:
+                result["roofline"]["valu"] = valu
+            # SURVEY.md section 8d's secondary figure: the (pixel, entry) alpha evaluations E of the reference's walk (sum over
+            # pixels of the last contributor's list position, mean over the cameras) against the compositors' own durations,
+            # priced at the survey's 14 FMA + exp forward / 45 FMA + exp backward per evaluation (29 / 91 flop) -- what the
+            # kernels deliver in the reference's own unit of work, whatever strips and lanes they evaluate to get there
+            k6, k7 = per["render_fwd"]["avg_ms"], per["render_bwd"]["avg_ms"]
+            if k6 > 0 and k7 > 0 and info.get("E"):
+                E = info["E"]
+                result["roofline"]["alpha_evaluations"] = {
+                    "per_view": E, "per_pixel": round(E / HW, 1),
+                    "fwd_Geval_per_s": round(E / (k6 * 1e-3) / 1e9, 1), "bwd_Geval_per_s": round(E / (k7 * 1e-3) / 1e9, 1),
+                    "fwd_TFLOPs_equiv": round(29 * E / (k6 * 1e-3) / 1e12, 1), "bwd_TFLOPs_equiv": round(91 * E / (k7 * 1e-3) / 1e12, 1),
+                    "fp32_vector_peak_TFLOPs": 157.3,
+                    "note": "render_fwd includes the tile-schedule kernel; one-stream stage durations of the untimed pass"}
         if pipelined is not None:
             result["pipelined_streams"] = pipelined
         if seq is not None:
@@ -664,14 +733,15 @@ def main():
             result["allreduce_ms"] = None if ar_ms is None else round(ar_ms, 4)
             result["bytes_reduced"] = bytes_reduced[0] or 59 * 4 * P
             result["views_per_rank"] = B
-            result["independent_views"] = indep
+            if args.full:
+                result["independent_views"] = indep
             result["allreduce_chunks"] = args.ar_chunks if (pgd_loop and min(args.streams, B) == 1) else 1
             result["allreduce_ms_is"] = ("time the compute stream waits for the collective after the step's last "
                                          "rasteriser kernel (with --ar-chunks > 1 part of it ran behind K9)")
             result["scaling_note"] = ("N > 1 lines time whole PGD iterations (serialised render -> backward -> all-reduce -> "
                                       "step); compare them with `pgd.cfg4_one_gpu` of the N = 1 line, not with its `value` "
                                       "(independent views, no update)")
-        if world == 1 and not args.no_extras and args.dense_pairs > 0:
+        if args.full and world == 1 and not args.no_extras and args.dense_pairs > 0:
             # Second data point: the same scene with the splats scaled up until a view emits ~10 M pairs (BASELINE.md's
             # nominal N; the SURVEY section 8d distributions give 2.5 M).  scale_modifier is render()'s own argument.
             log("dense data point: searching scale_modifier ...")
@@ -703,9 +773,9 @@ def main():
                                            "emits ~10 M (tile, Gaussian) pairs (BASELINE.md section 3 nominal)"}
             scale_mod[0] = args.scale_modifier
             step_no[0] = 0
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             result["extras"], result["pgd"] = extras_and_pgd(args, D, dev, model, cams, pipe, bg, gc, streams)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sp, sw, sh = (int(x) for x in args.cpu_sample.split(","))
             log(f"cpu baseline (oracle-R) on a {sp}-Gaussian {sw}x{sh} sample ...")
             result["cpu_baseline"] = cpu_baseline(sp, sw, sh)

@@ -12,7 +12,7 @@ if [ "${TESTS:-0}" = "1" ]; then
   echo "tests rc=$?" | tee -a $OUT/tests.log
   grep -E "^FAILED|^ERROR|passed|failed" $OUT/tests.log | tail -15
 fi
-B="python3 bench.py --steps ${STEPS:-200} --warmup 5 --no-cpu-baseline --no-extras --dense-pairs 0 ${BENCH_ARGS:-}"
+B="python3 bench.py --full --steps ${STEPS:-200} --warmup 5 --no-cpu-baseline --no-extras --dense-pairs 0 ${BENCH_ARGS:-}"
 for var in ${VARIANTS:-}; do
   label=$(echo $var | cut -d'|' -f1); envs=$(echo $var | cut -d'|' -f2); s=$(echo $var | cut -d'|' -f3)
   ( for kv in $(echo $envs | tr ',' ' '); do [ -n "$kv" ] && export "$kv"; done

@@ -13,7 +13,7 @@ if [ "${TESTS:-0}" = "1" ]; then
   grep -E "^FAILED|^ERROR|passed|failed" $OUT/tests.log | tail -15
 fi
 [ -n "${PRE_CMD:-}" ] && bash -c "$PRE_CMD" > $OUT/pre.log 2>&1 && cat $OUT/pre.log
-B="python3 bench.py --steps ${STEPS:-200} --warmup 5 --no-cpu-baseline --no-extras --dense-pairs 0 ${BENCH_ARGS:-}"
+B="python3 bench.py --full --steps ${STEPS:-200} --warmup 5 --no-cpu-baseline --no-extras --dense-pairs 0 ${BENCH_ARGS:-}"
 for var in ${VARIANTS:-}; do
   label=$(echo $var | cut -d'|' -f1); envs=$(echo $var | cut -d'|' -f2); s=$(echo $var | cut -d'|' -f3); extra=$(echo $var | cut -d'|' -f4 | tr ':' ' ')
   ( for kv in $(echo $envs | tr ',' ' '); do [ -n "$kv" ] && export "$kv"; done

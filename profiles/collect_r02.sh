@@ -8,10 +8,10 @@ export TMPDIR=/tmp
 R=$PWD
 OUT=$R/gpurun_out/r02
 mkdir -p $OUT
-BENCH="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+BENCH="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 # kernel statistics over a run whose launches are almost all inside the timed region (300 steps), so that the average
 # duration of K7 is comparable with the bench line's live figure (r02_bench_under_rocprof.json is this run's line)
-STATS="python3 bench.py --steps 300 --warmup 10 --no-cpu-baseline --no-extras"
+STATS="python3 bench.py --full --steps 300 --warmup 10 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $STATS > $OUT/bench_stats.json 2> $OUT/bench_stats.err
 # the same with ONE stream: kernel durations without other views' kernels beside them
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -o s -- $STATS --streams 1 > $OUT/bench_stats1.json 2> $OUT/bench_stats1.err
@@ -42,7 +42,7 @@ for k in sorted(set(fetch) | set(write)):
               "hbm_bytes_raw": (f_kb + w_kb) * 1024, "hbm_bytes_fetch_x2": (2 * f_kb + w_kb) * 1024,
               # wave-level instruction counts per launch; SQ_ACTIVE_INST_VALU and SQ_WAVE_CYCLES count quad-cycles
               **{c: sq[c].get(k, 0.0) for c in sq}}
-json.dump({"command": "python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras", "per_kernel": res}, open(f"{out}/pmc_traffic.json", "w"), indent=1)
+json.dump({"command": "python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras", "per_kernel": res}, open(f"{out}/pmc_traffic.json", "w"), indent=1)
 print(json.dumps({k: v["hbm_bytes_fetch_x2"] / 1e6 for k, v in res.items()}, indent=1))
 PY
 cp $OUT/stats/s_kernel_stats.csv $R/gpurun_out/r02_kernel_stats.csv

@@ -9,8 +9,8 @@ export TMPDIR=/tmp
 R=$PWD
 OUT=$R/gpurun_out/r03
 mkdir -p $OUT
-PMCB="python3 $R/bench.py --steps 10 --warmup 2 --regions 1 --no-cpu-baseline --no-extras"
-STATS="python3 $R/bench.py --steps 100 --warmup 10 --regions 3 --no-cpu-baseline --no-extras"
+PMCB="python3 $R/bench.py --full --steps 10 --warmup 2 --regions 1 --no-cpu-baseline --no-extras"
+STATS="python3 $R/bench.py --full --steps 100 --warmup 10 --regions 3 --no-cpu-baseline --no-extras"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $STATS > $OUT/bench_stats.json 2> $OUT/bench_stats.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -o s -- $STATS --streams 1 > $OUT/bench_stats1.json 2> $OUT/bench_stats1.err || exit 1
@@ -41,7 +41,7 @@ for k in sorted(set(fetch) | set(write)):
               # gathers of 48-byte records are NOT calibrated, so both figures are kept
               "hbm_bytes_raw": (f_kb + w_kb) * 1024, "hbm_bytes_fetch_x2": (2 * f_kb + w_kb) * 1024,
               **{c: sq[c].get(k, 0.0) for c in sq}}
-json.dump({"command": "python3 bench.py --steps 10 --warmup 2 --regions 1 --no-cpu-baseline --no-extras", "per_kernel": res},
+json.dump({"command": "python3 bench.py --full --steps 10 --warmup 2 --regions 1 --no-cpu-baseline --no-extras", "per_kernel": res},
           open(f"{out}/pmc_traffic.json", "w"), indent=1)
 print(json.dumps({k: round(v["hbm_bytes_fetch_x2"] / 1e6, 1) for k, v in res.items()}, indent=1))
 PY
@@ -51,15 +51,15 @@ cp $OUT/pmc_traffic.json $R/gpurun_out/r03_pmc_traffic.json
 cp $OUT/bench_stats.json $R/gpurun_out/r03_bench_under_rocprof.json
 cp $OUT/bench_stats1.json $R/gpurun_out/r03_bench_1stream_under_rocprof.json
 # bench lines without the profiler
-python3 bench.py --steps 100 --warmup 10 > $R/gpurun_out/r03_bench.json 2> $OUT/bench.err || exit 1
-python3 bench.py --steps 100 --warmup 10 --streams 1 --no-cpu-baseline --no-extras > $R/gpurun_out/r03_bench_1stream.json 2> $OUT/bench1.err || exit 1
-python3 bench.py --steps 100 --warmup 10 --scene hydrant-full --no-cpu-baseline --no-extras > $R/gpurun_out/r03_bench_hydrantfull.json 2> $OUT/bench_c2.err || exit 1
-python3 bench.py --steps 50 --warmup 5 --scene airport-4K --no-cpu-baseline --no-extras > $R/gpurun_out/r03_bench_airport4k.json 2> $OUT/bench_c5.err || exit 1
-python3 bench.py --steps 50 --warmup 5 --objects --no-cpu-baseline --no-extras > $R/gpurun_out/r03_bench_objects.json 2> $OUT/bench_obj.err || exit 1
+python3 bench.py --full --steps 100 --warmup 10 > $OUT/../r03_bench.json 2> $OUT/bench.err || exit 1
+python3 bench.py --full --steps 100 --warmup 10 --streams 1 --no-cpu-baseline --no-extras > $OUT/../r03_bench_1stream.json 2> $OUT/bench1.err || exit 1
+python3 bench.py --full --steps 100 --warmup 10 --scene hydrant-full --no-cpu-baseline --no-extras > $OUT/../r03_bench_hydrantfull.json 2> $OUT/bench_c2.err || exit 1
+python3 bench.py --full --steps 50 --warmup 5 --scene airport-4K --no-cpu-baseline --no-extras > $OUT/../r03_bench_airport4k.json 2> $OUT/bench_c5.err || exit 1
+python3 bench.py --full --steps 50 --warmup 5 --objects --no-cpu-baseline --no-extras > $OUT/../r03_bench_objects.json 2> $OUT/bench_obj.err || exit 1
 # kernel statistics of config 2 (S-hydrant-full @800x800) and config 5 (S-airport-4K), one stream
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c2 -o s -- python3 $R/bench.py --steps 100 --warmup 10 --regions 2 --streams 1 --scene hydrant-full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/stats_c2.err || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c5 -o s -- python3 $R/bench.py --steps 50 --warmup 5 --regions 2 --streams 1 --scene airport-4K --no-cpu-baseline --no-extras > /dev/null 2> $OUT/stats_c5.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c2 -o s -- python3 $R/bench.py --full --steps 100 --warmup 10 --regions 2 --streams 1 --scene hydrant-full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/stats_c2.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c5 -o s -- python3 $R/bench.py --full --steps 50 --warmup 5 --regions 2 --streams 1 --scene airport-4K --no-cpu-baseline --no-extras > /dev/null 2> $OUT/stats_c5.err || exit 1
 cd $R
 cp $OUT/stats_c2/s_kernel_stats.csv $R/gpurun_out/r03_kernel_stats_hydrantfull_1stream.csv
 cp $OUT/stats_c5/s_kernel_stats.csv $R/gpurun_out/r03_kernel_stats_airport4k_1stream.csv

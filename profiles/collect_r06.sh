@@ -12,12 +12,12 @@ export TMPDIR=/tmp
 R=$PWD
 OUT=$R/gpurun_out/r06
 mkdir -p $OUT
-PMCB="python3 $R/bench.py --steps 10 --warmup 2 --regions 1 --no-cpu-baseline --no-extras --headline-only"
-STATS="python3 $R/bench.py --steps 100 --warmup 10 --regions 3 --no-cpu-baseline --no-extras --headline-only"
+PMCB="python3 $R/bench.py --full --steps 10 --warmup 2 --regions 1 --no-cpu-baseline --no-extras --headline-only"
+STATS="python3 $R/bench.py --full --steps 100 --warmup 10 --regions 3 --no-cpu-baseline --no-extras --headline-only"
 if [ "${PART:-A}" = "A" ]; then
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $STATS > $OUT/bench_stats.json 2> $OUT/bench_stats.err || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -o s -- python3 $R/bench.py --steps 100 --warmup 10 --regions 3 --no-cpu-baseline --no-extras --headline streams --streams 1 --batch 0 > $OUT/bench_stats1.json 2> $OUT/bench_stats1.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -o s -- python3 $R/bench.py --full --steps 100 --warmup 10 --regions 3 --no-cpu-baseline --no-extras --headline streams --streams 1 --batch 0 > $OUT/bench_stats1.json 2> $OUT/bench_stats1.err || exit 1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o f -- $PMCB > /dev/null 2> $OUT/fetch.err || exit 1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o w -- $PMCB > /dev/null 2> $OUT/write.err || exit 1
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAVES --kernel-trace --output-format csv -d $OUT/sq -o q -- $PMCB > /dev/null 2> $OUT/sq.err || exit 1
@@ -56,7 +56,7 @@ def digest():
         h.update(os.path.basename(f).encode() + b"\0")
         h.update(open(f, "rb").read())
     return h.hexdigest()
-json.dump({"command": "python3 bench.py --steps 10 --warmup 2 --regions 1 --no-cpu-baseline --no-extras --headline-only (every launch of the compositors covers the headline regime's 5 views: --steps 10, 20 and 100 all group views by 5)",
+json.dump({"command": "python3 bench.py --full --steps 10 --warmup 2 --regions 1 --no-cpu-baseline --no-extras --headline-only (every launch of the compositors covers the headline regime's 5 views: --steps 10, 20 and 100 all group views by 5)",
            "views_per_launch": 5,
            "sources_sha256": digest(), "per_kernel": res},
           open(f"{out}/pmc_traffic.json", "w"), indent=1)
@@ -69,7 +69,7 @@ cp $OUT/pmc_traffic.json $R/profiles/r06_pmc_traffic.json     # (on the box: the
 cp $OUT/bench_stats.json $R/gpurun_out/r06_bench_under_rocprof.json
 cp $OUT/bench_stats1.json $R/gpurun_out/r06_bench_1stream_under_rocprof.json
 # bench lines without the profiler
-python3 bench.py --steps 100 --warmup 10 > $R/gpurun_out/r06_bench.json 2> $OUT/bench.err || exit 1
+python3 bench.py --full --steps 100 --warmup 10 > $OUT/../r06_bench.json 2> $OUT/bench.err || exit 1
 # what shares the chip with what: under the profiler's kernel trace, and without a profiler (the library's own stage events)
 python3 profiles/coresidency.py $OUT/stats/s_kernel_trace.csv "round 6, four streams, under rocprofv3 --kernel-trace" > $R/gpurun_out/r06_coresidency.txt
 python3 profiles/coresidency.py $OUT/stats1/s_kernel_trace.csv "round 6, one stream, under rocprofv3 --kernel-trace" >> $R/gpurun_out/r06_coresidency.txt
@@ -77,14 +77,14 @@ python3 tests/diag_coresidency.py 4 64 2>/dev/null | grep -v amdgpu.ids >> $R/gp
 python3 tests/diag_coresidency.py 1 32 2>/dev/null | grep -v amdgpu.ids >> $R/gpurun_out/r06_coresidency.txt
 fi
 if [ "${PART:-A}" = "B" ]; then
-python3 bench.py --steps 100 --warmup 10 --headline streams --streams 1 --batch 0 --no-cpu-baseline --no-extras > $R/gpurun_out/r06_bench_1stream.json 2> $OUT/bench1.err || exit 1
-python3 bench.py --steps 100 --warmup 10 --scene hydrant-full --no-cpu-baseline --no-extras > $R/gpurun_out/r06_bench_hydrantfull.json 2> $OUT/bench_c2.err || exit 1
-python3 bench.py --steps 50 --warmup 5 --scene airport-4K --no-cpu-baseline --no-extras > $R/gpurun_out/r06_bench_airport4k.json 2> $OUT/bench_c5.err || exit 1
-python3 bench.py --steps 50 --warmup 5 --objects --no-cpu-baseline --no-extras > $R/gpurun_out/r06_bench_objects.json 2> $OUT/bench_obj.err || exit 1
+python3 bench.py --full --steps 100 --warmup 10 --headline streams --streams 1 --batch 0 --no-cpu-baseline --no-extras > $OUT/../r06_bench_1stream.json 2> $OUT/bench1.err || exit 1
+python3 bench.py --full --steps 100 --warmup 10 --scene hydrant-full --no-cpu-baseline --no-extras > $OUT/../r06_bench_hydrantfull.json 2> $OUT/bench_c2.err || exit 1
+python3 bench.py --full --steps 50 --warmup 5 --scene airport-4K --no-cpu-baseline --no-extras > $OUT/../r06_bench_airport4k.json 2> $OUT/bench_c5.err || exit 1
+python3 bench.py --full --steps 50 --warmup 5 --objects --no-cpu-baseline --no-extras > $OUT/../r06_bench_objects.json 2> $OUT/bench_obj.err || exit 1
 # kernel statistics of config 2 (S-hydrant-full @800x800) and config 5 (S-airport-4K), one stream
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c2 -o s -- python3 $R/bench.py --steps 100 --warmup 10 --regions 2 --streams 1 --scene hydrant-full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/stats_c2.err || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c5 -o s -- python3 $R/bench.py --steps 50 --warmup 5 --regions 2 --streams 1 --scene airport-4K --no-cpu-baseline --no-extras > /dev/null 2> $OUT/stats_c5.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c2 -o s -- python3 $R/bench.py --full --steps 100 --warmup 10 --regions 2 --streams 1 --scene hydrant-full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/stats_c2.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c5 -o s -- python3 $R/bench.py --full --steps 50 --warmup 5 --regions 2 --streams 1 --scene airport-4K --no-cpu-baseline --no-extras > /dev/null 2> $OUT/stats_c5.err || exit 1
 cd $R
 cp $OUT/stats_c2/s_kernel_stats.csv $R/gpurun_out/r06_kernel_stats_hydrantfull_1stream.csv
 cp $OUT/stats_c5/s_kernel_stats.csv $R/gpurun_out/r06_kernel_stats_airport4k_1stream.csv
@@ -100,6 +100,6 @@ python3 tests/diag_batch.py nyc-1M 4 10 batched 2>/dev/null | grep -v amdgpu.ids
 python3 tests/diag_batch.py nyc-1M 16 6 batched 2>/dev/null | grep -v amdgpu.ids >> $R/gpurun_out/r06_batch_vs_loop.txt
 python3 tests/diag_batch.py airport-4K 4 6 2>/dev/null | grep -v amdgpu.ids >> $R/gpurun_out/r06_batch_vs_loop.txt
 python3 tests/diag_batch.py hydrant-full 8 10 2>/dev/null | grep -v amdgpu.ids >> $R/gpurun_out/r06_batch_vs_loop.txt
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $R/gpurun_out/r06_bench_driver_shape.json 2> $OUT/bench_ds.err || exit 1
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $OUT/../r06_bench_driver_shape.json 2> $OUT/bench_ds.err || exit 1
 fi
 echo collected part ${PART:-A}

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$PWD
 OUT=$R/gpurun_out/${1:-r3p}
 mkdir -p $OUT
-STATS="python3 $R/bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-extras --dense-pairs 0 --streams 1 ${BENCH_ARGS:-}"
+STATS="python3 $R/bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-extras --dense-pairs 0 --streams 1 ${BENCH_ARGS:-}"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -o s -- $STATS > $OUT/bench_stats1.json 2> $OUT/bench_stats1.err || { tail -5 $OUT/bench_stats1.err; exit 1; }
 cd $R

@@ -126,7 +126,7 @@ def test_bench_pgd_loop_rehearsal_prints_the_multi_gpu_fields(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--regions", "2", "--views-per-rank", "2", "--P", "20000", "--width", "320", "--height", "192", "--no-cpu-baseline",
-           "--no-extras"]
+           "--no-extras", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -163,7 +163,7 @@ def test_bench_started_as_a_plain_command_fans_out_by_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(BENCH_REHEARSE_GLOO="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--regions", "2",
-           "--P", "20000", "--width", "320", "--height", "192", "--no-cpu-baseline", "--no-extras"]
+           "--P", "20000", "--width", "320", "--height", "192", "--no-cpu-baseline", "--no-extras", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
