@@ -584,7 +584,7 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
   ra.wave_clock = g_wave_clock_fwd.load();
   ra.bnd = c->bnd; ra.segoff = c->bnd ? c->segoff : nullptr; ra.seg_shift = c->bnd ? c->seg_shift : 0u;
   ra.out_color = out_color; ra.out_objects = out_objects; ra.final_T = c->final_T; ra.n_contrib = c->n_contrib;
-  ra.tpv = c->tpv; ra.vpack = c->vpack;
+  ra.tpv = c->tpv; ra.vpack = c->vpack; ra.Ppad = c->Ppad;
   const dim3 blkT(64);
   // pixels per lane of K6: fewer = more, shorter waves per tile (see k_render_fwd); images with fewer tiles than
   // half the chip's wave slots are split down to one 16x4 strip per wave.  GSR_FLAG_FWD_SPLIT(n) overrides.
@@ -608,7 +608,7 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
     else hipLaunchKernelGGL((k_render_fwd<true, 1>), gridT, blkT, 0, st, ra);
   } else {
     if (out_objects) {
-      hipError_t e = hipMemsetAsync(out_objects, 0, sizeof(float) * NUM_OBJ * HW, st);
+      hipError_t e = hipMemsetAsync(out_objects, 0, sizeof(float) * NUM_OBJ * HW * (size_t)c->B, st);   // (a batch: [B,16,H,W])
       if (e != hipSuccess) {
         (void)comp_leave(st_main, comp_s, comp_used);
         return set_err(GSR_ERR_DEVICE, "objects: %s", hipGetErrorString(e));
@@ -1108,38 +1108,97 @@ int gsr_forward_raw(const GsrSettings* s, int32_t P, const float* xyz, const flo
                       rotation_raw, nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true);
 }
 
+}  // extern "C"
+
 // A batch of views of ONE set of raw parameters through one launch chain (include/gsraster.h): the views must agree in
-// image size, scale modifier, SH degree, flags; cameras, tan(fov / 2) and backgrounds are per view.
-int gsr_forward_raw_batch(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
-                          const float* features_rest, const float* opacity_logit, const float* log_scaling,
-                          const float* rotation_raw, float* out_color, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered,
-                          void* stream) {
+// image size, scale modifier, SH degree, flags; cameras, tan(fov / 2) and backgrounds are per view.  `fn` names the entry
+// point in the messages; with_obj: gsr_forward_raw_batch_obj (objects_dc required, out_objects [B,16,H,W] or null).
+static int forward_raw_batch_impl(const char* fn, bool with_obj, const GsrSettings* s, int32_t B, int32_t P, const float* xyz,
+                                  const float* features_dc, const float* features_rest, const float* objects_dc,
+                                  const float* opacity_logit, const float* log_scaling, const float* rotation_raw,
+                                  float* out_color, float* out_objects, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered,
+                                  void* stream) {
   if (ctx_out) *ctx_out = nullptr;
-  if (!s || B < 1 || B > MAX_BATCH) return set_err(GSR_ERR_INVALID, "gsr_forward_raw_batch: 1..%d views, got %d", MAX_BATCH, B);
+  if (!s || B < 1 || B > MAX_BATCH) return set_err(GSR_ERR_INVALID, "%s: 1..%d views, got %d", fn, MAX_BATCH, B);
   if (P > 0 && (!features_dc || !features_rest || !log_scaling || !rotation_raw))
-    return set_err(GSR_ERR_INVALID, "gsr_forward_raw_batch: null features_dc / features_rest / log_scaling / rotation_raw");
+    return set_err(GSR_ERR_INVALID, "%s: null features_dc / features_rest / log_scaling / rotation_raw", fn);
+  if (with_obj && P > 0 && !objects_dc) return set_err(GSR_ERR_INVALID, "%s: objects_dc is null", fn);
   for (int v = 0; v < B; ++v) {
     if (!s[v].bg || !s[v].viewmatrix || !s[v].projmatrix || !s[v].campos)
-      return set_err(GSR_ERR_INVALID, "gsr_forward_raw_batch: view %d: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers", v);
+      return set_err(GSR_ERR_INVALID, "%s: view %d: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers", fn, v);
     if (s[v].image_height != s[0].image_height || s[v].image_width != s[0].image_width || s[v].scale_modifier != s[0].scale_modifier ||
         s[v].sh_degree != s[0].sh_degree || s[v].flags != s[0].flags)
-      return set_err(GSR_ERR_INVALID, "gsr_forward_raw_batch: view %d differs from view 0 in image size, scale modifier, SH degree or "
-                     "flags (a batch shares them)", v);
+      return set_err(GSR_ERR_INVALID, "%s: view %d differs from view 0 in image size, scale modifier, SH degree or "
+                     "flags (a batch shares them)", fn, v);
   }
-  if (s[0].flags & GSR_FLAG_NEEDLE_DOUBLE) return set_err(GSR_ERR_INVALID, "gsr_forward_raw_batch: GSR_FLAG_NEEDLE_DOUBLE is a single-view flag");
-  if (!out_color) return set_err(GSR_ERR_INVALID, "gsr_forward_raw_batch: out_color is null");
+  if (s[0].flags & GSR_FLAG_NEEDLE_DOUBLE) return set_err(GSR_ERR_INVALID, "%s: GSR_FLAG_NEEDLE_DOUBLE is a single-view flag", fn);
+  if (!out_color) return set_err(GSR_ERR_INVALID, "%s: out_color is null", fn);
   if (P == 0 && B > 1) {                 // an empty scene: B backgrounds; the context (of view 0) has nothing to differentiate
-    const size_t img = (size_t)3 * (size_t)s[0].image_height * (size_t)s[0].image_width;
+    const size_t px = (size_t)s[0].image_height * (size_t)s[0].image_width;
     for (int v = 0; v < B; ++v) {
       const int rc = forward_impl(s + v, 0, 16, xyz, features_rest, features_dc, nullptr, nullptr, opacity_logit, log_scaling,
-                                  rotation_raw, nullptr, out_color + (size_t)v * img, nullptr, radii, v == 0 ? ctx_out : nullptr,
-                                  num_rendered, stream, true);
+                                  rotation_raw, nullptr, out_color + (size_t)v * 3 * px,
+                                  out_objects ? out_objects + (size_t)v * NUM_OBJ * px : nullptr, radii,
+                                  v == 0 ? ctx_out : nullptr, num_rendered, stream, true);
       if (rc != GSR_OK) return rc;
     }
     return GSR_OK;
   }
-  return forward_impl(s, P, 16, xyz, features_rest, features_dc, nullptr, nullptr, opacity_logit, log_scaling, rotation_raw,
-                      nullptr, out_color, nullptr, radii, ctx_out, num_rendered, stream, true, nullptr, false, B);
+  return forward_impl(s, P, 16, xyz, features_rest, features_dc, objects_dc, nullptr, opacity_logit, log_scaling, rotation_raw,
+                      nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true, nullptr, false, B);
+}
+
+// gsr_forward_raw2_batch(_obj): TWO parameter sets as one scene per view, forward only (see below)
+static int forward_raw2_batch_impl(const char* fn, bool with_obj, const GsrSettings* s, int32_t B, int32_t Pa, const float* xyz_a,
+                                   const float* features_dc_a, const float* features_rest_a, const float* objects_dc_a,
+                                   const float* opacity_logit_a, const float* log_scaling_a, const float* rotation_raw_a, int32_t Pb,
+                                   const float* xyz_b, const float* features_dc_b, const float* features_rest_b,
+                                   const float* objects_dc_b, const float* opacity_logit_b, const float* log_scaling_b,
+                                   const float* rotation_raw_b, float* out_color, float* out_objects, int32_t* radii,
+                                   GsrCtx** ctx_out, int64_t* num_rendered, void* stream) {
+  if (ctx_out) *ctx_out = nullptr;
+  if (Pa <= 0 || Pb <= 0 || (long long)Pa + Pb > 0x7FFFFFFFll)
+    return set_err(GSR_ERR_INVALID, "%s: both segments must hold Gaussians (Pa=%d Pb=%d)", fn, Pa, Pb);
+  if (!s || B < 1 || B > MAX_BATCH) return set_err(GSR_ERR_INVALID, "%s: 1..%d views, got %d", fn, MAX_BATCH, B);
+  if (!xyz_a || !features_dc_a || !features_rest_a || !opacity_logit_a || !log_scaling_a || !rotation_raw_a || !xyz_b ||
+      !features_dc_b || !features_rest_b || !opacity_logit_b || !log_scaling_b || !rotation_raw_b)
+    return set_err(GSR_ERR_INVALID, "%s: null parameter tensor", fn);
+  if (with_obj && ((objects_dc_a == nullptr) != (objects_dc_b == nullptr)))
+    return set_err(GSR_ERR_INVALID, "%s: objects_dc_a and objects_dc_b: both or neither", fn);
+  for (int v = 0; v < B; ++v) {
+    if (!s[v].bg || !s[v].viewmatrix || !s[v].projmatrix || !s[v].campos)
+      return set_err(GSR_ERR_INVALID, "%s: view %d: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers", fn, v);
+    if (s[v].image_height != s[0].image_height || s[v].image_width != s[0].image_width || s[v].scale_modifier != s[0].scale_modifier ||
+        s[v].sh_degree != s[0].sh_degree || s[v].flags != s[0].flags)
+      return set_err(GSR_ERR_INVALID, "%s: view %d differs from view 0 in image size, scale modifier, SH degree or "
+                     "flags (a batch shares them)", fn, v);
+  }
+  if (s[0].flags & GSR_FLAG_NEEDLE_DOUBLE) return set_err(GSR_ERR_INVALID, "%s: GSR_FLAG_NEEDLE_DOUBLE is a single-view flag", fn);
+  if (!out_color) return set_err(GSR_ERR_INVALID, "%s: out_color is null", fn);
+  SegB b;
+  b.Pb = Pb; b.xyz = xyz_b; b.features_dc = features_dc_b; b.features_rest = features_rest_b; b.objects_dc = objects_dc_b;
+  b.opacity = opacity_logit_b; b.scaling = log_scaling_b; b.rotation = rotation_raw_b;
+  return forward_impl(s, Pa + Pb, 16, xyz_a, features_rest_a, features_dc_a, objects_dc_a, nullptr, opacity_logit_a, log_scaling_a,
+                      rotation_raw_a, nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true, &b, true, B);
+}
+
+extern "C" {
+
+int gsr_forward_raw_batch(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
+                          const float* features_rest, const float* opacity_logit, const float* log_scaling,
+                          const float* rotation_raw, float* out_color, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered,
+                          void* stream) {
+  return forward_raw_batch_impl("gsr_forward_raw_batch", false, s, B, P, xyz, features_dc, features_rest, nullptr, opacity_logit,
+                                log_scaling, rotation_raw, out_color, nullptr, radii, ctx_out, num_rendered, stream);
+}
+
+int gsr_forward_raw_batch_obj(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
+                              const float* features_rest, const float* objects_dc, const float* opacity_logit,
+                              const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
+                              int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, void* stream) {
+  return forward_raw_batch_impl("gsr_forward_raw_batch_obj", true, s, B, P, xyz, features_dc, features_rest, objects_dc,
+                                opacity_logit, log_scaling, rotation_raw, out_color, out_objects, radii, ctx_out, num_rendered,
+                                stream);
 }
 
 // gsr_forward_raw_batch for TWO parameter sets as one scene per view (the success renders of a batch, reference
@@ -1150,28 +1209,23 @@ int gsr_forward_raw2_batch(const GsrSettings* s, int32_t B, int32_t Pa, const fl
                            const float* features_rest_b, const float* opacity_logit_b, const float* log_scaling_b,
                            const float* rotation_raw_b, float* out_color, int32_t* radii, GsrCtx** ctx_out,
                            int64_t* num_rendered, void* stream) {
-  if (ctx_out) *ctx_out = nullptr;
-  if (Pa <= 0 || Pb <= 0 || (long long)Pa + Pb > 0x7FFFFFFFll)
-    return set_err(GSR_ERR_INVALID, "gsr_forward_raw2_batch: both segments must hold Gaussians (Pa=%d Pb=%d)", Pa, Pb);
-  if (!s || B < 1 || B > MAX_BATCH) return set_err(GSR_ERR_INVALID, "gsr_forward_raw2_batch: 1..%d views, got %d", MAX_BATCH, B);
-  if (!xyz_a || !features_dc_a || !features_rest_a || !opacity_logit_a || !log_scaling_a || !rotation_raw_a || !xyz_b ||
-      !features_dc_b || !features_rest_b || !opacity_logit_b || !log_scaling_b || !rotation_raw_b)
-    return set_err(GSR_ERR_INVALID, "gsr_forward_raw2_batch: null parameter tensor");
-  for (int v = 0; v < B; ++v) {
-    if (!s[v].bg || !s[v].viewmatrix || !s[v].projmatrix || !s[v].campos)
-      return set_err(GSR_ERR_INVALID, "gsr_forward_raw2_batch: view %d: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers", v);
-    if (s[v].image_height != s[0].image_height || s[v].image_width != s[0].image_width || s[v].scale_modifier != s[0].scale_modifier ||
-        s[v].sh_degree != s[0].sh_degree || s[v].flags != s[0].flags)
-      return set_err(GSR_ERR_INVALID, "gsr_forward_raw2_batch: view %d differs from view 0 in image size, scale modifier, SH degree or "
-                     "flags (a batch shares them)", v);
-  }
-  if (s[0].flags & GSR_FLAG_NEEDLE_DOUBLE) return set_err(GSR_ERR_INVALID, "gsr_forward_raw2_batch: GSR_FLAG_NEEDLE_DOUBLE is a single-view flag");
-  if (!out_color) return set_err(GSR_ERR_INVALID, "gsr_forward_raw2_batch: out_color is null");
-  SegB b;
-  b.Pb = Pb; b.xyz = xyz_b; b.features_dc = features_dc_b; b.features_rest = features_rest_b; b.objects_dc = nullptr;
-  b.opacity = opacity_logit_b; b.scaling = log_scaling_b; b.rotation = rotation_raw_b;
-  return forward_impl(s, Pa + Pb, 16, xyz_a, features_rest_a, features_dc_a, nullptr, nullptr, opacity_logit_a, log_scaling_a,
-                      rotation_raw_a, nullptr, out_color, nullptr, radii, ctx_out, num_rendered, stream, true, &b, true, B);
+  return forward_raw2_batch_impl("gsr_forward_raw2_batch", false, s, B, Pa, xyz_a, features_dc_a, features_rest_a, nullptr,
+                                 opacity_logit_a, log_scaling_a, rotation_raw_a, Pb, xyz_b, features_dc_b, features_rest_b,
+                                 nullptr, opacity_logit_b, log_scaling_b, rotation_raw_b, out_color, nullptr, radii, ctx_out,
+                                 num_rendered, stream);
+}
+
+int gsr_forward_raw2_batch_obj(const GsrSettings* s, int32_t B, int32_t Pa, const float* xyz_a, const float* features_dc_a,
+                               const float* features_rest_a, const float* objects_dc_a, const float* opacity_logit_a,
+                               const float* log_scaling_a, const float* rotation_raw_a, int32_t Pb, const float* xyz_b,
+                               const float* features_dc_b, const float* features_rest_b, const float* objects_dc_b,
+                               const float* opacity_logit_b, const float* log_scaling_b, const float* rotation_raw_b,
+                               float* out_color, float* out_objects, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered,
+                               void* stream) {
+  return forward_raw2_batch_impl("gsr_forward_raw2_batch_obj", true, s, B, Pa, xyz_a, features_dc_a, features_rest_a,
+                                 objects_dc_a, opacity_logit_a, log_scaling_a, rotation_raw_a, Pb, xyz_b, features_dc_b,
+                                 features_rest_b, objects_dc_b, opacity_logit_b, log_scaling_b, rotation_raw_b, out_color,
+                                 out_objects, radii, ctx_out, num_rendered, stream);
 }
 
 // Re-render of a kept context whose colour inputs (SH coefficients) may have changed and nothing else has: the colour
@@ -1181,8 +1235,9 @@ int gsr_ctx_rerender(GsrCtx* c, const float* features_dc, const float* features_
                      void* stream) {
   if (!c) return set_err(GSR_ERR_STATE, "gsr_ctx_rerender: null context");
   if (!out_color) return set_err(GSR_ERR_INVALID, "gsr_ctx_rerender: out_color is null");
-  // a batch context (gsr_forward_raw_batch / gsr_forward_raw2_batch): out_color [B,3,H,W], bg [B,3] or null; no object channels
-  if (c->B > 1 && out_objects)
+  // a batch context (gsr_forward_raw_batch / gsr_forward_raw2_batch and their _obj forms): out_color [B,3,H,W], bg [B,3] or
+  // null; out_objects [B,16,H,W] only if the batch's forward composited object channels
+  if (c->B > 1 && out_objects && !c->objects_out)
     return set_err(GSR_ERR_INVALID, "gsr_ctx_rerender: a batch context (%d views) has no object channels", c->B);
   if (c->P > 0 && (!c->lanegroup || !c->shs))
     return set_err(GSR_ERR_INVALID, "gsr_ctx_rerender: the context was not rendered from SH coefficients (raw parameters, "
@@ -1350,7 +1405,7 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     const bool segs = c->bnd != nullptr && !obj;
     ra.bnd = segs ? c->bnd : nullptr; ra.segoff = c->segoff; ra.rec_item = c->rec_item; ra.nrec = c->dv + DV_NREC;
     ra.seg_shift = c->seg_shift; ra.extra_blocks = segs ? c->rec_cap * nsub : 0u;
-    ra.tpv = c->tpv; ra.vpack = c->vpack;
+    ra.tpv = c->tpv; ra.vpack = c->vpack; ra.Ppad = c->Ppad;
     const dim3 gridT(ra.extra_blocks + (unsigned)render_grid(c->ntiles * (int)nsub)), blk(64);
     CompStream comp_s{};
     bool comp_used = false;
@@ -1391,7 +1446,8 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     pa.means = c->means3D; pa.scales = c->scales; pa.rots = c->rots; pa.cov3d = c->cov3d; pa.sh = c->shs;
     pa.sh_dc = c->sh_dc; pa.dsh_dc = dsh_dc; pa.D = c->D; pa.abc = c->abc;
     pa.needle_double = (c->st.flags & GSR_FLAG_NEEDLE_DOUBLE) != 0u ? 1 : 0;
-    pa.dmeans3D = dmeans3D; pa.dmeans2D = dmeans2D; pa.dsh = c->shs ? dshs : nullptr; pa.dsh_objs = dsh_objs;
+    // (a batch: the object-feature gradient is k_obj_grad_batch's below, the per-Gaussian kernels leave it alone)
+    pa.dmeans3D = dmeans3D; pa.dmeans2D = dmeans2D; pa.dsh = c->shs ? dshs : nullptr; pa.dsh_objs = c->B > 1 ? nullptr : dsh_objs;
     pa.dcolors = c->colors ? dcolors_precomp : nullptr; pa.dopac = dopacities;
     pa.dscales = c->cov3d ? nullptr : dscales; pa.drots = c->cov3d ? nullptr : drotations;
     pa.dcov3d = c->cov3d ? dcov3D : nullptr;
@@ -1407,6 +1463,14 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     // The per-Gaussian stage covers the Gaussians in `nchunks` ranges (multiples of 64), one launch each; after a
     // range's launch is enqueued the caller is told (chunk_done): its gradients are complete in stream order, so a
     // collective over that range can be issued while the next range is still being computed.
+    if (c->B > 1 && dsh_objs) {
+      // dL/d object features of a batch: view by view as k_pre_bwd forms them, summed in view order (or per view)
+      ObjGradBatchArgs oa;
+      oa.P = P; oa.B = c->B; oa.Ppad = c->Ppad; oa.nsub = nsub; oa.tag_lo = tag_lo; oa.tag_hi = tag_hi;
+      oa.offg = c->offg; oa.part = part; oa.part_obj = (obj && N > 0) ? part_obj : nullptr; oa.dobj = dsh_objs;
+      oa.vstride = view_stride != 0 ? (long long)P * NUM_OBJ : 0;
+      hipLaunchKernelGGL(k_obj_grad_batch, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, oa);
+    }
     nchunks = std::max(1, std::min(nchunks, (P + 63) / 64));
     const int per = (((P + nchunks - 1) / nchunks) + 63) / 64 * 64;
     // gsr_ctx_request_sumsq (one-shot): the overwriting raw-parameter kernel also leaves per-workgroup sums of squares of
@@ -1561,6 +1625,23 @@ int gsr_backward_raw_batch_views(GsrCtx* c, const float* grad_color, float* dxyz
   if (view_stride <= 0) return set_err(GSR_ERR_INVALID, "gsr_backward_raw_batch_views: view_stride must be positive (floats between two views' buffers)");
   return backward_impl(c, grad_color, nullptr, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, nullptr, nullptr, dopacity_logit,
                        dlog_scaling, drotation_raw, nullptr, stream, false, 1, nullptr, nullptr, view_stride);
+}
+
+int gsr_backward_raw_batch_obj_into(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dxyz, float* dmeans2D,
+                                    float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc, float* dopacity_logit,
+                                    float* dlog_scaling, float* drotation_raw, int32_t accumulate, void* stream) {
+  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw_batch_obj_into: context came from gsr_forward; use gsr_backward");
+  return backward_impl(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, dobjects_dc, nullptr,
+                       dopacity_logit, dlog_scaling, drotation_raw, nullptr, stream, accumulate != 0);
+}
+
+int gsr_backward_raw_batch_obj_views(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dxyz, float* dmeans2D,
+                                     float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc, float* dopacity_logit,
+                                     float* dlog_scaling, float* drotation_raw, int64_t view_stride, void* stream) {
+  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw_batch_obj_views: context came from gsr_forward; use gsr_backward");
+  if (view_stride <= 0) return set_err(GSR_ERR_INVALID, "gsr_backward_raw_batch_obj_views: view_stride must be positive (floats between two views' buffers)");
+  return backward_impl(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, dobjects_dc, nullptr,
+                       dopacity_logit, dlog_scaling, drotation_raw, nullptr, stream, false, 1, nullptr, nullptr, view_stride);
 }
 
 int gsr_mark_visible(const GsrSettings* s, int32_t P, const float* means3D, uint8_t* present, void* stream) {

@@ -518,6 +518,9 @@ struct RenderArgs {
   // the B images one after another; vpack[view].bg is that view's background.  One view: tpv = ntiles, vpack = null.
   int tpv;
   const ViewDev* vpack;
+  // object channels of a batch (OBJ only): the view's Gaussians are the virtual rows [view * Ppad, view * Ppad + P), so the
+  // feature row of virtual row r is r - view * Ppad (a second segment from Pa on, as above); out_objects holds [B,16,H,W]
+  int Ppad;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -816,6 +819,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
   const int view = a.tpv < a.ntiles ? __builtin_amdgcn_readfirstlane(tile / a.tpv) : 0;     // a batch of views: ViewDev
   const int ltile = tile - view * a.tpv;
   const int tx = ltile % a.gridx, ty = ltile / a.gridx;
+  const uint32_t obase = OBJ ? (uint32_t)view * (uint32_t)a.Ppad : 0u;   // first virtual row of the view (object features)
   const uint2 rg = a.ranges[tile];
   // a split tile (see "Segments"): this wave stores (T, C) of its pixels at every segment boundary it walks past
   // (also with object channels composited: the records hold T and the colour sums, which is all a backward WITHOUT
@@ -860,8 +864,9 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
       rown = r;                                           // the pair's value IS the Gaussian's storage index
       s0[slot] = sp.a; s1[slot] = sp.b; s2[slot] = make_float4(sp.c.x, sp.c.y, __uint_as_float(r), 0.f);
       if (OBJ && !GSR_K6_OBJ_SCALAR && (GSR_K6_OBJ_STAGE_ALL || mine != 0u)) {   // (an entry no strip of this wave reaches is never read)
-        const float4* src = reinterpret_cast<const float4*>(r >= (uint32_t)a.Pa ? a.sh_objs_b + (size_t)(r - (uint32_t)a.Pa) * NUM_OBJ
-                                                                                 : a.sh_objs + (size_t)r * NUM_OBJ);
+        const uint32_t lr = r - obase;                    // the view-local Gaussian
+        const float4* src = reinterpret_cast<const float4*>(lr >= (uint32_t)a.Pa ? a.sh_objs_b + (size_t)(lr - (uint32_t)a.Pa) * NUM_OBJ
+                                                                                  : a.sh_objs + (size_t)lr * NUM_OBJ);
         float4* dst = reinterpret_cast<float4*>(&so[slot][0]);
         dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
       }
@@ -911,7 +916,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
     auto load_feat = [&](const int j) -> Feat {
       Feat f;
       if (OBJ && GSR_K6_OBJ_SCALAR) {
-        const uint32_t og = __builtin_amdgcn_readlane(rvec, j);
+        const uint32_t og = __builtin_amdgcn_readlane(rvec, j) - obase;
         const float* row = og >= (uint32_t)a.Pa ? a.sh_objs_b + (size_t)(og - (uint32_t)a.Pa) * NUM_OBJ : a.sh_objs + (size_t)og * NUM_OBJ;
         // (the feature table is read-only for the whole launch: read through the constant address space, a uniform address
         // there is a scalar load; left in the global address space the compiler issues vector loads into 16 VGPRs)
@@ -1065,7 +1070,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
       nc[pix] = last[k];
       if (OBJ) {
 #pragma unroll
-        for (int c = 0; c < NUM_OBJ; ++c) a.out_objects[c * HW + pix] = O[k][c];
+        for (int c = 0; c < NUM_OBJ; ++c) a.out_objects[NUM_OBJ * HW * (size_t)view + c * HW + pix] = O[k][c];
       }
     }
   }
@@ -1141,6 +1146,7 @@ struct RenderBwdArgs {
   unsigned long long* wave_clock;   // diagnostic (gsr_debug_wave_clock): [ntiles][2] start/end of each tile's wave, 100 MHz
   int tpv;                    // a batch of views, as in RenderArgs: view = tile / tpv; grad_color holds the B images' gradients
   const ViewDev* vpack;
+  int Ppad;                   // OBJ: as in RenderArgs (feature row = r - view * Ppad); grad_objects holds [B,16,H,W]
 };
 
 constexpr int PART_F4 = 3;
@@ -1237,6 +1243,8 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
   const float* const fT = a.final_T + HW * (size_t)view;
   const uint32_t* const nc = a.n_contrib + HW * (size_t)view;
   const float* const gcol = a.grad_color + 3 * HW * (size_t)view;
+  const float* const gobj = OBJ ? a.grad_objects + NUM_OBJ * HW * (size_t)view : nullptr;
+  const uint32_t obase = OBJ ? (uint32_t)view * (uint32_t)a.Ppad : 0u;
   float pyf[NPX], T[NPX], Acc[NPX], g0[NPX], g1[NPX], g2[NPX];
   float gO[OBJ ? NPX : 1][NUM_OBJ];
   uint32_t ncon[NPX], smax[NPX];
@@ -1257,7 +1265,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
       Acc[k] = bg0 * g0[k] + bg1 * g1[k] + bg2 * g2[k];
       if (OBJ) {
 #pragma unroll
-        for (int c = 0; c < NUM_OBJ; ++c) gO[k][c] = a.grad_objects[c * HW + pix];
+        for (int c = 0; c < NUM_OBJ; ++c) gO[k][c] = gobj[c * HW + pix];
       }
       if (!OBJ && rec0 != SEG_NONE) {
         if (ncon[k] > b_pos) {
@@ -1304,7 +1312,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
       const uint32_t minx = rx & RECT_MASK, wx = ((rx >> 12) & RECT_MASK) - minx, miny = ry & RECT_MASK;
       sslot[lane] = (a.offg[r] + ((uint32_t)ty - miny) * wx + ((uint32_t)tx - minx)) * NSUB + sub;
       if (OBJ) {
-        const float4* src = reinterpret_cast<const float4*>(a.sh_objs + (size_t)r * NUM_OBJ);
+        const float4* src = reinterpret_cast<const float4*>(a.sh_objs + (size_t)(r - obase) * NUM_OBJ);
         float4* dst = reinterpret_cast<float4*>(&so[lane][0]);
         dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
       }
@@ -2374,6 +2382,61 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
   flush_sumsq();
 }
 
+// ------------------------------------------------------------------------------------------------
+// dL/d object features of a BATCH of views (gsr_backward_raw_batch_obj_*): one lane per Gaussian walks the views in order
+// and forms view v's sum over its tagged object rows exactly as k_pre_bwd does for one view (same rows, same order, same
+// tag test).  vstride == 0: dobj [P,16] = ((s_0 + s_1) + s_2) + ... -- the float32 adds autograd makes when B single-view
+// backwards accumulate into .grad; vstride != 0: view v's s_v at dobj + v * vstride.  A Gaussian no view sees gets zeros;
+// dobj is always overwritten.  Kept out of k_pre_bwd_batch: 16 more live sums there would cost that kernel its occupancy.
+// ------------------------------------------------------------------------------------------------
+struct ObjGradBatchArgs {
+  int P, B, Ppad;
+  uint32_t nsub, tag_lo, tag_hi;
+  const uint32_t* offg;   // [B * Ppad + 1]
+  const float4* part;     // the tags (word 2 of a row)
+  const float4* part_obj; // [N][4] or null (no dL/dobjects: zeros)
+  float* dobj;
+  long long vstride;
+};
+__global__ void __launch_bounds__(256) k_obj_grad_batch(ObjGradBatchArgs a) {
+  const int g = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (g >= a.P) return;
+  float tot[NUM_OBJ];
+#pragma unroll
+  for (int c = 0; c < NUM_OBJ; ++c) tot[c] = 0.f;
+#pragma unroll 1
+  for (int v = 0; v < a.B; ++v) {
+    const size_t i = (size_t)v * (size_t)a.Ppad + (size_t)g;
+    float s[NUM_OBJ];
+#pragma unroll
+    for (int c = 0; c < NUM_OBJ; ++c) s[c] = 0.f;
+    if (a.part_obj) {
+      const uint32_t o0 = a.offg[i] * a.nsub, o1 = a.offg[i + 1] * a.nsub;
+      for (uint32_t e = o0; e < o1; ++e) {
+        const float4 tg = a.part[(size_t)e * PART_F4 + 2];
+        if (__float_as_uint(tg.y) != a.tag_lo || __float_as_uint(tg.z) != a.tag_hi) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 v4 = a.part_obj[(size_t)e * 4 + q];
+          s[4 * q] += v4.x; s[4 * q + 1] += v4.y; s[4 * q + 2] += v4.z; s[4 * q + 3] += v4.w;
+        }
+      }
+    }
+    if (a.vstride != 0) {
+      float* d = a.dobj + (size_t)v * (size_t)a.vstride + (size_t)g * NUM_OBJ;
+#pragma unroll
+      for (int c = 0; c < NUM_OBJ; ++c) d[c] = s[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < NUM_OBJ; ++c) tot[c] = v == 0 ? s[c] : tot[c] + s[c];
+    }
+  }
+  if (a.vstride == 0) {
+    float* d = a.dobj + (size_t)g * NUM_OBJ;
+#pragma unroll
+    for (int c = 0; c < NUM_OBJ; ++c) d[c] = tot[c];
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 // K8+K9 of a BATCH of views (gsr_backward_raw_batch_into; raw parameters): one wave per 64 consecutive Gaussians walks

@@ -137,6 +137,17 @@ def _load():
         lib.gsr_backward_raw_batch_into.argtypes = [vp] * 9 + [i32, vp]
         lib.gsr_backward_raw_batch_views.restype = ctypes.c_int
         lib.gsr_backward_raw_batch_views.argtypes = [vp] * 9 + [ctypes.c_int64, vp]
+    if hasattr(lib, "gsr_forward_raw_batch_obj"):          # (C ABI 602)
+        lib.gsr_forward_raw_batch_obj.restype = ctypes.c_int
+        lib.gsr_forward_raw_batch_obj.argtypes = ([ctypes.POINTER(_CSettings), i32, i32] + [vp] * 7
+                                                  + [vp, vp, vp, ctypes.POINTER(vp), i64p, vp])
+        lib.gsr_forward_raw2_batch_obj.restype = ctypes.c_int
+        lib.gsr_forward_raw2_batch_obj.argtypes = ([ctypes.POINTER(_CSettings), i32, i32] + [vp] * 7 + [i32] + [vp] * 7
+                                                   + [vp, vp, vp, ctypes.POINTER(vp), i64p, vp])
+        lib.gsr_backward_raw_batch_obj_into.restype = ctypes.c_int
+        lib.gsr_backward_raw_batch_obj_into.argtypes = [vp] * 11 + [i32, vp]
+        lib.gsr_backward_raw_batch_obj_views.restype = ctypes.c_int
+        lib.gsr_backward_raw_batch_obj_views.argtypes = [vp] * 11 + [ctypes.c_int64, vp]
     if hasattr(lib, "gsr_forward_raw2_batch"):
         lib.gsr_forward_raw2_batch.restype = ctypes.c_int
         lib.gsr_forward_raw2_batch.argtypes = ([ctypes.POINTER(_CSettings), i32, i32] + [vp] * 6 + [i32] + [vp] * 6
@@ -924,11 +935,13 @@ class _BatchPack:
 class _RasterizeGaussiansRawBatch(torch.autograd.Function):
     """B views of one set of RAW parameters through ONE launch chain (gsr_forward_raw_batch / gsr_backward_raw_batch_into):
     what the reference's batch loop does with B render() calls and one accumulated .grad (attack.py:476-494).
-    -> (color[B,3,H,W], radii[B,P]); the attribute gradients are the SUM over the views of dL/dC[v] pulled back."""
+    -> (color[B,3,H,W], radii[B,P]); the attribute gradients are the SUM over the views of dL/dC[v] pulled back.
+    With objects_dc ([P,16] object features): the _obj entry points, -> (color, radii, objects[B,16,H,W]), and the object
+    features' gradient is the view-ordered sum of the single-view ones."""
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, settings_list, keep=True,
-                bucket=None, norms=None, cache_slot=None, color_only=False):
+                bucket=None, norms=None, cache_slot=None, color_only=False, objects_dc=None):
         lib = _load()
         ctx.bucket = bucket
         ctx.norms = norms
@@ -948,6 +961,10 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
             return None if t is None or t.numel() == 0 else _f32c(t.detach(), device)
         x, dc, rest = prep(xyz), prep(features_dc), prep(features_rest)
         op, sc, ro = prep(opacity), prep(scaling), prep(rotation)
+        with_obj = objects_dc is not None
+        obj = prep(objects_dc) if with_obj else None
+        if obj is not None and obj.numel() != P * NUM_OBJECTS:
+            raise ValueError(f"objects_dc must hold P*{NUM_OBJECTS} values, got {tuple(objects_dc.shape)}")
         H, W = int(settings_list[0].image_height), int(settings_list[0].image_width)
         packs = [_SettingsPack(rs, device) for rs in settings_list]
         carr = (_CSettings * B)()
@@ -955,6 +972,7 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
             carr[v] = pk.c
         color = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
         radii = torch.empty(B, P, dtype=torch.int32, device=device)
+        objects = torch.empty(B, NUM_OBJECTS, H, W, dtype=torch.float32, device=device) if with_obj else None
         handle = ctypes.c_void_p(None)
         nren = ctypes.c_int64(0)
         # a kept batch context (RenderCache): the key's geometry tensors and ALL its views' camera tensors unchanged since the
@@ -963,8 +981,11 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
         if cache_slot is not None and P > 0:
             cache, key = cache_slot
             geo = (xyz, opacity, scaling, rotation)
-            if all(a.data_ptr() == b.data_ptr() for a, b in zip(geo, (x, op, sc, ro))):
-                extra = [B]
+            used = (x, op, sc, ro)
+            if with_obj and obj is not None:       # (the context reads the object features through the forward's pointer)
+                geo, used = geo + (objects_dc,), used + (obj,)
+            if all(a.data_ptr() == b.data_ptr() for a, b in zip(geo, used)):
+                extra = [B] + (["obj"] if with_obj else [])
                 for rs in settings_list[1:]:
                     extra += [float(rs.tanfovx), float(rs.tanfovy)]
                     for t in (rs.viewmatrix, rs.projmatrix, rs.campos):
@@ -986,8 +1007,8 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
                     # other background tensors than the context's forward saw: their values as one [B,3] tensor
                     bgt = torch.stack([pk.bg[:3] for pk in packs]).contiguous()
                     bp.bgt, bp.bg_src = bgt, ptrs       # (bp.packs stays: the context's camera pointers point into them)
-                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(dc), _ptr(rest), None, None, _ptr(bgt), _ptr(color), None,
-                                          1 if color_only else 0, stream)
+                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(dc), _ptr(rest), None, None, _ptr(bgt), _ptr(color),
+                                          _ptr(objects), 1 if color_only else 0, stream)
                 entry.gen += 1
                 nren.value = entry.nren
                 if rc == GSR_ERR_OVERFLOW:             # (see _RasterizeGaussiansRaw: the entry can never be re-rendered)
@@ -996,8 +1017,14 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
                     entry = None
             if entry is None:
                 want_ctx = keep or sig is not None
-                rc = lib.gsr_forward_raw_batch(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(op), _ptr(sc), _ptr(ro), _ptr(color),
-                                               _ptr(radii), ctypes.byref(handle) if want_ctx else None, ctypes.byref(nren), stream)
+                if with_obj:
+                    rc = lib.gsr_forward_raw_batch_obj(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op), _ptr(sc),
+                                                       _ptr(ro), _ptr(color), _ptr(objects), _ptr(radii),
+                                                       ctypes.byref(handle) if want_ctx else None, ctypes.byref(nren), stream)
+                else:
+                    rc = lib.gsr_forward_raw_batch(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(op), _ptr(sc), _ptr(ro),
+                                                   _ptr(color), _ptr(radii), ctypes.byref(handle) if want_ctx else None,
+                                                   ctypes.byref(nren), stream)
         if rc != 0:
             raise Exception(_err(lib)) if rc == 1 else (PairCapacityExceeded if rc == GSR_ERR_OVERFLOW else RuntimeError)(_err(lib))
         if entry is not None:
@@ -1021,24 +1048,28 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
         ctx.B = B
         ctx._nren = nren.value
         ctx.shapes = (xyz.shape, None if means2D is None else means2D.shape, features_dc.shape, features_rest.shape,
-                      opacity.shape, scaling.shape, rotation.shape)
+                      opacity.shape, scaling.shape, rotation.shape, None if objects_dc is None else objects_dc.shape)
         ctx.kept = (x, dc, rest, op, sc, ro)
-        ctx.versions = _versions(ctx.kept)
+        ctx.obj, ctx.with_obj = obj, with_obj
+        ctx.versions = _versions(ctx.kept + (obj,))
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
+        if with_obj:
+            return color, radii, objects
         return color, radii
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii):
-        _check_versions(ctx.kept, ctx.versions)
+    def backward(ctx, grad_color, grad_radii, grad_objects=None):
+        _check_versions(ctx.kept + (ctx.obj,), ctx.versions)
         x, dc, rest, op, sc, ro = ctx.kept
         if x is None:                                  # an empty scene: empty gradients
             need = ctx.needs_input_grad
             s = ctx.shapes
             dev0 = ctx.packs[0].device
             z = lambda i, shp: torch.zeros(shp, dtype=torch.float32, device=dev0) if (need[i] and shp is not None) else None
-            return (z(0, s[0]), z(1, s[1]), z(2, s[2]), z(3, s[3]), z(4, s[4]), z(5, s[5]), z(6, s[6]), None, None, None, None,
-                    None, None)
+            res = (z(0, s[0]), z(1, s[1]), z(2, s[2]), z(3, s[3]), z(4, s[4]), z(5, s[5]), z(6, s[6]), None, None, None, None,
+                   None, None, z(13, s[7]) if ctx.with_obj else None)
+            return res if ctx.with_obj else res[:13]
         lib = ctx.holder.lib
         device = x.device
         if ctx.entry is not None:
@@ -1080,6 +1111,11 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
             d_sc = out(need[5], P, 3)
             d_ro = out(need[6], P, 4)
         d_m2 = out(need[1], B, P, 3)
+        # object channels: dL/dobjects [B,16,H,W] (or None: the segmented composite of the no-object batch runs) and the
+        # object features' gradient [P,16], always written (zeros without dL/dobjects)
+        with_obj = ctx.with_obj
+        gobj = _f32c(grad_objects, device) if (with_obj and grad_objects is not None and ctx.obj is not None) else None
+        d_obj = out(with_obj and need[13], P, NUM_OBJECTS)
         norms = getattr(ctx, "norms", None)
         if norms is not None:
             # the batch's ONE backward writes the summed gradient: its sums of squares are the L2 steps' norms (GradNorms)
@@ -1096,7 +1132,18 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
             with torch.cuda.device(device):
                 stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
                 acc = 1 if (bucket is not None and bset is None and not bucket.fresh) else 0
-                if bset is not None:
+                if bset is not None and with_obj:
+                    # per-view object gradients [B,P,16], summed here in view order (autograd's association)
+                    d_objv = out(d_obj is not None, B, P, NUM_OBJECTS)
+                    rc = lib.gsr_backward_raw_batch_obj_views(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2),
+                                                              _ptr(d_dc), _ptr(d_rest), _ptr(d_objv), _ptr(d_op), _ptr(d_sc),
+                                                              _ptr(d_ro), 59 * P, stream)
+                    bset.used = B
+                    if rc == 0 and d_objv is not None:
+                        d_obj.copy_(d_objv[0])
+                        for v in range(1, B):
+                            d_obj.add_(d_objv[v])
+                elif bset is not None:
                     rc = lib.gsr_backward_raw_batch_views(ctx.holder.handle, _ptr(gcol), _ptr(d_x), _ptr(d_m2), _ptr(d_dc),
                                                           _ptr(d_rest), _ptr(d_op), _ptr(d_sc), _ptr(d_ro), 59 * P, stream)
                     bset.used = B
@@ -1112,12 +1159,16 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
                         except BaseException as e:       # an exception must not unwind through the C frames
                             errs.append(e)
                     cb = _CHUNK_FN(_done)
-                    rc = lib.gsr_backward_raw_chunked(ctx.holder.handle, _ptr(gcol), None, _ptr(d_x), _ptr(d_m2), _ptr(d_dc),
-                                                      _ptr(d_rest), None, _ptr(d_op), _ptr(d_sc), _ptr(d_ro), acc,
-                                                      int(bucket.chunks), cb, None, stream)
+                    rc = lib.gsr_backward_raw_chunked(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2),
+                                                      _ptr(d_dc), _ptr(d_rest), _ptr(d_obj), _ptr(d_op), _ptr(d_sc), _ptr(d_ro),
+                                                      acc, int(bucket.chunks), cb, None, stream)
                     bucket.chunks = 1
                     if errs:
                         raise errs[0]
+                elif with_obj:
+                    rc = lib.gsr_backward_raw_batch_obj_into(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2),
+                                                             _ptr(d_dc), _ptr(d_rest), _ptr(d_obj), _ptr(d_op), _ptr(d_sc),
+                                                             _ptr(d_ro), acc, stream)
                 else:
                     rc = lib.gsr_backward_raw_batch_into(ctx.holder.handle, _ptr(gcol), _ptr(d_x), _ptr(d_m2), _ptr(d_dc),
                                                          _ptr(d_rest), _ptr(d_op), _ptr(d_sc), _ptr(d_ro), acc, stream)
@@ -1127,40 +1178,50 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
             for t in (d_x, d_dc, d_rest, d_op, d_sc, d_ro, d_m2):
                 if t is not None and bucket is None:
                     t.zero_()
+            if d_obj is not None:
+                d_obj.zero_()
         if ctx.entry is not None:
             _entry_leave(ctx.entry, device)
             ctx.token.done = True
         s = ctx.shapes
+        # (one gradient per input: the 14th, objects_dc, only when it was passed)
+        g_obj = (None if d_obj is None else d_obj.reshape(s[7]),) if with_obj else ()
         if bset is not None:
             return (None, None if d_m2 is None else d_m2.reshape(s[1]), None, None, None, None, None, None, None, None, None,
-                    None, None)
+                    None, None) + g_obj
         if bucket is not None:
             bucket.fresh, bucket.used = False, True
             return (None, None if d_m2 is None else d_m2.reshape(s[1]), None, None, None, None, None, None, None, None, None,
-                    None, None)
+                    None, None) + g_obj
 
         def shaped(t, shape, wanted=True):
             return None if (t is None or not wanted) else t.reshape(shape)
         return (shaped(d_x, s[0]), shaped(d_m2, s[1]), shaped(d_dc, s[2], need[2]), shaped(d_rest, s[3], need[3]),
-                shaped(d_op, s[4]), shaped(d_sc, s[5]), shaped(d_ro, s[6]), None, None, None, None, None, None)
+                shaped(d_op, s[4]), shaped(d_sc, s[5]), shaped(d_ro, s[6]), None, None, None, None, None, None) + g_obj
 
 
 def rasterize_gaussians_raw_batch(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, settings_list,
                                   grad_bucket: Optional["GradBucket"] = None, grad_norms: Optional["GradNorms"] = None,
-                                  cache: Optional["RenderCache"] = None, cache_key=None):
+                                  cache: Optional["RenderCache"] = None, cache_key=None, objects_dc=None):
     """(color[B,3,H,W], radii[B,P]) of B views (a list of GaussianRasterizationSettings that agree in image size, scale
     modifier and SH degree) of one set of RAW parameters, through one launch chain: every image and radius is bit for bit
     what rasterize_gaussians_raw gives for that view alone, and the backward leaves the SUM over the views of the
     attribute gradients, written once.  means2D: a [B,P,3] tensor whose .grad receives the per-view screen-space gradient
-    (viewspace_points.grad of the reference, one slice per view), or None.  No object channels."""
-    keep = _wants_backward(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation)
+    (viewspace_points.grad of the reference, one slice per view), or None.
+    objects_dc ([P,16] or [P,1,16] object features, or None = no object channels): -> (color, radii, objects[B,16,H,W]),
+    every object map bit for bit rasterize_gaussians_raw's for that view; objects_dc.grad receives the single-view object
+    gradients summed in view order (a GradBucket or GradBucketSet does not hold it)."""
+    keep = _wants_backward(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, objects_dc)
     # `cache` (a RenderCache) + `cache_key` (one per tuple of cameras): a batch whose geometry inputs and cameras are unchanged
     # since the key's last render re-uses that render's binning for all B views (gsr_ctx_rerender on the batch context)
     slot = (cache, cache_key) if cache is not None else None
     color_only = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad
                                                        for t in (xyz, means2D, opacity, scaling, rotation)))
+    if objects_dc is None:
+        return _RasterizeGaussiansRawBatch.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
+                                                 list(settings_list), keep, grad_bucket, grad_norms, slot, color_only)
     return _RasterizeGaussiansRawBatch.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                             list(settings_list), keep, grad_bucket, grad_norms, slot, color_only)
+                                             list(settings_list), keep, grad_bucket, grad_norms, slot, color_only, objects_dc)
 
 
 def _wants_backward(*tensors) -> bool:
@@ -1276,14 +1337,17 @@ def rasterize_gaussians_raw2(params_a, params_b, raster_settings, objects: bool 
 
 
 @torch.no_grad()
-def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Optional["RenderCache"] = None, cache_key=None):
+def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Optional["RenderCache"] = None, cache_key=None,
+                                   objects_dc=None):
     """rasterize_gaussians_raw2 for a BATCH of views through one launch chain (gsr_forward_raw2_batch): the success renders
     of a batch of cameras (reference attack.py:513-530 renders the combined scene once per camera).  `params_*`: (xyz,
     features_dc, features_rest, opacity, scaling, rotation), RAW tensors, both non-empty.  -> (color[B,3,H,W],
     radii[B,Pa+Pb]); every image bit for bit rasterize_gaussians_raw2's for that view.  No object channels, not
     differentiable.  With a cache the batch's context is kept: while both models' geometry and the cameras are unchanged a
     render is the batch's colour kernel -- over the first model's Gaussians only while the second model's coefficient
-    tensors are untouched -- and one compositor launch."""
+    tensors are untouched -- and one compositor launch.
+    objects_dc = (objects_dc_a [Pa,16], objects_dc_b [Pb,16]) (gsr_forward_raw2_batch_obj): -> (color, radii,
+    objects[B,16,H,W]), every object map bit for bit rasterize_gaussians_raw2's for that view."""
     lib = _load()
     xa = params_a[0]
     if not xa.is_cuda:
@@ -1300,19 +1364,28 @@ def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Opt
     for P, (x, dc, rest, op, sc, ro) in ((Pa, a), (Pb, b)):
         if tuple(dc.shape) != (P, 1, 3) or tuple(rest.shape) != (P, 15, 3):
             raise ValueError("fused path needs _features_dc [P,1,3] and _features_rest [P,15,3] (SH degree 3 storage)")
+    with_obj = objects_dc is not None
+    oa = ob = None
+    if with_obj:
+        oa, ob = (_f32c(t.detach(), device) for t in objects_dc)
+        if oa.numel() != Pa * NUM_OBJECTS or ob.numel() != Pb * NUM_OBJECTS:
+            raise ValueError(f"objects_dc must hold Pa*{NUM_OBJECTS} and Pb*{NUM_OBJECTS} values")
     H, W = int(settings_list[0].image_height), int(settings_list[0].image_width)
     packs = [_SettingsPack(rs, device) for rs in settings_list]
     carr = (_CSettings * B)()
     for v, pk in enumerate(packs):
         carr[v] = pk.c
     color = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
+    objs = torch.empty(B, NUM_OBJECTS, H, W, dtype=torch.float32, device=device) if with_obj else None
     nren = ctypes.c_int64(0)
     entry = sig = refs = None
     if cache is not None:
         geo = tuple(params_a[i] for i in (0, 3, 4, 5)) + tuple(params_b[i] for i in (0, 3, 4, 5))
         used = (a[0], a[3], a[4], a[5], b[0], b[3], b[4], b[5])
+        if with_obj:                                # (the context reads the object features through the forward's pointers)
+            geo, used = geo + tuple(objects_dc), used + (oa, ob)
         if all(t.data_ptr() == u.data_ptr() for t, u in zip(geo, used)):
-            extra = ["pair-batch", B]
+            extra = ["pair-batch", B] + (["obj"] if with_obj else [])
             for rs in settings_list[1:]:
                 extra += [float(rs.tanfovx), float(rs.tanfovy)]
                 for t in (rs.viewmatrix, rs.projmatrix, rs.campos):
@@ -1336,13 +1409,13 @@ def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Opt
             # the second model is the frozen background: while its coefficient tensors are those of the entry's last render,
             # unmodified, the colour kernel covers the first model's Gaussians only
             if b_sig is not None and bp.b_sig == b_sig:
-                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(a[1]), _ptr(a[2]), None, None, _ptr(bgt), _ptr(color), None,
-                                          1 | 2, stream)
+                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(a[1]), _ptr(a[2]), None, None, _ptr(bgt), _ptr(color),
+                                          _ptr(objs), 1 | 2, stream)
             else:
                 rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(a[1]), _ptr(a[2]), _ptr(b[1]), _ptr(b[2]), _ptr(bgt),
-                                          _ptr(color), None, 1, stream)
+                                          _ptr(color), _ptr(objs), 1, stream)
             bp.b_sig = b_sig
-            bp.last_inputs = (a, b, packs)             # read on the stream: referenced until the next render
+            bp.last_inputs = (a, b, packs, oa, ob)     # read on the stream: referenced until the next render
             entry.gen += 1
             if rc == GSR_ERR_OVERFLOW:
                 cache.entries.pop(cache_key, None)
@@ -1351,18 +1424,26 @@ def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Opt
         if entry is None:
             radii = torch.empty(B, Pa + Pb, dtype=torch.int32, device=device)
             handle = ctypes.c_void_p(None)
-            rc = lib.gsr_forward_raw2_batch(carr, B, Pa, *[_ptr(t) for t in a], Pb, *[_ptr(t) for t in b], _ptr(color),
-                                            _ptr(radii), ctypes.byref(handle) if sig is not None else None, ctypes.byref(nren),
-                                            stream)
+            if with_obj:
+                rc = lib.gsr_forward_raw2_batch_obj(carr, B, Pa, *[_ptr(t) for t in a[:3]], _ptr(oa), *[_ptr(t) for t in a[3:]],
+                                                    Pb, *[_ptr(t) for t in b[:3]], _ptr(ob), *[_ptr(t) for t in b[3:]],
+                                                    _ptr(color), _ptr(objs), _ptr(radii),
+                                                    ctypes.byref(handle) if sig is not None else None, ctypes.byref(nren), stream)
+            else:
+                rc = lib.gsr_forward_raw2_batch(carr, B, Pa, *[_ptr(t) for t in a], Pb, *[_ptr(t) for t in b], _ptr(color),
+                                                _ptr(radii), ctypes.byref(handle) if sig is not None else None,
+                                                ctypes.byref(nren), stream)
             if rc == 0 and handle.value:
                 bp = _BatchPack(packs, radii)
-                bp.b_sig, bp.last_inputs = b_sig, (a, b, packs)
+                bp.b_sig, bp.last_inputs = b_sig, (a, b, packs, oa, ob)
                 entry = _CacheEntry(_CtxHolder(lib, handle), sig, tuple(weakref.ref(t) for t in refs), bp, nren.value)
                 cache._store(cache_key, entry)
         if entry is not None and rc == 0:
             _entry_leave(entry, device)
     if rc != 0:
         raise (Exception if rc == 1 else PairCapacityExceeded if rc == GSR_ERR_OVERFLOW else RuntimeError)(_err(lib))
+    if with_obj:
+        return color, radii, objs
     return color, radii
 
 

@@ -209,16 +209,23 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     return _result(image, screenspace_points, radii, objects)
 
 
-def can_batch(cameras, pc, pipe, override_color=None) -> bool:
-    """True when render_batch() can take `cameras` through one launch chain: the fused raw-parameter path, no object
-    channels, one image size, at most MAX_BATCH views."""
+def _has_objects(pc) -> bool:
+    """The model carries the reference's object features: P x 16 floats in _objects_dc."""
+    o = getattr(pc, "_objects_dc", None)
+    return o is not None and o.numel() == 16 * int(pc._xyz.shape[0]) and int(pc._xyz.shape[0]) > 0
+
+
+def can_batch(cameras, pc, pipe, override_color=None, objects=False) -> bool:
+    """True when render_batch() can take `cameras` through one launch chain: the fused raw-parameter path, one image size,
+    at most MAX_BATCH views, and either no object channels (pipe.skip_objects) or -- objects=True -- the model's P x 16
+    object features composited as well."""
     cams = list(cameras)
     return bool(1 <= len(cams) <= MAX_BATCH and takes_fused_path(pc, pipe, override_color)
-                and bool(getattr(pipe, "skip_objects", False))
+                and (_has_objects(pc) if objects else bool(getattr(pipe, "skip_objects", False)))
                 and len({(int(c.image_height), int(c.image_width)) for c in cams}) == 1)
 
 
-def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0):
+def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, objects=False):
     """render() of a BATCH of cameras of one model through ONE launch chain (gsr_forward_raw_batch).  The reference's batch is
     a Python loop of render() calls whose backward passes add up in .grad (attack.py:476-494); here the B views are one
     virtual scene: one scan, one depth sort, one emission, one tile sort, one schedule, one forward and one backward
@@ -228,11 +235,16 @@ def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0
     broadcast zero (no object channels: needs pipe.skip_objects).  Every image and radius is bit for bit render()'s for that
     camera; the gradients are those of the B render() calls summed in view order.  With pipe.render_cache (a RenderCache)
     the batch's context is kept under the tuple of cameras: a later batch of the same cameras whose geometry tensors are
-    unchanged (a colour attack) runs the batch's colour kernel and one compositor launch over the kept lists."""
+    unchanged (a colour attack) runs the batch's colour kernel and one compositor launch over the kept lists.
+    objects=True: the model's _objects_dc (P x 16) is composited as well, whatever pipe.skip_objects says: render_object is
+    the [B,16,H,W] object map, every view's bit for bit render()'s with object channels, and _objects_dc.grad receives the
+    single-view object gradients summed in view order."""
     cams = list(cameras)
-    if not can_batch(cams, pc, pipe):
-        raise ValueError("render_batch needs the fused raw-parameter path without object channels (PipelineParams("
-                         f"skip_objects=True)), one image size and 1..{MAX_BATCH} cameras")
+    if objects and not _has_objects(pc):
+        raise ValueError("render_batch(objects=True) needs a model with P x 16 object features (_objects_dc)")
+    if not can_batch(cams, pc, pipe, objects=objects):
+        raise ValueError("render_batch needs the fused raw-parameter path, object channels asked for explicitly (objects=True) "
+                         f"or none (PipelineParams(skip_objects=True)), one image size and 1..{MAX_BATCH} cameras")
     B, P = len(cams), int(pc.get_xyz.shape[0])
     want_vs = bool(getattr(pipe, "viewspace_grad", True))
     # one zero leaf [B,P,3] (no allocation per call: _zero_points keeps one zero buffer per shape)
@@ -241,13 +253,18 @@ def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0
     bucket = getattr(pipe, "grad_bucket", None)
     if callable(bucket):
         bucket = bucket()
-    image, radii = rasterize_gaussians_raw_batch(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
-                                                 pc._scaling, pc._rotation, sts, grad_bucket=bucket,
-                                                 grad_norms=getattr(pipe, "grad_norms", None),
-                                                 cache=getattr(pipe, "render_cache", None),
-                                                 cache_key=(getattr(pipe, "cache_tag", "view"), "batch") + tuple(id(c) for c in cams))
-    objects = _zero_scalar(image.device).unsqueeze(0).expand(B, 16, image.shape[2], image.shape[3])
-    return _result(image, screenspace_points, radii, objects)
+    key = (getattr(pipe, "cache_tag", "view"), "batch-obj" if objects else "batch") + tuple(id(c) for c in cams)
+    out = rasterize_gaussians_raw_batch(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
+                                        pc._scaling, pc._rotation, sts, grad_bucket=bucket,
+                                        grad_norms=getattr(pipe, "grad_norms", None),
+                                        cache=getattr(pipe, "render_cache", None), cache_key=key,
+                                        objects_dc=pc._objects_dc if objects else None)
+    if objects:
+        image, radii, obj_map = out
+    else:
+        image, radii = out
+        obj_map = _zero_scalar(image.device).unsqueeze(0).expand(B, 16, image.shape[2], image.shape[3])
+    return _result(image, screenspace_points, radii, obj_map)
 
 
 @torch.no_grad()
@@ -270,22 +287,59 @@ def render_pair(viewpoint_camera, pc_a, pc_b, pipe, bg_color: torch.Tensor, scal
 
 
 @torch.no_grad()
-def render_pair_batch(cameras, pc_a, pc_b, pipe, bg_color: torch.Tensor, scaling_modifier=1.0):
+def render_pair_batch(cameras, pc_a, pc_b, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, objects=False):
     """render_pair() of a BATCH of cameras through one launch chain (gsr_forward_raw2_batch): the success renders of the
     attack's batch (reference attack.py:513-530, once per camera of :476-485).  -> dict with a leading view axis like
     render_batch()'s, `viewspace_points` None; every image bit for bit render_pair()'s for that camera.  Needs
-    pipe.skip_objects (no object channels in a batch), one image size, 1..MAX_BATCH cameras."""
+    pipe.skip_objects (no object channels) or objects=True (both models' P x 16 object features composited: render_object
+    [B,16,H,W], bit for bit render_pair()'s with object channels), one image size, 1..MAX_BATCH cameras."""
     cams = list(cameras)
     if not (_has_raw_layout(pc_a) and _has_raw_layout(pc_b)):
         raise ValueError("render_pair_batch needs two models in the reference's raw storage layout on a HIP device")
-    if not can_batch(cams, pc_a, pipe):
-        raise ValueError("render_pair_batch needs PipelineParams(skip_objects=True), one image size and "
+    if objects and not (_has_objects(pc_a) and _has_objects(pc_b)):
+        raise ValueError("render_pair_batch(objects=True) needs two models with P x 16 object features (_objects_dc)")
+    if not can_batch(cams, pc_a, pipe, objects=objects):
+        raise ValueError("render_pair_batch needs PipelineParams(skip_objects=True) or objects=True, one image size and "
                          f"1..{MAX_BATCH} cameras")
     sts = [_settings(cam, pc_a, pipe, bg_color, scaling_modifier) for cam in cams]
 
     def raw(pc):
         return (pc._xyz, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation)
-    image, radii = rasterize_gaussians_raw2_batch(raw(pc_a), raw(pc_b), sts, cache=getattr(pipe, "render_cache", None),
-                                                  cache_key=("pair", "batch") + tuple(id(c) for c in cams))
-    objects = _zero_scalar(image.device).unsqueeze(0).expand(len(cams), 16, image.shape[2], image.shape[3])
-    return _result(image, None, radii, objects)
+    out = rasterize_gaussians_raw2_batch(raw(pc_a), raw(pc_b), sts, cache=getattr(pipe, "render_cache", None),
+                                         cache_key=("pair", "batch-obj" if objects else "batch") + tuple(id(c) for c in cams),
+                                         objects_dc=(pc_a._objects_dc, pc_b._objects_dc) if objects else None)
+    if objects:
+        image, radii, obj_map = out
+    else:
+        image, radii = out
+        obj_map = _zero_scalar(image.device).unsqueeze(0).expand(len(cams), 16, image.shape[2], image.shape[3])
+    return _result(image, None, radii, obj_map)
+
+
+@torch.no_grad()
+def render_views(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, max_batch=MAX_BATCH):
+    """render() of every camera of a set, forward only, with the object map: the reference's evaluation loop (render.py:
+    125-131 renders each view and hands render_object to the object classifier) through as few launch chains as possible.
+    Consecutive cameras of one image size are grouped into batches of at most `max_batch` and rendered by
+    render_batch(objects=True); a group that cannot batch (no fused path, no object features) is rendered camera by camera
+    with render().  -> one render()-shaped dict per camera, in input order; every image, radius and object map is bit for
+    bit render()'s for that camera with object channels."""
+    cams = list(cameras)
+    max_batch = max(1, min(int(max_batch), MAX_BATCH))
+    want_vs = bool(getattr(pipe, "viewspace_grad", True))
+    out = []
+    i = 0
+    while i < len(cams):
+        size = (int(cams[i].image_height), int(cams[i].image_width))
+        j = i + 1
+        while j < len(cams) and j - i < max_batch and (int(cams[j].image_height), int(cams[j].image_width)) == size:
+            j += 1
+        group = cams[i:j]
+        if can_batch(group, pc, pipe, objects=True):
+            r = render_batch(group, pc, pipe, bg_color, scaling_modifier, objects=True)
+            for v in range(len(group)):
+                out.append(_result(r["render"][v], _zero_points(pc.get_xyz, want_vs), r["radii"][v], r["render_object"][v]))
+        else:
+            out.extend(render(c, pc, pipe, bg_color, scaling_modifier) for c in group)
+        i = j
+    return out

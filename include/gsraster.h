@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define GSR_VERSION 601 /* 0.6.1: the batch entry points, gsr_pgd_step_multi; + gsr_forward_raw2_batch, gsr_ctx_rerender on batch contexts */
+#define GSR_VERSION 602 /* 0.6.2: the batch entry points with object channels (gsr_*_batch_obj*); 0.6.1: the batch entry points, gsr_pgd_step_multi, gsr_forward_raw2_batch, gsr_ctx_rerender on batch contexts */
 #define GSR_NUM_OBJECTS 16 /* object-feature channels, reference scene/gaussian_model.py:52 */
 
 enum {
@@ -242,6 +242,44 @@ int gsr_backward_raw_batch_views(GsrCtx* ctx, const float* grad_color, float* dx
                                  float* dfeatures_rest, float* dopacity_logit, float* dlog_scaling, float* drotation_raw,
                                  int64_t view_stride, void* stream);
 
+/* The batch entry points WITH the 16 object channels (the map the reference's render() returns as render_object and its
+ * evaluation loop hands to the object classifier, reference render.py:125-131).  Same checks as gsr_forward_raw_batch
+ * (messages name the function), plus objects_dc [P,16] non-NULL.
+ *   out_objects  [B,16,H,W], or NULL: no object map; as in gsr_forward_raw the features are then kept for the backward only
+ *                under GSR_FLAG_OBJECTS_FOR_BACKWARD_ONLY
+ * Every view's image, radii and object map are bit for bit those of gsr_forward_raw with objects_dc on that view's settings.
+ * gsr_backward_raw_batch_obj_into: as gsr_backward_raw_batch_into, plus grad_objects [B,16,H,W] or NULL and dobjects_dc
+ * [P,16] or NULL.  dobjects_dc is always OVERWRITTEN (like gsr_backward_raw's, it is not part of the 59-float bucket and
+ * ignores `accumulate`) with ((s_0 + s_1) + s_2) + ..., s_v the object gradient gsr_backward_raw on view v alone writes: bit
+ * for bit what .grad of the object features holds after B single-view backwards in view order (zeros for a Gaussian no view
+ * sees).  With grad_objects the backward composite walks whole tile lists (as a single view given dL/dobjects does);
+ * without it, it is the segmented composite of gsr_backward_raw_batch_into, and the 59 gradients are the same bits as the
+ * no-object batch's.
+ * gsr_backward_raw_batch_obj_views: as gsr_backward_raw_batch_views, plus grad_objects and dobjects_dc [B,P,16]: view v's
+ * s_v at dobjects_dc + v * 16 P.
+ * gsr_forward_raw2_batch_obj: gsr_forward_raw2_batch with objects_dc_a [Pa,16] / objects_dc_b [Pb,16] (both or neither) and
+ * out_objects [B,16,H,W] or NULL; every object map bit for bit gsr_forward_raw2's for that view.
+ * gsr_ctx_rerender on a context of these forwards takes out_objects [B,16,H,W] when the forward composited object channels. */
+int gsr_forward_raw_batch_obj(const GsrSettings* settings, int32_t B, int32_t P, const float* xyz, const float* features_dc,
+                              const float* features_rest, const float* objects_dc, const float* opacity_logit,
+                              const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
+                              int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, void* stream);
+int gsr_forward_raw2_batch_obj(const GsrSettings* settings, int32_t B, int32_t Pa, const float* xyz_a,
+                               const float* features_dc_a, const float* features_rest_a, const float* objects_dc_a,
+                               const float* opacity_logit_a, const float* log_scaling_a, const float* rotation_raw_a, int32_t Pb,
+                               const float* xyz_b, const float* features_dc_b, const float* features_rest_b,
+                               const float* objects_dc_b, const float* opacity_logit_b, const float* log_scaling_b,
+                               const float* rotation_raw_b, float* out_color, float* out_objects, int32_t* radii,
+                               GsrCtx** ctx_out, int64_t* num_rendered, void* stream);
+int gsr_backward_raw_batch_obj_into(GsrCtx* ctx, const float* grad_color, const float* grad_objects, float* dxyz,
+                                    float* dmeans2D, float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc,
+                                    float* dopacity_logit, float* dlog_scaling, float* drotation_raw, int32_t accumulate,
+                                    void* stream);
+int gsr_backward_raw_batch_obj_views(GsrCtx* ctx, const float* grad_color, const float* grad_objects, float* dxyz,
+                                     float* dmeans2D, float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc,
+                                     float* dopacity_logit, float* dlog_scaling, float* drotation_raw, int64_t view_stride,
+                                     void* stream);
+
 /* Forward-only render of TWO parameter sets as one scene: the attacked target (a) followed by the frozen background (b),
  * Gaussians numbered a then b (radii [Pa+Pb]).  Replaces what the reference does after every PGD step to check the
  * attack: deep-copy the attacked model, append the background to each of its seven tensors (seven concat_setup calls,
@@ -304,7 +342,8 @@ int gsr_forward_raw2_batch(const GsrSettings* settings, int32_t B, int32_t Pa, c
  *                  changed since the context's last render (the frozen background of reference attack.py:513-530): the
  *                  colour kernel covers the first segment's Gaussians only; features_*_b must be NULL.
  * A BATCH context (gsr_forward_raw_batch): out_color [B,3,H,W]; bg [B,3] (view v's background at bg + 3 v) or NULL = the
- *                  views' previous background pointers, whose contents are read again; out_objects must be NULL
+ *                  views' previous background pointers, whose contents are read again; out_objects [B,16,H,W] if the
+ *                  forward composited object channels (gsr_*_batch_obj), else NULL
  *                  (features_*_b and GSR_RERENDER_FIRST_SEGMENT_ONLY as above for a gsr_forward_raw2_batch context).  One launch of the batch's colour kernel (every SH row read once for all views that see the
  *                  Gaussian) and one compositor launch over the B views' kept lists: images and the gradients of a following
  *                  gsr_backward_raw_batch_* are bit for bit those of a fresh gsr_forward_raw_batch with the same inputs.
