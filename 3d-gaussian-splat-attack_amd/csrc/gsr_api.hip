@@ -25,6 +25,8 @@
 #include "gsr_sort.hip.h"
 #include "gsr_knn.hip.h"
 #include "gsr_pgd.hip.h"
+#include "gsr_groups.hip.h"
+#include "gsr_hull.h"
 
 using namespace gsr;
 
@@ -1902,6 +1904,76 @@ int gsr_knn_dist2(const float* points, int32_t P, float* mean_dist2, void* strea
   hipLaunchKernelGGL(k_knn_search, dim3((n + 255) / 256), dim3(256), 0, st, points, P, g, sidx, cell_range, mean_dist2);
   pool_free(dev, blk);
   LAUNCH_CHECK("knn");
+  return GSR_OK;
+}
+
+int gsr_group_classify(const float* objects, int32_t P, const float* W, const float* b, int32_t C, const int32_t* ids,
+                       int32_t nids, float thresh, float* psel, uint8_t* mask, void* stream) {
+  if (P < 0) return set_err(GSR_ERR_INVALID, "gsr_group_classify: P=%d", P);
+  if (C < 1 || C > GROUP_MAX_CLASSES) return set_err(GSR_ERR_INVALID, "gsr_group_classify: C=%d classes (1..%d)", C, GROUP_MAX_CLASSES);
+  if (!ids || nids < 1 || nids > C) return set_err(GSR_ERR_INVALID, "gsr_group_classify: %d selected ids (1..C=%d, host array)", nids, C);
+  if (!std::isfinite(thresh)) return set_err(GSR_ERR_INVALID, "gsr_group_classify: threshold is not finite");
+  GroupSel sel;
+  memset(&sel, 0, sizeof(sel));
+  for (int32_t k = 0; k < nids; ++k) {
+    const int32_t c = ids[k];
+    if (c < 0 || c >= C) return set_err(GSR_ERR_INVALID, "gsr_group_classify: id %d outside [0, %d)", c, C);
+    if ((sel.bits[c >> 5] >> (c & 31)) & 1u) return set_err(GSR_ERR_INVALID, "gsr_group_classify: duplicate id %d", c);
+    sel.bits[c >> 5] |= 1u << (c & 31);
+  }
+  if (P == 0) return GSR_OK;
+  if (!objects || !W || !b || !psel || !mask) return set_err(GSR_ERR_INVALID, "gsr_group_classify: null argument");
+  if (((uintptr_t)objects & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_group_classify: objects must be 16-byte aligned");
+  hipLaunchKernelGGL(k_group_classify, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     objects, P, W, b, C, sel, thresh, psel, mask);
+  LAUNCH_CHECK("gsr_group_classify");
+  return GSR_OK;
+}
+
+int gsr_convex_hull_planes(const double* pts, int64_t M, double* planes, int64_t max_facets, int64_t* nfacets, double* bbox) {
+  if (!nfacets || !bbox) return set_err(GSR_ERR_INVALID, "gsr_convex_hull_planes: null nfacets / bbox");
+  *nfacets = 0;
+  for (int a = 0; a < 6; ++a) bbox[a] = 0.0;
+  if (M < 0 || max_facets < 0) return set_err(GSR_ERR_INVALID, "gsr_convex_hull_planes: M=%lld max_facets=%lld", (long long)M,
+                                              (long long)max_facets);
+  if (M > 0 && !pts) return set_err(GSR_ERR_INVALID, "gsr_convex_hull_planes: null points");
+  if (max_facets > 0 && !planes) return set_err(GSR_ERR_INVALID, "gsr_convex_hull_planes: null planes");
+  gsr_hull::Result r;
+  try {
+    r = gsr_hull::convex_hull(pts, M);
+  } catch (const std::bad_alloc&) {
+    return set_err(GSR_ERR_NOMEM, "gsr_convex_hull_planes: host allocation failed (M=%lld)", (long long)M);
+  }
+  if (M > 0)
+    for (int a = 0; a < 6; ++a) bbox[a] = r.bbox[a];
+  switch (r.status) {
+    case gsr_hull::HULL_DEGENERATE: set_err(GSR_OK, "gsr_convex_hull_planes: degenerate point set (M=%lld)", (long long)M); return GSR_OK;
+    case gsr_hull::HULL_CHECK_FAILED:
+      return set_err(GSR_ERR_HULL, "gsr_convex_hull_planes: self-check failed: a point lies %.3e beyond a plane, tau %.3e",
+                     r.worst, r.tau);
+    case gsr_hull::HULL_OK: break;
+    default: return set_err(GSR_ERR_HULL, "gsr_convex_hull_planes: the construction lost its topology (M=%lld)", (long long)M);
+  }
+  *nfacets = (int64_t)r.planes.size();
+  if (*nfacets > max_facets)
+    return set_err(GSR_ERR_NOMEM, "gsr_convex_hull_planes: %lld facets, room for %lld", (long long)*nfacets, (long long)max_facets);
+  for (size_t f = 0; f < r.planes.size(); ++f) {
+    planes[4 * f] = r.planes[f].nx; planes[4 * f + 1] = r.planes[f].ny;
+    planes[4 * f + 2] = r.planes[f].nz; planes[4 * f + 3] = r.planes[f].c;
+  }
+  return GSR_OK;
+}
+
+int gsr_points_in_hull(const float* xyz, int32_t P, const double* planes, int32_t F, const double* bbox, double tau,
+                       const uint8_t* mask_in, uint8_t* out, void* stream) {
+  if (P < 0 || F < 0) return set_err(GSR_ERR_INVALID, "gsr_points_in_hull: P=%d F=%d", P, F);
+  if (!(tau >= 0.0) || !std::isfinite(tau)) return set_err(GSR_ERR_INVALID, "gsr_points_in_hull: tau must be finite and >= 0");
+  if (P == 0) return GSR_OK;
+  if (!xyz || !out || !bbox || (F > 0 && !planes)) return set_err(GSR_ERR_INVALID, "gsr_points_in_hull: null argument");
+  if (F > 0 && ((uintptr_t)planes & 31) != 0) return set_err(GSR_ERR_INVALID, "gsr_points_in_hull: planes must be 32-byte aligned");
+  hipLaunchKernelGGL(k_points_in_hull, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     xyz, P, reinterpret_cast<const double4*>(planes), F, bbox, tau, mask_in, out);
+  LAUNCH_CHECK("gsr_points_in_hull");
   return GSR_OK;
 }
 

@@ -638,6 +638,13 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.5)
     ap.add_argument("--epsilon", type=float, default=5.0)
     ap.add_argument("--streams", type=int, default=4, help="HIP streams the rank's views are pipelined over")
+    ap.add_argument("--select-ids", default=None,
+                    help="groups mode: comma list of object ids; only the Gaussians of these objects (and those inside "
+                         "their convex hull) are attacked, the rest of the scene is the frozen background")
+    ap.add_argument("--select-thresh", type=float, default=0.5, help="groups mode: softmax probability threshold")
+    ap.add_argument("--classifier", default=None,
+                    help="groups mode: Conv2d(16, C, 1) state dict (classifier.pth); without it the Gaussians in the middle "
+                         "of the synthetic scene are labelled with the first id (scenes.synthetic_grouping)")
     args = ap.parse_args()
     from .scenes import make_scene
     rank, world, local = gdist.init_from_env()
@@ -645,14 +652,29 @@ def main():
     torch.cuda.set_device(local)
     model, cams, spec = make_scene(args.scene, device=dev, P=args.P, width=args.width, height=args.height,
                                    n_views=max(args.views, 1))
+    extra, background = {}, None
+    if args.select_ids is not None:
+        from .groups import select_group, split_group
+        ids = [int(x) for x in args.select_ids.split(",") if x.strip()]
+        classifier = args.classifier
+        if classifier is None:
+            from .scenes import synthetic_grouping
+            xyz = model._xyz.detach()
+            lo, hi = xyz.amin(dim=0), xyz.amax(dim=0)
+            mid, half = (lo + hi) * 0.5, (hi - lo) * 0.125
+            classifier = synthetic_grouping(model, ((xyz - mid).abs() <= half).all(dim=1), ids[0])
+        mask3d, info = select_group(model, classifier, ids, select_thresh=args.select_thresh)
+        model, background = split_group(model, mask3d)
+        extra = {"select": info}
     recs = []
     hist = pgd_attack(model, cams[:args.views], iters=args.iters, alpha=args.alpha, epsilon=args.epsilon,
-                      groups=args.groups.split(","), norm=args.norm, log=recs.append, streams=args.streams)
+                      groups=args.groups.split(","), norm=args.norm, log=recs.append, streams=args.streams,
+                      background=background)
     if rank == 0:
         secs = [r["seconds"] for r in recs[2:]] or [r["seconds"] for r in recs]
         print(json.dumps({"scene": spec.name, "P": int(model.get_xyz.shape[0]), "views": args.views, "gpus": world,
                           "iters": args.iters, "groups": args.groups, "loss_first": hist[0], "loss_last": hist[-1],
-                          "s_per_pgd_iter": sum(secs) / len(secs)}))
+                          "s_per_pgd_iter": sum(secs) / len(secs), **extra}))
 
 
 if __name__ == "__main__":

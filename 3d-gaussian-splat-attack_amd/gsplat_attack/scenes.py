@@ -157,3 +157,26 @@ def make_scene(key: str, device="cpu", P: int | None = None, width: int | None =
         raise KeyError(key)
     model = GaussianModel.from_tensors(**attrs, device=device)
     return model, cams, spec
+
+
+def synthetic_grouping(model: GaussianModel, rows, class_id: int, num_classes: int = 256, seed: int = 0):
+    """A Gaussian-Grouping stand-in for the groups set-up (gsplat_attack.groups): the object features of `rows` (an index
+    tensor or a [P] bool mask) are overwritten IN PLACE with one class prototype, and the returned Conv2d(16, C, 1) state
+    dict (``weight`` [C,16,1,1], ``bias`` [C], the reference's classifier.pth layout) maps that prototype to `class_id`
+    with probability 1 - O(C e^-20) and every other feature vector of the synthetic scenes (N(0, 0.5^2) per channel) to
+    `class_id` with a probability below e^-5.  Its own generator: the scene keys' tensors and RNG streams are untouched."""
+    if not 0 <= class_id < num_classes:
+        raise ValueError(f"synthetic_grouping: class_id {class_id} outside [0, {num_classes})")
+    g = torch.Generator().manual_seed(seed)
+    u = torch.randn(NUM_OBJECTS, generator=g, dtype=torch.float64)
+    u = u / u.norm()
+    proto = (8.0 * u).float()                                    # |proto| = 8; a scene feature row has norm ~2
+    weight = torch.randn(num_classes, NUM_OBJECTS, generator=g) * 0.05
+    bias = torch.zeros(num_classes)
+    weight[class_id] = (5.0 * u).float()                         # prototype: 5 * 8 - 20 = 20; u . f ~ N(0, 0.25) elsewhere
+    bias[class_id] = -20.0
+    with torch.no_grad():
+        obj = model._objects_dc
+        idx = rows.to(obj.device)
+        obj[idx] = proto.to(obj.device).view(1, 1, NUM_OBJECTS)
+    return {"weight": weight.view(num_classes, NUM_OBJECTS, 1, 1).contiguous(), "bias": bias}

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define GSR_VERSION 602 /* 0.6.2: the batch entry points with object channels (gsr_*_batch_obj*); 0.6.1: the batch entry points, gsr_pgd_step_multi, gsr_forward_raw2_batch, gsr_ctx_rerender on batch contexts */
+#define GSR_VERSION 603 /* 0.6.3: the groups set-up (gsr_group_classify, gsr_convex_hull_planes, gsr_points_in_hull); 0.6.2: the batch entry points with object channels (gsr_*_batch_obj*); 0.6.1: the batch entry points, gsr_pgd_step_multi, gsr_forward_raw2_batch, gsr_ctx_rerender on batch contexts */
 #define GSR_NUM_OBJECTS 16 /* object-feature channels, reference scene/gaussian_model.py:52 */
 
 enum {
@@ -53,7 +53,8 @@ enum {
   GSR_ERR_DEVICE = 2,   /* a HIP call failed (message names the stage) */
   GSR_ERR_NOMEM = 3,
   GSR_ERR_STATE = 4,    /* e.g. backward called twice on a released context */
-  GSR_ERR_OVERFLOW = 5  /* GSR_FLAG_ASYNC_COUNT only: the forward emitted more pairs than the guessed capacity */
+  GSR_ERR_OVERFLOW = 5, /* GSR_FLAG_ASYNC_COUNT only: the forward emitted more pairs than the guessed capacity */
+  GSR_ERR_HULL = 6      /* gsr_convex_hull_planes: the hull failed its own check (no planes returned) */
 };
 
 /* flags */
@@ -404,6 +405,39 @@ int gsr_pgd_step_multi(int32_t n, float* const* x, const float* const* grad, con
  * points [P,3] float32 device, mean_dist2 [P] float32 device.  Synchronises the stream once (scene set-up routine, not
  * part of the per-view path).  With fewer than 4 points the missing neighbours count as FLT_MAX, like the original. */
 int gsr_knn_dist2(const float* points, int32_t P, float* mean_dist2, void* stream);
+
+/* ---- groups set-up (C ABI 603) -----------------------------------------------------------------------------------
+ * The reference's third way to set up an attack (attack.py:292-323): one Gaussian-Grouping scene, a 1x1-conv classifier
+ * over the 16 object features, and the Gaussians of the selected object ids -- plus every Gaussian inside the convex
+ * hull of those -- are the attacked group; the rest of the scene is the frozen background.  Semantics where the
+ * reference cannot run (its points_inside_convex_hull is not defined in attack.py): INTEGRATION.md, groups mode.
+ *
+ * gsr_group_classify: per Gaussian, psel[i] = max over the selected ids of softmax_c(b[c] + sum_k W[c,k] objects[i,k])
+ * and mask[i] = psel[i] > thresh, which is the reference's (softmax(logits)[ids] > thresh).any(0).  The logits are
+ * formed in double (k = 0..15 in order) and never stored: no [C,P] buffer.  objects [P,16] float32 (the [P,1,16]
+ * _objects_dc), W [C,16] float32 (a Conv2d(16, C, 1) weight), b [C] float32, psel [P] float32 and mask [P] uint8 are
+ * DEVICE pointers; ids [nids] int32 is a HOST array (checked before any device call): 1 <= C <= 1024, 1 <= nids <= C,
+ * every id in [0, C), no id twice.  Bitwise reproducible. */
+int gsr_group_classify(const float* objects, int32_t P, const float* W, const float* b, int32_t C, const int32_t* ids,
+                       int32_t nids, float thresh, float* psel, uint8_t* mask, void* stream);
+
+/* gsr_convex_hull_planes: HOST only (no device needed).  Quickhull in double over pts [M,3] (host, double): the hull's
+ * facets as planes[4 * f .. 4 * f + 3] = (nx, ny, nz, c) with a unit outward normal, so that x is inside iff
+ * n . x - c <= tau for every facet, tau = 1e-9 * D, D the diagonal of the points' bounding box; bbox[6] (host) = min
+ * xyz, max xyz of the points, always written (zeros for M = 0).  *nfacets = the number of facets; 0 with GSR_OK = a
+ * DEGENERATE point set (fewer than 4 points, or all within tau of a point, a line or a plane; Qhull raises there).
+ * Before it returns, every point is checked against every plane within tau; GSR_ERR_HULL if that fails, with no planes.
+ * More than max_facets facets: GSR_ERR_NOMEM, *nfacets = the number needed and nothing written to planes (call again
+ * with a buffer that size). */
+int gsr_convex_hull_planes(const double* pts, int64_t M, double* planes, int64_t max_facets, int64_t* nfacets, double* bbox);
+
+/* gsr_points_in_hull: per Gaussian, inside = xyz[i] lies within bbox grown by tau on every side AND
+ * n_f . xyz[i] - c_f <= tau for every facet f, evaluated in double as ((nx*x + ny*y) + nz*z) - c with every operation
+ * rounded on its own (bit for bit the host's evaluation).  xyz [P,3] float32, planes [F,4] double (from
+ * gsr_convex_hull_planes), bbox [6] double, mask_in [P] uint8 or NULL, out [P] uint8: DEVICE pointers.
+ * out[i] = inside, or (mask_in[i] != 0) | inside.  F = 0 (a degenerate hull): nothing is inside.  F >= 0, tau >= 0. */
+int gsr_points_in_hull(const float* xyz, int32_t P, const double* planes, int32_t F, const double* bbox, double tau,
+                       const uint8_t* mask_in, uint8_t* out, void* stream);
 
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info). */
