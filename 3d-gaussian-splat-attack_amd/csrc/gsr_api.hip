@@ -1496,7 +1496,7 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
       // asked for accumulation -- and the others adding; the per-view arrays of the virtual scene are offset by v * Ppad)
       if (batch_fused && ge > gb) {
         PreBwdBatchArgs ba;
-        ba.P = ge; ba.g0 = gb; ba.B = c->B; ba.Ppad = c->Ppad; ba.vpack = c->vpack;
+        ba.P = ge; ba.g0 = gb; ba.B = c->B; ba.Ppad = c->Ppad; ba.Pscene = P; ba.vpack = c->vpack;
         ba.H = c->st.image_height; ba.W = c->st.image_width; ba.deg = c->st.sh_degree; ba.mod = c->st.scale_modifier;
         ba.offg = c->offg; ba.G0 = c->G0; ba.G1 = c->G1; ba.G2 = c->G2; ba.part = part;
         ba.tag_lo = tag_lo; ba.tag_hi = tag_hi; ba.nsub = nsub;

@@ -2452,6 +2452,7 @@ __global__ void __launch_bounds__(256) k_obj_grad_batch(ObjGradBatchArgs a) {
 struct PreBwdBatchArgs {
   int P, g0;              // Gaussians [g0, P) (g0 a multiple of 64); block b owns g0 + 64 b ...
   int B, Ppad;
+  int Pscene;             // Gaussians of the scene: the view pitch of dmeans2D (P is the END of a chunked launch's range)
   const ViewDev* vpack;
   int H, W, deg;
   float mod;
@@ -2466,7 +2467,7 @@ struct PreBwdBatchArgs {
   const float* rots;      // raw: un-normalised quaternions
   const float* D;         // [B * Ppad, 9]
   float* dmeans3D;
-  float* dmeans2D;        // [B, P, 3] or null
+  float* dmeans2D;        // [B, Pscene, 3] or null
   float* dsh;             // gradient of _features_rest
   float* dsh_dc;          // gradient of _features_dc
   float* dopac;
@@ -2594,7 +2595,7 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
         const float dndcy = (float)(-((double)Bc * mx + (double)C * my) * (0.5 * (double)vw.H));
         const double dA = -0.5 * mxx, dB = -mxy, dC = -0.5 * myy;
         if (a.dmeans2D) {
-          float* m2 = a.dmeans2D + 3 * ((size_t)v * (size_t)a.P + (size_t)g);
+          float* m2 = a.dmeans2D + 3 * ((size_t)v * (size_t)a.Pscene + (size_t)g);
           m2[0] = dndcx; m2[1] = dndcy; m2[2] = 0.f;
         }
         dops += dop;
@@ -2617,7 +2618,7 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
         for (int i = 0; i < 6; ++i) dc6s[i] += dc6[i];
       }
     } else if (GEOM && mine && a.dmeans2D) {
-      float* m2 = a.dmeans2D + 3 * ((size_t)v * (size_t)a.P + (size_t)g);
+      float* m2 = a.dmeans2D + 3 * ((size_t)v * (size_t)a.Pscene + (size_t)g);
       m2[0] = 0.f; m2[1] = 0.f; m2[2] = 0.f;
     }
     float* hs = shrgb + ((size_t)v * 64 + lane) * 3;

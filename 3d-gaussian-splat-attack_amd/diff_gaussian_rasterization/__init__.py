@@ -331,7 +331,7 @@ def _zero_scalar(device):
     return z
 
 
-_OBJ_ZERO = {}        # data_ptr -> (numel, _version, all zero?) of object-feature tensors that have been looked at
+_OBJ_ZERO = {}        # data_ptr -> (numel, _version, all zero?, weakref to the tensor) of object-feature tensors looked at
 
 
 def _objects_all_zero(t: torch.Tensor, src: torch.Tensor) -> bool:
@@ -340,23 +340,31 @@ def _objects_all_zero(t: torch.Tensor, src: torch.Tensor) -> bool:
     forward compositor costs 0.27 ms against 0.16 at 1 M Gaussians / 1080p, plus 133 MB of output).  That is the attack's
     case: `combine_splats` gives every Gaussian of a combined scene zero object features (reference
     scene/gaussian_model.py:528), and the reference's render() passes them all the same (gaussian_renderer/__init__.py:81).
-    The answer is cached per storage and autograd version: one reduction and one host read the first time a tensor (version)
-    is seen.  A tensor found non-zero is not looked at again while it keeps its storage (a training loop that steps the
-    features every iteration never pays a second read); a zero one is re-checked when its version changes."""
+    The answer is cached per tensor object, storage and autograd version: one reduction and one host read the first time a
+    tensor (version) is seen.  A tensor found non-zero is not looked at again while it keeps its storage (a training loop
+    that steps the features every iteration never pays a second read); a zero one is re-checked when its version changes.
+    An entry is served to the very tensor object it was made for only (weak reference, as RenderCache holds its geometry):
+    the allocator hands a freed tensor's block to the next one of the same size, whose version starts at 0 again.
+    No shortcut (False) when `t` is a temporary copy of a strided or non-float32 `src` -- its address says nothing about
+    the caller's tensor -- and for an unseen tensor while the stream is being captured, where no host read is possible."""
     if not _OBJ_SHORTCUT:
         return False
     key = t.data_ptr()
+    if key != src.data_ptr():
+        return False
     ver = src._version
     hit = _OBJ_ZERO.get(key)
-    if hit is not None and hit[0] == t.numel():
+    if hit is not None and hit[0] == t.numel() and hit[3]() is src:
         if not hit[2]:
             return False                    # seen non-zero before: assume it still is
         if hit[1] == ver:
             return True
+    if t.is_cuda and torch.cuda.is_current_stream_capturing():
+        return False
     zero = not bool(torch.any(t != 0).item())
     if len(_OBJ_ZERO) > 256:
         _OBJ_ZERO.clear()
-    _OBJ_ZERO[key] = (t.numel(), ver, zero)
+    _OBJ_ZERO[key] = (t.numel(), ver, zero, weakref.ref(src))
     return zero
 
 

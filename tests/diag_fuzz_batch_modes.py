@@ -38,7 +38,8 @@ def yard(name, got, seq, exact):
 
 
 def loop_grads(model, cams, bgs, gcs, scale, start=None):
-    """Per-view single-view backward passes: (float32 accumulation in view order [from `start`], double sum [+ start])."""
+    """Per-view single-view backward passes: (float32 accumulation in view order [from `start`], double sum [+ start],
+    every view's screen-space gradient)."""
     import diff_gaussian_rasterization as D
     from gsplat_attack.renderer import PipelineParams, render
     P = int(model.get_xyz.shape[0])
@@ -49,12 +50,15 @@ def loop_grads(model, cams, bgs, gcs, scale, start=None):
         seq.flat.copy_(start)
         seq.fresh, seq.used = False, True
         exact += start.double()
+    vs = []
     for v, cam in enumerate(cams):
-        render(cam, model, PipelineParams(skip_objects=True, grad_bucket=seq), bgs[v], scale)["render"].backward(gcs[v])
+        out = render(cam, model, PipelineParams(skip_objects=True, grad_bucket=seq), bgs[v], scale)
+        out["render"].backward(gcs[v])
+        vs.append(out["viewspace_points"].grad.clone())
         own = D.GradBucket(P, dev)
         render(cam, model, PipelineParams(skip_objects=True, grad_bucket=own), bgs[v], scale)["render"].backward(gcs[v])
         exact += own.flat.double()
-    return seq, exact
+    return seq, exact, vs
 
 
 def batch_call(model, cams, bgs, gcs, scale, bucket=None, norms=None):
@@ -69,6 +73,13 @@ def batch_call(model, cams, bgs, gcs, scale, bucket=None, norms=None):
                                                model._scaling, model._rotation, sts, grad_bucket=bucket, grad_norms=norms)
     image.backward(torch.stack(gcs))
     torch.cuda.synchronize()
+    return vsp.grad
+
+
+def check_vsp(got, vs):
+    """viewspace_points.grad of the batch, view by view, bit for bit the single-view backward's."""
+    for v, ref in enumerate(vs):
+        assert torch.equal(got[v].view(torch.int32), ref.view(torch.int32)), f"view {v}: screen-space gradient differs"
 
 
 def one(seed, dev):
@@ -109,22 +120,22 @@ def one(seed, dev):
         return f"{desc} subset={'+'.join(pick)}"
     if mode == "accumulate":
         start = torch.randn(59 * P, generator=g).to(dev) * 3.0
-        seq, exact = loop_grads(model, cams, bgs, gcs, scale, start=start)
+        seq, exact, vs = loop_grads(model, cams, bgs, gcs, scale, start=start)
         b = D.GradBucket(P, dev)
         b.flat.copy_(start)
         b.fresh, b.used = False, True
-        batch_call(model, cams, bgs, gcs, scale, bucket=b)
+        check_vsp(batch_call(model, cams, bgs, gcs, scale, bucket=b), vs)
         for name, s1, s2, c0, c1 in zip(b.NAMES, seq.slices(), b.slices(), b.CUTS[:-1], b.CUTS[1:]):
             yard(name, s2, s1, exact[c0 * P:c1 * P])
         return f"{desc} accumulate"
     if mode == "chunks":
         k = int(torch.randint(2, 6, (), generator=g))
-        seq, exact = loop_grads(model, cams, bgs, gcs, scale)
+        seq, exact, vs = loop_grads(model, cams, bgs, gcs, scale)
         b = D.GradBucket(P, dev)
         b.flat.fill_(float("nan"))
         seen = []
         b.chunks, b.on_chunk = k, (lambda c, g0, g1: seen.append((c, g0, g1)))
-        batch_call(model, cams, bgs, gcs, scale, bucket=b)
+        check_vsp(batch_call(model, cams, bgs, gcs, scale, bucket=b), vs)
         assert torch.isfinite(b.flat).all(), "a float of the chunked batch's bucket was not written"
         if P > 0:
             assert seen and seen[0][1] == 0 and seen[-1][2] == P and all(a[2] == c[1] for a, c in zip(seen, seen[1:])), seen

@@ -67,3 +67,32 @@ def test_an_entry_waiting_for_its_backward_is_bypassed_and_lru_evicts():
     cache._lookup("k", "s", (t,))                                                   # k is now the most recently used
     cache._store("k3", _entry(D, "s", (t,)))
     assert list(cache.entries) == ["k", "k3"]                                       # k2 went
+
+
+def test_zero_object_cache_serves_only_the_tensor_it_was_made_for(monkeypatch):
+    """_objects_all_zero on CPU tensors: an entry left by a dead all-zero tensor, planted under a live non-zero tensor's
+    address with its size and version (what the allocator produces when it hands the block on), is not served; a temporary
+    copy (another address than the caller's tensor) is never cached; the live tensor's own entries still are."""
+    import diff_gaussian_rasterization as D
+    monkeypatch.setattr(D, "_OBJ_SHORTCUT", True)
+    D._OBJ_ZERO.clear()
+    a = torch.zeros(10, 16)
+    assert D._objects_all_zero(a, a) is True
+    entry = D._OBJ_ZERO[a.data_ptr()]
+    assert entry[:3] == (160, a._version, True)
+    del a
+    gc.collect()
+    b = torch.ones(10, 16)
+    assert b._version == entry[1]
+    D._OBJ_ZERO[b.data_ptr()] = entry
+    assert D._objects_all_zero(b, b) is False, "a dead tensor's entry was served to the tensor that got its address"
+    assert D._OBJ_ZERO[b.data_ptr()][2] is False                                   # ... and replaced by b's own
+    z = torch.zeros(10, 16)
+    assert D._objects_all_zero(z, z) is True and D._objects_all_zero(z, z) is True
+    z.add_(1.0)                                                                    # a zero tensor is re-checked when its version moves
+    assert D._objects_all_zero(z, z) is False
+    # a dense float32 temporary made from a float16 / strided source: no shortcut, nothing cached under its address
+    D._OBJ_ZERO.clear()
+    half = torch.zeros(10, 16, dtype=torch.float16)
+    tmp = half.float()
+    assert D._objects_all_zero(tmp, half) is False and not D._OBJ_ZERO
