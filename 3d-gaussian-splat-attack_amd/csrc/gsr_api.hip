@@ -494,7 +494,17 @@ struct GsrCtx {
   bool objects_out = false;       // the forward composited the 16 object channels
   bool D_stale = false;           // the last re-render skipped d colour / d direction: no geometry backward until the next
   double* sumsq_out = nullptr;    // gsr_ctx_request_sumsq: where the next overwrite-mode raw backward leaves its six sums of squares
+  // depth / alpha maps (gsr_forward*_aux): the forward wrote at least one of them; where (the caller's buffers, used by the
+  // forward's K6 launch only); the gradients gsr_ctx_set_aux_grads armed for the next backward
+  bool aux = false;
+  float *aux_depth_out = nullptr, *aux_alpha_out = nullptr;
+  const float *aux_gd = nullptr, *aux_ga = nullptr;
 };
+
+// The _aux entry points hand their two extra output pointers to forward_impl through this (per host thread; taken, and
+// cleared, at the top of forward_impl): the plain entry points' argument lists stay as they are.
+struct AuxOut { float* depth = nullptr; float* alpha = nullptr; };
+static thread_local AuxOut tl_aux_out;
 
 // Host copy of the forward's device-side scalars: waits for the (early) copy if it has not landed yet.
 static int ctx_resolve_count(GsrCtx* c) {
@@ -587,6 +597,8 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
   ra.bnd = c->bnd; ra.segoff = c->bnd ? c->segoff : nullptr; ra.seg_shift = c->bnd ? c->seg_shift : 0u;
   ra.out_color = out_color; ra.out_objects = out_objects; ra.final_T = c->final_T; ra.n_contrib = c->n_contrib;
   ra.tpv = c->tpv; ra.vpack = c->vpack; ra.Ppad = c->Ppad;
+  ra.out_depth = c->aux_depth_out; ra.out_alpha = c->aux_alpha_out;
+  const bool aux = ra.out_depth != nullptr || ra.out_alpha != nullptr;
   const dim3 blkT(64);
   // pixels per lane of K6: fewer = more, shorter waves per tile (see k_render_fwd); images with fewer tiles than
   // half the chip's wave slots are split down to one 16x4 strip per wave.  GSR_FLAG_FWD_SPLIT(n) overrides.
@@ -602,7 +614,13 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
   static const int k6_env = [] { const char* e = getenv("GSR_K6_SHARED"); return e ? atoi(e) : 0; }();
   const bool k6_shared = k6_env != 0 || (s->flags & GSR_FLAG_FWD_SHARED) != 0;
   const dim3 gridS(render_grid(ntiles)), blkS2(128), blkS4(256);
-  if (out_objects && sh_objs) {
+  if (aux && out_objects && sh_objs) {
+    if (fwd_npx == 4) hipLaunchKernelGGL((k_render_fwd<true, 4, 1, true>), gridT, blkT, 0, st, ra);
+    else if (fwd_npx == 2 && k6_shared) hipLaunchKernelGGL((k_render_fwd<true, 2, 2, true>), gridS, blkS2, 0, st, ra);
+    else if (fwd_npx == 2) hipLaunchKernelGGL((k_render_fwd<true, 2, 1, true>), gridT, blkT, 0, st, ra);
+    else if (k6_shared) hipLaunchKernelGGL((k_render_fwd<true, 1, 4, true>), gridS, blkS4, 0, st, ra);
+    else hipLaunchKernelGGL((k_render_fwd<true, 1, 1, true>), gridT, blkT, 0, st, ra);
+  } else if (out_objects && sh_objs) {
     if (fwd_npx == 4) hipLaunchKernelGGL((k_render_fwd<true, 4>), gridT, blkT, 0, st, ra);
     else if (fwd_npx == 2 && k6_shared) hipLaunchKernelGGL((k_render_fwd<true, 2, 2>), gridS, blkS2, 0, st, ra);
     else if (fwd_npx == 2) hipLaunchKernelGGL((k_render_fwd<true, 2>), gridT, blkT, 0, st, ra);
@@ -616,6 +634,13 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
         return set_err(GSR_ERR_DEVICE, "objects: %s", hipGetErrorString(e));
       }
     }
+    if (aux) {
+      if (fwd_npx == 4) hipLaunchKernelGGL((k_render_fwd<false, 4, 1, true>), gridT, blkT, 0, st, ra);
+      else if (fwd_npx == 2 && k6_shared) hipLaunchKernelGGL((k_render_fwd<false, 2, 2, true>), gridS, blkS2, 0, st, ra);
+      else if (fwd_npx == 2) hipLaunchKernelGGL((k_render_fwd<false, 2, 1, true>), gridT, blkT, 0, st, ra);
+      else if (k6_shared) hipLaunchKernelGGL((k_render_fwd<false, 1, 4, true>), gridS, blkS4, 0, st, ra);
+      else hipLaunchKernelGGL((k_render_fwd<false, 1, 1, true>), gridT, blkT, 0, st, ra);
+    } else
     if (fwd_npx == 4) hipLaunchKernelGGL((k_render_fwd<false, 4>), gridT, blkT, 0, st, ra);
     else if (fwd_npx == 2 && k6_shared) hipLaunchKernelGGL((k_render_fwd<false, 2, 2>), gridS, blkS2, 0, st, ra);
     else if (fwd_npx == 2) hipLaunchKernelGGL((k_render_fwd<false, 2>), gridT, blkT, 0, st, ra);
@@ -635,7 +660,14 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
                         float* out_objects, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, void* stream,
                         bool raw, const SegB* segb = nullptr, bool fwd_only = false, int nviews = 1) {
   // nviews > 1 (gsr_forward_raw_batch): `s` points at nviews settings; the batch is one virtual scene (GsrCtx::B)
+  const AuxOut aux_out = tl_aux_out;           // (one-shot, whatever this call's fate)
+  tl_aux_out = AuxOut{};
+  const bool want_aux = aux_out.depth != nullptr || aux_out.alpha != nullptr;
   if (ctx_out) *ctx_out = nullptr;
+  if (want_aux && s && (s->flags & GSR_FLAG_NEEDLE_DOUBLE))
+    return set_err(GSR_ERR_INVALID, "gsr_forward_aux: depth / alpha maps are not available under GSR_FLAG_NEEDLE_DOUBLE");
+  if (want_aux && (segb || fwd_only))
+    return set_err(GSR_ERR_INVALID, "gsr_forward_aux: depth / alpha maps are not available from the two-segment forwards");
   if (!s || !out_color) return set_err(GSR_ERR_INVALID, "gsr_forward: null settings / out_color");
   if (P < 0 || s->image_height <= 0 || s->image_width <= 0)
     return set_err(GSR_ERR_INVALID, "gsr_forward: bad sizes P=%d H=%d W=%d", P, s->image_height, s->image_width);
@@ -681,6 +713,7 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
   c->scales = scales; c->rots = rotations; c->cov3d = cov3D_precomp;
   c->raw = raw; c->sh_dc = sh_dc;
   c->fwd_only = fwd_only; c->objects_out = out_objects != nullptr && sh_objs != nullptr;
+  c->aux = want_aux; c->aux_depth_out = aux_out.depth; c->aux_alpha_out = aux_out.alpha;
   if (segb) {
     c->has_b = true;
     c->b.Pb = segb->Pb; c->b.xyz = segb->xyz; c->b.features_dc = segb->features_dc; c->b.features_rest = segb->features_rest;
@@ -1041,6 +1074,7 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
     F_LAUNCH("tile schedule");
     const int rk6 = launch_render_fwd(c, out_color, out_objects, st);
     if (rk6 != GSR_OK) return fail(rk6);
+    c->aux_depth_out = nullptr; c->aux_alpha_out = nullptr;      // the caller's buffers: written once, by this launch
   }
   pool_free(dev, scratch_blk);
   if (num_rendered) *num_rendered = c->n_known ? (int64_t)c->n64 : (int64_t)-1;   // -1: not known yet (asynchronous count)
@@ -1110,6 +1144,30 @@ int gsr_forward_raw(const GsrSettings* s, int32_t P, const float* xyz, const flo
                       rotation_raw, nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true);
 }
 
+int gsr_forward_aux(const GsrSettings* s, int32_t P, int32_t K, const float* means3D, const float* shs,
+                    const float* sh_objs, const float* colors_precomp, const float* opacities, const float* scales,
+                    const float* rotations, const float* cov3D_precomp, float* out_color, float* out_objects,
+                    int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha,
+                    void* stream) {
+  tl_aux_out.depth = out_depth; tl_aux_out.alpha = out_alpha;
+  const int rc = gsr_forward(s, P, K, means3D, shs, sh_objs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                             out_color, out_objects, radii, ctx_out, num_rendered, stream);
+  tl_aux_out = AuxOut{};
+  return rc;
+}
+
+int gsr_forward_raw_aux(const GsrSettings* s, int32_t P, const float* xyz, const float* features_dc,
+                        const float* features_rest, const float* objects_dc, const float* opacity_logit,
+                        const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
+                        int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha,
+                        void* stream) {
+  tl_aux_out.depth = out_depth; tl_aux_out.alpha = out_alpha;
+  const int rc = gsr_forward_raw(s, P, xyz, features_dc, features_rest, objects_dc, opacity_logit, log_scaling, rotation_raw,
+                                 out_color, out_objects, radii, ctx_out, num_rendered, stream);
+  tl_aux_out = AuxOut{};
+  return rc;
+}
+
 }  // extern "C"
 
 // A batch of views of ONE set of raw parameters through one launch chain (include/gsraster.h): the views must agree in
@@ -1137,7 +1195,10 @@ static int forward_raw_batch_impl(const char* fn, bool with_obj, const GsrSettin
   if (!out_color) return set_err(GSR_ERR_INVALID, "%s: out_color is null", fn);
   if (P == 0 && B > 1) {                 // an empty scene: B backgrounds; the context (of view 0) has nothing to differentiate
     const size_t px = (size_t)s[0].image_height * (size_t)s[0].image_width;
+    const AuxOut ax = tl_aux_out;
     for (int v = 0; v < B; ++v) {
+      tl_aux_out.depth = ax.depth ? ax.depth + (size_t)v * px : nullptr;
+      tl_aux_out.alpha = ax.alpha ? ax.alpha + (size_t)v * px : nullptr;
       const int rc = forward_impl(s + v, 0, 16, xyz, features_rest, features_dc, nullptr, nullptr, opacity_logit, log_scaling,
                                   rotation_raw, nullptr, out_color + (size_t)v * 3 * px,
                                   out_objects ? out_objects + (size_t)v * NUM_OBJ * px : nullptr, radii,
@@ -1194,6 +1255,17 @@ int gsr_forward_raw_batch(const GsrSettings* s, int32_t B, int32_t P, const floa
                                 log_scaling, rotation_raw, out_color, nullptr, radii, ctx_out, num_rendered, stream);
 }
 
+int gsr_forward_raw_batch_aux(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
+                              const float* features_rest, const float* opacity_logit, const float* log_scaling,
+                              const float* rotation_raw, float* out_color, int32_t* radii, GsrCtx** ctx_out,
+                              int64_t* num_rendered, float* out_depth, float* out_alpha, void* stream) {
+  tl_aux_out.depth = out_depth; tl_aux_out.alpha = out_alpha;
+  const int rc = gsr_forward_raw_batch(s, B, P, xyz, features_dc, features_rest, opacity_logit, log_scaling, rotation_raw,
+                                       out_color, radii, ctx_out, num_rendered, stream);
+  tl_aux_out = AuxOut{};
+  return rc;
+}
+
 int gsr_forward_raw_batch_obj(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
                               const float* features_rest, const float* objects_dc, const float* opacity_logit,
                               const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
@@ -1237,6 +1309,9 @@ int gsr_ctx_rerender(GsrCtx* c, const float* features_dc, const float* features_
                      void* stream) {
   if (!c) return set_err(GSR_ERR_STATE, "gsr_ctx_rerender: null context");
   if (!out_color) return set_err(GSR_ERR_INVALID, "gsr_ctx_rerender: out_color is null");
+  if (c->aux)
+    return set_err(GSR_ERR_STATE, "gsr_ctx_rerender: the context's forward produced depth / alpha maps (gsr_forward*_aux); "
+                   "such a context is not re-rendered");
   // a batch context (gsr_forward_raw_batch / gsr_forward_raw2_batch and their _obj forms): out_color [B,3,H,W], bg [B,3] or
   // null; out_objects [B,16,H,W] only if the batch's forward composited object channels
   if (c->B > 1 && out_objects && !c->objects_out)
@@ -1339,6 +1414,11 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
   // a backward that fails early must not leave the next one writing six doubles to a buffer that may be gone by then
   double* ss_out = c->sumsq_out;
   c->sumsq_out = nullptr;
+  // gsr_ctx_set_aux_grads is one-shot in the same way
+  const float* const aux_gd = c->aux_gd;
+  const float* const aux_ga = c->aux_ga;
+  c->aux_gd = nullptr; c->aux_ga = nullptr;
+  const bool aux = aux_gd != nullptr || aux_ga != nullptr;
   if (!grad_color) return set_err(GSR_ERR_INVALID, "gsr_backward: grad_color is null");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int dev = c->dev;
@@ -1350,6 +1430,25 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
   // Only colour-side gradients wanted (SH / precomputed colours / object features): K7 and K8+K9 drop the geometry
   // sums and the projection chain rule (the colour attack; BASELINE configs 2 and 3).
   const bool geom = dmeans3D || dmeans2D || dopacities || dscales || drotations || dcov3D;
+  if (aux) {
+    // (argument checks only: nothing has been launched)
+    if (view_stride != 0)
+      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: the per-view batch backward (gsr_backward_raw_batch_views / _obj_views) "
+                     "does not take depth / alpha gradients");
+    if (nchunks > 1)
+      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: gsr_backward_raw_chunked with more than one range does not take "
+                     "depth / alpha gradients");
+    if (grad_objects != nullptr)
+      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: depth / alpha gradients and grad_objects in one backward are not supported");
+    if (!geom)
+      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: depth / alpha gradients reach geometry and opacity only, and this "
+                     "backward asks for no such gradient");
+    if (!c->lanegroup)
+      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: a gsr_forward context with K != 16 SH coefficients does not take "
+                     "depth / alpha gradients");
+    if (c->st.flags & GSR_FLAG_NEEDLE_DOUBLE)
+      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: not available under GSR_FLAG_NEEDLE_DOUBLE");
+  }
   // an asynchronous-count forward: its pair count must have fitted the capacity guess (else the image it produced was
   // poisoned with NaN and nothing downstream of it is meaningful).  (A forward recorded into a hipGraph publishes
   // nothing to the host: c->slot is empty and this is a no-op.)
@@ -1373,7 +1472,7 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
   // (The rule looks at the tiles of ONE view, also for a batch: the split decides how many partial rows K9 adds up per
   // pair -- the float32 association of the sums -- and a batch's per-view gradients are the single-view call's bit for bit.
   // Found by tests/diag_fuzz_batch.py with GSR_FLAG_NO_SEGMENTS on batches of >= 4096 tiles of views with fewer.)
-  const bool segs_on = c->bnd != nullptr && !obj;
+  const bool segs_on = c->bnd != nullptr && !obj && aux_gd == nullptr;   // (dL/ddepth walks whole lists: no running depth in the records)
   const int bwd_npx = flag_bwd_npx(c->st.flags) ? flag_bwd_npx(c->st.flags) : ((c->tpv < 4096 && !segs_on) ? 2 : 4);
   const uint32_t nsub = (uint32_t)(PXL / bwd_npx);
   if (N > 0) {
@@ -1404,7 +1503,8 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     ra.gridx = c->gridx; ra.ntiles = c->ntiles; ra.final_T = c->final_T; ra.n_contrib = c->n_contrib;
     ra.grad_color = grad_color; ra.grad_objects = obj ? grad_objects : nullptr; ra.part = part; ra.part_obj = part_obj;
     // split tiles: one extra work item per boundary record, in front of the per-tile items
-    const bool segs = c->bnd != nullptr && !obj;
+    const bool segs = segs_on;
+    ra.grad_depth = aux_gd; ra.grad_alpha = aux_ga;
     ra.bnd = segs ? c->bnd : nullptr; ra.segoff = c->segoff; ra.rec_item = c->rec_item; ra.nrec = c->dv + DV_NREC;
     ra.seg_shift = c->seg_shift; ra.extra_blocks = segs ? c->rec_cap * nsub : 0u;
     ra.tpv = c->tpv; ra.vpack = c->vpack; ra.Ppad = c->Ppad;
@@ -1425,6 +1525,9 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
         if (bwd_npx == 4) LAUNCH_K7((k_render_bwd<true, 4, false>));
         else LAUNCH_K7((k_render_bwd<true, 2, false>));
       }
+    } else if (aux) {
+      if (bwd_npx == 4) LAUNCH_K7((k_render_bwd<false, 4, true, true>));
+      else LAUNCH_K7((k_render_bwd<false, 2, true, true>));
     } else if (geom) {
       if (bwd_npx == 4) LAUNCH_K7((k_render_bwd<false, 4, true>));
       else LAUNCH_K7((k_render_bwd<false, 2, true>));
@@ -1505,7 +1608,10 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
         ba.dscales = dscales; ba.drots = drotations; ba.sumsq = pa.sumsq;
         const dim3 gridB((unsigned)((ge - gb + 63) / 64)), blkB(64 * BATCH_K9_WAVES);
         const size_t lds = sizeof(float) * 3 * 64 * (size_t)c->B;
-        if (geom) {
+        if (aux) {
+          if (accumulate) hipLaunchKernelGGL((k_pre_bwd_batch<true, true, true>), gridB, blkB, lds, st, ba);
+          else hipLaunchKernelGGL((k_pre_bwd_batch<true, false, true>), gridB, blkB, lds, st, ba);
+        } else if (geom) {
           if (accumulate) hipLaunchKernelGGL((k_pre_bwd_batch<true, true>), gridB, blkB, lds, st, ba);
           else hipLaunchKernelGGL((k_pre_bwd_batch<true, false>), gridB, blkB, lds, st, ba);
         } else {
@@ -1546,7 +1652,11 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
         const dim3 gridK9((unsigned)((ge - gb + PRE_BLOCK - 1) / PRE_BLOCK));
         if (c->lanegroup) {
           const bool ndl = pa.needle_double != 0 && pa.abc != nullptr;
-          if (c->raw && acc_v) {
+          if (aux) {
+            if (c->raw && acc_v) hipLaunchKernelGGL((k_pre_bwd<true, true, true, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
+            else if (c->raw) hipLaunchKernelGGL((k_pre_bwd<true, true, false, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
+            else hipLaunchKernelGGL((k_pre_bwd<false, true, false, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
+          } else if (c->raw && acc_v) {
             if (geom && ndl) hipLaunchKernelGGL((k_pre_bwd<true, true, true, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
             else if (geom) hipLaunchKernelGGL((k_pre_bwd<true, true, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
             else hipLaunchKernelGGL((k_pre_bwd<true, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
@@ -1734,6 +1844,15 @@ void gsr_trim_pool(void) {
     else { (void)hipFree(b.p); pl.total -= b.bytes; }
   }
   pl.blocks.swap(keep);
+}
+
+int gsr_ctx_set_aux_grads(GsrCtx* c, const float* grad_depth, const float* grad_alpha) {
+  if (!c) return set_err(GSR_ERR_STATE, "gsr_ctx_set_aux_grads: null context");
+  if (!c->aux)
+    return set_err(GSR_ERR_STATE, "gsr_ctx_set_aux_grads: the context's forward did not produce depth / alpha maps (use gsr_forward*_aux)");
+  if (c->fwd_only) return set_err(GSR_ERR_STATE, "gsr_ctx_set_aux_grads: the context has no backward state");
+  c->aux_gd = grad_depth; c->aux_ga = grad_alpha;
+  return GSR_OK;
 }
 
 int gsr_ctx_request_sumsq(GsrCtx* c, double* out6) {

@@ -521,6 +521,10 @@ struct RenderArgs {
   // object channels of a batch (OBJ only): the view's Gaussians are the virtual rows [view * Ppad, view * Ppad + P), so the
   // feature row of virtual row r is r - view * Ppad (a second segment from Pa on, as above); out_objects holds [B,16,H,W]
   int Ppad;
+  // depth / alpha maps (k_render_fwd<., ., ., AUX = true> only; include/gsraster.h "Depth and alpha maps"): [H*W] per view,
+  // the B maps of a batch one after another; either may be null
+  float* out_depth;
+  float* out_alpha;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -792,7 +796,10 @@ constexpr float PX_OFF = 1.0e30f;   // y coordinate of a finished / out-of-image
 #define GSR_K6_OBJ_SCALAR 0         // 0: object features staged through LDS; 1: fetched by scalar loads into SGPRs (measured
                                     // slower on S-nyc-1M: K6 0.353 ms against 0.304 -- EXPERIMENTS.md, round 5)
 #endif
-template <bool OBJ, int NPX, int WPB = 1>
+// AUX = true: the walk also carries D = sum z_i alpha_i T_i per pixel (z_i rides in the spare fourth word of the staged s2
+// entry: no extra LDS, one more register per register set and pixel) and stores out_depth / out_alpha = 1 - T beside
+// final_T.  Colour, final_T, n_contrib, the object map and the boundary records are those of AUX = false bit for bit.
+template <bool OBJ, int NPX, int WPB = 1, bool AUX = false>
 __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_K6_OBJ_WAVES : 1) k_render_fwd(RenderArgs a) {
   constexpr int NSUB = PXL / NPX;
   static_assert(WPB == 1 || WPB == NSUB, "a shared workgroup holds all the waves of a tile");
@@ -833,6 +840,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
   int y[NPX];
   float pyf[NPX], T[NPX], C[NPX][3];
   float O[OBJ ? NPX : 1][NUM_OBJ];
+  float Dz[AUX ? NPX : 1];                  // AUX: running sum of z_i alpha_i T_i
   uint32_t last[NPX];
   uint32_t alive = 0;                       // bit k: strip k still has an unfinished pixel (wave-uniform)
 #pragma unroll
@@ -842,6 +850,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
     pyf[k] = inside ? (float)(y[k] - ty * TILE) : PX_OFF;
     T[k] = 1.f;
     C[k][0] = C[k][1] = C[k][2] = 0.f;
+    if constexpr (AUX) Dz[k] = 0.f;
     last[k] = 0;
     if (__ballot(inside) != 0ull) alive |= 1u << k;
     if (OBJ) {
@@ -862,7 +871,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
       mine = WPB > 1 ? (pv >> RANK_BITS) & 0xFu : ((pv >> RANK_BITS) >> (sub * NPX)) & ((1u << NPX) - 1u);
       const StagedSplat sp = stage_splat(a.R0[REC * r], a.R1[REC * r], c, mine, tx, ty);
       rown = r;                                           // the pair's value IS the Gaussian's storage index
-      s0[slot] = sp.a; s1[slot] = sp.b; s2[slot] = make_float4(sp.c.x, sp.c.y, __uint_as_float(r), 0.f);
+      s0[slot] = sp.a; s1[slot] = sp.b; s2[slot] = make_float4(sp.c.x, sp.c.y, __uint_as_float(r), AUX ? c.y : 0.f);   // (AUX: + the view depth)
       if (OBJ && !GSR_K6_OBJ_SCALAR && (GSR_K6_OBJ_STAGE_ALL || mine != 0u)) {   // (an entry no strip of this wave reaches is never read)
         const uint32_t lr = r - obase;                    // the view-local Gaussian
         const float4* src = reinterpret_cast<const float4*>(lr >= (uint32_t)a.Pa ? a.sh_objs_b + (size_t)(lr - (uint32_t)a.Pa) * NUM_OBJ
@@ -930,7 +939,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
       }
       return f;
     };
-    auto composite = [&](const float4& e0, const float4& e1, const float2& e2, const Feat& fe, const int jc) {
+    auto composite = [&](const float4& e0, const float4& e1, const float2& e2, const float ez, const Feat& fe, const int jc) {
       const uint32_t pos = base - rg.x + (uint32_t)(jb + jc) + 1;
       {
       const float dx = e0.x - pxf;
@@ -964,6 +973,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
           }
           const float w = contrib ? alpha * T[k] : 0.f;
           C[k][0] = fmaf(e1.z, w, C[k][0]); C[k][1] = fmaf(e1.w, w, C[k][1]); C[k][2] = fmaf(e2.x, w, C[k][2]);
+          if constexpr (AUX) Dz[k] = fmaf(ez, w, Dz[k]);
           if (OBJ && GSR_K6_OBJ_SCALAR) {
             const float f[NUM_OBJ] = {fe.q[0].x, fe.q[0].y, fe.q[0].z, fe.q[0].w, fe.q[1].x, fe.q[1].y, fe.q[1].z, fe.q[1].w,
                                       fe.q[2].x, fe.q[2].y, fe.q[2].z, fe.q[2].w, fe.q[3].x, fe.q[3].y, fe.q[3].z, fe.q[3].w};
@@ -999,6 +1009,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
     int j = __builtin_ctzll(todo);
     float4 a0 = s0[jb + j], a1 = s1[jb + j];
     float2 a2 = make_float2(s2[jb + j].x, s2[jb + j].y);
+    float az = AUX ? s2[jb + j].w : 0.f;
     Feat fa = load_feat(j);
     // (the entry behind the one on which the wave's last pixel finished has been fetched already: it is skipped on its
     // empty strip mask, and the cleared `todo` ends the walk behind it)
@@ -1008,15 +1019,17 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
       j = jraw & 63;                          // prefetch the next entry while this one is composited
       const float4 b0 = s0[jb + j], b1 = s1[jb + j];
       const float2 b2 = make_float2(s2[jb + j].x, s2[jb + j].y);
+      const float bz = AUX ? s2[jb + j].w : 0.f;
       const Feat fb = load_feat(j);
-      composite(a0, a1, a2, fa, jc);
+      composite(a0, a1, a2, az, fa, jc);
       if (jraw < 0) break;
       jc = j;
       asm volatile("s_bitset0_b64 %0, %2\n\ts_ff1_i32_b64 %1, %0" : "+s"(todo), "=s"(jraw) : "s"(jc));
       j = jraw & 63;
       a0 = s0[jb + j]; a1 = s1[jb + j]; a2 = make_float2(s2[jb + j].x, s2[jb + j].y);
+      if constexpr (AUX) az = s2[jb + j].w;
       fa = load_feat(j);
-      composite(b0, b1, b2, fb, jc);
+      composite(b0, b1, b2, bz, fb, jc);
       if (jraw < 0) break;
     }
     }
@@ -1049,11 +1062,13 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
   if (a.wave_clock && lane == 0) a.wave_clock[2 * item + 1] = wall_clock64();
   const float* bgp = a.vpack != nullptr ? a.vpack[view].bg : a.bg;
   float bg0 = bgp[0], bg1 = bgp[1], bg2 = bgp[2];
+  bool aux_poison = false;                               // AUX: the overflow below poisons both maps too (alpha = NaN, not 0)
   if (a.dv != nullptr && a.dv[DV_OVF] != 0u) {
     // the pair count overflowed the capacity this forward was sized for: nothing was composited -- make that unmissable
     bg0 = bg1 = bg2 = __uint_as_float(0x7FC00000u);
 #pragma unroll
-    for (int k = 0; k < NPX; ++k) T[k] = 1.f;
+    for (int k = 0; k < NPX; ++k) { T[k] = 1.f; if constexpr (AUX) Dz[k] = bg0; }
+    if constexpr (AUX) aux_poison = true;
   }
   const size_t HW = (size_t)a.H * a.W;
   float* const oc = a.out_color + 3 * HW * (size_t)view;
@@ -1068,6 +1083,10 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
       oc[2 * HW + pix] = C[k][2] + T[k] * bg2;
       fT[pix] = T[k];
       nc[pix] = last[k];
+      if constexpr (AUX) {
+        if (a.out_depth != nullptr) a.out_depth[HW * (size_t)view + pix] = Dz[k];
+        if (a.out_alpha != nullptr) a.out_alpha[HW * (size_t)view + pix] = aux_poison ? bg0 : 1.0f - T[k];
+      }
       if (OBJ) {
 #pragma unroll
         for (int c = 0; c < NUM_OBJ; ++c) a.out_objects[NUM_OBJ * HW * (size_t)view + c * HW + pix] = O[k][c];
@@ -1147,6 +1166,10 @@ struct RenderBwdArgs {
   int tpv;                    // a batch of views, as in RenderArgs: view = tile / tpv; grad_color holds the B images' gradients
   const ViewDev* vpack;
   int Ppad;                   // OBJ: as in RenderArgs (feature row = r - view * Ppad); grad_objects holds [B,16,H,W]
+  // AUX only (gsr_ctx_set_aux_grads): dL/d depth map and dL/d alpha map, [H*W] per view, either may be null (= zero).
+  // The host hands over boundary records (bnd) only when grad_depth is null: they hold no running depth.
+  const float* grad_depth;
+  const float* grad_alpha;
 };
 
 constexpr int PART_F4 = 3;
@@ -1162,8 +1185,17 @@ constexpr int PART_F4 = 3;
 // scratch per lane) and the parked-sum buffer kept to 2.5 KB, so that neither registers nor LDS (5.4 KB per wave)
 // stop the sixth wave.  Measured on S-nyc-1M: 0.332 -> 0.323 ms, pipelined 1233 -> 1267 views/s; seven and eight
 // waves per SIMD spill 36 / 64 bytes per lane and run 0.365 / 0.51 ms.
-template <bool OBJ, int NPX, bool GEOM>
-__global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(RenderBwdArgs a) {
+// AUX = true (GEOM, no object channels): the two maps' gradients join the walk -- per pixel c_i . g_C becomes
+// c_i . g_C + z_i g_D + g_A (both extra channels have background 0, so Acc starts from the same T_final (bg . g_C); behind a
+// segment boundary the alpha channel adds (A_final - A_b) g_A = (T_b - T_final) g_A) -- and a TENTH sum per entry, S w g_D =
+// dL/dz_i, goes to the row's spare word 11.  The nine sums keep their eight parked registers and their transposed sum
+// exactly as they are, so that with all-zero aux gradients every row word is the plain kernel's bit for bit; the tenth is
+// summed by six DPP adds (wave_sum_to_hi) and stored by lane 63, only when grad_depth is given (else word 11 = 0).  Folding
+// it into the parked layout instead -- (dr | dz) by a second v_permlane32_swap -- is cheaper per entry but changes the
+// association of the red sum.  One wave per SIMD less than the plain kernel: two more gradients per pixel do not fit 80 VGPRs.
+template <bool OBJ, int NPX, bool GEOM, bool AUX = false>
+__global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? (AUX ? 5 : 6) : 1) k_render_bwd(RenderBwdArgs a) {
+  static_assert(!AUX || (GEOM && !OBJ), "aux gradients: geometry walk without object channels");
   constexpr int NSUB = PXL / NPX;
   // Registers parked per contributing entry: the per-lane sums as they are, except that the LAST one holds two values
   // (dg in lanes < 32, db in lanes >= 32, folded by one v_permlane32_swap + add): 8 registers for the nine sums,
@@ -1177,6 +1209,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
   __shared__ float4 s1[64];
   __shared__ float2 s2[64];
   __shared__ uint32_t sslot[64];
+  __shared__ float sz[AUX ? 64 : 1];                    // AUX: the staged entries' view depth
   __shared__ __attribute__((aligned(16))) float so[OBJ ? 64 : 1][NUM_OBJ];
   __shared__ __attribute__((aligned(16))) float sred[RB * RENTRY];
   const int lane = threadIdx.x;
@@ -1246,6 +1279,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
   const float* const gobj = OBJ ? a.grad_objects + NUM_OBJ * HW * (size_t)view : nullptr;
   const uint32_t obase = OBJ ? (uint32_t)view * (uint32_t)a.Ppad : 0u;
   float pyf[NPX], T[NPX], Acc[NPX], g0[NPX], g1[NPX], g2[NPX];
+  float gD[AUX ? NPX : 1], gA[AUX ? NPX : 1];
   float gO[OBJ ? NPX : 1][NUM_OBJ];
   uint32_t ncon[NPX], smax[NPX];
   uint32_t maxc = 0;
@@ -1259,6 +1293,10 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
       T[k] = fT[pix];
       ncon[k] = nc[pix];
       g0[k] = gcol[pix]; g1[k] = gcol[HW + pix]; g2[k] = gcol[2 * HW + pix];
+      if constexpr (AUX) {
+        gD[k] = a.grad_depth != nullptr ? a.grad_depth[HW * (size_t)view + pix] : 0.f;
+        gA[k] = a.grad_alpha != nullptr ? a.grad_alpha[HW * (size_t)view + pix] : 0.f;
+      }
       // Acc_i = sum over the entries j behind i of alpha_j (c_j.g) prod_{i<k<j} (1 - alpha_k): what the pixel shows
       // behind entry i, dotted with dL/dC.  The background is the list's last "entry" (alpha 1, colour bg): seeding
       // Acc with bg.g makes T_i (c_i.g - Acc_i) carry the -T_final/(1-alpha_i) (bg.g) term of dL/dalpha_i by itself.
@@ -1274,7 +1312,8 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
           const float4 B = a.bnd[(size_t)(rec0 + seg) * (PXL * 64) + px];
           if (GEOM) {
             const float4 F = a.bnd[(size_t)(rec0 + nseg - 1u) * (PXL * 64) + px];
-            const float behind = fmaf(F.y - B.y, g0[k], fmaf(F.z - B.z, g1[k], (F.w - B.w) * g2[k]));
+            float behind = fmaf(F.y - B.y, g0[k], fmaf(F.z - B.z, g1[k], (F.w - B.w) * g2[k]));
+            if constexpr (AUX) behind = fmaf(B.x - T[k], gA[k], behind);  // the alpha channel behind b: A_final - A_b = T_b - T_final
             Acc[k] = fmaf(T[k], Acc[k], behind) / B.x;          // T[k] = T_final, Acc[k] = bg . g here
           }
           T[k] = B.x;
@@ -1285,6 +1324,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
       }
     } else {
       T[k] = 1.f; ncon[k] = 0; g0[k] = g1[k] = g2[k] = 0.f;
+      if constexpr (AUX) { gD[k] = 0.f; gA[k] = 0.f; }
       if (OBJ) {
 #pragma unroll
         for (int c = 0; c < NUM_OBJ; ++c) gO[k][c] = 0.f;
@@ -1308,6 +1348,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
       for (int k = 0; k < NPX; ++k) live |= (pos <= smax[k] ? 1u : 0u) << k;
       const StagedSplat sp = stage_splat(a.R0[REC * r], a.R1[REC * r], c, ((pv >> RANK_BITS) >> (sub * NPX)) & live, tx, ty);
       s0[lane] = sp.a; s1[lane] = sp.b; s2[lane] = sp.c;
+      if constexpr (AUX) sz[lane] = c.y;
       const uint32_t rx = __float_as_uint(c.z), ry = __float_as_uint(c.w);
       const uint32_t minx = rx & RECT_MASK, wx = ((rx >> 12) & RECT_MASK) - minx, miny = ry & RECT_MASK;
       sslot[lane] = (a.offg[r] + ((uint32_t)ty - miny) * wx + ((uint32_t)tx - minx)) * NSUB + sub;
@@ -1330,6 +1371,8 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
       const float dx = e0.x - pxf;
       const float qa = e0.z * dx * dx, bdx = e0.w * dx;
       float sq = 0.f, sqy = 0.f, sqyy = 0.f, dop = 0.f, dr = 0.f, dg = 0.f, db = 0.f;
+      float dzs = 0.f;                                   // AUX: S w g_D
+      const float ez = AUX ? sz[j] : 0.f;
       float dobj[OBJ ? NUM_OBJ : 1];
       if (OBJ) {
 #pragma unroll
@@ -1350,6 +1393,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
         T[k] *= inv1m;
         const float w = ae * T[k];
         dr = fmaf(w, g0[k], dr); dg = fmaf(w, g1[k], dg); db = fmaf(w, g2[k], db);
+        if constexpr (AUX) dzs = fmaf(w, gD[k], dzs);
         if (OBJ) {
 #pragma unroll
           for (int c = 0; c < NUM_OBJ; ++c) dobj[c] = fmaf(w, gO[k][c], dobj[c]);
@@ -1360,6 +1404,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
 #pragma unroll
             for (int c = 0; c < NUM_OBJ; ++c) cg = fmaf(so[j][c], gO[k][c], cg);
           }
+          if constexpr (AUX) cg = fmaf(ez, gD[k], cg) + gA[k];
           const float dcg = cg - Acc[k];
           const float dLda = valid ? T[k] * dcg : 0.f;
           Acc[k] = fmaf(ae, dcg, Acc[k]);                  // ae*cg + (1-ae)*Acc: now includes this entry
@@ -1411,6 +1456,10 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? 6 : 1) k_render_bwd(R
         }
         if (RB > 1) red_j = lane == red_n ? j : red_j;      // (one entry per sum: its index is the scalar j itself)
         ++red_n;
+        if constexpr (AUX) {                                          // the tenth sum: word 11 of the row
+          if (a.grad_depth != nullptr) dzs = wave_sum_to_hi(dzs);
+          if (lane == 63) reinterpret_cast<float*>(a.part + (size_t)sslot[j] * PART_F4)[11] = dzs;
+        }
         if (OBJ) {
 #pragma unroll
           for (int c = 0; c < NUM_OBJ; ++c) dobj[c] = wave_sum_to_hi(dobj[c]);
@@ -2079,8 +2128,11 @@ constexpr int HAND_W = 7;          // hand-over: unit direction (3) + clamped dL
 // NDL (GSR_FLAG_NEEDLE_DOUBLE): the Gaussians k_pre_geom marked as needles (a number, not NaN, in their first abc word) run
 // their whole chain rule in double (gsr_math.h needle_bwd_d); a separate instantiation, because the double chain's
 // registers cost the kernel a wave per SIMD.
-template <bool RAW, bool GEOM, bool ACC = false, bool NDL = false>
+// AUX (a backward armed by gsr_ctx_set_aux_grads): the rows' word 11 holds S w g_D; its sum over the Gaussian's rows is
+// dL/d(view depth), which reaches the mean through the third column of the view matrix.
+template <bool RAW, bool GEOM, bool ACC = false, bool NDL = false, bool AUX = false>
 __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
+  static_assert(!AUX || (GEOM && !NDL), "aux gradients: geometry chain, no double needles");
   __shared__ float4 srow[PRE_WAVES * ROW_CHUNK * PART_F4];
   __shared__ float shand[PRE_WAVES * 64 * HAND_W];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2121,6 +2173,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
   // (the second moments are summed in double: what they feed -- dL/dconic -> dL/dcov2D -- cancels to first order for an
   // elongated splat, see project_splat_bwd, and amplifies the rounding of a float32 running sum over hundreds of rows)
   float dop = 0.f, dr = 0.f, dg = 0.f, db = 0.f;
+  float dzv = 0.f;                                                 // AUX: dL/d(view depth)
   double mx = 0.0, my = 0.0, mxx = 0.0, mxy = 0.0, myy = 0.0;      // (conic . (mx, my) cancels the same way)
   {
     const uint32_t S = a.offg[gw0] * a.nsub, E = a.offg[gw0 + nw] * a.nsub;
@@ -2140,6 +2193,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
           if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
           if (GEOM) { mx += (double)p0.x; my += (double)p0.y; mxx += (double)p0.z; mxy += (double)p0.w; myy += (double)p1.x; dop += p1.y; }
           dr += p1.z; dg += p1.w; db += p2.x;
+          if constexpr (AUX) dzv += p2.w;
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2152,13 +2206,16 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
       bm &= bm - 1;
       const uint32_t b0 = __shfl(o0, L, 64), b1 = __shfl(o1, L, 64);
       float t[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      float tz = 0.f;
       double t2[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
       for (uint32_t e = b0 + lane; e < b1; e += 64) {
         const float4 p0 = a.part[(size_t)e * PART_F4], p1 = a.part[(size_t)e * PART_F4 + 1], p2 = a.part[(size_t)e * PART_F4 + 2];
         if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
         if (GEOM) { t2[3] += (double)p0.x; t2[4] += (double)p0.y; t2[0] += (double)p0.z; t2[1] += (double)p0.w; t2[2] += (double)p1.x; t[5] += p1.y; }
         t[6] += p1.z; t[7] += p1.w; t[8] += p2.x;
+        if constexpr (AUX) tz += p2.w;
       }
+      if constexpr (AUX) { tz = __shfl(wave_sum_to_hi(tz), 63, 64); if (lane == L) dzv = tz; }
 #pragma unroll
       for (int i = 0; i < 9; ++i) t[i] = __shfl(wave_sum_to_hi(t[i]), 63, 64);
       if (GEOM) {
@@ -2261,6 +2318,9 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
           dp[1] += (ddy - hdir[1] * dot) * inv;
           dp[2] += (ddz - hdir[2] * dot) * inv;
         }
+      }
+      if constexpr (AUX) {   // dL/dz through z = [p, 1] . V[:, 2]
+        dp[0] = fmaf(dzv, v.V[2], dp[0]); dp[1] = fmaf(dzv, v.V[6], dp[1]); dp[2] = fmaf(dzv, v.V[10], dp[2]);
       }
       if (GEOM) {
         float c6[6];
@@ -2485,8 +2545,9 @@ constexpr int BATCH_K9_WAVES = 2;
 #ifndef GSR_BATCH_K9_OCC
 #define GSR_BATCH_K9_OCC 3
 #endif
-template <bool GEOM, bool ACC>
+template <bool GEOM, bool ACC, bool AUX = false>      // AUX: as in k_pre_bwd
 __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC : 1) k_pre_bwd_batch(PreBwdBatchArgs a) {
+  static_assert(!AUX || GEOM, "aux gradients: geometry chain");
   __shared__ float4 srow_all[BATCH_K9_WAVES][ROW_CHUNK * PART_F4];
   __shared__ float spos[64 * 3];
   __shared__ uint32_t sany[BATCH_K9_WAVES][64];
@@ -2530,6 +2591,7 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
     if (has) { e0 = a.G0[REC * (o + g)]; e1 = a.G1[REC * (o + g)]; e2 = a.G2[REC * (o + g)]; }
     // ---- this view's partial rows of the wave's Gaussians (one contiguous span), as in k_pre_bwd -----------------------
     float dop = 0.f, dr = 0.f, dg = 0.f, db = 0.f;
+    float dzv = 0.f;
     double mx = 0.0, my = 0.0, mxx = 0.0, mxy = 0.0, myy = 0.0;
     {
       const uint32_t S = offg[gw0] * a.nsub, E = offg[gw0 + nw] * a.nsub;
@@ -2549,6 +2611,7 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
             if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
             if (GEOM) { mx += (double)p0.x; my += (double)p0.y; mxx += (double)p0.z; mxy += (double)p0.w; myy += (double)p1.x; dop += p1.y; }
             dr += p1.z; dg += p1.w; db += p2.x;
+            if constexpr (AUX) dzv += p2.w;
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2567,7 +2630,9 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
           if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
           if (GEOM) { t2[3] += (double)p0.x; t2[4] += (double)p0.y; t2[0] += (double)p0.z; t2[1] += (double)p0.w; t2[2] += (double)p1.x; t[5] += p1.y; }
           t[6] += p1.z; t[7] += p1.w; t[8] += p2.x;
+          if constexpr (AUX) t[0] += p2.w;                           // (t[0..4] are otherwise unused: the second moments are in t2)
         }
+        if constexpr (AUX) { t[0] = __shfl(wave_sum_to_hi(t[0]), 63, 64); if (lane == L) dzv = t[0]; }
 #pragma unroll
         for (int i = 5; i < 9; ++i) t[i] = __shfl(wave_sum_to_hi(t[i]), 63, 64);
         if (GEOM) {
@@ -2612,6 +2677,9 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
         dp[0] += (ddx - hx * dot) * inv;
         dp[1] += (ddy - hy * dot) * inv;
         dp[2] += (ddz - hz * dot) * inv;
+        if constexpr (AUX) {   // dL/dz through z = [p, 1] . V[:, 2]
+          dp[0] = fmaf(dzv, vw.V[2], dp[0]); dp[1] = fmaf(dzv, vw.V[6], dp[1]); dp[2] = fmaf(dzv, vw.V[10], dp[2]);
+        }
         float dc6[6];
         project_splat_bwd(vw, p, c6, dA, dB, dC, dndcx, dndcy, dp, dc6);
 #pragma unroll

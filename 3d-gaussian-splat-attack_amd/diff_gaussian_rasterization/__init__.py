@@ -152,6 +152,15 @@ def _load():
         lib.gsr_forward_raw2_batch.restype = ctypes.c_int
         lib.gsr_forward_raw2_batch.argtypes = ([ctypes.POINTER(_CSettings), i32, i32] + [vp] * 6 + [i32] + [vp] * 6
                                                + [vp, vp, ctypes.POINTER(vp), i64p, vp])
+    if hasattr(lib, "gsr_forward_aux"):                # 0.6.4: depth / alpha maps
+        lib.gsr_forward_aux.restype = ctypes.c_int
+        lib.gsr_forward_aux.argtypes = list(lib.gsr_forward.argtypes[:-1]) + [vp, vp, vp]
+        lib.gsr_forward_raw_aux.restype = ctypes.c_int
+        lib.gsr_forward_raw_aux.argtypes = list(lib.gsr_forward_raw.argtypes[:-1]) + [vp, vp, vp]
+        lib.gsr_forward_raw_batch_aux.restype = ctypes.c_int
+        lib.gsr_forward_raw_batch_aux.argtypes = list(lib.gsr_forward_raw_batch.argtypes[:-1]) + [vp, vp, vp]
+        lib.gsr_ctx_set_aux_grads.restype = ctypes.c_int
+        lib.gsr_ctx_set_aux_grads.argtypes = [vp, vp, vp]
     lib.gsr_ctx_rerender.restype = ctypes.c_int
     lib.gsr_ctx_rerender.argtypes = [vp] * 8 + [ctypes.c_uint32, vp]
     lib.gsr_ctx_free.restype = None
@@ -371,11 +380,24 @@ def _objects_all_zero(t: torch.Tensor, src: torch.Tensor) -> bool:
 _OBJ_SHORTCUT = os.environ.get("GSR_ZERO_OBJECT_SHORTCUT", "1") != "0"
 
 
+def _arm_aux_grads(lib, holder, grad_depth, grad_alpha, shape, device):
+    """Hands the two maps' incoming gradients (either may be None = zero) to the context's next backward
+    (gsr_ctx_set_aux_grads).  -> the tensors to keep alive until that backward has been enqueued."""
+    gd = None if grad_depth is None else _f32c(grad_depth.reshape(shape), device)
+    ga = None if grad_alpha is None else _f32c(grad_alpha.reshape(shape), device)
+    if gd is None and ga is None:
+        return ()
+    if lib.gsr_ctx_set_aux_grads(holder.handle, _ptr(gd), _ptr(ga)) != 0:
+        raise RuntimeError(_err(lib))
+    return (gd, ga)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, keep=True):
+                raster_settings, keep=True, aux=False):
         lib = _load()
+        ctx.aux = bool(aux)
         if not means3D.is_cuda:
             raise RuntimeError("diff_gaussian_rasterization: tensors must live on a HIP device (got "
                                f"{means3D.device}); there is no CPU path")
@@ -414,10 +436,18 @@ class _RasterizeGaussians(torch.autograd.Function):
         # (segment boundaries, d colour / d direction)
         with torch.cuda.device(device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            rc = lib.gsr_forward(ctypes.byref(pack.c), P, K, _ptr(m3), _ptr(shc), _ptr(shoc), _ptr(colc), _ptr(opc),
-                                 _ptr(scc), _ptr(roc), _ptr(covc), _ptr(color), _ptr(objects) if with_obj else None,
-                                 _ptr(radii),
-                                 ctypes.byref(handle) if keep else None, ctypes.byref(nren), stream)
+            if aux:
+                depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
+                alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
+                rc = lib.gsr_forward_aux(ctypes.byref(pack.c), P, K, _ptr(m3), _ptr(shc), _ptr(shoc), _ptr(colc), _ptr(opc),
+                                         _ptr(scc), _ptr(roc), _ptr(covc), _ptr(color), _ptr(objects) if with_obj else None,
+                                         _ptr(radii), ctypes.byref(handle) if keep else None, ctypes.byref(nren),
+                                         _ptr(depth), _ptr(alpha), stream)
+            else:
+                rc = lib.gsr_forward(ctypes.byref(pack.c), P, K, _ptr(m3), _ptr(shc), _ptr(shoc), _ptr(colc), _ptr(opc),
+                                     _ptr(scc), _ptr(roc), _ptr(covc), _ptr(color), _ptr(objects) if with_obj else None,
+                                     _ptr(radii),
+                                     ctypes.byref(handle) if keep else None, ctypes.byref(nren), stream)
         if rc != 0:
             msg = _err(lib)
             if raster_settings.debug:
@@ -442,10 +472,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.versions = _versions(ctx.kept)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
+        if aux:
+            return color, radii, objects, depth, alpha
         return color, radii, objects
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_objects):
+    def backward(ctx, grad_color, grad_radii, grad_objects, grad_depth=None, grad_alpha=None):
         lib = ctx.holder.lib
         _check_versions(ctx.kept, ctx.versions)
         m3, shc, shoc, colc, opc, scc, roc, covc = ctx.kept
@@ -471,6 +503,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         d_cov = out(need[8] and covc is not None, P, 6)
         with torch.cuda.device(device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            # (the maps reach geometry and opacity only: with none of those gradients wanted theirs are not handed over)
+            geo = need[0] or need[1] or need[5] or need[6] or need[7] or need[8]
+            aux_keep = _arm_aux_grads(lib, ctx.holder, grad_depth, grad_alpha, (H, W), device) if (ctx.aux and P > 0 and geo) else ()
             rc = lib.gsr_backward(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_m3), _ptr(d_m2), _ptr(d_sh),
                                   _ptr(d_obj), _ptr(d_col), _ptr(d_op), _ptr(d_sc), _ptr(d_ro), _ptr(d_cov), stream)
         if rc != 0:
@@ -488,7 +523,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         def shaped(t, shape):
             return None if t is None else t.reshape(shape)
         return (shaped(d_m3, s[0]), shaped(d_m2, s[1]), shaped(d_sh, s[2]), shaped(d_obj, s[3]), shaped(d_col, s[4]),
-                shaped(d_op, s[5]), shaped(d_sc, s[6]), shaped(d_ro, s[7]), shaped(d_cov, s[8]), None, None)
+                shaped(d_op, s[5]), shaped(d_sc, s[6]), shaped(d_ro, s[7]), shaped(d_cov, s[8]), None, None, None)
 
 
 class _RenderToken:
@@ -717,8 +752,11 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation, raster_settings,
-                keep=True, bucket=None, cache_slot=None, color_only=False, norms=None):
+                keep=True, bucket=None, cache_slot=None, color_only=False, norms=None, aux=False):
         lib = _load()
+        ctx.aux = bool(aux)
+        if aux:
+            cache_slot = None                 # a kept context is never re-rendered with maps: aux renders bypass the cache
         ctx.bucket = bucket
         ctx.norms = norms
         ctx.entry = None
@@ -784,10 +822,18 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             if entry is None:
                 want_ctx = keep or (cache_slot is not None and P > 0 and sig is not None)
                 radii = torch.empty(P, dtype=torch.int32, device=device)
-                rc = lib.gsr_forward_raw(ctypes.byref(pack.c), P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op), _ptr(sc),
-                                         _ptr(ro), _ptr(color), _ptr(objects) if with_obj else None, _ptr(radii),
-                                         ctypes.byref(handle) if want_ctx else None,
-                                         ctypes.byref(nren), stream)
+                if aux:
+                    depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
+                    alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
+                    rc = lib.gsr_forward_raw_aux(ctypes.byref(pack.c), P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op),
+                                                 _ptr(sc), _ptr(ro), _ptr(color), _ptr(objects) if with_obj else None,
+                                                 _ptr(radii), ctypes.byref(handle) if want_ctx else None, ctypes.byref(nren),
+                                                 _ptr(depth), _ptr(alpha), stream)
+                else:
+                    rc = lib.gsr_forward_raw(ctypes.byref(pack.c), P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op), _ptr(sc),
+                                             _ptr(ro), _ptr(color), _ptr(objects) if with_obj else None, _ptr(radii),
+                                             ctypes.byref(handle) if want_ctx else None,
+                                             ctypes.byref(nren), stream)
         if rc != 0:
             msg = _err(lib)
             if raster_settings.debug:
@@ -820,10 +866,12 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.versions = _versions(ctx.kept)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
+        if aux:
+            return color, radii, objects, depth, alpha
         return color, radii, objects
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_objects):
+    def backward(ctx, grad_color, grad_radii, grad_objects, grad_depth=None, grad_alpha=None):
         lib = ctx.holder.lib
         _check_versions(ctx.kept, ctx.versions)
         x, dc, rest, obj, op, sc, ro = ctx.kept
@@ -882,6 +930,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if P > 0:
             with torch.cuda.device(device):
                 stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+                # (the maps reach geometry and opacity only: with none of those gradients wanted theirs are not handed over)
+                geo = need[0] or need[1] or need[5] or need[6] or need[7]
+                aux_keep = _arm_aux_grads(lib, ctx.holder, grad_depth, grad_alpha, (H, W), device) if (ctx.aux and geo) else ()
                 if bucket is not None and bucket.chunks > 1:
                     hook, bucket.on_chunk = bucket.on_chunk, None
                     errs = []
@@ -915,13 +966,14 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             bucket.fresh, bucket.used = False, True
             s = ctx.shapes
             return (None, None if d_m2 is None else d_m2.reshape(s[1]), None, None,
-                    None if d_obj is None else d_obj.reshape(s[4]), None, None, None, None, None, None, None, None, None)
+                    None if d_obj is None else d_obj.reshape(s[4]), None, None, None, None, None, None, None, None, None, None)
         s = ctx.shapes
 
         def shaped(t, shape, wanted=True):
             return None if (t is None or not wanted) else t.reshape(shape)
         return (shaped(d_x, s[0]), shaped(d_m2, s[1]), shaped(d_dc, s[2], need[2]), shaped(d_rest, s[3], need[3]),
-                shaped(d_obj, s[4]), shaped(d_op, s[5]), shaped(d_sc, s[6]), shaped(d_ro, s[7]), None, None, None, None, None, None)
+                shaped(d_obj, s[4]), shaped(d_op, s[5]), shaped(d_sc, s[6]), shaped(d_ro, s[7]), None, None, None, None, None, None,
+                None)
 
 
 MAX_BATCH = 16                # views per gsr_forward_raw_batch call (csrc/gsr_kernels.hip.h)
@@ -949,8 +1001,14 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, settings_list, keep=True,
-                bucket=None, norms=None, cache_slot=None, color_only=False, objects_dc=None):
+                bucket=None, norms=None, cache_slot=None, color_only=False, objects_dc=None, aux=False):
         lib = _load()
+        ctx.aux = bool(aux)
+        if aux:
+            cache_slot = None                 # aux renders bypass the cache (see _RasterizeGaussiansRaw)
+            if objects_dc is not None:
+                raise ValueError("rasterize_gaussians_raw_batch: aux=True with objects_dc is not supported (render the object "
+                                 "channels in a batch of their own)")
         ctx.bucket = bucket
         ctx.norms = norms
         ctx.entry = None
@@ -1029,6 +1087,12 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
                     rc = lib.gsr_forward_raw_batch_obj(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op), _ptr(sc),
                                                        _ptr(ro), _ptr(color), _ptr(objects), _ptr(radii),
                                                        ctypes.byref(handle) if want_ctx else None, ctypes.byref(nren), stream)
+                elif aux:
+                    depth = torch.empty(B, 1, H, W, dtype=torch.float32, device=device)
+                    alpha = torch.empty(B, 1, H, W, dtype=torch.float32, device=device)
+                    rc = lib.gsr_forward_raw_batch_aux(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(op), _ptr(sc), _ptr(ro),
+                                                       _ptr(color), _ptr(radii), ctypes.byref(handle) if want_ctx else None,
+                                                       ctypes.byref(nren), _ptr(depth), _ptr(alpha), stream)
                 else:
                     rc = lib.gsr_forward_raw_batch(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(op), _ptr(sc), _ptr(ro),
                                                    _ptr(color), _ptr(radii), ctypes.byref(handle) if want_ctx else None,
@@ -1062,12 +1126,23 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
         ctx.versions = _versions(ctx.kept + (obj,))
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
+        if aux:
+            return color, radii, depth, alpha
         if with_obj:
             return color, radii, objects
         return color, radii
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_objects=None):
+    def backward(ctx, grad_color, grad_radii, grad_objects=None, grad_alpha=None):
+        grad_depth = None
+        if ctx.aux:                                    # outputs (color, radii, depth, alpha)
+            grad_depth, grad_objects = grad_objects, None
+            res = _RasterizeGaussiansRawBatch._backward(ctx, grad_color, grad_objects, grad_depth, grad_alpha)
+            return res[:13] + (None, None)             # (objects_dc = None and aux: no gradients)
+        return _RasterizeGaussiansRawBatch._backward(ctx, grad_color, grad_objects, None, None)
+
+    @staticmethod
+    def _backward(ctx, grad_color, grad_objects, grad_depth, grad_alpha):
         _check_versions(ctx.kept + (ctx.obj,), ctx.versions)
         x, dc, rest, op, sc, ro = ctx.kept
         if x is None:                                  # an empty scene: empty gradients
@@ -1140,6 +1215,8 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
             with torch.cuda.device(device):
                 stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
                 acc = 1 if (bucket is not None and bset is None and not bucket.fresh) else 0
+                geo = need[0] or need[1] or need[4] or need[5] or need[6]
+                aux_keep = _arm_aux_grads(lib, ctx.holder, grad_depth, grad_alpha, (B, H, W), device) if (ctx.aux and geo) else ()
                 if bset is not None and with_obj:
                     # per-view object gradients [B,P,16], summed here in view order (autograd's association)
                     d_objv = out(d_obj is not None, B, P, NUM_OBJECTS)
@@ -1210,7 +1287,7 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
 
 def rasterize_gaussians_raw_batch(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, settings_list,
                                   grad_bucket: Optional["GradBucket"] = None, grad_norms: Optional["GradNorms"] = None,
-                                  cache: Optional["RenderCache"] = None, cache_key=None, objects_dc=None):
+                                  cache: Optional["RenderCache"] = None, cache_key=None, objects_dc=None, aux: bool = False):
     """(color[B,3,H,W], radii[B,P]) of B views (a list of GaussianRasterizationSettings that agree in image size, scale
     modifier and SH degree) of one set of RAW parameters, through one launch chain: every image and radius is bit for bit
     what rasterize_gaussians_raw gives for that view alone, and the backward leaves the SUM over the views of the
@@ -1218,7 +1295,13 @@ def rasterize_gaussians_raw_batch(xyz, means2D, features_dc, features_rest, opac
     (viewspace_points.grad of the reference, one slice per view), or None.
     objects_dc ([P,16] or [P,1,16] object features, or None = no object channels): -> (color, radii, objects[B,16,H,W]),
     every object map bit for bit rasterize_gaussians_raw's for that view; objects_dc.grad receives the single-view object
-    gradients summed in view order (a GradBucket or GradBucketSet does not hold it)."""
+    gradients summed in view order (a GradBucket or GradBucketSet does not hold it).
+    aux=True (not with objects_dc): -> (color, radii, depth[B,1,H,W], alpha[B,1,H,W]), both differentiable; every map bit for
+    bit rasterize_gaussians_raw(..., aux=True)'s for that view; the render cache is bypassed."""
+    if aux:
+        keep = _wants_backward(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation)
+        return _RasterizeGaussiansRawBatch.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
+                                                 list(settings_list), keep, grad_bucket, grad_norms, None, False, objects_dc, True)
     keep = _wants_backward(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, objects_dc)
     # `cache` (a RenderCache) + `cache_key` (one per tuple of cameras): a batch whose geometry inputs and cameras are unchanged
     # since the key's last render re-uses that render's binning for all B views (gsr_ctx_rerender on the batch context)
@@ -1240,10 +1323,17 @@ def _wants_backward(*tensors) -> bool:
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation,
                             raster_settings, grad_bucket: Optional["GradBucket"] = None, cache: Optional["RenderCache"] = None,
-                            cache_key=None, grad_norms: Optional["GradNorms"] = None):
+                            cache_key=None, grad_norms: Optional["GradNorms"] = None, aux: bool = False):
     """(color[3,H,W], radii[P], objects[16,H,W]) from the RAW parameters of a reference-style GaussianModel
     (_xyz, _features_dc, _features_rest, _objects_dc or None, _opacity, _scaling, _rotation): equal to the
-    getters (scene/gaussian_model.py:97-124) followed by GaussianRasterizer.forward, in one fused pass."""
+    getters (scene/gaussian_model.py:97-124) followed by GaussianRasterizer.forward, in one fused pass.
+    aux=True: -> (color, radii, objects, depth[1,H,W], alpha[1,H,W]) -- alpha = 1 - final transmittance, depth = sum of
+    z_i alpha_i T_i (not divided by alpha; depth / alpha is the expected depth of the covered part) -- both differentiable
+    w.r.t. xyz, opacity, scaling and rotation; the render cache is bypassed."""
+    if aux:
+        keep = _wants_backward(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation)
+        return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation,
+                                            raster_settings, keep, grad_bucket, None, False, grad_norms, True)
     keep = _wants_backward(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation)
     # `cache` (a RenderCache) + `cache_key` (one per camera): a render whose geometry inputs are unchanged since the key's
     # last render re-uses that render's binning (gsr_ctx_rerender)
@@ -1456,8 +1546,11 @@ def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Opt
 
 
 def rasterize_gaussians(means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, aux: bool = False):
     keep = _wants_backward(means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+    if aux:
+        return _RasterizeGaussians.apply(means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings, keep, True)
     return _RasterizeGaussians.apply(means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, keep)
 
@@ -1485,14 +1578,17 @@ class GaussianRasterizer(nn.Module):
             return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, sh_objs=None, colors_precomp=None, scales=None,
-                rotations=None, cov3D_precomp=None):
+                rotations=None, cov3D_precomp=None, aux=False):
+        """-> (color[3,H,W], radii[P], objects[16,H,W]); with aux=True -> (color, radii, objects, depth[1,H,W], alpha[1,H,W]):
+        alpha = 1 - final transmittance, depth = sum of z_i alpha_i T_i over the blended splats (view depth z_i; not divided
+        by alpha, no background term), both differentiable w.r.t. means, opacities, scales and rotations / cov3D."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, sh_objs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, self.raster_settings)
+                                   cov3D_precomp, self.raster_settings, aux)
 
 
 # ---- introspection used by the benchmark / tests -----------------------------------------------------------

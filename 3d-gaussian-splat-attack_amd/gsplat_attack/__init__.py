@@ -26,3 +26,11 @@ def patch_reference(module_name: str = "gaussian_renderer") -> int:
             setattr(m, "render", fused)
             n += 1
     return n
+
+
+def __getattr__(name):
+    # the consumers of the depth / alpha maps, importable from the package without loading the attack loop up front
+    if name in ("composite_over", "bbox_from_alpha", "benign_bboxes"):
+        from . import attack
+        return getattr(attack, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -571,11 +571,62 @@ def bbox_from_render(image: torch.Tensor, threshold: int = 20):
     return (int(cols[0]), int(rows[0]), int(cols[-1]) + 1, int(rows[-1]) + 1)
 
 
+def bbox_from_alpha(alpha: torch.Tensor, alpha_threshold: float):
+    """getbbox() of the pixels whose accumulated opacity (the rasteriser's alpha map, [H,W] or [1,H,W]) exceeds
+    `alpha_threshold`: the target's silhouette itself, dark parts included, instead of bbox_from_render's luma test.
+    (left, upper, right, lower) with right / lower exclusive, or None when no pixel is above the threshold."""
+    a = alpha.detach()
+    if a.dim() == 3 and a.shape[0] == 1:
+        a = a[0]
+    if a.dim() != 2:
+        raise ValueError(f"bbox_from_alpha: alpha must be [H,W] or [1,H,W], got {tuple(alpha.shape)}")
+    on = a > float(alpha_threshold)
+    rows = torch.nonzero(on.any(dim=1)).flatten()
+    if rows.numel() == 0:
+        return None
+    cols = torch.nonzero(on.any(dim=0)).flatten()
+    return (int(cols[0]), int(rows[0]), int(cols[-1]) + 1, int(rows[-1]) + 1)
+
+
+def composite_over(result, background: torch.Tensor) -> torch.Tensor:
+    """Paste a render made on a BLACK background over an arbitrary image, differentiably:
+    result["render"] + (1 - result["render_alpha"]) * background.  `result`: the dict of render() ([3,H,W] / [1,H,W]) or
+    render_batch() ([B,3,H,W] / [B,1,H,W]) under PipelineParams(aux_outputs=True); `background`: [3,H,W], or [B,3,H,W] for
+    a batch (a [3,H,W] image is pasted behind every view).  The rasteriser blends one constant colour per view; this is
+    how a loss sees the target in front of a photograph, with gradients through colour and alpha.
+    The render's own background must have been black -- it is part of result["render"] already, and a second one would
+    be added on top: checked on the pixels the target leaves fully uncovered (alpha == 0), which show the background alone."""
+    if "render_alpha" not in result:
+        raise KeyError("composite_over: the result has no 'render_alpha' (render with PipelineParams(aux_outputs=True))")
+    image, alpha = result["render"], result["render_alpha"]
+    if image.dim() not in (3, 4) or alpha.dim() != image.dim() or image.shape[-3] != 3 or alpha.shape[-3] != 1 \
+            or image.shape[-2:] != alpha.shape[-2:] or (image.dim() == 4 and image.shape[0] != alpha.shape[0]):
+        raise ValueError(f"composite_over: render {tuple(image.shape)} and render_alpha {tuple(alpha.shape)} do not belong together")
+    if background.dim() not in (3, image.dim()) or tuple(background.shape[-3:]) != tuple(image.shape[-3:]) \
+            or (background.dim() == 4 and background.shape[0] != image.shape[0]):
+        raise ValueError(f"composite_over: background {tuple(background.shape)} does not match the render {tuple(image.shape)}")
+    if background.device != image.device:
+        raise ValueError(f"composite_over: background on {background.device}, render on {image.device}")
+    with torch.no_grad():
+        bare = (alpha == 0).expand_as(image)
+        if bool((image.detach()[bare] != 0).any()):
+            raise ValueError("composite_over: the render was not made on a black background (uncovered pixels are not zero)")
+    return image + (1.0 - alpha) * background.to(image.dtype)
+
+
 @torch.no_grad()
-def benign_bboxes(model, cameras: Sequence, pipe: Optional[PipelineParams] = None, threshold: int = 20) -> list:
+def benign_bboxes(model, cameras: Sequence, pipe: Optional[PipelineParams] = None, threshold: int = 20,
+                  alpha_threshold: Optional[float] = None) -> list:
     """The benign pass in front of the attack loop (attack.py:434-461): every view rendered on a BLACK background
-    (whatever the attack's background is) and turned into the ground-truth box the detector loss is given."""
+    (whatever the attack's background is) and turned into the ground-truth box the detector loss is given.
+    alpha_threshold (default None = the reference's luma test): the box is getbbox() of the pixels whose accumulated
+    opacity exceeds it (bbox_from_alpha) -- the silhouette, which the luma test loses where the object is dark."""
+    if alpha_threshold is not None and not 0.0 <= float(alpha_threshold) < 1.0:
+        raise ValueError(f"benign_bboxes: alpha_threshold must lie in [0, 1), got {alpha_threshold}")
     pipe = pipe or PipelineParams(skip_objects=True)
+    if alpha_threshold is not None and not getattr(pipe, "aux_outputs", False):
+        pipe = copy.copy(pipe)
+        pipe.aux_outputs = True
     if getattr(pipe, "render_cache", None) is not None or getattr(pipe, "grad_bucket", None) is not None:
         # one forward per view, never rendered again under this background: no kept context (~250 MB per view at 1 M
         # Gaussians / 1080p), no gradient bucket
@@ -584,6 +635,8 @@ def benign_bboxes(model, cameras: Sequence, pipe: Optional[PipelineParams] = Non
         pipe.grad_bucket = None
     black = torch.zeros(3, device=model.get_xyz.device)
     with torch.no_grad():
+        if alpha_threshold is not None:
+            return [bbox_from_alpha(render(cam, model, pipe, black)["render_alpha"], alpha_threshold) for cam in cameras]
         return [bbox_from_render(render(cam, model, pipe, black)["render"], threshold) for cam in cameras]
 
 

@@ -23,7 +23,11 @@ class PipelineParams:
 
     def __init__(self, convert_SHs_python: bool = False, compute_cov3D_python: bool = False, debug: bool = False,
                  skip_objects: bool = False, fused_activations: bool = True, viewspace_grad: bool = True,
-                 grad_bucket=None, render_cache=None, grad_norms=None):
+                 grad_bucket=None, render_cache=None, grad_norms=None, aux_outputs: bool = False):
+        # extension (default off = exactly the reference's result keys): render() / render_batch() also return
+        # "render_depth" (sum of z_i alpha_i T_i, view depth; not divided by alpha) and "render_alpha" (1 - final
+        # transmittance), [1,H,W] ([B,1,H,W] for a batch), both differentiable; such renders bypass the render cache
+        self.aux_outputs = aux_outputs
         self.convert_SHs_python = convert_SHs_python
         self.compute_cov3D_python = compute_cov3D_python
         self.debug = debug
@@ -135,10 +139,14 @@ class RenderResult(dict):
         return dict.__repr__(self)
 
 
-def _result(image, screenspace_points, radii, objects) -> dict:
-    """The dict of reference gaussian_renderer/__init__.py:99-103 (the image is NOT clamped)."""
-    return RenderResult(render=image, viewspace_points=screenspace_points, visibility_filter=None, radii=radii,
-                        render_object=objects)
+def _result(image, screenspace_points, radii, objects, aux=None) -> dict:
+    """The dict of reference gaussian_renderer/__init__.py:99-103 (the image is NOT clamped); aux = (depth, alpha) adds the
+    two keys of PipelineParams(aux_outputs=True)."""
+    res = RenderResult(render=image, viewspace_points=screenspace_points, visibility_filter=None, radii=radii,
+                       render_object=objects)
+    if aux is not None:
+        res["render_depth"], res["render_alpha"] = aux
+    return res
 
 
 def _python_colours(cam, pc):
@@ -177,11 +185,18 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     screenspace_points = _zero_points(pc.get_xyz, bool(getattr(pipe, "viewspace_grad", True)))
     st = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     no_objects = bool(getattr(pipe, "skip_objects", False))
+    want_aux = bool(getattr(pipe, "aux_outputs", False))
 
     if takes_fused_path(pc, pipe, override_color):
         bucket = getattr(pipe, "grad_bucket", None)
         if callable(bucket):
             bucket = bucket()
+        if want_aux:
+            image, radii, objects, depth, alpha = rasterize_gaussians_raw(
+                pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, None if no_objects else pc._objects_dc,
+                pc._opacity, pc._scaling, pc._rotation, st, grad_bucket=bucket,
+                grad_norms=getattr(pipe, "grad_norms", None), aux=True)
+            return _result(image, screenspace_points, radii, objects, (depth, alpha))
         image, radii, objects = rasterize_gaussians_raw(
             pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, None if no_objects else pc._objects_dc,
             pc._opacity, pc._scaling, pc._rotation, st, grad_bucket=bucket,
@@ -205,6 +220,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         kw["colors_precomp"] = _python_colours(viewpoint_camera, pc)
     else:
         kw["shs"] = pc.get_features
+    if want_aux:
+        image, radii, objects, depth, alpha = GaussianRasterizer(raster_settings=st)(aux=True, **kw)
+        return _result(image, screenspace_points, radii, objects, (depth, alpha))
     image, radii, objects = GaussianRasterizer(raster_settings=st)(**kw)
     return _result(image, screenspace_points, radii, objects)
 
@@ -254,6 +272,14 @@ def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0
     if callable(bucket):
         bucket = bucket()
     key = (getattr(pipe, "cache_tag", "view"), "batch-obj" if objects else "batch") + tuple(id(c) for c in cams)
+    if bool(getattr(pipe, "aux_outputs", False)):
+        if objects:
+            raise ValueError("render_batch: PipelineParams(aux_outputs=True) with objects=True is not supported")
+        image, radii, depth, alpha = rasterize_gaussians_raw_batch(
+            pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation, sts,
+            grad_bucket=bucket, grad_norms=getattr(pipe, "grad_norms", None), aux=True)
+        obj_map = _zero_scalar(image.device).unsqueeze(0).expand(B, 16, image.shape[2], image.shape[3])
+        return _result(image, screenspace_points, radii, obj_map, (depth, alpha))
     out = rasterize_gaussians_raw_batch(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
                                         pc._scaling, pc._rotation, sts, grad_bucket=bucket,
                                         grad_norms=getattr(pipe, "grad_norms", None),

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define GSR_VERSION 603 /* 0.6.3: the groups set-up (gsr_group_classify, gsr_convex_hull_planes, gsr_points_in_hull); 0.6.2: the batch entry points with object channels (gsr_*_batch_obj*); 0.6.1: the batch entry points, gsr_pgd_step_multi, gsr_forward_raw2_batch, gsr_ctx_rerender on batch contexts */
+#define GSR_VERSION 604 /* 0.6.4: depth and alpha maps (gsr_forward*_aux, gsr_ctx_set_aux_grads); 0.6.3: the groups set-up (gsr_group_classify, gsr_convex_hull_planes, gsr_points_in_hull); 0.6.2: the batch entry points with object channels (gsr_*_batch_obj*); 0.6.1: the batch entry points, gsr_pgd_step_multi, gsr_forward_raw2_batch, gsr_ctx_rerender on batch contexts */
 #define GSR_NUM_OBJECTS 16 /* object-feature channels, reference scene/gaussian_model.py:52 */
 
 enum {
@@ -359,6 +359,55 @@ int gsr_ctx_rerender(GsrCtx* ctx, const float* features_dc, const float* feature
 
 /* Releases the context's workspace back to the pool (stream-ordered: safe right after enqueueing backward). */
 void gsr_ctx_free(GsrCtx* ctx);
+
+/*
+ * Depth and alpha maps from the compositors (0.6.4).  Two optional per-pixel outputs of the forward, accumulated in the
+ * same walk of the tile list that blends the colour, and two optional incoming gradients of the backward.
+ *   out_alpha [H,W]  A = 1 - T_final: the sum of alpha_i T_i over exactly the entries the colour walk blends (same
+ *                    alpha >= 1/255 test, power <= 0, min(0.99, .) cap, stop when T (1 - alpha) < 1e-4).  No background
+ *                    term.  Bit for bit 1.0f - final_T of the same forward (gsr_ctx_export item 3).
+ *   out_depth [H,W]  D = sum of z_i alpha_i T_i over the same entries, z_i the float32 view depth of the splat (the value
+ *                    the depth sort keys on).  A colour channel whose colour is z_i and whose background is 0: NOT divided
+ *                    by alpha and with no background term.  The expected depth of the covered part of a pixel is D / A,
+ *                    one tensor division for a caller who wants it (undefined where A = 0).
+ * The _aux entry points take the argument list of the function they are named after plus (out_depth, out_alpha) in front
+ * of `stream`; either may be NULL (not wanted; both NULL: the plain call).  Batch shapes are [B,H,W].  Everything else
+ * the plain call writes is bit for bit unchanged.  GSR_FLAG_NEEDLE_DOUBLE is refused (GSR_ERR_INVALID).
+ * Backward: gsr_ctx_set_aux_grads(ctx, grad_depth, grad_alpha) arms the NEXT gsr_backward / gsr_backward_raw /
+ * gsr_backward_raw_into / gsr_backward_raw_batch_into of this context (grad_depth, grad_alpha: [H,W] or [B,H,W] device
+ * pointers that must stay valid until that backward has run; either may be NULL = zero; both NULL disarms).  The armed
+ * backward adds, to the gradients of opacity, means (3D and dmeans2D), scales, rotations / cov3D, what the two maps
+ * contribute through alpha_i -- per pixel the colour walk's c_i . g_C becomes c_i . g_C + z_i g_D + g_A, both extra
+ * channels having background 0 -- and grad_depth additionally through z_i: dL/dz_i = sum over pixels of alpha_i T_i g_D,
+ * dz_i / dmean = viewmatrix[0..2][2].  The 0.99 cap is transparent as for colour.  SH / colour / object-feature gradients
+ * receive nothing from the maps.  With all-zero aux gradients every gradient is bit for bit that of the unarmed backward
+ * taking the same walk (the nine sums of the colour backward keep their arithmetic; see "Long tile lists" below).
+ * One-shot: every backward takes the request and disarms the context at its top, whatever its own fate.
+ * Long tile lists: a backward with grad_alpha alone walks segments as the colour backward does; one with grad_depth walks
+ * whole lists (the boundary records hold no running depth), like a backward with grad_objects.
+ * Refused with GSR_ERR_STATE: arming a context whose forward was not an _aux call, a forward-only or re-rendered (
+ * gsr_ctx_rerender refuses aux contexts) one.  Refused with GSR_ERR_INVALID by the backward that finds the context armed:
+ * gsr_backward_raw_batch_views / _obj_views (per-view gradients), gsr_backward_raw_chunked with more than one range, a
+ * backward that is also handed grad_objects, one that asks for no geometry gradient at all, and a gsr_forward context with
+ * K != 16 SH coefficients.  Never silently ignored.
+ * Non-finite inputs: a culled Gaussian leaves both maps and their gradients bit for bit as if it were not in the scene.
+ */
+int gsr_forward_aux(const GsrSettings* settings, int32_t P, int32_t K, const float* means3D, const float* shs,
+                    const float* sh_objs, const float* colors_precomp, const float* opacities, const float* scales,
+                    const float* rotations, const float* cov3D_precomp, float* out_color, float* out_objects,
+                    int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha,
+                    void* stream);
+int gsr_forward_raw_aux(const GsrSettings* settings, int32_t P, const float* xyz, const float* features_dc,
+                        const float* features_rest, const float* objects_dc, const float* opacity_logit,
+                        const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
+                        int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha,
+                        void* stream);
+int gsr_forward_raw_batch_aux(const GsrSettings* settings, int32_t B, int32_t P, const float* xyz,
+                              const float* features_dc, const float* features_rest, const float* opacity_logit,
+                              const float* log_scaling, const float* rotation_raw, float* out_color, int32_t* radii,
+                              GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha, void* stream);
+int gsr_ctx_set_aux_grads(GsrCtx* ctx, const float* grad_depth, const float* grad_alpha);
+
 
 /* Frustum test only (view-space z > 0.2): present[P] = 1/0.  Replaces GaussianRasterizer.markVisible. */
 int gsr_mark_visible(const GsrSettings* settings, int32_t P, const float* means3D, uint8_t* present, void* stream);
