@@ -1,6 +1,7 @@
 """Long tile lists walked as segments by the backward (north_star: prefix-scan for transmittance) against the whole-list
 walk they replace: same image bits, same gradients within float32 rounding -- at sizes where many tiles are split, for
-both backward tile splits."""
+both backward tile splits.  (Both walks against the float64 oracle, on lists built to end on the batch and segment
+boundaries: tests/test_gpu_list_edges.py.)"""
 import pytest
 import torch
 
