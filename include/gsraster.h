@@ -20,6 +20,35 @@
  *     the library owns an internal caching workspace pool per device and the opaque GsrCtx.
  *   - gradient outputs are fully written (zeros for culled Gaussians): no pre-zeroing needed.
  *
+ * Host threads (tests/test_gpu_reentrancy.py).  Exactly this is promised:
+ *   - calls on DIFFERENT contexts -- forwards, which create one, included -- may run concurrently from different host
+ *     threads: forwards beside each other when every thread passes a stream of its own, and a forward beside the
+ *     backward / free of another context on one shared stream.  (Two forwards at once on the SAME stream would share that
+ *     stream's side stream and its event pair; that is neither tested nor promised.)  The pool, the pinned count slots
+ *     and the other process-wide tables are locked inside.  Results are bit for bit those of the same calls made one
+ *     after another;
+ *   - ONE context is used by one thread at a time.  It may change hands (forward on one thread, gsr_ctx_set_aux_grads,
+ *     gsr_backward* and gsr_ctx_free on another -- the autograd engine's pattern) if the caller orders the calls, e.g.
+ *     through a queue; nothing inside a context is locked;
+ *   - gsr_last_error() and the hand-over of the _aux entry points' extra pointers are per thread: a thread reads the
+ *     text of its own last refused call;
+ *   - streams: a call's work is ordered by the stream it is given: whatever the caller enqueues on that stream afterwards
+ *     runs behind it.  (A forward forks part of its work onto a side stream the library keeps per caller stream -- and,
+ *     with GSR_COMP_CUMASK set, its compositors onto a companion stream -- and joins both back into the caller's stream
+ *     before it returns.)  A context's backward or re-render (gsr_ctx_rerender) on ANOTHER stream than its previous use is
+ *     legal when the caller has ordered that stream behind the previous use (an event, or a host wait); the context's
+ *     workspace then follows the new stream, and gsr_ctx_free returns it to the pool for that stream.
+ *     gsr_ctx_export does NOT move the workspace: it only enqueues a copy out of it.  An export on another stream than
+ *     the context's last forward / re-render / backward needs that stream ordered behind that use, as above, and before
+ *     the context's next use or its gsr_ctx_free the caller must join the export's stream back into the context's stream
+ *     (an event) or wait for it on the host: the freed blocks are re-used in the order of the context's stream, which
+ *     knows nothing of the copy.  gsr_ctx_free itself waits for nothing: the context's last use must have been
+ *     enqueued, on whatever thread, before it is called.  A free block last used on one stream is handed
+ *     to a request on another only once the pool holds its soft cap (an eighth of the device memory, GSR_POOL_CAP_MB
+ *     overrides; read once per process) or the device is out of memory, and then behind a host wait for the old stream;
+ *   - gsr_trim_pool and gsr_profile* act on the whole process: gsr_trim_pool waits for the device and may be called while
+ *     contexts are alive (their blocks stay), but not while another thread is inside a call.
+ *
  * Non-finite and extreme inputs (a position or scale step of the attack can produce them: reference attack.py:500-511).
  * The published kernels turn them into undefined float -> int conversions and fully opaque garbage splats; here:
  *   - a Gaussian whose projected conic, pixel centre or view depth is not finite -- NaN or +-inf in its mean, scale,
