@@ -27,6 +27,7 @@
 #include "gsr_pgd.hip.h"
 #include "gsr_groups.hip.h"
 #include "gsr_hull.h"
+#include "gsr_image.hip.h"
 
 using namespace gsr;
 
@@ -1775,6 +1776,7 @@ int gsr_query(int32_t what, int64_t* out) {
       *out = (int64_t)pl.total;
       return GSR_OK;
     }
+    case 3: *out = GSR_CAP_IMAGE; return GSR_OK;     // capability bits
     default: return set_err(GSR_ERR_INVALID, "gsr_query: unknown item %d", what);
   }
 }
@@ -2093,6 +2095,86 @@ int gsr_points_in_hull(const float* xyz, int32_t P, const double* planes, int32_
   hipLaunchKernelGGL(k_points_in_hull, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      xyz, P, reinterpret_cast<const double4*>(planes), F, bbox, tau, mask_in, out);
   LAUNCH_CHECK("gsr_points_in_hull");
+  return GSR_OK;
+}
+
+// ---- image front end (gsr_image.h / gsr_image.hip.h): no allocation, no copy, no host wait; the spec and the
+// per-channel affine travel by value in the kernel arguments, so the calls are capturable and never touch the pool ----
+static int image_spec(const char* fn, const GsrResample* r, gsr_image::Spec& sp) {
+  if (!r) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (r->B < 1 || r->C < 1 || r->H < 1 || r->W < 1 || r->out_h < 1 || r->out_w < 1 || r->rh < 1 || r->rw < 1)
+    return set_err(GSR_ERR_INVALID, "%s: sizes must be >= 1 (B=%d C=%d H=%d W=%d out=%dx%d resized=%dx%d)", fn, r->B, r->C, r->H,
+                   r->W, r->out_h, r->out_w, r->rh, r->rw);
+  if (r->C > gsr_image::MAX_C) return set_err(GSR_ERR_INVALID, "%s: C=%d channels (1..%d)", fn, r->C, gsr_image::MAX_C);
+  if (r->top < 0 || r->left < 0) return set_err(GSR_ERR_INVALID, "%s: negative offset top=%d left=%d", fn, r->top, r->left);
+  if ((long long)r->top + r->rh > r->out_h || (long long)r->left + r->rw > r->out_w)
+    return set_err(GSR_ERR_INVALID, "%s: the resized image %dx%d at (top=%d, left=%d) does not fit the destination %dx%d", fn,
+                   r->rh, r->rw, r->top, r->left, r->out_h, r->out_w);
+  const unsigned long long lim = 0x7fffffffull, bc = (unsigned long long)r->B * (unsigned long long)r->C;
+  const unsigned long long sp_px = (unsigned long long)r->H * (unsigned long long)r->W;
+  const unsigned long long op_px = (unsigned long long)r->out_h * (unsigned long long)r->out_w;
+  if (sp_px > lim || op_px > lim || bc * sp_px > lim || bc * op_px > lim)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in the source or the destination", fn);
+  if (r->flags & ~GSR_RESAMPLE_CLAMP01) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, r->flags);
+  sp.C = r->C; sp.H = r->H; sp.W = r->W; sp.out_h = r->out_h; sp.out_w = r->out_w;
+  sp.rh = r->rh; sp.rw = r->rw; sp.top = r->top; sp.left = r->left;
+  sp.pad_value = r->pad_value;
+  sp.sy = gsr_image::axis_scale(r->H, r->rh);
+  sp.sx = gsr_image::axis_scale(r->W, r->rw);
+  sp.flags = r->flags;
+  sp.affine = (r->mean || r->inv_std) ? 1 : 0;
+  for (int c = 0; c < gsr_image::MAX_C; ++c) {
+    sp.mean[c] = (r->mean && c < r->C) ? r->mean[c] : 0.0f;
+    sp.inv_std[c] = (r->inv_std && c < r->C) ? r->inv_std[c] : 1.0f;
+  }
+  return GSR_OK;
+}
+
+int gsr_image_resample(const GsrResample* r, const float* src, float* dst, void* stream) {
+  gsr_image::Spec sp;
+  if (int rc = image_spec("gsr_image_resample", r, sp)) return rc;
+  if (!src || !dst) return set_err(GSR_ERR_INVALID, "gsr_image_resample: null src / dst");
+  const unsigned nbx = (unsigned)((sp.out_w + gsr_image::IMG_BX - 1) / gsr_image::IMG_BX);
+  const unsigned nby = (unsigned)((sp.out_h + gsr_image::IMG_BY - 1) / gsr_image::IMG_BY);
+  const unsigned long long blocks = (unsigned long long)nbx * nby * (unsigned long long)r->B;
+  if (blocks > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "gsr_image_resample: too many workgroups for one launch");
+  hipLaunchKernelGGL(gsr_image::k_image_resample, dim3((unsigned)blocks), dim3(gsr_image::IMG_BX, gsr_image::IMG_BY), 0,
+                     static_cast<hipStream_t>(stream), sp, src, dst, nbx, nby);
+  LAUNCH_CHECK("gsr_image_resample");
+  return GSR_OK;
+}
+
+int gsr_image_resample_backward(const GsrResample* r, const float* src, const float* grad_dst, float* grad_src,
+                                int32_t accumulate, void* stream) {
+  gsr_image::Spec sp;
+  if (int rc = image_spec("gsr_image_resample_backward", r, sp)) return rc;
+  if (!grad_dst || !grad_src) return set_err(GSR_ERR_INVALID, "gsr_image_resample_backward: null grad_dst / grad_src");
+  if ((sp.flags & GSR_RESAMPLE_CLAMP01) && !src)
+    return set_err(GSR_ERR_INVALID, "gsr_image_resample_backward: GSR_RESAMPLE_CLAMP01 needs src (the clamp's mask)");
+  const unsigned nbx = (unsigned)((sp.W + gsr_image::IMG_BX * 4 - 1) / (gsr_image::IMG_BX * 4));
+  const unsigned nby = (unsigned)((sp.H + gsr_image::IMG_BY - 1) / gsr_image::IMG_BY);
+  const unsigned long long blocks = (unsigned long long)nbx * nby * (unsigned long long)r->B;
+  if (blocks > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "gsr_image_resample_backward: too many workgroups for one launch");
+  const bool vec = (sp.W & 3) == 0 && ((uintptr_t)grad_src & 15) == 0 && (!(sp.flags & GSR_RESAMPLE_CLAMP01) || ((uintptr_t)src & 15) == 0);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)blocks), block(gsr_image::IMG_BX, gsr_image::IMG_BY);
+  if (vec) hipLaunchKernelGGL((gsr_image::k_image_resample_bwd<true>), grid, block, 0, st, sp, src, grad_dst, grad_src, (int)accumulate, nbx, nby);
+  else hipLaunchKernelGGL((gsr_image::k_image_resample_bwd<false>), grid, block, 0, st, sp, src, grad_dst, grad_src, (int)accumulate, nbx, nby);
+  LAUNCH_CHECK("gsr_image_resample_backward");
+  return GSR_OK;
+}
+
+int gsr_image_to_u8(const float* src, int32_t B, int32_t H, int32_t W, uint8_t* dst, void* stream) {
+  if (B < 1 || H < 1 || W < 1) return set_err(GSR_ERR_INVALID, "gsr_image_to_u8: sizes must be >= 1 (B=%d H=%d W=%d)", B, H, W);
+  const unsigned long long plane = (unsigned long long)H * (unsigned long long)W;
+  if (plane > 0x7fffffffull || 3ull * (unsigned long long)B * plane > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "gsr_image_to_u8: more than 2^31 - 1 elements");
+  if (!src || !dst) return set_err(GSR_ERR_INVALID, "gsr_image_to_u8: null src / dst");
+  const unsigned nbx = (unsigned)((plane + 1023) / 1024);
+  const int aligned = (plane & 3) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 3) == 0;
+  hipLaunchKernelGGL(gsr_image::k_image_to_u8, dim3(nbx * (unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), src,
+                     (size_t)plane, dst, nbx, aligned);
+  LAUNCH_CHECK("gsr_image_to_u8");
   return GSR_OK;
 }
 

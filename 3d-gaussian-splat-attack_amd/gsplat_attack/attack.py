@@ -698,6 +698,9 @@ def main():
     ap.add_argument("--classifier", default=None,
                     help="groups mode: Conv2d(16, C, 1) state dict (classifier.pth); without it the Gaussians in the middle "
                          "of the synthetic scene are labelled with the first id (scenes.synthetic_grouping)")
+    ap.add_argument("--letterbox", type=int, default=0, metavar="N",
+                    help="letterbox every render to N x N in front of the surrogate detector (detector_input.letterbox, "
+                         "the YOLO wrappers' input stage); 0: off")
     args = ap.parse_args()
     from .scenes import make_scene
     rank, world, local = gdist.init_from_env()
@@ -720,9 +723,13 @@ def main():
         model, background = split_group(model, mask3d)
         extra = {"select": info}
     recs = []
+    loss_fn = None
+    if args.letterbox > 0:
+        from .detector_input import DetectorInput, with_detector_input
+        loss_fn = with_detector_input(SurrogateDetector().to(dev), DetectorInput(letterbox=(args.letterbox, args.letterbox)))
     hist = pgd_attack(model, cams[:args.views], iters=args.iters, alpha=args.alpha, epsilon=args.epsilon,
                       groups=args.groups.split(","), norm=args.norm, log=recs.append, streams=args.streams,
-                      background=background)
+                      background=background, loss_fn=loss_fn)
     if rank == 0:
         secs = [r["seconds"] for r in recs[2:]] or [r["seconds"] for r in recs]
         print(json.dumps({"scene": spec.name, "P": int(model.get_xyz.shape[0]), "views": args.views, "gpus": world,

@@ -517,8 +517,57 @@ int gsr_convex_hull_planes(const double* pts, int64_t M, double* planes, int64_t
 int gsr_points_in_hull(const float* xyz, int32_t P, const double* planes, int32_t F, const double* bbox, double tau,
                        const uint8_t* mask_in, uint8_t* out, void* stream);
 
+/* ---- Image front end: what sits between the renders and a detector -------------------------------------------------
+ * gsr_image_resample: bilinear resize of src [B,C,H,W] to rh x rw, placed at (top, left) of dst [B,C,out_h,out_w], the
+ * rest of dst filled with pad_value (a letterbox; rh = out_h, rw = out_w, top = left = 0: a plain resize).  These are
+ * torch.nn.functional.interpolate's mode="bilinear", align_corners=False, size=(rh, rw) semantics.  Per axis (input
+ * size `in`, resized size `out`, output index d), all in float32 with every operation rounded on its own (no fused
+ * multiply-add):
+ *     scale = (float)in / (float)out
+ *     src   = scale * (d + 0.5f) - 0.5f;   if (src < 0) src = 0
+ *     i0    = min((int)src, in - 1);       i1 = i0 + (i0 < in - 1 ? 1 : 0)
+ *     l1    = clamp(src - (float)i0, 0, 1); l0 = 1 - l1
+ *     value = h0*(w0*a + w1*b) + h1*(w0*c + w1*d)     a, b from row i0; c, d from row i1; a, c from column i0
+ * GSR_RESAMPLE_CLAMP01: every source value is taken as v < 0 ? 0 : v > 1 ? 1 : v first.  mean / inv_std (HOST arrays of
+ * C floats, read during the call; NULL = 0 / 1; both NULL: no affine at all): value -> (value - mean[c]) * inv_std[c].
+ * pad_value is written as given, not normalised.
+ *
+ * gsr_image_resample_backward: grad_src [B,C,H,W] from grad_dst [B,C,out_h,out_w] in GATHER form.  grad_src[y,x] is the
+ * sum of ((h*w) * g) terms -- the weight product rounded, the product with g rounded, then added -- over the destination
+ * pixels that sample (y,x): output rows ascending, inside a row output columns ascending, inside one output pixel the
+ * roles (row i0, col i0), (i0, i1), (i1, i0), (i1, i1).  A role counts only if it names (y,x); at the clamped last row or
+ * column i0 and i1 name the same pixel and both terms count.  The total is multiplied by inv_std[c] under the affine and
+ * by (0 <= v && v <= 1) under GSR_RESAMPLE_CLAMP01 (torch.clamp's inclusive mask; a NaN source gives 0; src is read
+ * only then and may be NULL otherwise).  Every source pixel is written exactly once (zero where nothing samples it), or
+ * added to what grad_src holds when accumulate != 0: no memset, no atomics, the same bits on every run.  16-byte stores
+ * when W % 4 == 0 and the tensors start on 16-byte boundaries.
+ *
+ * gsr_image_to_u8: src [B,3,H,W] float -> dst [B,H,W,3] uint8, (uint8)(clamp(v,0,1) * 255.0f) with truncation, NaN -> 0:
+ * integer-equal to (x.clamp(0,1) * 255).byte().permute(0,2,3,1) for finite input.
+ *
+ * All three: src, dst, grad_* are DEVICE pointers; 1 <= C <= 4; every size >= 1; 0 <= top, top + rh <= out_h, 0 <= left,
+ * left + rw <= out_w; at most 2^31 - 1 elements per tensor.  Violations return GSR_ERR_INVALID before any device call.
+ * One kernel launch on `stream`, no allocation, no copy, no host synchronisation: capturable and re-entrant. */
+#define GSR_RESAMPLE_CLAMP01 1u
+typedef struct GsrResample {
+  int32_t B, C, H, W;        /* source [B,C,H,W], 1 <= C <= 4 */
+  int32_t out_h, out_w;      /* destination [B,C,out_h,out_w] */
+  int32_t rh, rw, top, left; /* resized image and where it sits in the destination */
+  float pad_value;
+  const float* mean;         /* HOST, C floats, or NULL (0) */
+  const float* inv_std;      /* HOST, C floats, or NULL (1) */
+  uint32_t flags;
+} GsrResample;
+int gsr_image_resample(const GsrResample* spec, const float* src, float* dst, void* stream);
+int gsr_image_resample_backward(const GsrResample* spec, const float* src, const float* grad_dst, float* grad_src,
+                                int32_t accumulate, void* stream);
+int gsr_image_to_u8(const float* src, int32_t B, int32_t H, int32_t W, uint8_t* dst, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
- * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info). */
+ * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
+ * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
+ * (gsr_image_resample, gsr_image_resample_backward, gsr_image_to_u8). */
+#define GSR_CAP_IMAGE 1
 int gsr_query(int32_t what, int64_t* out);
 
 /* Per-context numbers for roofline accounting: what 0 = num_rendered (N; waits for the forward's count if it was
