@@ -28,6 +28,7 @@
 #include "gsr_groups.hip.h"
 #include "gsr_hull.h"
 #include "gsr_image.hip.h"
+#include "gsr_detect.hip.h"
 
 using namespace gsr;
 
@@ -1776,7 +1777,7 @@ int gsr_query(int32_t what, int64_t* out) {
       *out = (int64_t)pl.total;
       return GSR_OK;
     }
-    case 3: *out = GSR_CAP_IMAGE; return GSR_OK;     // capability bits
+    case 3: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT; return GSR_OK;     // capability bits
     default: return set_err(GSR_ERR_INVALID, "gsr_query: unknown item %d", what);
   }
 }
@@ -2175,6 +2176,144 @@ int gsr_image_to_u8(const float* src, int32_t B, int32_t H, int32_t W, uint8_t* 
   hipLaunchKernelGGL(gsr_image::k_image_to_u8, dim3(nbx * (unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), src,
                      (size_t)plane, dst, nbx, aligned);
   LAUNCH_CHECK("gsr_image_to_u8");
+  return GSR_OK;
+}
+
+// ---- detector output stage (gsr_detect.h / gsr_detect.hip.h): no allocation, no copy, no host wait; everything is
+// checked on the host before the first launch.  Workspace: [score B*A f32][class B*A i32][order B*maxc i32][ncand B i32],
+// each region rounded up to 256 bytes.
+static inline size_t det_round(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct DetWs {
+  size_t score, cls, order, ncand, bytes;
+};
+
+static DetWs det_layout(long long B, long long A, long long maxc) {
+  DetWs w;
+  w.score = 0;
+  w.cls = w.score + det_round((size_t)(B * A) * 4);
+  w.order = w.cls + det_round((size_t)(B * A) * 4);
+  w.ncand = w.order + det_round((size_t)(B * maxc) * 4);
+  w.bytes = w.ncand + det_round((size_t)B * 4);
+  return w;
+}
+
+static int det_spec(const char* fn, const GsrDetSpec* d, gsr_detect::Spec& sp) {
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->A < 1 || d->C < 1) return set_err(GSR_ERR_INVALID, "%s: sizes must be >= 1 (B=%d A=%d C=%d)", fn, d->B, d->A, d->C);
+  if ((d->layout != 0 && d->layout != 1) || (d->has_obj != 0 && d->has_obj != 1) || (d->box_format != 0 && d->box_format != 1))
+    return set_err(GSR_ERR_INVALID, "%s: layout, has_obj and box_format are 0 or 1 (got %d, %d, %d)", fn, d->layout, d->has_obj, d->box_format);
+  if (d->max_candidates < 1 || d->max_candidates > gsr_detect::MAX_CAND)
+    return set_err(GSR_ERR_INVALID, "%s: max_candidates=%d (1..%d)", fn, d->max_candidates, gsr_detect::MAX_CAND);
+  if (d->max_det < 1 || d->max_det > d->max_candidates)
+    return set_err(GSR_ERR_INVALID, "%s: max_det=%d (1..max_candidates=%d)", fn, d->max_det, d->max_candidates);
+  if (d->flags & ~GSR_DET_CLASS_AGNOSTIC) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
+  const unsigned long long K = 4ull + (unsigned long long)d->has_obj + (unsigned long long)d->C;
+  if ((unsigned long long)d->B * (unsigned long long)d->A > 0x7fffffffull ||
+      (unsigned long long)d->B * (unsigned long long)d->A * K > 0x7fffffffull ||
+      (unsigned long long)d->B * (unsigned long long)d->max_det * 6ull > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in pred or dets", fn);
+  sp.B = d->B; sp.A = d->A; sp.C = d->C; sp.layout = d->layout; sp.has_obj = d->has_obj; sp.box_format = d->box_format;
+  sp.conf_thr = d->conf_thr; sp.iou_thr = d->iou_thr; sp.max_candidates = d->max_candidates; sp.max_det = d->max_det;
+  sp.flags = d->flags; sp.ox = d->ox; sp.oy = d->oy; sp.sx = d->sx; sp.sy = d->sy;
+  return GSR_OK;
+}
+
+int gsr_det_workspace_bytes(const GsrDetSpec* d, int64_t* bytes) {
+  gsr_detect::Spec sp;
+  if (int rc = det_spec("gsr_det_workspace_bytes", d, sp)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_det_workspace_bytes: null bytes");
+  *bytes = (int64_t)det_layout(sp.B, sp.A, sp.max_candidates).bytes;
+  return GSR_OK;
+}
+
+int gsr_det_postprocess(const GsrDetSpec* d, const float* pred, void* ws, int64_t ws_bytes, float* dets, int32_t* counts,
+                        void* stream) {
+  gsr_detect::Spec sp;
+  if (int rc = det_spec("gsr_det_postprocess", d, sp)) return rc;
+  if (!pred || !ws || !dets || !counts) return set_err(GSR_ERR_INVALID, "gsr_det_postprocess: null pred / ws / dets / counts");
+  const DetWs w = det_layout(sp.B, sp.A, sp.max_candidates);
+  if (ws_bytes < (int64_t)w.bytes)
+    return set_err(GSR_ERR_INVALID, "gsr_det_postprocess: workspace of %lld bytes, %zu needed (gsr_det_workspace_bytes)", (long long)ws_bytes, w.bytes);
+  if (((uintptr_t)ws & 7) != 0) return set_err(GSR_ERR_INVALID, "gsr_det_postprocess: the workspace must be 8-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  float* score = reinterpret_cast<float*>(base + w.score);
+  int32_t* cls = reinterpret_cast<int32_t*>(base + w.cls);
+  int32_t* order = reinterpret_cast<int32_t*>(base + w.order);
+  int32_t* ncand = reinterpret_cast<int32_t*>(base + w.ncand);
+  const unsigned long long anchors = (unsigned long long)sp.B * (unsigned long long)sp.A;
+  if (sp.layout == 1) {
+    const unsigned blocks = (unsigned)((anchors + gsr_detect::SCORE_THREADS - 1) / gsr_detect::SCORE_THREADS);
+    hipLaunchKernelGGL((gsr_detect::k_det_score<1>), dim3(blocks), dim3(gsr_detect::SCORE_THREADS), 0, st, sp, pred, score, cls);
+  } else {
+    const unsigned per = gsr_detect::SCORE_THREADS / 16;
+    const unsigned blocks = (unsigned)((anchors + per - 1) / per);
+    hipLaunchKernelGGL((gsr_detect::k_det_score<0>), dim3(blocks), dim3(gsr_detect::SCORE_THREADS), 0, st, sp, pred, score, cls);
+  }
+  LAUNCH_CHECK("gsr_det_postprocess (score)");
+  hipLaunchKernelGGL(gsr_detect::k_det_select_sort, dim3((unsigned)sp.B), dim3(gsr_detect::SEL_THREADS), 0, st, sp.A,
+                     sp.max_candidates, (const float*)score, 1, sp.conf_thr, (const int32_t*)nullptr, order, ncand, counts + 1, 2);
+  LAUNCH_CHECK("gsr_det_postprocess (select)");
+  gsr_detect::NmsArgs na;
+  na.sp = sp; na.pred = pred; na.score = score; na.cls = cls; na.boxes = nullptr; na.order = order; na.ncand = ncand;
+  na.dets = dets; na.keep = nullptr; na.counts = counts;
+  hipLaunchKernelGGL((gsr_detect::k_det_nms<true>), dim3((unsigned)sp.B), dim3(gsr_detect::NMS_THREADS), 0, st, na);
+  LAUNCH_CHECK("gsr_det_postprocess (nms)");
+  return GSR_OK;
+}
+
+int gsr_det_nms(int32_t B, int32_t n, const float* boxes, const float* scores, const int32_t* classes, const int32_t* n_valid,
+                float iou_thr, int32_t max_det, void* ws, int64_t ws_bytes, int32_t* keep, int32_t* counts, void* stream) {
+  if (B < 1 || n < 1 || n > gsr_detect::MAX_CAND)
+    return set_err(GSR_ERR_INVALID, "gsr_det_nms: B=%d (>= 1), n=%d (1..%d)", B, n, gsr_detect::MAX_CAND);
+  if (max_det < 1 || max_det > n) return set_err(GSR_ERR_INVALID, "gsr_det_nms: max_det=%d (1..n=%d)", max_det, n);
+  if ((unsigned long long)B * (unsigned long long)n * 4ull > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "gsr_det_nms: more than 2^31 - 1 elements in boxes");
+  if (!boxes || !scores || !ws || !keep || !counts) return set_err(GSR_ERR_INVALID, "gsr_det_nms: null boxes / scores / ws / keep / counts");
+  const DetWs w = det_layout(B, n, n);
+  if (ws_bytes < (int64_t)w.bytes)
+    return set_err(GSR_ERR_INVALID, "gsr_det_nms: workspace of %lld bytes, %zu needed (gsr_det_workspace_bytes with A = max_candidates = n)",
+                   (long long)ws_bytes, w.bytes);
+  if (((uintptr_t)ws & 7) != 0) return set_err(GSR_ERR_INVALID, "gsr_det_nms: the workspace must be 8-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  int32_t* order = reinterpret_cast<int32_t*>(base + w.order);
+  int32_t* ncand = reinterpret_cast<int32_t*>(base + w.ncand);
+  hipLaunchKernelGGL(gsr_detect::k_det_select_sort, dim3((unsigned)B), dim3(gsr_detect::SEL_THREADS), 0, st, n, n, scores, 0, 0.0f,
+                     n_valid, order, ncand, (int32_t*)nullptr, 0);
+  LAUNCH_CHECK("gsr_det_nms (select)");
+  gsr_detect::NmsArgs na;
+  na.sp = gsr_detect::Spec{};
+  na.sp.B = B; na.sp.A = n; na.sp.C = 1; na.sp.box_format = 1; na.sp.iou_thr = iou_thr; na.sp.max_candidates = n; na.sp.max_det = max_det;
+  na.sp.flags = classes ? 0u : gsr_detect::CLASS_AGNOSTIC;
+  na.pred = nullptr; na.score = scores; na.cls = classes; na.boxes = boxes; na.order = order; na.ncand = ncand;
+  na.dets = nullptr; na.keep = keep; na.counts = counts;
+  hipLaunchKernelGGL((gsr_detect::k_det_nms<false>), dim3((unsigned)B), dim3(gsr_detect::NMS_THREADS), 0, st, na);
+  LAUNCH_CHECK("gsr_det_nms (nms)");
+  return GSR_OK;
+}
+
+int gsr_det_box_iou(const float* a, int32_t n, const float* b, int32_t m, float* iou, void* stream) {
+  if (n < 1 || m < 1) return set_err(GSR_ERR_INVALID, "gsr_det_box_iou: sizes must be >= 1 (n=%d m=%d)", n, m);
+  const unsigned long long total = (unsigned long long)n * (unsigned long long)m;
+  if (total > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "gsr_det_box_iou: more than 2^31 - 1 elements");
+  if (!a || !b || !iou) return set_err(GSR_ERR_INVALID, "gsr_det_box_iou: null a / b / iou");
+  hipLaunchKernelGGL(gsr_detect::k_det_box_iou, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     a, n, b, m, iou);
+  LAUNCH_CHECK("gsr_det_box_iou");
+  return GSR_OK;
+}
+
+int gsr_det_verdict(const float* dets, const int32_t* counts, int32_t B, int32_t max_det, const float* gt, int32_t target,
+                    int32_t untarget, int32_t is_targeted, float iou_match, int32_t* verdict, float* best, void* stream) {
+  if (B < 1 || max_det < 1) return set_err(GSR_ERR_INVALID, "gsr_det_verdict: sizes must be >= 1 (B=%d max_det=%d)", B, max_det);
+  if ((unsigned long long)B * (unsigned long long)max_det * 6ull > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "gsr_det_verdict: more than 2^31 - 1 elements in dets");
+  if (!dets || !counts || !verdict || !best) return set_err(GSR_ERR_INVALID, "gsr_det_verdict: null dets / counts / verdict / best");
+  hipLaunchKernelGGL(gsr_detect::k_det_verdict, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream), dets, counts,
+                     max_det, gt, target, untarget < 0 ? -1 : untarget, is_targeted != 0 ? 1 : 0, iou_match, verdict, best);
+  LAUNCH_CHECK("gsr_det_verdict");
   return GSR_OK;
 }
 

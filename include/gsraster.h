@@ -563,11 +563,92 @@ int gsr_image_resample_backward(const GsrResample* spec, const float* src, const
                                 int32_t accumulate, void* stream);
 int gsr_image_to_u8(const float* src, int32_t B, int32_t H, int32_t W, uint8_t* dst, void* stream);
 
+/* ---- Detector output stage: what sits behind a detector's network ----------------------------------------------------
+ * The reference runs this per view in host Python (predict_and_save of each detector wrapper under detectors/: score filter,
+ * ultralytics' NMS, torchvision's box_iou, an argmax and a Python bool).  Here it is four entries whose results are
+ * fixed bit for bit; csrc/gsr_detect.h holds the arithmetic, compiled for the kernels and for a host harness alike.
+ *
+ * gsr_det_postprocess: raw head output `pred` -> dets [B,max_det,6] (x1 y1 x2 y2 score class-as-float) and
+ * counts [B,2] (kept, above_thr).
+ *   Candidates.  One per anchor: score_c = cls_c, or with has_obj the single rounded float32 product obj * cls_c; the
+ *   anchor's class is the first maximum of score_c over c (lowest index on ties; a NaN score_c is never the maximum; if
+ *   no class compares above -inf the anchor has class 0 and score -inf), its score that maximum.  The anchor is a
+ *   candidate iff score > conf_thr, so a NaN score is dropped.  With has_obj, ultralytics also tests obj > conf_thr on
+ *   its own; for class scores in [0,1] the product cannot exceed obj, so that test is implied and is not made here.  One
+ *   label per anchor: ultralytics' multi_label mode (one candidate per class above the threshold) is not provided.
+ *   counts[b,1] is the number of candidates before any cap; if it exceeds max_candidates the first max_candidates of the
+ *   order below are kept, whatever the launch geometry.
+ *   Order, within an image: score descending (-0 and +0 equal), then anchor index ascending -- a total order, so every
+ *   output is identical on every run.
+ *   Boxes.  box_format 0: x1 = xc - w*0.5f, y1 = yc - h*0.5f, x2 = xc + w*0.5f, y2 = yc + h*0.5f; 1: as given.
+ *   IoU, float32, every operation rounded on its own (no fused multiply-add), torchvision's box_iou:
+ *       area = (x2 - x1) * (y2 - y1)
+ *       iw = max(min(ax2,bx2) - max(ax1,bx1), 0);  ih likewise;  inter = iw * ih
+ *       iou = inter / ((area_a + area_b) - inter)
+ *   NMS.  Greedy in the order above: a box is suppressed iff an earlier KEPT box has iou > iou_thr (strict; a NaN IoU,
+ *   from 0/0, suppresses nothing) and -- unless GSR_DET_CLASS_AGNOSTIC -- the same class integer.  ultralytics instead
+ *   shifts every box by class * 7680 and runs an agnostic NMS: boxes of different classes then never overlap, and boxes
+ *   of one class overlap as before up to the rounding of the shifted coordinates; the integer compare is that rule
+ *   without the rounding.  The walk stops after max_det keeps; counts[b,0] is their number.
+ *   Output.  Kept boxes in walk order, mapped x' = (x - ox) * sx, y' = (y - oy) * sy (each operation rounded on its
+ *   own; ox = oy = 0, sx = sy = 1 leaves them as they are), the score and the class; rows beyond counts[b,0] are zero.
+ *   ws: gsr_det_workspace_bytes(spec) bytes of device memory, 8-byte aligned, scratch for the duration of the call's
+ *   kernels.  Three launches on `stream`.
+ *
+ * gsr_det_nms: the same order and walk on caller boxes [B,n,4] (x1 y1 x2 y2), scores [B,n] and classes [B,n] (NULL:
+ * agnostic); entries at or beyond n_valid[b] (NULL: n) do not take part.  1 <= n <= 4096, 1 <= max_det <= n.  Scores
+ * order by their float comparison; NaN scores order by their bit image (above +inf with a clear sign bit, below -inf
+ * with a set one).  keep [B,max_det]: indices into the n entries in walk order, -1 beyond counts[b].  ws: what
+ * gsr_det_workspace_bytes reports for a spec with this B, A = max_candidates = n and this max_det.  Two launches.
+ *
+ * gsr_det_box_iou: iou [n,m] of boxes a [n,4] against b [m,4] (x1 y1 x2 y2), the arithmetic above.  One launch.
+ *
+ * gsr_det_verdict: the reference's success test (yolov5_detector.py:175-193, 239-245) for every image of a batch.
+ * dets / counts as gsr_det_postprocess writes them (counts [B,2]; only counts[b,0] is read, clamped to 0..max_det).
+ * gt [B,4] x1 y1 x2 y2 in the frame of dets; gt == NULL or a row holding a NaN: that image has no gt box.
+ *   with a gt box and rows: best = the first maximum of IoU(row, gt) over the kept rows, a NaN IoU counting as 0;
+ *       target_exists = best_iou > iou_match && class == target
+ *       untarget_absent = !(best_iou > iou_match && class == untarget)
+ *   without a gt box: target_exists = some kept class equals target; untarget_absent = none equals untarget
+ *   with no rows: target_exists = false, untarget_absent = true
+ * untarget < 0: none.  verdict[b]: bit 0 = success (is_targeted: target_exists && (untarget < 0 || untarget_absent);
+ * otherwise untarget_absent), bit 1 = target_exists, bit 2 = untarget_absent.  best [B,4]: (iou, score, class, row) of
+ * that best row, all -1 where there is none (no gt box or no rows).  The reference compares against 0.5; pass it as
+ * iou_match.  One launch, one wave per image.
+ *
+ * All entries: every tensor argument is a DEVICE pointer.  Sizes < 1, max_candidates > 4096, max_det > max_candidates
+ * (gsr_det_nms: n > 4096, max_det > n), layout / has_obj / box_format outside {0,1}, unknown flags, a workspace that
+ * is too small or not 8-byte aligned, a NULL required pointer, or more than 2^31 - 1 elements in a tensor return
+ * GSR_ERR_INVALID with a gsr_last_error text before any device call.  No allocation, no copy, no host synchronisation:
+ * everything is enqueued on `stream`; calls are re-entrant from several host threads (each with its own workspace). */
+#define GSR_DET_CLASS_AGNOSTIC 1u
+typedef struct GsrDetSpec {
+  int32_t B, A, C;           /* images, anchors per image, classes; all >= 1 */
+  int32_t layout;            /* 0: pred[B, A, 4+has_obj+C] (YOLOv3/v5);  1: pred[B, 4+has_obj+C, A] (YOLOv8/v11) */
+  int32_t has_obj;           /* 1: channel 4 is objectness, score = obj * cls (one rounded float32 product); 0: score = cls */
+  int32_t box_format;        /* 0: (xc, yc, w, h) -> x1 = xc - w*0.5f, x2 = xc + w*0.5f, ...;  1: (x1, y1, x2, y2) */
+  float   conf_thr, iou_thr;
+  int32_t max_candidates;    /* 1 .. 4096 */
+  int32_t max_det;           /* 1 .. max_candidates */
+  uint32_t flags;            /* GSR_DET_CLASS_AGNOSTIC */
+  float   ox, oy, sx, sy;    /* after NMS: x' = (x - ox) * sx, y' = (y - oy) * sy, each operation rounded on its own */
+} GsrDetSpec;
+int gsr_det_workspace_bytes(const GsrDetSpec* spec, int64_t* bytes);
+int gsr_det_postprocess(const GsrDetSpec* spec, const float* pred, void* ws, int64_t ws_bytes, float* dets, int32_t* counts,
+                        void* stream);
+int gsr_det_nms(int32_t B, int32_t n, const float* boxes, const float* scores, const int32_t* classes, const int32_t* n_valid,
+                float iou_thr, int32_t max_det, void* ws, int64_t ws_bytes, int32_t* keep, int32_t* counts, void* stream);
+int gsr_det_box_iou(const float* a, int32_t n, const float* b, int32_t m, float* iou, void* stream);
+int gsr_det_verdict(const float* dets, const int32_t* counts, int32_t B, int32_t max_det, const float* gt, int32_t target,
+                    int32_t untarget, int32_t is_targeted, float iou_match, int32_t* verdict, float* best, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
- * (gsr_image_resample, gsr_image_resample_backward, gsr_image_to_u8). */
+ * (gsr_image_resample, gsr_image_resample_backward, gsr_image_to_u8); GSR_CAP_DETECT = the detector output stage
+ * (gsr_det_workspace_bytes, gsr_det_postprocess, gsr_det_nms, gsr_det_box_iou, gsr_det_verdict). */
 #define GSR_CAP_IMAGE 1
+#define GSR_CAP_DETECT 2
 int gsr_query(int32_t what, int64_t* out);
 
 /* Per-context numbers for roofline accounting: what 0 = num_rendered (N; waits for the forward's count if it was
