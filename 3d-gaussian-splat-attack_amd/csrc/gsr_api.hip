@@ -29,6 +29,7 @@
 #include "gsr_hull.h"
 #include "gsr_image.hip.h"
 #include "gsr_detect.hip.h"
+#include "gsr_detloss.hip.h"
 
 using namespace gsr;
 
@@ -1777,7 +1778,7 @@ int gsr_query(int32_t what, int64_t* out) {
       *out = (int64_t)pl.total;
       return GSR_OK;
     }
-    case 3: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT; return GSR_OK;     // capability bits
+    case 3: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS; return GSR_OK;     // capability bits
     default: return set_err(GSR_ERR_INVALID, "gsr_query: unknown item %d", what);
   }
 }
@@ -2314,6 +2315,122 @@ int gsr_det_verdict(const float* dets, const int32_t* counts, int32_t B, int32_t
   hipLaunchKernelGGL(gsr_detect::k_det_verdict, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream), dets, counts,
                      max_det, gt, target, untarget < 0 ? -1 : untarget, is_targeted != 0 ? 1 : 0, iou_match, verdict, best);
   LAUNCH_CHECK("gsr_det_verdict");
+  return GSR_OK;
+}
+
+// ---- detector loss stage (gsr_detloss.h / gsr_detloss.hip.h): four launches, no allocation, no copy, no host wait;
+// everything is checked on the host before the first launch.  Workspace: [ov B*M*A f32][metric B*M*A f32][tgt B*A i32]
+// [ts B*A f32][ts_sum B f32][slab blocks*3 f32], each region rounded up to 256 bytes; the slab is sized for one anchor
+// per lane (the most blocks either path launches).
+struct DetLossWs {
+  size_t ov, metric, tgt, ts, ts_sum, slab, bytes;
+};
+
+static unsigned detloss_tiles(long long A, int v) {
+  const long long per = (long long)gsr_dloss::TERM_THREADS * v;
+  return (unsigned)((A + per - 1) / per);
+}
+
+static unsigned detloss_chunks(int C) { return 1u + (unsigned)((C + gsr_dloss::CLS_CHUNK - 1) / gsr_dloss::CLS_CHUNK); }
+
+static DetLossWs detloss_layout(const gsr_dloss::Spec& sp) {
+  const size_t BA = (size_t)sp.B * (size_t)sp.A, BMA = BA * (size_t)sp.M;
+  const size_t blocks = (size_t)detloss_tiles(sp.A, 1) * (size_t)detloss_chunks(sp.C) * (size_t)sp.B;
+  DetLossWs w;
+  w.ov = 0;
+  w.metric = w.ov + det_round(BMA * 4);
+  w.tgt = w.metric + det_round(BMA * 4);
+  w.ts = w.tgt + det_round(BA * 4);
+  w.ts_sum = w.ts + det_round(BA * 4);
+  w.slab = w.ts_sum + det_round((size_t)sp.B * 4);
+  w.bytes = w.slab + det_round(blocks * 3 * 4);
+  return w;
+}
+
+static int detloss_spec(const char* fn, const GsrDetLossSpec* d, gsr_dloss::Spec& sp) {
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->A < 1 || d->C < 1) return set_err(GSR_ERR_INVALID, "%s: sizes must be >= 1 (B=%d A=%d C=%d)", fn, d->B, d->A, d->C);
+  if (d->M < 1 || d->M > gsr_dloss::MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: M=%d gt rows per image (1..%d)", fn, d->M, gsr_dloss::MAX_ROWS);
+  if (d->nl < 1 || d->nl > gsr_dloss::MAX_LEVELS) return set_err(GSR_ERR_INVALID, "%s: nl=%d levels (1..%d)", fn, d->nl, gsr_dloss::MAX_LEVELS);
+  if (d->reg_max != gsr_dloss::REG_MAX) return set_err(GSR_ERR_INVALID, "%s: reg_max=%d (only %d is built)", fn, d->reg_max, gsr_dloss::REG_MAX);
+  if (d->topk < 1 || d->topk > gsr_dloss::MAX_TOPK) return set_err(GSR_ERR_INVALID, "%s: topk=%d (1..%d)", fn, d->topk, gsr_dloss::MAX_TOPK);
+  if (d->flags != 0u) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
+  const float fl[5] = {d->alpha, d->beta, d->w_box, d->w_cls, d->w_dfl};
+  for (int i = 0; i < 5; ++i)
+    if (!(fl[i] >= 0.0f) || !(fl[i] <= 3.0e38f))
+      return set_err(GSR_ERR_INVALID, "%s: alpha, beta, w_box, w_cls, w_dfl must be finite and >= 0", fn);
+  unsigned long long total = 0;
+  for (int i = 0; i < d->nl; ++i) {
+    if (d->level_h[i] < 1 || d->level_w[i] < 1 || !(d->level_stride[i] > 0.0f) || !(d->level_stride[i] <= 3.0e38f))
+      return set_err(GSR_ERR_INVALID, "%s: level %d is %d x %d with stride %g (sizes >= 1, a finite stride > 0)", fn, i,
+                     d->level_h[i], d->level_w[i], (double)d->level_stride[i]);
+    sp.h[i] = d->level_h[i]; sp.w[i] = d->level_w[i]; sp.stride[i] = d->level_stride[i];
+    sp.start[i] = (int32_t)(total > 0x7fffffffull ? 0x7fffffffull : total);
+    total += (unsigned long long)d->level_h[i] * (unsigned long long)d->level_w[i];
+    if (total > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "%s: the levels hold more than 2^31 - 1 anchors", fn);
+  }
+  for (int i = d->nl; i < gsr_dloss::MAX_LEVELS; ++i) { sp.h[i] = 1; sp.w[i] = 1; sp.stride[i] = 1.0f; sp.start[i] = 0x7fffffff; }
+  if (total != (unsigned long long)d->A)
+    return set_err(GSR_ERR_INVALID, "%s: the levels hold %llu anchors, A=%d", fn, total, d->A);
+  const unsigned long long K = 64ull + (unsigned long long)d->C;
+  if ((unsigned long long)d->B * (unsigned long long)d->A * K > 0x7fffffffull ||
+      (unsigned long long)d->B * (unsigned long long)d->A * (unsigned long long)d->M > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in pred or in the workspace's [B,M,A] arrays", fn);
+  if (d->B > 65535 || detloss_chunks(d->C) > 65535u)
+    return set_err(GSR_ERR_INVALID, "%s: B=%d (<= 65535), C=%d (<= %d)", fn, d->B, d->C, 65534 * gsr_dloss::CLS_CHUNK);
+  sp.B = d->B; sp.A = d->A; sp.C = d->C; sp.M = d->M; sp.nl = d->nl; sp.topk = d->topk;
+  sp.alpha = d->alpha; sp.beta = d->beta; sp.w_box = d->w_box; sp.w_cls = d->w_cls; sp.w_dfl = d->w_dfl;
+  return GSR_OK;
+}
+
+int gsr_detloss_workspace_bytes(const GsrDetLossSpec* d, int64_t* bytes) {
+  gsr_dloss::Spec sp;
+  if (int rc = detloss_spec("gsr_detloss_workspace_bytes", d, sp)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_detloss_workspace_bytes: null bytes");
+  *bytes = (int64_t)detloss_layout(sp).bytes;
+  return GSR_OK;
+}
+
+int gsr_detloss(const GsrDetLossSpec* d, const float* pred, const float* gt_boxes, const int32_t* gt_cls, void* ws,
+                int64_t ws_bytes, float* loss, float* grad_pred, int32_t* tgt, float* ts, void* stream) {
+  gsr_dloss::Spec sp;
+  if (int rc = detloss_spec("gsr_detloss", d, sp)) return rc;
+  if (!pred || !gt_boxes || !gt_cls || !ws || !loss)
+    return set_err(GSR_ERR_INVALID, "gsr_detloss: null pred / gt_boxes / gt_cls / ws / loss");
+  const DetLossWs w = detloss_layout(sp);
+  if (ws_bytes < (int64_t)w.bytes)
+    return set_err(GSR_ERR_INVALID, "gsr_detloss: workspace of %lld bytes, %zu needed (gsr_detloss_workspace_bytes)", (long long)ws_bytes, w.bytes);
+  if (((uintptr_t)ws & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_detloss: the workspace must be 16-byte aligned");
+  if ((((uintptr_t)pred | (uintptr_t)gt_boxes | (uintptr_t)gt_cls | (uintptr_t)loss | (uintptr_t)grad_pred | (uintptr_t)tgt |
+        (uintptr_t)ts) & 3) != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_detloss: every tensor must be 4-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  gsr_dloss::Args ar;
+  ar.sp = sp; ar.pred = pred; ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls;
+  ar.ov = reinterpret_cast<float*>(base + w.ov);
+  ar.metric = reinterpret_cast<float*>(base + w.metric);
+  ar.tgt = reinterpret_cast<int32_t*>(base + w.tgt);
+  ar.ts = reinterpret_cast<float*>(base + w.ts);
+  ar.ts_sum = reinterpret_cast<float*>(base + w.ts_sum);
+  ar.slab = reinterpret_cast<float*>(base + w.slab);
+  ar.loss = loss; ar.grad_pred = grad_pred; ar.tgt_out = tgt; ar.ts_out = ts;
+  const unsigned long long anchors = (unsigned long long)sp.B * (unsigned long long)sp.A;
+  hipLaunchKernelGGL(gsr_dloss::k_detloss_metrics, dim3((unsigned)((anchors + gsr_dloss::MET_THREADS - 1) / gsr_dloss::MET_THREADS)),
+                     dim3(gsr_dloss::MET_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_detloss (metrics)");
+  hipLaunchKernelGGL(gsr_dloss::k_detloss_assign, dim3((unsigned)sp.B), dim3(gsr_dloss::ASG_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_detloss (assign)");
+  const bool vec = (sp.A & 3) == 0 && ((uintptr_t)pred & 15) == 0 && ((uintptr_t)grad_pred & 15) == 0;
+  const unsigned tiles = detloss_tiles(sp.A, vec ? 4 : 1), chunks = detloss_chunks(sp.C);
+  const dim3 grid(tiles, chunks, (unsigned)sp.B);
+  if (vec)
+    hipLaunchKernelGGL((gsr_dloss::k_detloss_terms<4>), grid, dim3(gsr_dloss::TERM_THREADS), 0, st, ar);
+  else
+    hipLaunchKernelGGL((gsr_dloss::k_detloss_terms<1>), grid, dim3(gsr_dloss::TERM_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_detloss (terms)");
+  hipLaunchKernelGGL(gsr_dloss::k_detloss_final, dim3(1), dim3(gsr_dloss::FIN_THREADS), 0, st, ar, tiles * chunks * (unsigned)sp.B);
+  LAUNCH_CHECK("gsr_detloss (final)");
   return GSR_OK;
 }
 

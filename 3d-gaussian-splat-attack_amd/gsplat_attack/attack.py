@@ -5,7 +5,9 @@ per iteration, render the current batch of views (``attack.py:476-485``), turn t
 ``loss.backward()`` (:494), apply a projected step to the raw attributes (:496-511; the live call is the L2 colour step
 with alpha 0.5 / epsilon 5.0, ``configs/config.yaml:47-48``) and clear the gradients.  The victim detector is third
 party and out of scope: a fixed random convolutional "surrogate detector" supplies a
-differentiable scalar per render, or any callable ``loss_fn(renders[B,3,H,W]) -> scalar`` can be passed in.
+differentiable scalar per render, or any callable ``loss_fn(renders[B,3,H,W]) -> scalar`` can be passed in (one with the
+attribute ``takes_view_index = True``, such as detector_loss.make_loss_fn's, is also given ``idx=``, the global view
+indices of the renders).
 
 Defaults that differ from the reference, each with a switch that restores its behaviour:
   * gradients are zeroed every iteration; ``accumulate_grads=True`` reproduces the reference, whose
@@ -234,6 +236,12 @@ def pgd_attack(model, cameras: Sequence, *, iters: int = 20, alpha: float = 0.5,
     pipe = pipe or PipelineParams(skip_objects=True)
     bg = torch.zeros(3, device=dev) if bg is None else bg.to(dev)
     loss_fn = loss_fn or SurrogateDetector().to(dev)
+    if getattr(loss_fn, "takes_view_index", False):
+        # a loss that needs to know which views it is shown (detector_loss.make_loss_fn: every view has its own gt box)
+        # gets the global view indices of the renders; every other loss is called as before
+        loss_of = lambda imgs, ids: loss_fn(imgs, idx=list(ids))
+    else:
+        loss_of = lambda imgs, ids: loss_fn(imgs)
     rank, world = _world()
     my_idx = gdist.views_of_rank(len(cameras), rank, world)
     mine = [cameras[i] for i in my_idx]
@@ -359,13 +367,13 @@ def pgd_attack(model, cameras: Sequence, *, iters: int = 20, alpha: float = 0.5,
                 if timer is not None:
                     timer.lap("render")
                 if batch_loss:
-                    loss = loss_fn(imgs_b)
+                    loss = loss_of(imgs_b, my_idx)
                     if loss_reduction == "mean":
                         loss = loss * (len(mine) / len(cameras))
                     losses.append(loss.detach())
                 else:
                     # (unbind, not slices: a slice's backward materialises a zero [B,3,H,W] tensor per view and adds it in)
-                    per_view = [loss_fn(im[None]) for im in imgs_b.unbind(0)]
+                    per_view = [loss_of(im[None], [i]) for im, i in zip(imgs_b.unbind(0), my_idx)]
                     if loss_reduction == "mean":
                         per_view = [l_ / len(cameras) for l_ in per_view]
                     losses.extend(l_.detach() for l_ in per_view)
@@ -378,7 +386,7 @@ def pgd_attack(model, cameras: Sequence, *, iters: int = 20, alpha: float = 0.5,
             elif batch_loss:
                 if mine:
                     renders = torch.stack([render(cam, model, pipe, bg)["render"] for cam in mine])
-                    loss = loss_fn(renders)
+                    loss = loss_of(renders, my_idx)
                     if loss_reduction == "mean":
                         loss = loss * (len(mine) / len(cameras))
                     loss.backward()
@@ -399,7 +407,7 @@ def pgd_attack(model, cameras: Sequence, *, iters: int = 20, alpha: float = 0.5,
                             cleared = True
                         if timer is not None:
                             timer.lap("render")
-                        loss = loss_fn(img[None])
+                        loss = loss_of(img[None], [my_idx[vi]])
                         if loss_reduction == "mean":
                             loss = loss / len(cameras)
                         if timer is not None:

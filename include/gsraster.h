@@ -642,13 +642,95 @@ int gsr_det_box_iou(const float* a, int32_t n, const float* b, int32_t m, float*
 int gsr_det_verdict(const float* dets, const int32_t* counts, int32_t B, int32_t max_det, const float* gt, int32_t target,
                     int32_t untarget, int32_t is_targeted, float iou_match, int32_t* verdict, float* best, void* stream);
 
+/* ---- Detector loss stage: the anchor-free YOLO detection loss and its gradient -----------------------------------------
+ * The reference's four YOLO wrappers end infer() by calling the ultralytics DetectionModel in training mode
+ * (detectors/yolov8_detector.py:140-156): a task-aligned assigner, BCE on the class logits, CIoU on the decoded boxes
+ * and the distribution focal loss (DFL) on the 4 x 16 distance bins, returned as box*7.5 + cls*0.5 + dfl*1.5.
+ * gsr_detloss computes that loss and d total / d pred in four launches.  The formulas below are the specification
+ * (written from ultralytics 8.x's v8DetectionLoss, TaskAlignedAssigner and bbox_iou; INTEGRATION.md lists the stated
+ * deviations); csrc/gsr_detloss.h holds the arithmetic, compiled for the kernels and for a host harness alike.  All
+ * arithmetic is float32, index-valued results are int32.
+ *
+ * Inputs.  pred [B, 64 + C, A] (channel-major: channels 0..63 are the sides l, t, r, b x 16 bins, channels 64.. the
+ * class logits; ultralytics' cat(feats, 2)).  The levels: nl <= 5 entries (h_i, w_i, stride_i) with sum h_i * w_i = A;
+ * anchor a of level i at row y, column x has the grid point (gx, gy) = (x + 0.5, y + 0.5) and the pixel point
+ * p = grid * stride_i -- derived by the kernels, there is no anchor tensor.  gt_boxes [B, M, 4]: x1 y1 x2 y2 in
+ * network-input pixels; gt_cls [B, M] int32; 1 <= M <= 32.  A row is PRESENT iff 0 <= gt_cls < C: gt_cls lives in device
+ * memory, so a class >= C cannot be refused without a device read and the row is treated as absent, like a negative one.
+ *
+ * Decode.  Per anchor and side: d = sum_k k * softmax(bins)_k (max-subtracted); the predicted box in grid units is
+ * (gx - d_l, gy - d_t, gx + d_r, gy + d_b); times the stride: pixels.
+ *
+ * CIoU(b1, b2), eps = 1e-7:
+ *     w1 = b1.x2 - b1.x1        h1 = b1.y2 - b1.y1 + eps        (w2, h2 alike)
+ *     inter = max(min(x2s) - max(x1s), 0) * max(min(y2s) - max(y1s), 0)
+ *     union = w1*h1 + w2*h2 - inter + eps;   iou = inter / union
+ *     cw, ch = extent of the enclosing box;  c2 = cw^2 + ch^2 + eps
+ *     rho2 = ((b2.x1 + b2.x2 - b1.x1 - b1.x2)^2 + (b2.y1 + b2.y2 - b1.y1 - b1.y2)^2) / 4
+ *     v = 4/pi^2 * (atan(w2/h2) - atan(w1/h1))^2;   a = v / (v - iou + (1 + eps));   ciou = iou - (rho2/c2 + v*a)
+ * `a` is a constant in the backward; a max / min of two equal arguments shares its gradient in halves and the clamp at 0
+ * passes it where its argument is >= 0, as torch does.
+ *
+ * Assignment (nothing here is differentiated).  Per image and present row m:
+ *   candidate:  anchor a iff min(p.x - x1, p.y - y1, x2 - p.x, y2 - p.y) > 1e-9
+ *   for candidates: ov[m,a] = max(CIoU(gt, pred_px), 0), s = sigmoid(logit[cls_m, a]), metric[m,a] = s^alpha * ov^beta;
+ *               both are 0 for non-candidates
+ *   top-k:      the candidates ordered by metric descending, then anchor index ascending; the first
+ *               min(topk, #candidates) are positive for m (where torch.topk is arbitrary among equal metrics, the anchor
+ *               index decides here)
+ *   conflict:   an anchor positive for more than one row goes to the row with the largest ov[m,a] over ALL present rows
+ *               (the lowest m on ties); as in the library, that row need not be one whose top-k held the anchor
+ *   result:     tgt[b,a] = the row, or -1 for background; for foreground, with pos(m) the final positives of row m,
+ *               ts[b,a] = metric[m,a] * max_{a' in pos(m)} ov[m,a'] / (max_{a' in pos(m)} metric[m,a'] + 1e-9); 0 elsewhere
+ *   tss = max(sum_{b,a} ts, 1), over the whole batch
+ *
+ * Loss.
+ *   cls = sum_{b,c,a} BCEWithLogits(x, t) / tss, t = ts[b,a] at the row's class of a foreground anchor, 0 elsewhere, in
+ *         the stable form max(x,0) - x*t + log1p(exp(-|x|))
+ *   box = sum_fg (1 - CIoU(pred_grid, gt_grid)) * ts / tss, both boxes in grid units, gt_grid = gt / stride
+ *   dfl = sum_fg ts * 1/4 sum_sides [CE(bins, tl) * wl + CE(bins, tl+1) * wr] / tss, the target distance being
+ *         clamp(side distance of gt_grid from the grid point, 0, 14.99), tl = floor(target), wl = tl + 1 - target,
+ *         wr = 1 - wl
+ *   total = B * (w_box*box + w_cls*cls + w_dfl*dfl)
+ *
+ * Outputs.  loss[4] = (box, cls, dfl, total), the first three unweighted.  grad_pred [B, 64+C, A] = d total / d pred, or
+ * NULL (the loss bits are the same either way); when given, every element is written exactly once, background anchors
+ * getting zeros in their 64 box channels.  Optional tgt [B,A] int32 and ts [B,A] float32.
+ *
+ * Determinism.  Every sum is taken in an order fixed by the sizes (and by whether the 16-byte path runs: A % 4 == 0 with
+ * pred and grad_pred on 16-byte boundaries) alone -- per-thread runs, LDS trees, per-block partials added by one block --
+ * and there are no float atomics: two calls on the same input give the same bits, on any stream and from any host thread
+ * (each with its own workspace).  No allocation, no copy, no host synchronisation: capturable.  Non-finite pred gives
+ * unspecified floats, but every index stays in range and every loop ends.
+ *   ws: gsr_detloss_workspace_bytes(spec) bytes of device memory, 16-byte aligned, scratch for the duration of the call's
+ *   kernels.
+ * B, A, C < 1, B > 65535, M outside 1..32, nl outside 1..5, a level with a size < 1 or a stride that is not finite and
+ * > 0, levels that do not add up to A, reg_max != 16, topk outside 1..16, a negative or non-finite alpha / beta / weight,
+ * non-zero flags, a workspace that is too small or misaligned, a NULL required pointer, or more than 2^31 - 1 elements
+ * in a tensor return GSR_ERR_INVALID with a gsr_last_error text before any device call. */
+typedef struct GsrDetLossSpec {
+  int32_t B, A, C, M, nl;    /* images, anchors per image, classes, gt rows per image (1..32), levels (1..5) */
+  int32_t level_h[5], level_w[5];
+  float   level_stride[5];
+  int32_t reg_max;           /* 16 */
+  int32_t topk;              /* 1..16; ultralytics: 10 */
+  float   alpha, beta;       /* ultralytics: 0.5, 6.0 */
+  float   w_box, w_cls, w_dfl; /* ultralytics: 7.5, 0.5, 1.5 */
+  uint32_t flags;            /* 0 */
+} GsrDetLossSpec;
+int gsr_detloss_workspace_bytes(const GsrDetLossSpec* spec, int64_t* bytes);
+int gsr_detloss(const GsrDetLossSpec* spec, const float* pred, const float* gt_boxes, const int32_t* gt_cls, void* ws,
+                int64_t ws_bytes, float* loss, float* grad_pred, int32_t* tgt, float* ts, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
  * (gsr_image_resample, gsr_image_resample_backward, gsr_image_to_u8); GSR_CAP_DETECT = the detector output stage
- * (gsr_det_workspace_bytes, gsr_det_postprocess, gsr_det_nms, gsr_det_box_iou, gsr_det_verdict). */
+ * (gsr_det_workspace_bytes, gsr_det_postprocess, gsr_det_nms, gsr_det_box_iou, gsr_det_verdict); GSR_CAP_DETLOSS = the
+ * detector loss stage (gsr_detloss_workspace_bytes, gsr_detloss). */
 #define GSR_CAP_IMAGE 1
 #define GSR_CAP_DETECT 2
+#define GSR_CAP_DETLOSS 4
 int gsr_query(int32_t what, int64_t* out);
 
 /* Per-context numbers for roofline accounting: what 0 = num_rendered (N; waits for the forward's count if it was

@@ -1,0 +1,204 @@
+"""The detector loss stage without a GPU: the host build of csrc/gsr_detloss.h (the scalar source the kernels compile)
+against the float64 PyTorch oracle of tests/detloss_cases.py, hand-derived literals, and the hand-written backward against
+central finite differences of its own forward in double.
+
+Bound on float errors (detloss_cases.bound): err = max|q - q64| / max|q64| of the host build may be at most 4 x the err of
+the float32 oracle (the yardstick) for the same case and tensor, floor 2^-22, never above 1e-3.  Measured ratios are
+recorded in DESIGN.md; every figure is printed before it is asserted."""
+import numpy as np
+import pytest
+import torch
+
+import detloss_cases as DC
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return DC.host_lib()
+
+
+@pytest.mark.parametrize("c", DC.CASES, ids=lambda c: c.id)
+def test_the_cases_cover_what_they_claim(c):
+    ref = DC.reference(c)
+    o = ref["o64"]
+    # the margin conditions: no discrete decision sits where float32 rounding could cross it
+    print(f"{c.id}: gaps topk {o['gap_topk']:.3e} candidate {o['gap_candidate']:.3e} conflict {o['gap_conflict']:.3e} "
+          f"dfl {o['gap_dfl']:.3e}")
+    assert o["gap_topk"] > 1e-3
+    assert o["gap_candidate"] > 1e-3
+    assert o["gap_conflict"] > 1e-4
+    assert o["gap_dfl"] > 1e-4
+    assert ref["yard_tgt_equal"], "the float32 oracle assigns differently: a margin is too small"
+    tgt, ts = o["tgt"], o["ts"]
+    assert c.A == tgt.shape[1] and tgt.shape[0] == c.B
+    assert (tgt >= 0).any() and (tgt[ts > 0] >= 0).all()      # (a conflict's winner may score 0)
+    if c.id == "tiny":
+        assert c.A == 84 and len(c.levels) == 3
+        lv = np.repeat(np.arange(3), [h * w for h, w, _ in c.levels])
+        assert len(set(lv[(tgt >= 0).any(0).numpy()])) >= 2            # foreground on more than one level
+    if c.id == "ragged":
+        assert c.A == 315 and c.A % 64 != 0
+        assert (ref["gt_cls"][1] < 0).all() and (tgt[1] < 0).all()     # one image with every row absent
+        assert ref["gt_cls"][2, 3] >= c.C and (tgt[2] != 3).all()      # a class past the head's is absent too
+        assert o["n_conflicts"] > 0 and o["outside_topk"] > 0          # a conflict won by a row whose top-k lacked the anchor
+        wide = (ref["gt_boxes"][:, :, 2] - ref["gt_boxes"][:, :, 0]) / 8.0
+        assert (wide > 15).any() and o["n_clamped"] > 0                # the 14.99 clamp acts
+    if c.id == "sparse":
+        n = o["n_candidates"]
+        assert ((n[:, 0] >= 1) & (n[:, 0] <= 9)).all() and (n[:, 1] == 0).all()
+        assert (tgt != 1).all()
+    if c.id == "one-class":
+        assert (c.B, c.C, c.M) == (1, 1, 1)
+    if c.id == "saturated":
+        assert np.abs(ref["pred"]).min() == 80.0 and np.abs(ref["pred"]).max() == 80.0
+        assert torch.isfinite(o["loss"]).all() and torch.isfinite(o["grad"]).all()
+    if c.id == "full":
+        assert c.A == 8400 and c.A % 4 == 0
+    if c.id == "max-rows":
+        assert c.M == 32 and o["n_conflicts"] > 0
+    if c.id in ("tiny", "sparse", "one-class", "saturated", "max-rows"):
+        assert c.A == 84
+
+
+def check_against_oracle(c, got, ref, who):
+    """tgt integer-equal, ts / loss / grad within the bound; prints each figure first."""
+    o = ref["o64"]
+    assert np.array_equal(np.asarray(got["tgt"]), o["tgt"].numpy()), f"{who} {c.id}: tgt differs"
+    fails = []
+    for k in DC.COMPARED:
+        if got.get(k) is None:
+            continue
+        e, y = DC.err(got[k], o[k]), ref["yard"][k]
+        b = DC.bound(y)
+        print(f"{who} {c.id} {k}: err {e:.3e} yardstick {y:.3e} ratio {e / max(y, 1e-30):.2f} bound {b:.3e}")
+        if not e <= b:
+            fails.append((k, e, b))
+    assert not fails, f"{who} {c.id}: {fails}"
+
+
+@pytest.mark.parametrize("c", DC.CASES, ids=lambda c: c.id)
+def test_host_build_against_the_oracle(lib, c):
+    ref = DC.reference(c)
+    got = DC.host_run(lib, c.levels, ref["pred"], ref["gt_boxes"], ref["gt_cls"])
+    assert np.isfinite(got["grad"]).all() and np.isfinite(got["ts"]).all()
+    check_against_oracle(c, got, ref, "host")
+    # without grad_pred the loss is the same bits
+    again = DC.host_run(lib, c.levels, ref["pred"], ref["gt_boxes"], ref["gt_cls"], want_grad=False)
+    assert again["loss"].tobytes() == got["loss"].tobytes()
+    # background anchors: zeros in the 64 box channels
+    bg = got["tgt"] < 0
+    assert (np.moveaxis(got["grad"][:, :64], 1, 2)[bg] == 0).all()
+
+
+def test_double_host_build_equals_the_oracle(lib):
+    """The same code in double against the float64 oracle: what is left is rounding alone."""
+    c = DC.BY_ID["ragged"]
+    ref = DC.reference(c)
+    got = DC.host_run(lib, c.levels, ref["pred"], ref["gt_boxes"], ref["gt_cls"], double=True)
+    assert np.array_equal(got["tgt"], ref["o64"]["tgt"].numpy())
+    for k in DC.COMPARED:
+        assert DC.err(got[k], ref["o64"][k]) < 1e-12, k
+
+
+# ---- hand-derived literals --------------------------------------------------------------------------------------------------
+def test_no_gt_leaves_the_softplus_sum(lib):
+    c = DC.BY_ID["tiny"]
+    ref = DC.reference(c)
+    gtc = np.full_like(ref["gt_cls"], -1)
+    x = ref["pred"].astype(np.float64)
+    want = c.B * DC.W_CLS * np.logaddexp(0.0, x[:, 64:]).sum()         # tss = max(0, 1) = 1
+    got = DC.host_run(lib, c.levels, x, ref["gt_boxes"], gtc, double=True)
+    assert (got["tgt"] == -1).all() and (got["ts"] == 0).all()
+    assert got["loss"][0] == 0 and got["loss"][2] == 0
+    assert abs(got["loss"][3] - want) <= 1e-12 * want
+    assert (got["grad"][:, :64] == 0).all()
+    g32 = DC.host_run(lib, c.levels, ref["pred"], ref["gt_boxes"], gtc)
+    assert abs(g32["loss"][3] - want) <= 2.0 ** -22 * want
+
+
+ONE_LEVEL = [(4, 4, 8.0)]        # 16 anchors; anchor 5 = (x 1, y 1): grid point (1.5, 1.5), pixel point (12, 12)
+
+
+def _single_anchor_inputs(rng, one_hot):
+    """gt (4, 4, 20, 20): only the pixel point (12, 12) lies strictly inside, and its side distances are exactly 1 cell."""
+    pred = rng.normal(0, 1, (1, 64 + 2, 16))
+    if one_hot:
+        pred[0, :64, 5] = -80.0
+        pred[0, [1, 17, 33, 49], 5] = 80.0                              # every side decodes to exactly 1
+    return pred, np.array([[[4.0, 4.0, 20.0, 20.0]]]), np.array([[1]], np.int32)
+
+
+def test_bins_that_decode_to_the_gt_give_no_box_loss(lib):
+    pred, gtb, gtc = _single_anchor_inputs(np.random.default_rng(1), one_hot=True)
+    got = DC.host_run(lib, ONE_LEVEL, pred, gtb, gtc)                   # float32: exp(-160) is 0, the decode is exact
+    assert (got["tgt"][0] >= 0).sum() == 1 and got["tgt"][0, 5] == 0
+    assert got["ts"][0, 5] > 0
+    assert got["loss"][0] == 0.0
+    dbl = DC.host_run(lib, ONE_LEVEL, pred, gtb, gtc, double=True)      # double keeps the eps of h = y2 - y1 + eps: 1e-7 level
+    assert 0 <= dbl["loss"][0] < 1e-6
+
+
+def test_an_integer_dfl_target_gives_one_bins_cross_entropy(lib):
+    pred, gtb, gtc = _single_anchor_inputs(np.random.default_rng(2), one_hot=False)
+    got = DC.host_run(lib, ONE_LEVEL, pred, gtb, gtc, double=True)
+    assert (got["tgt"][0] >= 0).sum() == 1 and got["tgt"][0, 5] == 0
+    ts = got["ts"][0, 5]
+    bins = pred[0, :64, 5].reshape(4, 16)
+    ce = np.log(np.exp(bins).sum(1)) - bins[:, 1]                        # target 1.0: tl = 1, wl = 1, wr = 0
+    want = ts * ce.mean() / max(ts, 1.0)
+    assert abs(got["loss"][2] - want) <= 1e-12 * abs(want)
+
+
+# ---- the hand-written backward against its own forward ------------------------------------------------------------------------
+def test_gradient_equals_the_finite_difference_of_the_forward(lib):
+    """In double, on 200 sampled elements of `tiny`, with what the contract's backward holds constant held fixed: the
+    assignment (tgt and ts) and the `a` of every CIoU.  Central differences with h = 1e-5 on a double forward: truncation
+    ~ h^2 |f'''| ~ 1e-10, rounding ~ 1e-16 |total| / h ~ 1e-10; the tolerance is 1e-6 of the largest gradient."""
+    c = DC.BY_ID["tiny"]
+    ref = DC.reference(c)
+    x = ref["pred"].astype(np.float64)
+    base = DC.host_run(lib, c.levels, x, ref["gt_boxes"], ref["gt_cls"], double=True)
+    frozen = (base["tgt"], base["ts"], base["ciou_a"])
+    again = DC.host_run(lib, c.levels, x, ref["gt_boxes"], ref["gt_cls"], double=True, frozen=frozen)
+    assert again["loss"].tobytes() == base["loss"].tobytes() and again["grad"].tobytes() == base["grad"].tobytes()
+    rng = np.random.default_rng(3)
+    fg = np.argwhere(base["tgt"] >= 0)
+    picks = []
+    for _ in range(120):                                                # box channels of foreground anchors
+        b, a = fg[rng.integers(len(fg))]
+        picks.append((b, rng.integers(0, 64), a))
+    for _ in range(40):                                                 # class channels of foreground anchors
+        b, a = fg[rng.integers(len(fg))]
+        picks.append((b, 64 + rng.integers(0, c.C), a))
+    for _ in range(40):                                                 # anything
+        picks.append((rng.integers(c.B), rng.integers(64 + c.C), rng.integers(c.A)))
+    h = 1e-5
+    scale = np.abs(base["grad"]).max()
+    worst = 0.0
+    for b, k, a in picks:
+        xp, xm = x.copy(), x.copy()
+        xp[b, k, a] += h
+        xm[b, k, a] -= h
+        fp = DC.host_run(lib, c.levels, xp, ref["gt_boxes"], ref["gt_cls"], double=True, want_grad=False, frozen=frozen)["loss"][3]
+        fm = DC.host_run(lib, c.levels, xm, ref["gt_boxes"], ref["gt_cls"], double=True, want_grad=False, frozen=frozen)["loss"][3]
+        worst = max(worst, abs((fp - fm) / (2 * h) - base["grad"][b, k, a]))
+    print(f"finite differences: worst {worst:.3e} of max|grad| {scale:.3e}")
+    assert worst <= 1e-6 * scale
+
+
+def test_non_finite_pred_keeps_every_index_in_range(lib):
+    """Non-finite pred gives unspecified floats, but tgt stays in -1 .. M-1 and the run ends; the candidate test and the
+    DFL bins depend on the geometry alone, so the foreground set cannot grow past the gt boxes' anchors."""
+    c = DC.BY_ID["ragged"]
+    ref = DC.reference(c)
+    rng = np.random.default_rng(4)
+    x = ref["pred"].copy()
+    bad = rng.uniform(0, 1, x.shape)
+    x[bad < 0.05] = np.nan
+    x[(bad >= 0.05) & (bad < 0.08)] = np.inf
+    x[(bad >= 0.08) & (bad < 0.11)] = -np.inf
+    got = DC.host_run(lib, c.levels, x, ref["gt_boxes"], ref["gt_cls"])
+    assert got["tgt"].min() >= -1 and got["tgt"].max() < c.M
+    assert (got["tgt"][1] == -1).all()                                  # the image without rows stays background
+    inside = (ref["o64"]["n_candidates"].sum().item())
+    assert (got["tgt"] >= 0).sum() <= inside
