@@ -442,6 +442,14 @@ struct StageTimer {
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
+// raw parameters of one attribute segment: n Gaussians.  gsr_forward_raw2's second segment (numbered after the first
+// P - n Gaussians) travels and is kept as one of these; the raw entry points also describe their first segment with it.
+struct RawSeg {
+  int32_t n = 0;
+  const float *xyz = nullptr, *features_dc = nullptr, *features_rest = nullptr, *objects_dc = nullptr,
+              *opacity = nullptr, *scaling = nullptr, *rotation = nullptr;
+};
+
 struct GsrCtx {
   int dev = 0;
   GsrSettings st{};
@@ -488,12 +496,8 @@ struct GsrCtx {
   // what gsr_ctx_rerender needs beyond the above
   bool async_count = false;       // the forward sized its pair buffers from a guess: K6 looks at dv[DV_OVF]
   bool fwd_only = false;          // kept by gsr_forward_raw2_keep: re-renderable, not differentiable
-  bool has_b = false;             // two attribute segments (gsr_forward_raw2_keep): Gaussians >= P - segb.Pb read segb
-  struct {
-    int32_t Pb = 0;
-    const float *xyz = nullptr, *features_dc = nullptr, *features_rest = nullptr, *objects_dc = nullptr,
-                *opacity = nullptr, *scaling = nullptr, *rotation = nullptr;
-  } b;
+  bool has_b = false;             // two attribute segments (gsr_forward_raw2_keep): Gaussians >= P - b.n read b
+  RawSeg b;
   bool objects_out = false;       // the forward composited the 16 object channels
   bool D_stale = false;           // the last re-render skipped d colour / d direction: no geometry backward until the next
   double* sumsq_out = nullptr;    // gsr_ctx_request_sumsq: where the next overwrite-mode raw backward leaves its six sums of squares
@@ -503,11 +507,6 @@ struct GsrCtx {
   float *aux_depth_out = nullptr, *aux_alpha_out = nullptr;
   const float *aux_gd = nullptr, *aux_ga = nullptr;
 };
-
-// The _aux entry points hand their two extra output pointers to forward_impl through this (per host thread; taken, and
-// cleared, at the top of forward_impl): the plain entry points' argument lists stay as they are.
-struct AuxOut { float* depth = nullptr; float* alpha = nullptr; };
-static thread_local AuxOut tl_aux_out;
 
 // Host copy of the forward's device-side scalars: waits for the (early) copy if it has not landed yet.
 static int ctx_resolve_count(GsrCtx* c) {
@@ -566,18 +565,105 @@ void gsr_ctx_free(GsrCtx* c) {
 
 }  // extern "C"
 
-// raw != 0: scales / rotations / opacities are the reference model's RAW parameters, shs is _features_rest and
-// sh_dc is _features_dc (K must be 16); activations and their chain rule run inside K1 / K9.
 // diagnostic: device buffer [ntiles][2] that the next backward composites stamp with their waves' start/end clocks
 static std::atomic<unsigned long long*> g_wave_clock{nullptr};
 static std::atomic<unsigned long long*> g_wave_clock_fwd{nullptr};
 
-// second attribute segment of gsr_forward_raw2 (raw parameters of Pb more Gaussians, numbered after the first P - Pb)
-struct SegB {
-  int32_t Pb = 0;
-  const float *xyz = nullptr, *features_dc = nullptr, *features_rest = nullptr, *objects_dc = nullptr,
-              *opacity = nullptr, *scaling = nullptr, *rotation = nullptr;
-};
+// ---------------------------------------------------------------------------------------------
+// kernel pickers: run-time conditions -> the instantiation to launch.  Each table lists exactly the instantiations that
+// exist (the kernels' static_asserts forbid the rest); a launch site calls its picker and launches once.
+// ---------------------------------------------------------------------------------------------
+template <typename Args>
+using Kern = void (*)(Args);   // a kernel that takes its arguments as one struct
+
+// K6.  npx: pixels per lane (1, 2, 4); shared: the tile's 4 / npx waves as one workgroup that stages every batch once
+// (k_render_fwd's WPB) -- four pixels per lane have no such form.  wpb == 1: one workgroup of 64 per tile part, else one
+// of 64 * wpb per tile.
+struct RenderFwdPick { Kern<RenderArgs> kern; int wpb; };
+static RenderFwdPick pick_render_fwd(bool obj, int npx, bool shared, bool aux) {
+  static constexpr Kern<RenderArgs> table[2][2][5] = {   // [obj][aux][npx 4 | 2 shared | 2 | 1 shared | 1]
+      {{k_render_fwd<false, 4>, k_render_fwd<false, 2, 2>, k_render_fwd<false, 2>, k_render_fwd<false, 1, 4>, k_render_fwd<false, 1>},
+       {k_render_fwd<false, 4, 1, true>, k_render_fwd<false, 2, 2, true>, k_render_fwd<false, 2, 1, true>,
+        k_render_fwd<false, 1, 4, true>, k_render_fwd<false, 1, 1, true>}},
+      {{k_render_fwd<true, 4>, k_render_fwd<true, 2, 2>, k_render_fwd<true, 2>, k_render_fwd<true, 1, 4>, k_render_fwd<true, 1>},
+       {k_render_fwd<true, 4, 1, true>, k_render_fwd<true, 2, 2, true>, k_render_fwd<true, 2, 1, true>,
+        k_render_fwd<true, 1, 4, true>, k_render_fwd<true, 1, 1, true>}}};
+  const int form = npx == 4 ? 0 : npx == 2 ? (shared ? 1 : 2) : (shared ? 3 : 4);
+  return RenderFwdPick{table[obj][aux][form], (form == 1 || form == 3) ? PXL / npx : 1};
+}
+
+// K7.  npx: pixels per lane (4, else 2).  Object channels come first: their walk knows no aux form; without them the aux
+// form exists for the geometry walk only and is taken whenever aux gradients are armed (backward_impl has refused the rest).
+static Kern<RenderBwdArgs> pick_render_bwd(bool obj, int npx, bool geom, bool aux) {
+  static constexpr Kern<RenderBwdArgs> table[2][2][2] = {   // [obj][geom][npx == 4]
+      {{k_render_bwd<false, 2, false>, k_render_bwd<false, 4, false>}, {k_render_bwd<false, 2, true>, k_render_bwd<false, 4, true>}},
+      {{k_render_bwd<true, 2, false>, k_render_bwd<true, 4, false>}, {k_render_bwd<true, 2, true>, k_render_bwd<true, 4, true>}}};
+  static constexpr Kern<RenderBwdArgs> with_aux[2] = {k_render_bwd<false, 2, true, true>, k_render_bwd<false, 4, true, true>};
+  return (aux && !obj) ? with_aux[npx == 4] : table[obj][geom][npx == 4];
+}
+
+// K8+K9 of the lane-group layouts.  A non-raw context never accumulates; the double needles are looked at only by the
+// geometry chain, and not at all by the aux forms (which are geometry chains whatever `geom` says).
+static Kern<PreBwdArgs> pick_pre_bwd(bool raw, bool geom, bool acc, bool ndl, bool aux) {
+  static constexpr Kern<PreBwdArgs> table[3][3] = {         // [non-raw | raw | raw accumulating][colour only | geometry | ... double needles]
+      {k_pre_bwd<false, false>, k_pre_bwd<false, true>, k_pre_bwd<false, true, false, true>},
+      {k_pre_bwd<true, false>, k_pre_bwd<true, true>, k_pre_bwd<true, true, false, true>},
+      {k_pre_bwd<true, false, true>, k_pre_bwd<true, true, true>, k_pre_bwd<true, true, true, true>}};
+  static constexpr Kern<PreBwdArgs> with_aux[3] = {k_pre_bwd<false, true, false, false, true>, k_pre_bwd<true, true, false, false, true>,
+                                           k_pre_bwd<true, true, true, false, true>};
+  const int row = raw ? (acc ? 2 : 1) : 0;
+  return aux ? with_aux[row] : table[row][geom ? (ndl ? 2 : 1) : 0];
+}
+
+// K8+K9 of a batch in one launch (the aux form is a geometry chain whatever `geom` says)
+static Kern<PreBwdBatchArgs> pick_pre_bwd_batch(bool geom, bool acc, bool aux) {
+  static constexpr Kern<PreBwdBatchArgs> table[3][2] = {    // [colour only | geometry | aux][overwrite | accumulate]
+      {k_pre_bwd_batch<false, false>, k_pre_bwd_batch<false, true>},
+      {k_pre_bwd_batch<true, false>, k_pre_bwd_batch<true, true>},
+      {k_pre_bwd_batch<true, false, true>, k_pre_bwd_batch<true, true, true>}};
+  return table[aux ? 2 : (geom ? 1 : 0)][acc];
+}
+
+// K1, geometry half
+static Kern<PreArgs> pick_pre_geom(bool raw, bool needle_double) {
+  static constexpr Kern<PreArgs> table[2][2] = {{k_pre_geom<false>, k_pre_geom<false, true>}, {k_pre_geom<true>, k_pre_geom<true, true>}};
+  return table[raw][needle_double];
+}
+
+// the views' constants of a batch context in one device array (the compositors find a tile's background there)
+static void launch_pack_views(const GsrCtx* c, hipStream_t st) {
+  ViewPtrs vp{};
+  for (int v = 0; v < c->B; ++v) {
+    const GsrSettings& sv = c->views[v];
+    vp.vm[v] = sv.viewmatrix; vp.pm[v] = sv.projmatrix; vp.cam[v] = sv.campos; vp.bg[v] = sv.bg;
+    vp.tanfovx[v] = sv.tanfovx; vp.tanfovy[v] = sv.tanfovy;
+  }
+  hipLaunchKernelGGL(k_pack_views, dim3(c->B), dim3(64), 0, st, vp, c->B, c->vpack);
+}
+
+// Arguments of K1's colour half from a context, for k_pre_color (PreArgs: view 0, or the only one) and for
+// k_pre_color_batch: the one or two segments' positions and SH coefficients, the records, D.  Which Gaussians emit pairs
+// the kernel reads from `tcnt` (the forward, whose geometry half has just written it) or, tcnt == null, from the kept offg.
+template <typename Args>
+static void fill_color_inputs(const GsrCtx* c, uint32_t* tcnt, Args& a) {
+  a.P = c->P; a.means = c->means3D; a.sh = c->shs; a.sh_dc = c->sh_dc;
+  a.Pa = c->has_b ? c->P - c->b.n : c->P; a.means_b = c->has_b ? c->b.xyz : nullptr;
+  a.sh_b = c->has_b ? c->b.features_rest : nullptr; a.sh_dc_b = c->has_b ? c->b.features_dc : nullptr;
+  a.tcnt = tcnt; a.offg = tcnt ? nullptr : c->offg;
+  a.G1 = c->G1; a.G2 = c->G2; a.D = c->D;
+}
+static PreArgs color_args(const GsrCtx* c, uint32_t* tcnt) {
+  PreArgs a{};
+  fill_color_inputs(c, tcnt, a);
+  a.va = view_args(c->st); a.G0 = c->G0;
+  return a;
+}
+static PreColorBatchArgs color_batch_args(const GsrCtx* c, uint32_t* tcnt) {
+  PreColorBatchArgs a{};
+  fill_color_inputs(c, tcnt, a);
+  a.B = c->B; a.Ppad = c->Ppad; a.deg = c->st.sh_degree; a.vpack = c->vpack;
+  return a;
+}
 
 // K6 of a context whose binning (pair list, tile ranges, schedule, boundary-record plan) and splat records are in place:
 // the last launch of a forward, and all that a re-render of a kept context needs behind the colour kernel.
@@ -592,7 +678,7 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
   RenderArgs ra;
   ra.ranges = c->ranges; ra.pair_rank = c->pair_rank; ra.R0 = c->G0; ra.R1 = c->G1; ra.R2 = c->G2;
   ra.sh_objs = sh_objs; ra.bg = s->bg; ra.W = W; ra.H = H; ra.gridx = c->gridx; ra.ntiles = ntiles;
-  ra.sh_objs_b = c->has_b ? c->b.objects_dc : nullptr; ra.Pa = c->has_b ? c->P - c->b.Pb : c->P;
+  ra.sh_objs_b = c->has_b ? c->b.objects_dc : nullptr; ra.Pa = c->has_b ? c->P - c->b.n : c->P;
   ra.map_mode = flag_tile_map(s->flags);
   ra.sched = c->sched;
   ra.dv = c->async_count ? c->dv : nullptr;
@@ -602,7 +688,6 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
   ra.tpv = c->tpv; ra.vpack = c->vpack; ra.Ppad = c->Ppad;
   ra.out_depth = c->aux_depth_out; ra.out_alpha = c->aux_alpha_out;
   const bool aux = ra.out_depth != nullptr || ra.out_alpha != nullptr;
-  const dim3 blkT(64);
   // pixels per lane of K6: fewer = more, shorter waves per tile (see k_render_fwd); images with fewer tiles than
   // half the chip's wave slots are split down to one 16x4 strip per wave.  GSR_FLAG_FWD_SPLIT(n) overrides.
   // From 32 000 tiles on (a 4K image, a batch of four or more 1080p views) one wave per tile: four rounds of waves fill the
@@ -616,40 +701,17 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
   // it is opt-in: GSR_FLAG_FWD_SHARED, or GSR_K6_SHARED=1 in the environment
   static const int k6_env = [] { const char* e = getenv("GSR_K6_SHARED"); return e ? atoi(e) : 0; }();
   const bool k6_shared = k6_env != 0 || (s->flags & GSR_FLAG_FWD_SHARED) != 0;
-  const dim3 gridS(render_grid(ntiles)), blkS2(128), blkS4(256);
-  if (aux && out_objects && sh_objs) {
-    if (fwd_npx == 4) hipLaunchKernelGGL((k_render_fwd<true, 4, 1, true>), gridT, blkT, 0, st, ra);
-    else if (fwd_npx == 2 && k6_shared) hipLaunchKernelGGL((k_render_fwd<true, 2, 2, true>), gridS, blkS2, 0, st, ra);
-    else if (fwd_npx == 2) hipLaunchKernelGGL((k_render_fwd<true, 2, 1, true>), gridT, blkT, 0, st, ra);
-    else if (k6_shared) hipLaunchKernelGGL((k_render_fwd<true, 1, 4, true>), gridS, blkS4, 0, st, ra);
-    else hipLaunchKernelGGL((k_render_fwd<true, 1, 1, true>), gridT, blkT, 0, st, ra);
-  } else if (out_objects && sh_objs) {
-    if (fwd_npx == 4) hipLaunchKernelGGL((k_render_fwd<true, 4>), gridT, blkT, 0, st, ra);
-    else if (fwd_npx == 2 && k6_shared) hipLaunchKernelGGL((k_render_fwd<true, 2, 2>), gridS, blkS2, 0, st, ra);
-    else if (fwd_npx == 2) hipLaunchKernelGGL((k_render_fwd<true, 2>), gridT, blkT, 0, st, ra);
-    else if (k6_shared) hipLaunchKernelGGL((k_render_fwd<true, 1, 4>), gridS, blkS4, 0, st, ra);
-    else hipLaunchKernelGGL((k_render_fwd<true, 1>), gridT, blkT, 0, st, ra);
-  } else {
-    if (out_objects) {
-      hipError_t e = hipMemsetAsync(out_objects, 0, sizeof(float) * NUM_OBJ * HW * (size_t)c->B, st);   // (a batch: [B,16,H,W])
-      if (e != hipSuccess) {
-        (void)comp_leave(st_main, comp_s, comp_used);
-        return set_err(GSR_ERR_DEVICE, "objects: %s", hipGetErrorString(e));
-      }
+  const dim3 gridS(render_grid(ntiles));
+  const bool obj = out_objects && sh_objs;
+  if (out_objects && !obj) {
+    hipError_t e = hipMemsetAsync(out_objects, 0, sizeof(float) * NUM_OBJ * HW * (size_t)c->B, st);   // (a batch: [B,16,H,W])
+    if (e != hipSuccess) {
+      (void)comp_leave(st_main, comp_s, comp_used);
+      return set_err(GSR_ERR_DEVICE, "objects: %s", hipGetErrorString(e));
     }
-    if (aux) {
-      if (fwd_npx == 4) hipLaunchKernelGGL((k_render_fwd<false, 4, 1, true>), gridT, blkT, 0, st, ra);
-      else if (fwd_npx == 2 && k6_shared) hipLaunchKernelGGL((k_render_fwd<false, 2, 2, true>), gridS, blkS2, 0, st, ra);
-      else if (fwd_npx == 2) hipLaunchKernelGGL((k_render_fwd<false, 2, 1, true>), gridT, blkT, 0, st, ra);
-      else if (k6_shared) hipLaunchKernelGGL((k_render_fwd<false, 1, 4, true>), gridS, blkS4, 0, st, ra);
-      else hipLaunchKernelGGL((k_render_fwd<false, 1, 1, true>), gridT, blkT, 0, st, ra);
-    } else
-    if (fwd_npx == 4) hipLaunchKernelGGL((k_render_fwd<false, 4>), gridT, blkT, 0, st, ra);
-    else if (fwd_npx == 2 && k6_shared) hipLaunchKernelGGL((k_render_fwd<false, 2, 2>), gridS, blkS2, 0, st, ra);
-    else if (fwd_npx == 2) hipLaunchKernelGGL((k_render_fwd<false, 2>), gridT, blkT, 0, st, ra);
-    else if (k6_shared) hipLaunchKernelGGL((k_render_fwd<false, 1, 4>), gridS, blkS4, 0, st, ra);
-    else hipLaunchKernelGGL((k_render_fwd<false, 1>), gridT, blkT, 0, st, ra);
   }
+  const RenderFwdPick k6 = pick_render_fwd(obj, fwd_npx, k6_shared, aux);
+  hipLaunchKernelGGL(k6.kern, k6.wpb > 1 ? gridS : gridT, dim3(64 * k6.wpb), 0, st, ra);
   hipError_t e = hipGetLastError();
   const bool joined = comp_leave(st_main, comp_s, comp_used);
   if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "render forward: launch failed: %s", hipGetErrorString(e));
@@ -657,48 +719,64 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
   return GSR_OK;
 }
 
-static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float* means3D, const float* shs,
-                        const float* sh_dc, const float* sh_objs, const float* colors_precomp, const float* opacities,
-                        const float* scales, const float* rotations, const float* cov3D_precomp, float* out_color,
-                        float* out_objects, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, void* stream,
-                        bool raw, const SegB* segb = nullptr, bool fwd_only = false, int nviews = 1) {
-  // nviews > 1 (gsr_forward_raw_batch): `s` points at nviews settings; the batch is one virtual scene (GsrCtx::B)
-  const AuxOut aux_out = tl_aux_out;           // (one-shot, whatever this call's fate)
-  tl_aux_out = AuxOut{};
-  const bool want_aux = aux_out.depth != nullptr || aux_out.alpha != nullptr;
-  if (ctx_out) *ctx_out = nullptr;
+// One forward, as every forward entry point hands it to forward_impl (filled member by member, under the entry point's
+// own parameter names where they differ: raw_call).
+struct FwdCall {
+  const GsrSettings* s = nullptr;   // nviews > 1 (gsr_forward_raw_batch): `s` points at nviews settings; the batch is one
+  int nviews = 1;                   // virtual scene (GsrCtx::B)
+  int32_t P = 0, K = 0;
+  // inputs.  raw: scales / rotations / opacities are the reference model's RAW parameters, shs is _features_rest and
+  // sh_dc is _features_dc (K must be 16); activations and their chain rule run inside K1 / K9.
+  const float *means3D = nullptr, *shs = nullptr, *sh_dc = nullptr, *sh_objs = nullptr, *colors_precomp = nullptr,
+              *opacities = nullptr, *scales = nullptr, *rotations = nullptr, *cov3D_precomp = nullptr;
+  const RawSeg* segb = nullptr;     // second attribute segment (gsr_forward_raw2*), counted in P
+  bool raw = false, fwd_only = false;   // fwd_only: no backward state is kept (gsr_forward_raw2*)
+  // outputs; out_depth / out_alpha: the _aux entry points' maps (either may be null)
+  float *out_color = nullptr, *out_objects = nullptr, *out_depth = nullptr, *out_alpha = nullptr;
+  int32_t* radii = nullptr;
+  GsrCtx** ctx_out = nullptr;
+  int64_t* num_rendered = nullptr;
+  void* stream = nullptr;
+};
+
+static int forward_impl(const FwdCall& f) {
+  const GsrSettings* const s = f.s;
+  const int32_t P = f.P, K = f.K;
+  const float* sh_objs = f.sh_objs;
+  const bool want_aux = f.out_depth != nullptr || f.out_alpha != nullptr;
+  if (f.ctx_out) *f.ctx_out = nullptr;
   if (want_aux && s && (s->flags & GSR_FLAG_NEEDLE_DOUBLE))
     return set_err(GSR_ERR_INVALID, "gsr_forward_aux: depth / alpha maps are not available under GSR_FLAG_NEEDLE_DOUBLE");
-  if (want_aux && (segb || fwd_only))
+  if (want_aux && (f.segb || f.fwd_only))
     return set_err(GSR_ERR_INVALID, "gsr_forward_aux: depth / alpha maps are not available from the two-segment forwards");
-  if (!s || !out_color) return set_err(GSR_ERR_INVALID, "gsr_forward: null settings / out_color");
+  if (!s || !f.out_color) return set_err(GSR_ERR_INVALID, "gsr_forward: null settings / out_color");
   if (P < 0 || s->image_height <= 0 || s->image_width <= 0)
     return set_err(GSR_ERR_INVALID, "gsr_forward: bad sizes P=%d H=%d W=%d", P, s->image_height, s->image_width);
   if (P > 0) {   // an empty scene carries no data pointers: it renders the background
-    if (!radii || !means3D || !opacities)
+    if (!f.radii || !f.means3D || !f.opacities)
       return set_err(GSR_ERR_INVALID, "gsr_forward: null means3D / opacities / radii");
-    if ((shs == nullptr) == (colors_precomp == nullptr))
+    if ((f.shs == nullptr) == (f.colors_precomp == nullptr))
       return set_err(GSR_ERR_INVALID, "gsr_forward: provide exactly one of shs / colors_precomp");
-    const bool has_sr = scales != nullptr && rotations != nullptr;
-    if (((scales != nullptr) != (rotations != nullptr)) || (has_sr == (cov3D_precomp != nullptr)))
+    const bool has_sr = f.scales != nullptr && f.rotations != nullptr;
+    if (((f.scales != nullptr) != (f.rotations != nullptr)) || (has_sr == (f.cov3D_precomp != nullptr)))
       return set_err(GSR_ERR_INVALID, "gsr_forward: provide exactly one of (scales, rotations) / cov3D_precomp");
   }
-  if (P > 0 && shs && (s->sh_degree < 0 || s->sh_degree > 3 || K < (s->sh_degree + 1) * (s->sh_degree + 1)))
+  if (P > 0 && f.shs && (s->sh_degree < 0 || s->sh_degree > 3 || K < (s->sh_degree + 1) * (s->sh_degree + 1)))
     return set_err(GSR_ERR_INVALID, "gsr_forward: sh_degree %d needs K >= %d, got K=%d (degree must be 0..3)",
                    s->sh_degree, (s->sh_degree + 1) * (s->sh_degree + 1), K);
   if (!s->bg || !s->viewmatrix || !s->projmatrix || !s->campos)
     return set_err(GSR_ERR_INVALID, "gsr_forward: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers");
   // objects not wanted -- unless the features are to be kept for the backward (GSR_FLAG_OBJECTS_FOR_BACKWARD_ONLY)
-  if (out_objects == nullptr && sh_objs != nullptr && !(s->flags & GSR_FLAG_OBJECTS_FOR_BACKWARD_ONLY)) sh_objs = nullptr;
+  if (f.out_objects == nullptr && sh_objs != nullptr && !(s->flags & GSR_FLAG_OBJECTS_FOR_BACKWARD_ONLY)) sh_objs = nullptr;
 
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = static_cast<hipStream_t>(f.stream);
   const int dev = cur_dev();
   const int H = s->image_height, W = s->image_width;
   const int gridx = (W + TILE - 1) / TILE, gridy = (H + TILE - 1) / TILE;
   const int tpv = gridx * gridy;                                       // tiles per view
   if (gridx > 4095 || gridy > 4095) return set_err(GSR_ERR_INVALID, "gsr_forward: image larger than 65520 px per side");
   // a batch: B views as one virtual scene of B * Ppad Gaussians and B * tpv tiles (a batch of one is an ordinary forward)
-  const int B = (nviews > 1 && P > 0) ? nviews : 1;
+  const int B = (f.nviews > 1 && P > 0) ? f.nviews : 1;
   const int Ppad = B > 1 ? (int)(((size_t)P + BATCH_PAD - 1) / BATCH_PAD * BATCH_PAD) : P;
   if ((size_t)B * (size_t)Ppad > (size_t)RANK_MASK)
     return set_err(GSR_ERR_INVALID, "gsr_forward: more than 2^28 Gaussians (times views of a batch)");
@@ -712,16 +790,12 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
   c->dev = dev; c->st = *s; c->P = P; c->K = K; c->gridx = gridx; c->gridy = gridy; c->ntiles = ntiles;
   c->B = B; c->Ppad = Ppad; c->Pv = Pv; c->tpv = tpv;
   if (B > 1) c->views.assign(s, s + B);
-  c->means3D = means3D; c->shs = shs; c->sh_objs = sh_objs; c->colors = colors_precomp; c->opac = opacities;
-  c->scales = scales; c->rots = rotations; c->cov3d = cov3D_precomp;
-  c->raw = raw; c->sh_dc = sh_dc;
-  c->fwd_only = fwd_only; c->objects_out = out_objects != nullptr && sh_objs != nullptr;
-  c->aux = want_aux; c->aux_depth_out = aux_out.depth; c->aux_alpha_out = aux_out.alpha;
-  if (segb) {
-    c->has_b = true;
-    c->b.Pb = segb->Pb; c->b.xyz = segb->xyz; c->b.features_dc = segb->features_dc; c->b.features_rest = segb->features_rest;
-    c->b.objects_dc = segb->objects_dc; c->b.opacity = segb->opacity; c->b.scaling = segb->scaling; c->b.rotation = segb->rotation;
-  }
+  c->means3D = f.means3D; c->shs = f.shs; c->sh_objs = sh_objs; c->colors = f.colors_precomp; c->opac = f.opacities;
+  c->scales = f.scales; c->rots = f.rotations; c->cov3d = f.cov3D_precomp;
+  c->raw = f.raw; c->sh_dc = f.sh_dc;
+  c->fwd_only = f.fwd_only; c->objects_out = f.out_objects != nullptr && sh_objs != nullptr;
+  c->aux = want_aux; c->aux_depth_out = f.out_depth; c->aux_alpha_out = f.out_alpha;
+  if (f.segb) { c->has_b = true; c->b = *f.segb; }
 
   const size_t Pp = (size_t)std::max(Pv, 1);
   pending_harvest();
@@ -744,11 +818,11 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
   kp.add<uint32_t>(Pp); kp.add<uint32_t>(Pp + 1); kp.add<uint32_t>(Pp + 1);   // order, off, offg
   kp.add<uint2>(ntiles); kp.add<float>(HW); kp.add<uint32_t>(HW); kp.add<uint32_t>(DV_WORDS); kp.add<uint32_t>(ntiles);
   // the SH layouts the reference uses (and precomputed colours) take the lane-group kernels
-  c->lanegroup = raw || (shs && K == 16) || colors_precomp != nullptr;
-  const bool want_D = c->lanegroup && shs != nullptr && ctx_out != nullptr && !fwd_only;
+  c->lanegroup = f.raw || (f.shs && K == 16) || f.colors_precomp != nullptr;
+  const bool want_D = c->lanegroup && f.shs != nullptr && f.ctx_out != nullptr && !f.fwd_only;
   if (want_D) kp.add<float>(9 * Pp);
   const bool needle_double = (s->flags & GSR_FLAG_NEEDLE_DOUBLE) != 0u;
-  const bool want_abc = needle_double && c->lanegroup && ctx_out != nullptr && !fwd_only;
+  const bool want_abc = needle_double && c->lanegroup && f.ctx_out != nullptr && !f.fwd_only;
   if (want_abc) kp.add<double>(Pp);
   if (B > 1) kp.add<ViewDev>((size_t)B);
   c->keep_bytes = kp.bytes + 256;
@@ -785,7 +859,6 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
   if (want_abc) c->abc = ks.take<double>(Pp);
   if (B > 1) c->vpack = ks.take<ViewDev>((size_t)B);
   Slab ss{static_cast<char*>(scratch_blk), sp.bytes + 256, 0};
-  float4* G0 = c->G0; float4* G1 = c->G1; float4* G2 = c->G2;
   uint32_t* dkey = ss.take<uint32_t>(Pp); uint32_t* k1 = ss.take<uint32_t>(Pp); uint32_t* vtmp = ss.take<uint32_t>(Pp);
   uint32_t* v2 = ss.take<uint32_t>(Pp); uint32_t* tcnt = ss.take<uint32_t>(Pp);
   uint32_t* table = ss.take<uint32_t>((size_t)RS_BINS_DEV * nbP); uint32_t* tsums = ss.take<uint32_t>(RS_BINS_DEV);
@@ -842,17 +915,11 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
     // a batch of views: ONE launch reads every SH row once for all the views that see the Gaussian (GSR_BATCH_COLOR=0:
     // the single-view kernel once per view -- the A/B form)
     static const int batch_color_env = [] { const char* e = getenv("GSR_BATCH_COLOR"); return e ? atoi(e) : 1; }();
-    if (B > 1 && raw && batch_color_env != 0) {
-      PreColorBatchArgs ca;
-      ca.P = P; ca.B = B; ca.Ppad = Ppad; ca.deg = s->sh_degree; ca.vpack = c->vpack; ca.means = means3D; ca.sh = shs; ca.sh_dc = sh_dc;
-      ca.Pa = segb ? P - segb->Pb : P; ca.means_b = segb ? segb->xyz : nullptr;
-      ca.sh_b = segb ? segb->features_rest : nullptr; ca.sh_dc_b = segb ? segb->features_dc : nullptr;
-      ca.tcnt = tcnt; ca.offg = nullptr; ca.G1 = G1; ca.G2 = G2; ca.D = c->D;
-      hipLaunchKernelGGL(k_pre_color_batch, gridC, blkCol, 0, cs, ca);
+    if (B > 1 && f.raw && batch_color_env != 0) {
+      hipLaunchKernelGGL(k_pre_color_batch, gridC, blkCol, 0, cs, color_batch_args(c, tcnt));
     } else {
       for (int v = 0; v < B; ++v) {
-        if (raw) hipLaunchKernelGGL((k_pre_color<true>), gridC, blkCol, 0, cs, color_pa[v]);
-        else hipLaunchKernelGGL((k_pre_color<false>), gridC, blkCol, 0, cs, color_pa[v]);
+        hipLaunchKernelGGL(f.raw ? k_pre_color<true> : k_pre_color<false>, gridC, blkCol, 0, cs, color_pa[v]);
       }
     }
     if (side_used) F_TRY("side stream", hipEventRecord(side.join, side.side));
@@ -869,54 +936,33 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
         F_TRY("ranges", hipMemset2DAsync(c->ranges, sizeof(uint2), 0xFF, sizeof(uint32_t), ntiles, st));
         F_TRY("ranges", hipMemset2DAsync(reinterpret_cast<char*>(c->ranges) + sizeof(uint32_t), sizeof(uint2), 0, sizeof(uint32_t), ntiles, st));
       }
-      if (B > 1) {
-        // the views' constants in one device array (the compositors find a tile's background there)
-        ViewPtrs vp{};
-        for (int v = 0; v < B; ++v) {
-          vp.vm[v] = s[v].viewmatrix; vp.pm[v] = s[v].projmatrix; vp.cam[v] = s[v].campos; vp.bg[v] = s[v].bg;
-          vp.tanfovx[v] = s[v].tanfovx; vp.tanfovy[v] = s[v].tanfovy;
-        }
-        hipLaunchKernelGGL(k_pack_views, dim3(B), dim3(64), 0, st, vp, B, c->vpack);
-      }
+      if (B > 1) launch_pack_views(c, st);
       if (c->lanegroup) {
         // (a batch: one launch per view over that view's padded range of the virtual scene -- the same kernels, their
         // per-Gaussian arrays offset by v * Ppad; everything behind K1 then runs once over the B * Ppad virtual Gaussians)
         // (a batch: ONE launch of the geometry kernel over the B views' padded ranges -- view = workgroup / workgroups per
         // view; everything behind K1 then runs once over the B * Ppad virtual Gaussians.  The colour kernel still runs once
         // per view, its per-Gaussian arrays offset by v * Ppad.)
-        PreArgs pa;
-        pa.P = P; pa.Pfill = B > 1 ? Ppad : P; pa.va = va;
-        pa.vpack = B > 1 ? c->vpack : nullptr; pa.bpv = (int)nk1v;
-        pa.means = means3D; pa.scales = scales; pa.rots = rotations; pa.cov3d = cov3D_precomp;
-        pa.opac = opacities; pa.sh = shs; pa.sh_dc = sh_dc; pa.colors = colors_precomp; pa.radii = radii;
-        pa.G0 = G0; pa.G1 = G1; pa.G2 = G2; pa.D = c->D; pa.dkey = dkey; pa.tcnt = tcnt; pa.offg = nullptr;
-        pa.tcnt8 = tcnt8;
-        pa.abc = c->abc;
-        pa.Pa = segb ? P - segb->Pb : P;
-        pa.means_b = segb ? segb->xyz : nullptr; pa.scales_b = segb ? segb->scaling : nullptr;
-        pa.rots_b = segb ? segb->rotation : nullptr; pa.opac_b = segb ? segb->opacity : nullptr;
-        pa.sh_b = segb ? segb->features_rest : nullptr; pa.sh_dc_b = segb ? segb->features_dc : nullptr;
+        PreArgs pa = color_args(c, tcnt);      // what the colour half reads; the geometry half adds:
+        pa.Pfill = B > 1 ? Ppad : P; pa.vpack = B > 1 ? c->vpack : nullptr; pa.bpv = (int)nk1v;
+        pa.scales = f.scales; pa.rots = f.rotations; pa.cov3d = f.cov3D_precomp; pa.opac = f.opacities;
+        pa.colors = f.colors_precomp; pa.radii = f.radii; pa.dkey = dkey; pa.tcnt8 = tcnt8; pa.abc = c->abc;
+        pa.scales_b = f.segb ? f.segb->scaling : nullptr; pa.rots_b = f.segb ? f.segb->rotation : nullptr;
+        pa.opac_b = f.segb ? f.segb->opacity : nullptr;
         pa.cull = cull; pa.bo = bo;
-        const dim3 gridG(nk1);
-        if (needle_double) {
-          if (raw) hipLaunchKernelGGL((k_pre_geom<true, true>), gridG, blkPre, 0, st, pa);
-          else hipLaunchKernelGGL((k_pre_geom<false, true>), gridG, blkPre, 0, st, pa);
-        } else {
-          if (raw) hipLaunchKernelGGL((k_pre_geom<true>), gridG, blkPre, 0, st, pa);
-          else hipLaunchKernelGGL((k_pre_geom<false>), gridG, blkPre, 0, st, pa);
-        }
-        for (int v = 0; v < B; ++v) {
+        hipLaunchKernelGGL(pick_pre_geom(f.raw, needle_double), dim3(nk1), blkPre, 0, st, pa);
+        for (int v = 0; v < B; ++v) {          // the colour kernel, view by view: its per-Gaussian arrays offset by v * Ppad
           const size_t o = (size_t)v * (size_t)Ppad;
-          color_pa[v] = pa;
-          color_pa[v].va = view_args(s[v]); color_pa[v].vpack = nullptr;
-          color_pa[v].G0 = G0 + REC * o; color_pa[v].G1 = G1 + REC * o; color_pa[v].G2 = G2 + REC * o;
-          color_pa[v].D = c->D ? c->D + 9 * o : nullptr; color_pa[v].tcnt = tcnt + o;
+          color_pa[v] = color_args(c, tcnt + o);
+          color_pa[v].va = view_args(s[v]);
+          color_pa[v].G0 += REC * o; color_pa[v].G1 += REC * o; color_pa[v].G2 += REC * o;
+          if (c->D) color_pa[v].D += 9 * o;
         }
-        want_color = !colors_precomp;
+        want_color = !f.colors_precomp;
         if (want_color && !fork_late) { const int rcol = launch_color(); if (rcol != GSR_OK) return rcol; }
       } else
-        hipLaunchKernelGGL(k_preprocess, gridPre, blkPre, 0, st, P, K, va, (cull ? 1 : 0) | (needle_double ? 2 : 0), means3D, scales, rotations, cov3D_precomp,
-                           opacities, shs, colors_precomp, radii, G0, G1, G2, dkey, tcnt, bo);
+        hipLaunchKernelGGL(k_preprocess, gridPre, blkPre, 0, st, P, K, va, (cull ? 1 : 0) | (needle_double ? 2 : 0), f.means3D, f.scales, f.rotations, f.cov3D_precomp,
+                           f.opacities, f.shs, f.colors_precomp, f.radii, c->G0, c->G1, c->G2, dkey, tcnt, bo);
       // storage-order numbering of the pairs (where the backward puts its partial rows), the depth sort's digit width
       // and first histogram, the device-side pair count -- published to the host slot by the kernel itself: one launch
       // stream capture (hipGraph): the forward must not wait for anything, so the count has to be asynchronous, and it is
@@ -1016,14 +1062,11 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
       // a batch: the view of a virtual Gaussian is g / Ppad (one multiply by ceil(2^32 / Ppad) and one correction)
       const uint32_t e_ppad = B > 1 ? (uint32_t)Ppad : 0u;
       const uint32_t e_magic = B > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)Ppad - 1ull) / (uint64_t)Ppad) : 0u;
-      if (rounds == RS_ROUNDS_MIN)
-        hipLaunchKernelGGL((k_emit<RS_ROUNDS_MIN>), dim3(nbN), dim3(rs_chunk(RS_ROUNDS_MIN) / EMIT_PER_THREAD), 0, st, (const uint32_t*)c->off, (const uint32_t*)c->order,
-                           (const uint32_t*)chunk_first, (const uint32_t*)c->dv, (const float4*)c->G0, (const float4*)c->G1, (const float4*)c->G2, gridx, W, H,
-                           (uint32_t)ntiles, cull, tileA, rankA, tableN, nbN, mask0, e_ppad, e_magic, (uint32_t)tpv);
-      else
-        hipLaunchKernelGGL((k_emit<RS_ROUNDS_MAX>), dim3(nbN), dim3(rs_chunk(RS_ROUNDS_MAX) / EMIT_PER_THREAD), 0, st, (const uint32_t*)c->off, (const uint32_t*)c->order,
-                           (const uint32_t*)chunk_first, (const uint32_t*)c->dv, (const float4*)c->G0, (const float4*)c->G1, (const float4*)c->G2, gridx, W, H,
-                           (uint32_t)ntiles, cull, tileA, rankA, tableN, nbN, mask0, e_ppad, e_magic, (uint32_t)tpv);
+      const bool rmin = rounds == RS_ROUNDS_MIN;
+      hipLaunchKernelGGL(rmin ? k_emit<RS_ROUNDS_MIN> : k_emit<RS_ROUNDS_MAX>, dim3(nbN),
+                         dim3(rs_chunk(rmin ? RS_ROUNDS_MIN : RS_ROUNDS_MAX) / EMIT_PER_THREAD), 0, st, (const uint32_t*)c->off, (const uint32_t*)c->order,
+                         (const uint32_t*)chunk_first, (const uint32_t*)c->dv, (const float4*)c->G0, (const float4*)c->G1, (const float4*)c->G2, gridx, W, H,
+                         (uint32_t)ntiles, cull, tileA, rankA, tableN, nbN, mask0, e_ppad, e_magic, (uint32_t)tpv);
       F_LAUNCH("emit");
     }
     int res;
@@ -1048,7 +1091,7 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
     // still walks segments; one WITH dL/dobjects ignores the records (the 16 running object sums are not stored).  Not
     // for a forward-only call, not under GSR_FLAG_NO_SEGMENTS.
     static const int seg_shift_env = [] { const char* e = getenv("GSR_SEG_SHIFT"); int v = e ? atoi(e) : 8; return (v >= 6 && v <= 16) ? v : 8; }();
-    if (nbound > 0 && ctx_out && !fwd_only && !(s->flags & GSR_FLAG_NO_SEGMENTS)) {
+    if (nbound > 0 && f.ctx_out && !f.fwd_only && !(s->flags & GSR_FLAG_NO_SEGMENTS)) {
       const uint32_t per = nbound >> seg_shift_env;
       c->seg_shift = (uint32_t)seg_shift_env;
       // sum over split tiles of ceil(len / seg) <= N / seg + min(T, N / seg): every split tile's records always fit
@@ -1075,26 +1118,138 @@ static int forward_impl(const GsrSettings* s, int32_t P, int32_t K, const float*
                        sched_lds_cap, c->ranges, c->sched, c->seg_shift, c->segoff, c->rec_item, c->rec_cap, c->dv + DV_NREC, B,
                        batch_sched_env);
     F_LAUNCH("tile schedule");
-    const int rk6 = launch_render_fwd(c, out_color, out_objects, st);
+    const int rk6 = launch_render_fwd(c, f.out_color, f.out_objects, st);
     if (rk6 != GSR_OK) return fail(rk6);
     c->aux_depth_out = nullptr; c->aux_alpha_out = nullptr;      // the caller's buffers: written once, by this launch
   }
   pool_free(dev, scratch_blk);
-  if (num_rendered) *num_rendered = c->n_known ? (int64_t)c->n64 : (int64_t)-1;   // -1: not known yet (asynchronous count)
-  if (ctx_out) *ctx_out = c; else gsr_ctx_free(c);
+  if (f.num_rendered) *f.num_rendered = c->n_known ? (int64_t)c->n64 : (int64_t)-1;   // -1: not known yet (asynchronous count)
+  if (f.ctx_out) *f.ctx_out = c; else gsr_ctx_free(c);
   return GSR_OK;
 #undef F_TRY
 #undef F_LAUNCH
 }
 
+// The raw entry points name their inputs as the reference model does (RawSeg); this is where those names meet
+// forward_impl's.  P: the Gaussians of the call (those of `a`, plus the second segment's when there is one).
+static void set_raw_inputs(FwdCall& f, int32_t P, const RawSeg& a) {
+  f.P = P; f.K = 16; f.raw = true;
+  f.means3D = a.xyz; f.sh_dc = a.features_dc; f.shs = a.features_rest; f.sh_objs = a.objects_dc;
+  f.opacities = a.opacity; f.scales = a.scaling; f.rotations = a.rotation;
+}
+
+static bool raw_seg_complete(const RawSeg& a) {
+  return a.xyz && a.features_dc && a.features_rest && a.opacity && a.scaling && a.rotation;
+}
+
+// What a batch's views must look like: 1..MAX_BATCH of them, each with its device tensors, agreeing in image size, scale
+// modifier, SH degree and flags (cameras, tan(fov / 2) and backgrounds are per view).  `fn` names the entry point.
+static int check_batch_views(const char* fn, const GsrSettings* s, int32_t B) {
+  if (!s || B < 1 || B > MAX_BATCH) return set_err(GSR_ERR_INVALID, "%s: 1..%d views, got %d", fn, MAX_BATCH, B);
+  for (int v = 0; v < B; ++v) {
+    if (!s[v].bg || !s[v].viewmatrix || !s[v].projmatrix || !s[v].campos)
+      return set_err(GSR_ERR_INVALID, "%s: view %d: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers", fn, v);
+    if (s[v].image_height != s[0].image_height || s[v].image_width != s[0].image_width || s[v].scale_modifier != s[0].scale_modifier ||
+        s[v].sh_degree != s[0].sh_degree || s[v].flags != s[0].flags)
+      return set_err(GSR_ERR_INVALID, "%s: view %d differs from view 0 in image size, scale modifier, SH degree or "
+                     "flags (a batch shares them)", fn, v);
+  }
+  if (s[0].flags & GSR_FLAG_NEEDLE_DOUBLE) return set_err(GSR_ERR_INVALID, "%s: GSR_FLAG_NEEDLE_DOUBLE is a single-view flag", fn);
+  return GSR_OK;
+}
+
+// A batch of views of ONE set of raw parameters through one launch chain (include/gsraster.h).  `f`: the views' settings
+// and their count, outputs, stream; `fn` names the entry point in the messages; with_obj: gsr_forward_raw_batch_obj
+// (objects_dc required, out_objects [B,16,H,W] or null).
+static int forward_raw_batch_impl(const char* fn, bool with_obj, FwdCall f, const RawSeg& a) {
+  if (f.ctx_out) *f.ctx_out = nullptr;
+  if (const int rc = check_batch_views(fn, f.s, f.nviews)) return rc;
+  if (a.n > 0 && (!a.features_dc || !a.features_rest || !a.scaling || !a.rotation))
+    return set_err(GSR_ERR_INVALID, "%s: null features_dc / features_rest / log_scaling / rotation_raw", fn);
+  if (with_obj && a.n > 0 && !a.objects_dc) return set_err(GSR_ERR_INVALID, "%s: objects_dc is null", fn);
+  if (!f.out_color) return set_err(GSR_ERR_INVALID, "%s: out_color is null", fn);
+  set_raw_inputs(f, a.n, a);
+  if (a.n == 0 && f.nviews > 1) {        // an empty scene: B backgrounds; the context (of view 0) has nothing to differentiate
+    const size_t px = (size_t)f.s[0].image_height * (size_t)f.s[0].image_width;
+    for (int v = 0; v < f.nviews; ++v) {
+      FwdCall fv = f;                    // view v alone, its outputs at their place in the batch's
+      fv.s = f.s + v; fv.nviews = 1; fv.sh_objs = nullptr;
+      fv.out_color = f.out_color + (size_t)v * 3 * px;
+      fv.out_objects = f.out_objects ? f.out_objects + (size_t)v * NUM_OBJ * px : nullptr;
+      fv.out_depth = f.out_depth ? f.out_depth + (size_t)v * px : nullptr;
+      fv.out_alpha = f.out_alpha ? f.out_alpha + (size_t)v * px : nullptr;
+      fv.ctx_out = v == 0 ? f.ctx_out : nullptr;
+      const int rc = forward_impl(fv);
+      if (rc != GSR_OK) return rc;
+    }
+    return GSR_OK;
+  }
+  return forward_impl(f);
+}
+
+// gsr_forward_raw2_batch(_obj): TWO parameter sets as one scene per view, forward only (see below)
+static int forward_raw2_batch_impl(const char* fn, bool with_obj, FwdCall f, const RawSeg& a, const RawSeg& b) {
+  if (f.ctx_out) *f.ctx_out = nullptr;
+  if (a.n <= 0 || b.n <= 0 || (long long)a.n + b.n > 0x7FFFFFFFll)
+    return set_err(GSR_ERR_INVALID, "%s: both segments must hold Gaussians (Pa=%d Pb=%d)", fn, a.n, b.n);
+  if (const int rc = check_batch_views(fn, f.s, f.nviews)) return rc;
+  if (!raw_seg_complete(a) || !raw_seg_complete(b)) return set_err(GSR_ERR_INVALID, "%s: null parameter tensor", fn);
+  if (with_obj && ((a.objects_dc == nullptr) != (b.objects_dc == nullptr)))
+    return set_err(GSR_ERR_INVALID, "%s: objects_dc_a and objects_dc_b: both or neither", fn);
+  if (!f.out_color) return set_err(GSR_ERR_INVALID, "%s: out_color is null", fn);
+  set_raw_inputs(f, a.n + b.n, a);
+  f.segb = &b; f.fwd_only = true;
+  return forward_impl(f);
+}
+
 extern "C" {
+
+// (The entry points that are another one with some arguments null -- gsr_forward, gsr_forward_raw, gsr_forward_raw2,
+// gsr_forward_raw_batch -- call that one, argument for argument in the same order.)
+int gsr_forward_aux(const GsrSettings* s, int32_t P, int32_t K, const float* means3D, const float* shs,
+                    const float* sh_objs, const float* colors_precomp, const float* opacities, const float* scales,
+                    const float* rotations, const float* cov3D_precomp, float* out_color, float* out_objects,
+                    int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha,
+                    void* stream) {
+  FwdCall f;
+  f.s = s; f.P = P; f.K = K; f.means3D = means3D; f.shs = shs; f.sh_objs = sh_objs; f.colors_precomp = colors_precomp;
+  f.opacities = opacities; f.scales = scales; f.rotations = rotations; f.cov3D_precomp = cov3D_precomp;
+  f.out_color = out_color; f.out_objects = out_objects; f.radii = radii; f.ctx_out = ctx_out; f.num_rendered = num_rendered;
+  f.out_depth = out_depth; f.out_alpha = out_alpha; f.stream = stream;
+  return forward_impl(f);
+}
 
 int gsr_forward(const GsrSettings* s, int32_t P, int32_t K, const float* means3D, const float* shs,
                 const float* sh_objs, const float* colors_precomp, const float* opacities, const float* scales,
                 const float* rotations, const float* cov3D_precomp, float* out_color, float* out_objects,
                 int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, void* stream) {
-  return forward_impl(s, P, K, means3D, shs, nullptr, sh_objs, colors_precomp, opacities, scales, rotations,
-                      cov3D_precomp, out_color, out_objects, radii, ctx_out, num_rendered, stream, false);
+  return gsr_forward_aux(s, P, K, means3D, shs, sh_objs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                         out_color, out_objects, radii, ctx_out, num_rendered, nullptr, nullptr, stream);
+}
+
+int gsr_forward_raw_aux(const GsrSettings* s, int32_t P, const float* xyz, const float* features_dc,
+                        const float* features_rest, const float* objects_dc, const float* opacity_logit,
+                        const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
+                        int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha,
+                        void* stream) {
+  if (P > 0 && (!features_dc || !features_rest || !log_scaling || !rotation_raw))
+    return set_err(GSR_ERR_INVALID, "gsr_forward_raw: null features_dc / features_rest / log_scaling / rotation_raw");
+  RawSeg a;
+  a.n = P; a.xyz = xyz; a.features_dc = features_dc; a.features_rest = features_rest; a.objects_dc = objects_dc;
+  a.opacity = opacity_logit; a.scaling = log_scaling; a.rotation = rotation_raw;
+  FwdCall f;
+  f.s = s; f.out_color = out_color; f.out_objects = out_objects; f.radii = radii; f.ctx_out = ctx_out;
+  f.num_rendered = num_rendered; f.out_depth = out_depth; f.out_alpha = out_alpha; f.stream = stream;
+  set_raw_inputs(f, P, a);
+  return forward_impl(f);
+}
+
+int gsr_forward_raw(const GsrSettings* s, int32_t P, const float* xyz, const float* features_dc,
+                    const float* features_rest, const float* objects_dc, const float* opacity_logit,
+                    const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
+                    int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, void* stream) {
+  return gsr_forward_raw_aux(s, P, xyz, features_dc, features_rest, objects_dc, opacity_logit, log_scaling, rotation_raw,
+                             out_color, out_objects, radii, ctx_out, num_rendered, nullptr, nullptr, stream);
 }
 
 int gsr_forward_raw2_keep(const GsrSettings* s, int32_t Pa, const float* xyz_a, const float* features_dc_a,
@@ -1105,25 +1260,24 @@ int gsr_forward_raw2_keep(const GsrSettings* s, int32_t Pa, const float* xyz_a, 
                           float* out_color, float* out_objects, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered,
                           void* stream) {
   if (Pa < 0 || Pb < 0 || (long long)Pa + Pb > 0x7FFFFFFFll) return set_err(GSR_ERR_INVALID, "gsr_forward_raw2: bad sizes Pa=%d Pb=%d", Pa, Pb);
-  if (Pb == 0)
-    return forward_impl(s, Pa, 16, xyz_a, features_rest_a, features_dc_a, objects_dc_a, nullptr, opacity_logit_a,
-                        log_scaling_a, rotation_raw_a, nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true,
-                        nullptr, true);
-  if (Pa == 0)
-    return forward_impl(s, Pb, 16, xyz_b, features_rest_b, features_dc_b, objects_dc_b, nullptr, opacity_logit_b,
-                        log_scaling_b, rotation_raw_b, nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true,
-                        nullptr, true);
-  if (!xyz_a || !features_dc_a || !features_rest_a || !opacity_logit_a || !log_scaling_a || !rotation_raw_a || !xyz_b ||
-      !features_dc_b || !features_rest_b || !opacity_logit_b || !log_scaling_b || !rotation_raw_b)
-    return set_err(GSR_ERR_INVALID, "gsr_forward_raw2: null parameter tensor");
+  RawSeg a, b;
+  a.n = Pa; a.xyz = xyz_a; a.features_dc = features_dc_a; a.features_rest = features_rest_a; a.objects_dc = objects_dc_a;
+  a.opacity = opacity_logit_a; a.scaling = log_scaling_a; a.rotation = rotation_raw_a;
+  b.n = Pb; b.xyz = xyz_b; b.features_dc = features_dc_b; b.features_rest = features_rest_b; b.objects_dc = objects_dc_b;
+  b.opacity = opacity_logit_b; b.scaling = log_scaling_b; b.rotation = rotation_raw_b;
+  FwdCall f;
+  f.s = s; f.fwd_only = true; f.out_color = out_color; f.out_objects = out_objects; f.radii = radii; f.ctx_out = ctx_out;
+  f.num_rendered = num_rendered; f.stream = stream;
+  if (Pa == 0 || Pb == 0) {              // one segment holds everything: an ordinary raw forward of that one
+    set_raw_inputs(f, Pa + Pb, Pb == 0 ? a : b);
+    return forward_impl(f);
+  }
+  if (!raw_seg_complete(a) || !raw_seg_complete(b)) return set_err(GSR_ERR_INVALID, "gsr_forward_raw2: null parameter tensor");
   if (out_objects && ((objects_dc_a == nullptr) != (objects_dc_b == nullptr)))
     return set_err(GSR_ERR_INVALID, "gsr_forward_raw2: object features must be given for both segments or for neither");
-  SegB b;
-  b.Pb = Pb; b.xyz = xyz_b; b.features_dc = features_dc_b; b.features_rest = features_rest_b; b.objects_dc = objects_dc_b;
-  b.opacity = opacity_logit_b; b.scaling = log_scaling_b; b.rotation = rotation_raw_b;
-  return forward_impl(s, Pa + Pb, 16, xyz_a, features_rest_a, features_dc_a, objects_dc_a, nullptr, opacity_logit_a,
-                      log_scaling_a, rotation_raw_a, nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream,
-                      true, &b, true);
+  set_raw_inputs(f, Pa + Pb, a);
+  f.segb = &b;
+  return forward_impl(f);
 }
 
 int gsr_forward_raw2(const GsrSettings* s, int32_t Pa, const float* xyz_a, const float* features_dc_a,
@@ -1137,145 +1291,38 @@ int gsr_forward_raw2(const GsrSettings* s, int32_t Pa, const float* xyz_a, const
                                log_scaling_b, rotation_raw_b, out_color, out_objects, radii, nullptr, num_rendered, stream);
 }
 
-int gsr_forward_raw(const GsrSettings* s, int32_t P, const float* xyz, const float* features_dc,
-                    const float* features_rest, const float* objects_dc, const float* opacity_logit,
-                    const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
-                    int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, void* stream) {
-  if (P > 0 && (!features_dc || !features_rest || !log_scaling || !rotation_raw))
-    return set_err(GSR_ERR_INVALID, "gsr_forward_raw: null features_dc / features_rest / log_scaling / rotation_raw");
-  return forward_impl(s, P, 16, xyz, features_rest, features_dc, objects_dc, nullptr, opacity_logit, log_scaling,
-                      rotation_raw, nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true);
+int gsr_forward_raw_batch_aux(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
+                              const float* features_rest, const float* opacity_logit, const float* log_scaling,
+                              const float* rotation_raw, float* out_color, int32_t* radii, GsrCtx** ctx_out,
+                              int64_t* num_rendered, float* out_depth, float* out_alpha, void* stream) {
+  RawSeg a;
+  a.n = P; a.xyz = xyz; a.features_dc = features_dc; a.features_rest = features_rest; a.opacity = opacity_logit;
+  a.scaling = log_scaling; a.rotation = rotation_raw;
+  FwdCall f;
+  f.s = s; f.nviews = B; f.out_color = out_color; f.radii = radii; f.ctx_out = ctx_out; f.num_rendered = num_rendered;
+  f.out_depth = out_depth; f.out_alpha = out_alpha; f.stream = stream;
+  return forward_raw_batch_impl("gsr_forward_raw_batch", false, f, a);   // (the messages name the plain entry point)
 }
-
-int gsr_forward_aux(const GsrSettings* s, int32_t P, int32_t K, const float* means3D, const float* shs,
-                    const float* sh_objs, const float* colors_precomp, const float* opacities, const float* scales,
-                    const float* rotations, const float* cov3D_precomp, float* out_color, float* out_objects,
-                    int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha,
-                    void* stream) {
-  tl_aux_out.depth = out_depth; tl_aux_out.alpha = out_alpha;
-  const int rc = gsr_forward(s, P, K, means3D, shs, sh_objs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                             out_color, out_objects, radii, ctx_out, num_rendered, stream);
-  tl_aux_out = AuxOut{};
-  return rc;
-}
-
-int gsr_forward_raw_aux(const GsrSettings* s, int32_t P, const float* xyz, const float* features_dc,
-                        const float* features_rest, const float* objects_dc, const float* opacity_logit,
-                        const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
-                        int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, float* out_depth, float* out_alpha,
-                        void* stream) {
-  tl_aux_out.depth = out_depth; tl_aux_out.alpha = out_alpha;
-  const int rc = gsr_forward_raw(s, P, xyz, features_dc, features_rest, objects_dc, opacity_logit, log_scaling, rotation_raw,
-                                 out_color, out_objects, radii, ctx_out, num_rendered, stream);
-  tl_aux_out = AuxOut{};
-  return rc;
-}
-
-}  // extern "C"
-
-// A batch of views of ONE set of raw parameters through one launch chain (include/gsraster.h): the views must agree in
-// image size, scale modifier, SH degree, flags; cameras, tan(fov / 2) and backgrounds are per view.  `fn` names the entry
-// point in the messages; with_obj: gsr_forward_raw_batch_obj (objects_dc required, out_objects [B,16,H,W] or null).
-static int forward_raw_batch_impl(const char* fn, bool with_obj, const GsrSettings* s, int32_t B, int32_t P, const float* xyz,
-                                  const float* features_dc, const float* features_rest, const float* objects_dc,
-                                  const float* opacity_logit, const float* log_scaling, const float* rotation_raw,
-                                  float* out_color, float* out_objects, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered,
-                                  void* stream) {
-  if (ctx_out) *ctx_out = nullptr;
-  if (!s || B < 1 || B > MAX_BATCH) return set_err(GSR_ERR_INVALID, "%s: 1..%d views, got %d", fn, MAX_BATCH, B);
-  if (P > 0 && (!features_dc || !features_rest || !log_scaling || !rotation_raw))
-    return set_err(GSR_ERR_INVALID, "%s: null features_dc / features_rest / log_scaling / rotation_raw", fn);
-  if (with_obj && P > 0 && !objects_dc) return set_err(GSR_ERR_INVALID, "%s: objects_dc is null", fn);
-  for (int v = 0; v < B; ++v) {
-    if (!s[v].bg || !s[v].viewmatrix || !s[v].projmatrix || !s[v].campos)
-      return set_err(GSR_ERR_INVALID, "%s: view %d: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers", fn, v);
-    if (s[v].image_height != s[0].image_height || s[v].image_width != s[0].image_width || s[v].scale_modifier != s[0].scale_modifier ||
-        s[v].sh_degree != s[0].sh_degree || s[v].flags != s[0].flags)
-      return set_err(GSR_ERR_INVALID, "%s: view %d differs from view 0 in image size, scale modifier, SH degree or "
-                     "flags (a batch shares them)", fn, v);
-  }
-  if (s[0].flags & GSR_FLAG_NEEDLE_DOUBLE) return set_err(GSR_ERR_INVALID, "%s: GSR_FLAG_NEEDLE_DOUBLE is a single-view flag", fn);
-  if (!out_color) return set_err(GSR_ERR_INVALID, "%s: out_color is null", fn);
-  if (P == 0 && B > 1) {                 // an empty scene: B backgrounds; the context (of view 0) has nothing to differentiate
-    const size_t px = (size_t)s[0].image_height * (size_t)s[0].image_width;
-    const AuxOut ax = tl_aux_out;
-    for (int v = 0; v < B; ++v) {
-      tl_aux_out.depth = ax.depth ? ax.depth + (size_t)v * px : nullptr;
-      tl_aux_out.alpha = ax.alpha ? ax.alpha + (size_t)v * px : nullptr;
-      const int rc = forward_impl(s + v, 0, 16, xyz, features_rest, features_dc, nullptr, nullptr, opacity_logit, log_scaling,
-                                  rotation_raw, nullptr, out_color + (size_t)v * 3 * px,
-                                  out_objects ? out_objects + (size_t)v * NUM_OBJ * px : nullptr, radii,
-                                  v == 0 ? ctx_out : nullptr, num_rendered, stream, true);
-      if (rc != GSR_OK) return rc;
-    }
-    return GSR_OK;
-  }
-  return forward_impl(s, P, 16, xyz, features_rest, features_dc, objects_dc, nullptr, opacity_logit, log_scaling, rotation_raw,
-                      nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true, nullptr, false, B);
-}
-
-// gsr_forward_raw2_batch(_obj): TWO parameter sets as one scene per view, forward only (see below)
-static int forward_raw2_batch_impl(const char* fn, bool with_obj, const GsrSettings* s, int32_t B, int32_t Pa, const float* xyz_a,
-                                   const float* features_dc_a, const float* features_rest_a, const float* objects_dc_a,
-                                   const float* opacity_logit_a, const float* log_scaling_a, const float* rotation_raw_a, int32_t Pb,
-                                   const float* xyz_b, const float* features_dc_b, const float* features_rest_b,
-                                   const float* objects_dc_b, const float* opacity_logit_b, const float* log_scaling_b,
-                                   const float* rotation_raw_b, float* out_color, float* out_objects, int32_t* radii,
-                                   GsrCtx** ctx_out, int64_t* num_rendered, void* stream) {
-  if (ctx_out) *ctx_out = nullptr;
-  if (Pa <= 0 || Pb <= 0 || (long long)Pa + Pb > 0x7FFFFFFFll)
-    return set_err(GSR_ERR_INVALID, "%s: both segments must hold Gaussians (Pa=%d Pb=%d)", fn, Pa, Pb);
-  if (!s || B < 1 || B > MAX_BATCH) return set_err(GSR_ERR_INVALID, "%s: 1..%d views, got %d", fn, MAX_BATCH, B);
-  if (!xyz_a || !features_dc_a || !features_rest_a || !opacity_logit_a || !log_scaling_a || !rotation_raw_a || !xyz_b ||
-      !features_dc_b || !features_rest_b || !opacity_logit_b || !log_scaling_b || !rotation_raw_b)
-    return set_err(GSR_ERR_INVALID, "%s: null parameter tensor", fn);
-  if (with_obj && ((objects_dc_a == nullptr) != (objects_dc_b == nullptr)))
-    return set_err(GSR_ERR_INVALID, "%s: objects_dc_a and objects_dc_b: both or neither", fn);
-  for (int v = 0; v < B; ++v) {
-    if (!s[v].bg || !s[v].viewmatrix || !s[v].projmatrix || !s[v].campos)
-      return set_err(GSR_ERR_INVALID, "%s: view %d: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers", fn, v);
-    if (s[v].image_height != s[0].image_height || s[v].image_width != s[0].image_width || s[v].scale_modifier != s[0].scale_modifier ||
-        s[v].sh_degree != s[0].sh_degree || s[v].flags != s[0].flags)
-      return set_err(GSR_ERR_INVALID, "%s: view %d differs from view 0 in image size, scale modifier, SH degree or "
-                     "flags (a batch shares them)", fn, v);
-  }
-  if (s[0].flags & GSR_FLAG_NEEDLE_DOUBLE) return set_err(GSR_ERR_INVALID, "%s: GSR_FLAG_NEEDLE_DOUBLE is a single-view flag", fn);
-  if (!out_color) return set_err(GSR_ERR_INVALID, "%s: out_color is null", fn);
-  SegB b;
-  b.Pb = Pb; b.xyz = xyz_b; b.features_dc = features_dc_b; b.features_rest = features_rest_b; b.objects_dc = objects_dc_b;
-  b.opacity = opacity_logit_b; b.scaling = log_scaling_b; b.rotation = rotation_raw_b;
-  return forward_impl(s, Pa + Pb, 16, xyz_a, features_rest_a, features_dc_a, objects_dc_a, nullptr, opacity_logit_a, log_scaling_a,
-                      rotation_raw_a, nullptr, out_color, out_objects, radii, ctx_out, num_rendered, stream, true, &b, true, B);
-}
-
-extern "C" {
 
 int gsr_forward_raw_batch(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
                           const float* features_rest, const float* opacity_logit, const float* log_scaling,
                           const float* rotation_raw, float* out_color, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered,
                           void* stream) {
-  return forward_raw_batch_impl("gsr_forward_raw_batch", false, s, B, P, xyz, features_dc, features_rest, nullptr, opacity_logit,
-                                log_scaling, rotation_raw, out_color, nullptr, radii, ctx_out, num_rendered, stream);
-}
-
-int gsr_forward_raw_batch_aux(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
-                              const float* features_rest, const float* opacity_logit, const float* log_scaling,
-                              const float* rotation_raw, float* out_color, int32_t* radii, GsrCtx** ctx_out,
-                              int64_t* num_rendered, float* out_depth, float* out_alpha, void* stream) {
-  tl_aux_out.depth = out_depth; tl_aux_out.alpha = out_alpha;
-  const int rc = gsr_forward_raw_batch(s, B, P, xyz, features_dc, features_rest, opacity_logit, log_scaling, rotation_raw,
-                                       out_color, radii, ctx_out, num_rendered, stream);
-  tl_aux_out = AuxOut{};
-  return rc;
+  return gsr_forward_raw_batch_aux(s, B, P, xyz, features_dc, features_rest, opacity_logit, log_scaling, rotation_raw, out_color,
+                                   radii, ctx_out, num_rendered, nullptr, nullptr, stream);
 }
 
 int gsr_forward_raw_batch_obj(const GsrSettings* s, int32_t B, int32_t P, const float* xyz, const float* features_dc,
                               const float* features_rest, const float* objects_dc, const float* opacity_logit,
                               const float* log_scaling, const float* rotation_raw, float* out_color, float* out_objects,
                               int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered, void* stream) {
-  return forward_raw_batch_impl("gsr_forward_raw_batch_obj", true, s, B, P, xyz, features_dc, features_rest, objects_dc,
-                                opacity_logit, log_scaling, rotation_raw, out_color, out_objects, radii, ctx_out, num_rendered,
-                                stream);
+  RawSeg a;
+  a.n = P; a.xyz = xyz; a.features_dc = features_dc; a.features_rest = features_rest; a.objects_dc = objects_dc;
+  a.opacity = opacity_logit; a.scaling = log_scaling; a.rotation = rotation_raw;
+  FwdCall f;
+  f.s = s; f.nviews = B; f.out_color = out_color; f.out_objects = out_objects; f.radii = radii; f.ctx_out = ctx_out;
+  f.num_rendered = num_rendered; f.stream = stream;
+  return forward_raw_batch_impl("gsr_forward_raw_batch_obj", true, f, a);
 }
 
 // gsr_forward_raw_batch for TWO parameter sets as one scene per view (the success renders of a batch, reference
@@ -1286,10 +1333,15 @@ int gsr_forward_raw2_batch(const GsrSettings* s, int32_t B, int32_t Pa, const fl
                            const float* features_rest_b, const float* opacity_logit_b, const float* log_scaling_b,
                            const float* rotation_raw_b, float* out_color, int32_t* radii, GsrCtx** ctx_out,
                            int64_t* num_rendered, void* stream) {
-  return forward_raw2_batch_impl("gsr_forward_raw2_batch", false, s, B, Pa, xyz_a, features_dc_a, features_rest_a, nullptr,
-                                 opacity_logit_a, log_scaling_a, rotation_raw_a, Pb, xyz_b, features_dc_b, features_rest_b,
-                                 nullptr, opacity_logit_b, log_scaling_b, rotation_raw_b, out_color, nullptr, radii, ctx_out,
-                                 num_rendered, stream);
+  RawSeg a, b;
+  a.n = Pa; a.xyz = xyz_a; a.features_dc = features_dc_a; a.features_rest = features_rest_a; a.opacity = opacity_logit_a;
+  a.scaling = log_scaling_a; a.rotation = rotation_raw_a;
+  b.n = Pb; b.xyz = xyz_b; b.features_dc = features_dc_b; b.features_rest = features_rest_b; b.opacity = opacity_logit_b;
+  b.scaling = log_scaling_b; b.rotation = rotation_raw_b;
+  FwdCall f;
+  f.s = s; f.nviews = B; f.out_color = out_color; f.radii = radii; f.ctx_out = ctx_out; f.num_rendered = num_rendered;
+  f.stream = stream;
+  return forward_raw2_batch_impl("gsr_forward_raw2_batch", false, f, a, b);
 }
 
 int gsr_forward_raw2_batch_obj(const GsrSettings* s, int32_t B, int32_t Pa, const float* xyz_a, const float* features_dc_a,
@@ -1299,10 +1351,15 @@ int gsr_forward_raw2_batch_obj(const GsrSettings* s, int32_t B, int32_t Pa, cons
                                const float* opacity_logit_b, const float* log_scaling_b, const float* rotation_raw_b,
                                float* out_color, float* out_objects, int32_t* radii, GsrCtx** ctx_out, int64_t* num_rendered,
                                void* stream) {
-  return forward_raw2_batch_impl("gsr_forward_raw2_batch_obj", true, s, B, Pa, xyz_a, features_dc_a, features_rest_a,
-                                 objects_dc_a, opacity_logit_a, log_scaling_a, rotation_raw_a, Pb, xyz_b, features_dc_b,
-                                 features_rest_b, objects_dc_b, opacity_logit_b, log_scaling_b, rotation_raw_b, out_color,
-                                 out_objects, radii, ctx_out, num_rendered, stream);
+  RawSeg a, b;
+  a.n = Pa; a.xyz = xyz_a; a.features_dc = features_dc_a; a.features_rest = features_rest_a; a.objects_dc = objects_dc_a;
+  a.opacity = opacity_logit_a; a.scaling = log_scaling_a; a.rotation = rotation_raw_a;
+  b.n = Pb; b.xyz = xyz_b; b.features_dc = features_dc_b; b.features_rest = features_rest_b; b.objects_dc = objects_dc_b;
+  b.opacity = opacity_logit_b; b.scaling = log_scaling_b; b.rotation = rotation_raw_b;
+  FwdCall f;
+  f.s = s; f.nviews = B; f.out_color = out_color; f.out_objects = out_objects; f.radii = radii; f.ctx_out = ctx_out;
+  f.num_rendered = num_rendered; f.stream = stream;
+  return forward_raw2_batch_impl("gsr_forward_raw2_batch_obj", true, f, a, b);
 }
 
 // Re-render of a kept context whose colour inputs (SH coefficients) may have changed and nothing else has: the colour
@@ -1349,50 +1406,30 @@ int gsr_ctx_rerender(GsrCtx* c, const float* features_dc, const float* features_
   } else if (bg) {
     c->st.bg = bg;
   }
-  if (c->P > 0 && c->B > 1) {
-    // the batch's colour kernel over the Gaussians that emit pairs in ANY view (every SH row read once), the views' constants
-    // packed again first: the CONTENTS of a background tensor may have changed, and the compositors read it from there
+  if (c->P > 0) {
     StageTimer t(GSR_STAGE_PREPROCESS, st);
-    ViewPtrs vp{};
-    for (int v = 0; v < c->B; ++v) {
-      const GsrSettings& sv = c->views[v];
-      vp.vm[v] = sv.viewmatrix; vp.pm[v] = sv.projmatrix; vp.cam[v] = sv.campos; vp.bg[v] = sv.bg;
-      vp.tanfovx[v] = sv.tanfovx; vp.tanfovy[v] = sv.tanfovy;
+    const bool skip_D = (flags & GSR_RERENDER_COLOR_GRADS_ONLY) != 0u;
+    c->D_stale = c->D != nullptr && skip_D;
+    // two segments, the second one's coefficients untouched since the last render: its colour words are still right
+    const bool first_only = c->has_b && (flags & GSR_RERENDER_FIRST_SEGMENT_ONLY);
+    const dim3 blkC(PREF_BLOCK);
+    if (c->B > 1) {
+      // the batch's colour kernel over the Gaussians that emit pairs in ANY view (every SH row read once), the views' constants
+      // packed again first: the CONTENTS of a background tensor may have changed, and the compositors read it from there
+      launch_pack_views(c, st);
+      PreColorBatchArgs ca = color_batch_args(c, nullptr);
+      if (first_only) ca.P = ca.Pa;
+      if (skip_D) ca.D = nullptr;
+      hipLaunchKernelGGL(k_pre_color_batch, dim3((unsigned)((ca.P + PREF_BLOCK - 1) / PREF_BLOCK)), blkC, 0, st, ca);
+    } else {
+      PreArgs pa = color_args(c, nullptr);
+      if (first_only) pa.P = pa.Pa;
+      if (skip_D) pa.D = nullptr;
+      hipLaunchKernelGGL(c->raw ? k_pre_color<true> : k_pre_color<false>, dim3((unsigned)((pa.P + PREF_BLOCK - 1) / PREF_BLOCK)), blkC, 0, st, pa);
     }
-    hipLaunchKernelGGL(k_pack_views, dim3(c->B), dim3(64), 0, st, vp, c->B, c->vpack);
-    PreColorBatchArgs ca;
-    ca.P = c->P; ca.B = c->B; ca.Ppad = c->Ppad; ca.deg = c->st.sh_degree; ca.vpack = c->vpack; ca.means = c->means3D;
-    ca.sh = c->shs; ca.sh_dc = c->sh_dc; ca.tcnt = nullptr; ca.offg = c->offg; ca.G1 = c->G1; ca.G2 = c->G2;
-    ca.Pa = c->has_b ? c->P - c->b.Pb : c->P; ca.means_b = c->has_b ? c->b.xyz : nullptr;
-    ca.sh_b = c->has_b ? c->b.features_rest : nullptr; ca.sh_dc_b = c->has_b ? c->b.features_dc : nullptr;
-    // two segments, the second one's coefficients untouched since the last render: its colour words are still right
-    if (c->has_b && (flags & GSR_RERENDER_FIRST_SEGMENT_ONLY)) ca.P = ca.Pa;
-    const bool skip_D = (flags & GSR_RERENDER_COLOR_GRADS_ONLY) != 0u;
-    ca.D = skip_D ? nullptr : c->D;
-    c->D_stale = c->D != nullptr && skip_D;
-    const dim3 gridC((unsigned)((ca.P + PREF_BLOCK - 1) / PREF_BLOCK)), blkC(PREF_BLOCK);
-    hipLaunchKernelGGL(k_pre_color_batch, gridC, blkC, 0, st, ca);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "rerender colours (batch): launch failed: %s", hipGetErrorString(e));
-  } else if (c->P > 0) {
-    StageTimer t(GSR_STAGE_PREPROCESS, st);
-    PreArgs pa{};
-    pa.P = c->P; pa.va = view_args(c->st); pa.means = c->means3D; pa.sh = c->shs; pa.sh_dc = c->sh_dc;
-    pa.Pa = c->has_b ? c->P - c->b.Pb : c->P;
-    pa.means_b = c->has_b ? c->b.xyz : nullptr;
-    pa.sh_b = c->has_b ? c->b.features_rest : nullptr; pa.sh_dc_b = c->has_b ? c->b.features_dc : nullptr;
-    pa.G0 = c->G0; pa.G1 = c->G1; pa.G2 = c->G2;
-    const bool skip_D = (flags & GSR_RERENDER_COLOR_GRADS_ONLY) != 0u;
-    pa.D = skip_D ? nullptr : c->D;
-    c->D_stale = c->D != nullptr && skip_D;
-    pa.tcnt = nullptr; pa.offg = c->offg;
-    // two segments, the second one's coefficients untouched since the last render: its colour words are still right
-    if (c->has_b && (flags & GSR_RERENDER_FIRST_SEGMENT_ONLY)) pa.P = pa.Pa;
-    const dim3 gridC((unsigned)((pa.P + PREF_BLOCK - 1) / PREF_BLOCK)), blkC(PREF_BLOCK);
-    if (c->raw) hipLaunchKernelGGL((k_pre_color<true>), gridC, blkC, 0, st, pa);
-    else hipLaunchKernelGGL((k_pre_color<false>), gridC, blkC, 0, st, pa);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "rerender colours: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess)
+      return set_err(GSR_ERR_DEVICE, "rerender colours%s: launch failed: %s", c->B > 1 ? " (batch)" : "", hipGetErrorString(e));
   }
   StageTimer t(GSR_STAGE_RENDER_FWD, st);
   return launch_render_fwd(c, out_color, out_objects, st);
@@ -1405,14 +1442,45 @@ static bool batch_k9_fused() {
   return env != 0;
 }
 
-static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dmeans3D, float* dmeans2D,
-                         float* dshs, float* dsh_dc, float* dsh_objs, float* dcolors_precomp, float* dopacities,
-                         float* dscales, float* drotations, float* dcov3D, void* stream, bool accumulate = false,
-                         int nchunks = 1, gsr_chunk_fn chunk_done = nullptr, void* chunk_user = nullptr,
-                         int64_t view_stride = 0) {
-  // view_stride != 0 (gsr_backward_raw_batch_views): a batch context's PER-VIEW gradients -- the attribute-gradient pointers
-  // are view 0's buffers, view v's lie v * view_stride floats further; every view's buffers are overwritten
+// where a backward leaves its gradients (null: not wanted), under forward_impl's names of the inputs
+struct GradOut {
+  float *means3D = nullptr, *means2D = nullptr, *shs = nullptr, *sh_dc = nullptr, *sh_objs = nullptr,
+        *colors_precomp = nullptr, *opacities = nullptr, *scales = nullptr, *rotations = nullptr, *cov3D = nullptr;
+  // view v's own buffers of a per-view batch backward: the six raw attribute gradients lie v * stride floats further
+  GradOut of_view(int v, int64_t stride) const {
+    GradOut g = *this;
+    for (float** p : {&g.means3D, &g.shs, &g.sh_dc, &g.opacities, &g.scales, &g.rotations})
+      if (*p) *p += (size_t)v * (size_t)stride;
+    return g;
+  }
+};
+
+// One backward, as every backward entry point hands it to backward_impl.
+struct BwdCall {
+  const float *grad_color = nullptr, *grad_objects = nullptr;
+  GradOut d;
+  bool accumulate = false;
+  int nchunks = 1;                  // gsr_backward_raw_chunked: ranges of the per-Gaussian stage, the caller told after each
+  gsr_chunk_fn chunk_done = nullptr;
+  void* chunk_user = nullptr;
+  // != 0 (gsr_backward_raw_batch_views): a batch context's PER-VIEW gradients -- the attribute-gradient pointers are
+  // view 0's buffers, view v's lie v * view_stride floats further; every view's buffers are overwritten
+  int64_t view_stride = 0;
+  void* stream = nullptr;
+};
+
+// An entry point serves the contexts of gsr_forward (want_raw false) or those of the raw forwards, not both.  (A null
+// context is backward_impl's to refuse.)
+static int check_ctx_kind(const char* fn, const GsrCtx* c, bool want_raw) {
+  if (!c || c->raw == want_raw) return GSR_OK;
+  if (!want_raw) return set_err(GSR_ERR_STATE, "%s: context came from gsr_forward_raw; use gsr_backward_raw", fn);
+  return set_err(GSR_ERR_STATE, "%s: context came from gsr_forward; use gsr_backward", fn);
+}
+
+static int backward_impl(GsrCtx* c, const BwdCall& b) {
   if (!c) return set_err(GSR_ERR_STATE, "gsr_backward: null context");
+  const GradOut& d = b.d;
+  int nchunks = b.nchunks;
   // gsr_ctx_request_sumsq is one-shot: the request is taken (and the context disarmed) here, whatever this call's fate --
   // a backward that fails early must not leave the next one writing six doubles to a buffer that may be gone by then
   double* ss_out = c->sumsq_out;
@@ -1422,26 +1490,26 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
   const float* const aux_ga = c->aux_ga;
   c->aux_gd = nullptr; c->aux_ga = nullptr;
   const bool aux = aux_gd != nullptr || aux_ga != nullptr;
-  if (!grad_color) return set_err(GSR_ERR_INVALID, "gsr_backward: grad_color is null");
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!b.grad_color) return set_err(GSR_ERR_INVALID, "gsr_backward: grad_color is null");
+  hipStream_t st = static_cast<hipStream_t>(b.stream);
   const int dev = c->dev;
   const int P = c->P;
   if (c->fwd_only)
     return set_err(GSR_ERR_STATE, "gsr_backward: the context was kept by gsr_forward_raw2_keep (re-render only, no backward state)");
   if (P == 0) return GSR_OK;
-  const bool obj = grad_objects != nullptr && c->sh_objs != nullptr;
+  const bool obj = b.grad_objects != nullptr && c->sh_objs != nullptr;
   // Only colour-side gradients wanted (SH / precomputed colours / object features): K7 and K8+K9 drop the geometry
   // sums and the projection chain rule (the colour attack; BASELINE configs 2 and 3).
-  const bool geom = dmeans3D || dmeans2D || dopacities || dscales || drotations || dcov3D;
+  const bool geom = d.means3D || d.means2D || d.opacities || d.scales || d.rotations || d.cov3D;
   if (aux) {
     // (argument checks only: nothing has been launched)
-    if (view_stride != 0)
+    if (b.view_stride != 0)
       return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: the per-view batch backward (gsr_backward_raw_batch_views / _obj_views) "
                      "does not take depth / alpha gradients");
     if (nchunks > 1)
       return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: gsr_backward_raw_chunked with more than one range does not take "
                      "depth / alpha gradients");
-    if (grad_objects != nullptr)
+    if (b.grad_objects != nullptr)
       return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: depth / alpha gradients and grad_objects in one backward are not supported");
     if (!geom)
       return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: depth / alpha gradients reach geometry and opacity only, and this "
@@ -1504,7 +1572,7 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     ra.sched = c->sched;
     ra.wave_clock = g_wave_clock.load();
     ra.gridx = c->gridx; ra.ntiles = c->ntiles; ra.final_T = c->final_T; ra.n_contrib = c->n_contrib;
-    ra.grad_color = grad_color; ra.grad_objects = obj ? grad_objects : nullptr; ra.part = part; ra.part_obj = part_obj;
+    ra.grad_color = b.grad_color; ra.grad_objects = obj ? b.grad_objects : nullptr; ra.part = part; ra.part_obj = part_obj;
     // split tiles: one extra work item per boundary record, in front of the per-tile items
     const bool segs = segs_on;
     ra.grad_depth = aux_gd; ra.grad_alpha = aux_ga;
@@ -1515,30 +1583,9 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     CompStream comp_s{};
     bool comp_used = false;
     hipStream_t st7 = comp_enter(dev, st, comp_s, comp_used);
-#define LAUNCH_K7(kern)                                                                      \
-  do {                                                                                       \
-    if (t.on) hipExtLaunchKernelGGL(kern, gridT, blk, 0, st7, t.a, t.b, 0, ra);              \
-    else hipLaunchKernelGGL(kern, gridT, blk, 0, st7, ra);                                   \
-  } while (0)
-    if (obj) {
-      if (geom) {
-        if (bwd_npx == 4) LAUNCH_K7((k_render_bwd<true, 4, true>));
-        else LAUNCH_K7((k_render_bwd<true, 2, true>));
-      } else {
-        if (bwd_npx == 4) LAUNCH_K7((k_render_bwd<true, 4, false>));
-        else LAUNCH_K7((k_render_bwd<true, 2, false>));
-      }
-    } else if (aux) {
-      if (bwd_npx == 4) LAUNCH_K7((k_render_bwd<false, 4, true, true>));
-      else LAUNCH_K7((k_render_bwd<false, 2, true, true>));
-    } else if (geom) {
-      if (bwd_npx == 4) LAUNCH_K7((k_render_bwd<false, 4, true>));
-      else LAUNCH_K7((k_render_bwd<false, 2, true>));
-    } else {
-      if (bwd_npx == 4) LAUNCH_K7((k_render_bwd<false, 4, false>));
-      else LAUNCH_K7((k_render_bwd<false, 2, false>));
-    }
-#undef LAUNCH_K7
+    const Kern<RenderBwdArgs> k7 = pick_render_bwd(obj, bwd_npx, geom, aux);
+    if (t.on) hipExtLaunchKernelGGL(k7, gridT, blk, 0, st7, t.a, t.b, 0, ra);
+    else hipLaunchKernelGGL(k7, gridT, blk, 0, st7, ra);
     hipError_t e = hipGetLastError();
     const bool joined = comp_leave(st, comp_s, comp_used);
     if (e != hipSuccess) return done(set_err(GSR_ERR_DEVICE, "render backward: launch failed: %s", hipGetErrorString(e)));
@@ -1552,14 +1599,17 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     pa.part = part; pa.part_obj = obj ? part_obj : nullptr;
     pa.tag_lo = tag_lo; pa.tag_hi = tag_hi; pa.nsub = nsub;
     pa.means = c->means3D; pa.scales = c->scales; pa.rots = c->rots; pa.cov3d = c->cov3d; pa.sh = c->shs;
-    pa.sh_dc = c->sh_dc; pa.dsh_dc = dsh_dc; pa.D = c->D; pa.abc = c->abc;
+    pa.sh_dc = c->sh_dc; pa.D = c->D; pa.abc = c->abc;
     pa.needle_double = (c->st.flags & GSR_FLAG_NEEDLE_DOUBLE) != 0u ? 1 : 0;
     // (a batch: the object-feature gradient is k_obj_grad_batch's below, the per-Gaussian kernels leave it alone)
-    pa.dmeans3D = dmeans3D; pa.dmeans2D = dmeans2D; pa.dsh = c->shs ? dshs : nullptr; pa.dsh_objs = c->B > 1 ? nullptr : dsh_objs;
-    pa.dcolors = c->colors ? dcolors_precomp : nullptr; pa.dopac = dopacities;
-    pa.dscales = c->cov3d ? nullptr : dscales; pa.drots = c->cov3d ? nullptr : drotations;
-    pa.dcov3d = c->cov3d ? dcov3D : nullptr;
-    pa.accumulate = accumulate ? 1 : 0;
+    auto set_grads = [&](const GradOut& g) {
+      pa.dmeans3D = g.means3D; pa.dmeans2D = g.means2D; pa.dsh = c->shs ? g.shs : nullptr; pa.dsh_dc = g.sh_dc;
+      pa.dsh_objs = c->B > 1 ? nullptr : g.sh_objs; pa.dcolors = c->colors ? g.colors_precomp : nullptr; pa.dopac = g.opacities;
+      pa.dscales = c->cov3d ? nullptr : g.scales; pa.drots = c->cov3d ? nullptr : g.rotations;
+      pa.dcov3d = c->cov3d ? g.cov3D : nullptr;
+    };
+    set_grads(d);
+    pa.accumulate = b.accumulate ? 1 : 0;
     pa.vpack = nullptr; pa.Ppad = 0; pa.Pscene = P; pa.vstride = 0;
     if (c->raw && ((pa.dsh == nullptr) != (pa.dsh_dc == nullptr)))
       return done(set_err(GSR_ERR_INVALID, "gsr_backward_raw: dfeatures_dc and dfeatures_rest must both be given"));
@@ -1571,12 +1621,12 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     // The per-Gaussian stage covers the Gaussians in `nchunks` ranges (multiples of 64), one launch each; after a
     // range's launch is enqueued the caller is told (chunk_done): its gradients are complete in stream order, so a
     // collective over that range can be issued while the next range is still being computed.
-    if (c->B > 1 && dsh_objs) {
+    if (c->B > 1 && d.sh_objs) {
       // dL/d object features of a batch: view by view as k_pre_bwd forms them, summed in view order (or per view)
       ObjGradBatchArgs oa;
       oa.P = P; oa.B = c->B; oa.Ppad = c->Ppad; oa.nsub = nsub; oa.tag_lo = tag_lo; oa.tag_hi = tag_hi;
-      oa.offg = c->offg; oa.part = part; oa.part_obj = (obj && N > 0) ? part_obj : nullptr; oa.dobj = dsh_objs;
-      oa.vstride = view_stride != 0 ? (long long)P * NUM_OBJ : 0;
+      oa.offg = c->offg; oa.part = part; oa.part_obj = (obj && N > 0) ? part_obj : nullptr; oa.dobj = d.sh_objs;
+      oa.vstride = b.view_stride != 0 ? (long long)P * NUM_OBJ : 0;
       hipLaunchKernelGGL(k_obj_grad_batch, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, oa);
     }
     nchunks = std::max(1, std::min(nchunks, (P + 63) / 64));
@@ -1585,12 +1635,12 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
     // what it writes; one small launch behind it adds them up per tensor (fixed order) into the caller's six doubles
     // a batch of views: ONE launch of k_pre_bwd_batch per range walks the B views and writes the gradients once
     // (GSR_BATCH_K9=0: one k_pre_bwd launch per view instead, the others in accumulate mode -- the A/B and the bit-exact form)
-    const bool batch_fused = c->B > 1 && c->raw && c->lanegroup && batch_k9_fused() && view_stride == 0;
+    const bool batch_fused = c->B > 1 && c->raw && c->lanegroup && batch_k9_fused() && b.view_stride == 0;
     void* ss_blk = nullptr;
     const int ss_blocks = batch_fused ? ((P + 63) / 64) * BATCH_K9_WAVES : (P + PRE_BLOCK - 1) / PRE_BLOCK;
     pa.sumsq = nullptr;
     if (ss_out) {
-      if (!(c->lanegroup && c->raw) || accumulate || nchunks != 1 || (c->B > 1 && !batch_fused))
+      if (!(c->lanegroup && c->raw) || b.accumulate || nchunks != 1 || (c->B > 1 && !batch_fused))
         return done(set_err(GSR_ERR_INVALID, "gsr_ctx_request_sumsq: served by an overwriting gsr_backward_raw* over one range only"));
       ss_blk = pool_alloc(dev, sizeof(float) * SUMSQ_W * (size_t)ss_blocks * PRE_WAVES, st);
       if (!ss_blk) return done(set_err(GSR_ERR_NOMEM, "gsr_backward_raw: sum-of-squares partials allocation failed"));
@@ -1607,78 +1657,47 @@ static int backward_impl(GsrCtx* c, const float* grad_color, const float* grad_o
         ba.offg = c->offg; ba.G0 = c->G0; ba.G1 = c->G1; ba.G2 = c->G2; ba.part = part;
         ba.tag_lo = tag_lo; ba.tag_hi = tag_hi; ba.nsub = nsub;
         ba.means = c->means3D; ba.scales = c->scales; ba.rots = c->rots; ba.D = c->D;
-        ba.dmeans3D = dmeans3D; ba.dmeans2D = dmeans2D; ba.dsh = dshs; ba.dsh_dc = dsh_dc; ba.dopac = dopacities;
-        ba.dscales = dscales; ba.drots = drotations; ba.sumsq = pa.sumsq;
+        ba.dmeans3D = d.means3D; ba.dmeans2D = d.means2D; ba.dsh = d.shs; ba.dsh_dc = d.sh_dc; ba.dopac = d.opacities;
+        ba.dscales = d.scales; ba.drots = d.rotations; ba.sumsq = pa.sumsq;
         const dim3 gridB((unsigned)((ge - gb + 63) / 64)), blkB(64 * BATCH_K9_WAVES);
         const size_t lds = sizeof(float) * 3 * 64 * (size_t)c->B;
-        if (aux) {
-          if (accumulate) hipLaunchKernelGGL((k_pre_bwd_batch<true, true, true>), gridB, blkB, lds, st, ba);
-          else hipLaunchKernelGGL((k_pre_bwd_batch<true, false, true>), gridB, blkB, lds, st, ba);
-        } else if (geom) {
-          if (accumulate) hipLaunchKernelGGL((k_pre_bwd_batch<true, true>), gridB, blkB, lds, st, ba);
-          else hipLaunchKernelGGL((k_pre_bwd_batch<true, false>), gridB, blkB, lds, st, ba);
-        } else {
-          if (accumulate) hipLaunchKernelGGL((k_pre_bwd_batch<false, true>), gridB, blkB, lds, st, ba);
-          else hipLaunchKernelGGL((k_pre_bwd_batch<false, false>), gridB, blkB, lds, st, ba);
-        }
+        hipLaunchKernelGGL(pick_pre_bwd_batch(geom, b.accumulate, aux), gridB, blkB, lds, st, ba);
       }
       // per-view gradients of a batch (gsr_backward_raw_batch_views): ONE launch whose grid.y is the view -- the B per-view
       // launches' ramp-ups and tails happen once (GSR_BATCH_K9_VIEWS=0: one launch per view, the A/B form; same bits)
       static const int views_one_launch = [] { const char* e = getenv("GSR_BATCH_K9_VIEWS"); return e ? atoi(e) : 1; }();
-      const bool views_fused = !batch_fused && view_stride != 0 && c->B > 1 && c->raw && c->lanegroup && views_one_launch != 0;
+      const bool views_fused = !batch_fused && b.view_stride != 0 && c->B > 1 && c->raw && c->lanegroup && views_one_launch != 0;
       if (views_fused && ge > gb) {
-        pa.vpack = c->vpack; pa.Ppad = c->Ppad; pa.Pscene = P; pa.vstride = (long long)view_stride;
+        pa.vpack = c->vpack; pa.Ppad = c->Ppad; pa.Pscene = P; pa.vstride = (long long)b.view_stride;
         pa.accumulate = 0; pa.abc = nullptr;
         pa.g0 = gb; pa.P = ge;
         const dim3 gridV((unsigned)((ge - gb + PRE_BLOCK - 1) / PRE_BLOCK), (unsigned)c->B);
-        if (geom) hipLaunchKernelGGL((k_pre_bwd<true, true>), gridV, dim3(PRE_BLOCK), 0, st, pa);
-        else hipLaunchKernelGGL((k_pre_bwd<true, false>), gridV, dim3(PRE_BLOCK), 0, st, pa);
+        hipLaunchKernelGGL(pick_pre_bwd(true, geom, false, false, false), gridV, dim3(PRE_BLOCK), 0, st, pa);
         pa.vpack = nullptr;
       }
       for (int v = 0; !batch_fused && !views_fused && ge > gb && v < c->B; ++v) {
         const size_t o = (size_t)v * (size_t)c->Ppad;
-        const bool acc_v = view_stride == 0 && (accumulate || v > 0);
+        const bool acc_v = b.view_stride == 0 && (b.accumulate || v > 0);
         if (c->B > 1) {
-          if (view_stride != 0) {               // this view's own gradient buffers
-            const size_t vs = (size_t)v * (size_t)view_stride;
-            pa.dmeans3D = dmeans3D ? dmeans3D + vs : nullptr; pa.dsh = dshs ? dshs + vs : nullptr;
-            pa.dsh_dc = dsh_dc ? dsh_dc + vs : nullptr; pa.dopac = dopacities ? dopacities + vs : nullptr;
-            pa.dscales = dscales ? dscales + vs : nullptr; pa.drots = drotations ? drotations + vs : nullptr;
-          }
+          if (b.view_stride != 0) set_grads(d.of_view(v, b.view_stride));   // this view's own gradient buffers
           pa.va = view_args(c->views[v]);
           pa.offg = c->offg + o; pa.G0 = c->G0 + REC * o; pa.G1 = c->G1 + REC * o; pa.G2 = c->G2 + REC * o;
           pa.D = c->D ? c->D + 9 * o : nullptr; pa.abc = c->abc ? c->abc + o : nullptr;
-          pa.dmeans2D = dmeans2D ? dmeans2D + 3 * (size_t)v * (size_t)P : nullptr;
+          pa.dmeans2D = d.means2D ? d.means2D + 3 * (size_t)v * (size_t)P : nullptr;
           pa.accumulate = acc_v ? 1 : 0;
         }
         pa.g0 = gb; pa.P = ge;
         const dim3 gridK9((unsigned)((ge - gb + PRE_BLOCK - 1) / PRE_BLOCK));
         if (c->lanegroup) {
           const bool ndl = pa.needle_double != 0 && pa.abc != nullptr;
-          if (aux) {
-            if (c->raw && acc_v) hipLaunchKernelGGL((k_pre_bwd<true, true, true, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-            else if (c->raw) hipLaunchKernelGGL((k_pre_bwd<true, true, false, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-            else hipLaunchKernelGGL((k_pre_bwd<false, true, false, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-          } else if (c->raw && acc_v) {
-            if (geom && ndl) hipLaunchKernelGGL((k_pre_bwd<true, true, true, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-            else if (geom) hipLaunchKernelGGL((k_pre_bwd<true, true, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-            else hipLaunchKernelGGL((k_pre_bwd<true, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-          } else if (c->raw) {
-            if (geom && ndl) hipLaunchKernelGGL((k_pre_bwd<true, true, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-            else if (geom) hipLaunchKernelGGL((k_pre_bwd<true, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-            else hipLaunchKernelGGL((k_pre_bwd<true, false>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-          } else {
-            if (geom && ndl) hipLaunchKernelGGL((k_pre_bwd<false, true, false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-            else if (geom) hipLaunchKernelGGL((k_pre_bwd<false, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-            else hipLaunchKernelGGL((k_pre_bwd<false, false>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-          }
+          hipLaunchKernelGGL(pick_pre_bwd(c->raw, geom, acc_v, ndl, aux), gridK9, dim3(PRE_BLOCK), 0, st, pa);
         } else {
           if (geom && pa.needle_double) hipLaunchKernelGGL((k_preprocess_bwd<true, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
           else if (geom) hipLaunchKernelGGL((k_preprocess_bwd<true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
           else hipLaunchKernelGGL((k_preprocess_bwd<false>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
         }
       }
-      if (chunk_done) chunk_done(chunk_user, ck, (int64_t)gb, (int64_t)ge);
+      if (b.chunk_done) b.chunk_done(b.chunk_user, ck, (int64_t)gb, (int64_t)ge);
     }
     if (ss_out) {
       hipLaunchKernelGGL(k_sumsq_reduce, dim3(6), dim3(256), 0, st, pa.sumsq, ss_blocks * PRE_WAVES, ss_out);
@@ -1695,68 +1714,81 @@ extern "C" {
 int gsr_backward(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dmeans3D, float* dmeans2D,
                  float* dshs, float* dsh_objs, float* dcolors_precomp, float* dopacities, float* dscales,
                  float* drotations, float* dcov3D, void* stream) {
-  if (c && c->raw) return set_err(GSR_ERR_STATE, "gsr_backward: context came from gsr_forward_raw; use gsr_backward_raw");
-  return backward_impl(c, grad_color, grad_objects, dmeans3D, dmeans2D, dshs, nullptr, dsh_objs, dcolors_precomp,
-                       dopacities, dscales, drotations, dcov3D, stream);
+  if (const int rc = check_ctx_kind("gsr_backward", c, false)) return rc;
+  BwdCall b;
+  b.grad_color = grad_color; b.grad_objects = grad_objects; b.stream = stream;
+  b.d.means3D = dmeans3D; b.d.means2D = dmeans2D; b.d.shs = dshs; b.d.sh_objs = dsh_objs; b.d.colors_precomp = dcolors_precomp;
+  b.d.opacities = dopacities; b.d.scales = dscales; b.d.rotations = drotations; b.d.cov3D = dcov3D;
+  return backward_impl(c, b);
+}
+
+// (The raw backwards that are gsr_backward_raw_chunked with one range, or gsr_backward_raw_batch_obj_views without object
+// channels, call that one -- behind their own refusal, which names them -- argument for argument in the same order.)
+int gsr_backward_raw_chunked(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dxyz, float* dmeans2D,
+                             float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc, float* dopacity_logit,
+                             float* dlog_scaling, float* drotation_raw, int32_t accumulate, int32_t nchunks,
+                             gsr_chunk_fn chunk_done, void* user, void* stream) {
+  if (const int rc = check_ctx_kind("gsr_backward_raw_chunked", c, true)) return rc;
+  BwdCall b;
+  b.grad_color = grad_color; b.grad_objects = grad_objects; b.stream = stream;
+  b.d.means3D = dxyz; b.d.means2D = dmeans2D; b.d.sh_dc = dfeatures_dc; b.d.shs = dfeatures_rest; b.d.sh_objs = dobjects_dc;
+  b.d.opacities = dopacity_logit; b.d.scales = dlog_scaling; b.d.rotations = drotation_raw;
+  b.accumulate = accumulate != 0; b.nchunks = nchunks; b.chunk_done = chunk_done; b.chunk_user = user;
+  return backward_impl(c, b);
 }
 
 int gsr_backward_raw(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dxyz, float* dmeans2D,
                      float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc, float* dopacity_logit,
                      float* dlog_scaling, float* drotation_raw, void* stream) {
-  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw: context came from gsr_forward; use gsr_backward");
-  return backward_impl(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, dobjects_dc, nullptr,
-                       dopacity_logit, dlog_scaling, drotation_raw, nullptr, stream);
+  if (const int rc = check_ctx_kind("gsr_backward_raw", c, true)) return rc;
+  return gsr_backward_raw_chunked(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_dc, dfeatures_rest, dobjects_dc,
+                                  dopacity_logit, dlog_scaling, drotation_raw, 0, 1, nullptr, nullptr, stream);
 }
 
 int gsr_backward_raw_into(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dxyz, float* dmeans2D,
                           float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc, float* dopacity_logit,
                           float* dlog_scaling, float* drotation_raw, int32_t accumulate, void* stream) {
-  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw_into: context came from gsr_forward; use gsr_backward");
-  return backward_impl(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, dobjects_dc, nullptr,
-                       dopacity_logit, dlog_scaling, drotation_raw, nullptr, stream, accumulate != 0);
-}
-
-int gsr_backward_raw_chunked(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dxyz, float* dmeans2D,
-                             float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc, float* dopacity_logit,
-                             float* dlog_scaling, float* drotation_raw, int32_t accumulate, int32_t nchunks,
-                             gsr_chunk_fn chunk_done, void* user, void* stream) {
-  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw_chunked: context came from gsr_forward; use gsr_backward");
-  return backward_impl(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, dobjects_dc, nullptr,
-                       dopacity_logit, dlog_scaling, drotation_raw, nullptr, stream, accumulate != 0, nchunks, chunk_done, user);
-}
-
-int gsr_backward_raw_batch_into(GsrCtx* c, const float* grad_color, float* dxyz, float* dmeans2D, float* dfeatures_dc,
-                                float* dfeatures_rest, float* dopacity_logit, float* dlog_scaling, float* drotation_raw,
-                                int32_t accumulate, void* stream) {
-  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw_batch_into: context came from gsr_forward; use gsr_backward");
-  return backward_impl(c, grad_color, nullptr, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, nullptr, nullptr, dopacity_logit,
-                       dlog_scaling, drotation_raw, nullptr, stream, accumulate != 0);
-}
-
-int gsr_backward_raw_batch_views(GsrCtx* c, const float* grad_color, float* dxyz, float* dmeans2D, float* dfeatures_dc,
-                                 float* dfeatures_rest, float* dopacity_logit, float* dlog_scaling, float* drotation_raw,
-                                 int64_t view_stride, void* stream) {
-  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw_batch_views: context came from gsr_forward; use gsr_backward");
-  if (view_stride <= 0) return set_err(GSR_ERR_INVALID, "gsr_backward_raw_batch_views: view_stride must be positive (floats between two views' buffers)");
-  return backward_impl(c, grad_color, nullptr, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, nullptr, nullptr, dopacity_logit,
-                       dlog_scaling, drotation_raw, nullptr, stream, false, 1, nullptr, nullptr, view_stride);
+  if (const int rc = check_ctx_kind("gsr_backward_raw_into", c, true)) return rc;
+  return gsr_backward_raw_chunked(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_dc, dfeatures_rest, dobjects_dc,
+                                  dopacity_logit, dlog_scaling, drotation_raw, accumulate, 1, nullptr, nullptr, stream);
 }
 
 int gsr_backward_raw_batch_obj_into(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dxyz, float* dmeans2D,
                                     float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc, float* dopacity_logit,
                                     float* dlog_scaling, float* drotation_raw, int32_t accumulate, void* stream) {
-  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw_batch_obj_into: context came from gsr_forward; use gsr_backward");
-  return backward_impl(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, dobjects_dc, nullptr,
-                       dopacity_logit, dlog_scaling, drotation_raw, nullptr, stream, accumulate != 0);
+  if (const int rc = check_ctx_kind("gsr_backward_raw_batch_obj_into", c, true)) return rc;
+  return gsr_backward_raw_chunked(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_dc, dfeatures_rest, dobjects_dc,
+                                  dopacity_logit, dlog_scaling, drotation_raw, accumulate, 1, nullptr, nullptr, stream);
+}
+
+int gsr_backward_raw_batch_into(GsrCtx* c, const float* grad_color, float* dxyz, float* dmeans2D, float* dfeatures_dc,
+                                float* dfeatures_rest, float* dopacity_logit, float* dlog_scaling, float* drotation_raw,
+                                int32_t accumulate, void* stream) {
+  if (const int rc = check_ctx_kind("gsr_backward_raw_batch_into", c, true)) return rc;
+  return gsr_backward_raw_chunked(c, grad_color, nullptr, dxyz, dmeans2D, dfeatures_dc, dfeatures_rest, nullptr, dopacity_logit,
+                                  dlog_scaling, drotation_raw, accumulate, 1, nullptr, nullptr, stream);
 }
 
 int gsr_backward_raw_batch_obj_views(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dxyz, float* dmeans2D,
                                      float* dfeatures_dc, float* dfeatures_rest, float* dobjects_dc, float* dopacity_logit,
                                      float* dlog_scaling, float* drotation_raw, int64_t view_stride, void* stream) {
-  if (c && !c->raw) return set_err(GSR_ERR_STATE, "gsr_backward_raw_batch_obj_views: context came from gsr_forward; use gsr_backward");
+  if (const int rc = check_ctx_kind("gsr_backward_raw_batch_obj_views", c, true)) return rc;
   if (view_stride <= 0) return set_err(GSR_ERR_INVALID, "gsr_backward_raw_batch_obj_views: view_stride must be positive (floats between two views' buffers)");
-  return backward_impl(c, grad_color, grad_objects, dxyz, dmeans2D, dfeatures_rest, dfeatures_dc, dobjects_dc, nullptr,
-                       dopacity_logit, dlog_scaling, drotation_raw, nullptr, stream, false, 1, nullptr, nullptr, view_stride);
+  BwdCall b;
+  b.grad_color = grad_color; b.grad_objects = grad_objects; b.stream = stream;
+  b.d.means3D = dxyz; b.d.means2D = dmeans2D; b.d.sh_dc = dfeatures_dc; b.d.shs = dfeatures_rest; b.d.sh_objs = dobjects_dc;
+  b.d.opacities = dopacity_logit; b.d.scales = dlog_scaling; b.d.rotations = drotation_raw;
+  b.view_stride = view_stride;
+  return backward_impl(c, b);
+}
+
+int gsr_backward_raw_batch_views(GsrCtx* c, const float* grad_color, float* dxyz, float* dmeans2D, float* dfeatures_dc,
+                                 float* dfeatures_rest, float* dopacity_logit, float* dlog_scaling, float* drotation_raw,
+                                 int64_t view_stride, void* stream) {
+  if (const int rc = check_ctx_kind("gsr_backward_raw_batch_views", c, true)) return rc;
+  if (view_stride <= 0) return set_err(GSR_ERR_INVALID, "gsr_backward_raw_batch_views: view_stride must be positive (floats between two views' buffers)");
+  return gsr_backward_raw_batch_obj_views(c, grad_color, nullptr, dxyz, dmeans2D, dfeatures_dc, dfeatures_rest, nullptr,
+                                          dopacity_logit, dlog_scaling, drotation_raw, view_stride, stream);
 }
 
 int gsr_mark_visible(const GsrSettings* s, int32_t P, const float* means3D, uint8_t* present, void* stream) {

@@ -30,8 +30,7 @@
  *   - ONE context is used by one thread at a time.  It may change hands (forward on one thread, gsr_ctx_set_aux_grads,
  *     gsr_backward* and gsr_ctx_free on another -- the autograd engine's pattern) if the caller orders the calls, e.g.
  *     through a queue; nothing inside a context is locked;
- *   - gsr_last_error() and the hand-over of the _aux entry points' extra pointers are per thread: a thread reads the
- *     text of its own last refused call;
+ *   - gsr_last_error() is per thread: a thread reads the text of its own last refused call;
  *   - streams: a call's work is ordered by the stream it is given: whatever the caller enqueues on that stream afterwards
  *     runs behind it.  (A forward forks part of its work onto a side stream the library keeps per caller stream -- and,
  *     with GSR_COMP_CUMASK set, its compositors onto a companion stream -- and joins both back into the caller's stream
