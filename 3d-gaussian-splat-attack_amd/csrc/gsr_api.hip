@@ -30,6 +30,7 @@
 #include "gsr_image.hip.h"
 #include "gsr_detect.hip.h"
 #include "gsr_detloss.hip.h"
+#include "gsr_setdet.hip.h"
 
 using namespace gsr;
 
@@ -1810,7 +1811,7 @@ int gsr_query(int32_t what, int64_t* out) {
       *out = (int64_t)pl.total;
       return GSR_OK;
     }
-    case 3: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS; return GSR_OK;     // capability bits
+    case 3: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS | GSR_CAP_SETDET; return GSR_OK;     // capability bits
     default: return set_err(GSR_ERR_INVALID, "gsr_query: unknown item %d", what);
   }
 }
@@ -2463,6 +2464,113 @@ int gsr_detloss(const GsrDetLossSpec* d, const float* pred, const float* gt_boxe
   LAUNCH_CHECK("gsr_detloss (terms)");
   hipLaunchKernelGGL(gsr_dloss::k_detloss_final, dim3(1), dim3(gsr_dloss::FIN_THREADS), 0, st, ar, tiles * chunks * (unsigned)sp.B);
   LAUNCH_CHECK("gsr_detloss (final)");
+  return GSR_OK;
+}
+
+// ---- set-prediction detector stage (gsr_setdet.h / gsr_setdet.hip.h): four launches for the loss, one for the output
+// stage; no allocation, no copy, no host wait; everything is checked on the host before the first launch.  Workspace:
+// [stats B*Q*2 f32][cost B*M*Q f32][tgt B*Q i32][nmatch B i32][slab blocks*3 f32], each region rounded up to 256 bytes.
+struct SetDetWs {
+  size_t stats, cost, tgt, nmatch, slab, bytes;
+};
+
+static unsigned setdet_term_blocks(const gsr_setdet::Spec& sp) {
+  const unsigned long long total = (unsigned long long)sp.B * (unsigned long long)sp.Q * (unsigned long long)(sp.C + 1);
+  return (unsigned)((total + gsr_setdet::TERM_TILE - 1) / gsr_setdet::TERM_TILE);
+}
+
+static SetDetWs setdet_layout(const gsr_setdet::Spec& sp) {
+  const size_t BQ = (size_t)sp.B * (size_t)sp.Q;
+  SetDetWs w;
+  w.stats = 0;
+  w.cost = w.stats + det_round(BQ * 2 * 4);
+  w.tgt = w.cost + det_round(BQ * (size_t)sp.M * 4);
+  w.nmatch = w.tgt + det_round(BQ * 4);
+  w.slab = w.nmatch + det_round((size_t)sp.B * 4);
+  w.bytes = w.slab + det_round((size_t)setdet_term_blocks(sp) * 3 * 4);
+  return w;
+}
+
+static int setdet_spec(const char* fn, const GsrSetDetSpec* d, gsr_setdet::Spec& sp) {
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->B > 65535) return set_err(GSR_ERR_INVALID, "%s: B=%d images (1..65535)", fn, d->B);
+  if (d->Q < 1 || d->Q > gsr_setdet::MAX_QUERIES) return set_err(GSR_ERR_INVALID, "%s: Q=%d queries (1..%d)", fn, d->Q, gsr_setdet::MAX_QUERIES);
+  if (d->C < 1 || d->C > gsr_setdet::MAX_CLASSES) return set_err(GSR_ERR_INVALID, "%s: C=%d classes (1..%d)", fn, d->C, gsr_setdet::MAX_CLASSES);
+  if (d->M < 1 || d->M > gsr_setdet::MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: M=%d gt rows per image (1..%d)", fn, d->M, gsr_setdet::MAX_ROWS);
+  if (d->Q < d->M) return set_err(GSR_ERR_INVALID, "%s: Q=%d queries cannot take M=%d rows (Q >= M)", fn, d->Q, d->M);
+  if (d->max_det < 1 || d->max_det > gsr_setdet::MAX_QUERIES)
+    return set_err(GSR_ERR_INVALID, "%s: max_det=%d (1..%d)", fn, d->max_det, gsr_setdet::MAX_QUERIES);
+  if (d->flags != 0u) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
+  const float fl[7] = {d->c_class, d->c_l1, d->c_giou, d->w_ce, d->w_l1, d->w_giou, d->eos_coef};
+  for (int i = 0; i < 7; ++i)
+    if (!(fl[i] >= 0.0f) || !(fl[i] <= 3.0e38f))
+      return set_err(GSR_ERR_INVALID, "%s: c_class, c_l1, c_giou, w_ce, w_l1, w_giou, eos_coef must be finite and >= 0", fn);
+  if (!(d->img_w > 0.0f) || !(d->img_w <= 3.0e38f) || !(d->img_h > 0.0f) || !(d->img_h <= 3.0e38f))
+    return set_err(GSR_ERR_INVALID, "%s: the frame is %g x %g (finite sizes > 0)", fn, (double)d->img_w, (double)d->img_h);
+  if ((unsigned long long)d->B * (unsigned long long)d->Q * (unsigned long long)(d->C + 1) > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in logits", fn);
+  sp.B = d->B; sp.Q = d->Q; sp.C = d->C; sp.M = d->M; sp.img_w = d->img_w; sp.img_h = d->img_h;
+  sp.c_class = d->c_class; sp.c_l1 = d->c_l1; sp.c_giou = d->c_giou; sp.w_ce = d->w_ce; sp.w_l1 = d->w_l1; sp.w_giou = d->w_giou;
+  sp.eos_coef = d->eos_coef; sp.conf_thr = d->conf_thr; sp.max_det = d->max_det;
+  return GSR_OK;
+}
+
+int gsr_setdet_workspace_bytes(const GsrSetDetSpec* d, int64_t* bytes) {
+  gsr_setdet::Spec sp;
+  if (int rc = setdet_spec("gsr_setdet_workspace_bytes", d, sp)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_setdet_workspace_bytes: null bytes");
+  *bytes = (int64_t)setdet_layout(sp).bytes;
+  return GSR_OK;
+}
+
+int gsr_setdet_loss(const GsrSetDetSpec* d, const float* logits, const float* boxes, const float* gt_boxes, const int32_t* gt_cls,
+                    void* ws, int64_t ws_bytes, float* loss, float* grad_logits, float* grad_boxes, int32_t* match, int32_t* tgt,
+                    void* stream) {
+  gsr_setdet::Spec sp;
+  if (int rc = setdet_spec("gsr_setdet_loss", d, sp)) return rc;
+  if (!logits || !boxes || !gt_boxes || !gt_cls || !ws || !loss)
+    return set_err(GSR_ERR_INVALID, "gsr_setdet_loss: null logits / boxes / gt_boxes / gt_cls / ws / loss");
+  const SetDetWs w = setdet_layout(sp);
+  if (ws_bytes < (int64_t)w.bytes)
+    return set_err(GSR_ERR_INVALID, "gsr_setdet_loss: workspace of %lld bytes, %zu needed (gsr_setdet_workspace_bytes)", (long long)ws_bytes, w.bytes);
+  if (((uintptr_t)ws & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_setdet_loss: the workspace must be 16-byte aligned");
+  if ((((uintptr_t)logits | (uintptr_t)boxes | (uintptr_t)gt_boxes | (uintptr_t)gt_cls | (uintptr_t)loss | (uintptr_t)grad_logits |
+        (uintptr_t)grad_boxes | (uintptr_t)match | (uintptr_t)tgt) & 3) != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_setdet_loss: every tensor must be 4-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  gsr_setdet::Args ar;
+  ar.sp = sp; ar.logits = logits; ar.boxes = boxes; ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls;
+  ar.stats = reinterpret_cast<float*>(base + w.stats);
+  ar.cost = reinterpret_cast<float*>(base + w.cost);
+  ar.tgt = reinterpret_cast<int32_t*>(base + w.tgt);
+  ar.nmatch = reinterpret_cast<int32_t*>(base + w.nmatch);
+  ar.slab = reinterpret_cast<float*>(base + w.slab);
+  ar.loss = loss; ar.grad_logits = grad_logits; ar.grad_boxes = grad_boxes; ar.match_out = match; ar.tgt_out = tgt;
+  const unsigned long long queries = (unsigned long long)sp.B * (unsigned long long)sp.Q;
+  hipLaunchKernelGGL(gsr_setdet::k_setdet_cost, dim3((unsigned)((queries + gsr_setdet::COST_WAVES - 1) / gsr_setdet::COST_WAVES)),
+                     dim3(gsr_setdet::COST_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_setdet_loss (cost)");
+  hipLaunchKernelGGL(gsr_setdet::k_setdet_match, dim3((unsigned)sp.B), dim3(gsr_setdet::MATCH_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_setdet_loss (match)");
+  const unsigned blocks = setdet_term_blocks(sp);
+  hipLaunchKernelGGL(gsr_setdet::k_setdet_terms, dim3(blocks), dim3(gsr_setdet::TERM_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_setdet_loss (terms)");
+  hipLaunchKernelGGL(gsr_setdet::k_setdet_final, dim3(1), dim3(gsr_setdet::FIN_THREADS), 0, st, ar, blocks);
+  LAUNCH_CHECK("gsr_setdet_loss (final)");
+  return GSR_OK;
+}
+
+int gsr_setdet_postprocess(const GsrSetDetSpec* d, const float* logits, const float* boxes, float* dets, int32_t* counts,
+                           void* stream) {
+  gsr_setdet::Spec sp;
+  if (int rc = setdet_spec("gsr_setdet_postprocess", d, sp)) return rc;
+  if (!logits || !boxes || !dets || !counts) return set_err(GSR_ERR_INVALID, "gsr_setdet_postprocess: null logits / boxes / dets / counts");
+  if ((((uintptr_t)logits | (uintptr_t)boxes | (uintptr_t)dets | (uintptr_t)counts) & 3) != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_setdet_postprocess: every tensor must be 4-byte aligned");
+  hipLaunchKernelGGL(gsr_setdet::k_setdet_post, dim3((unsigned)sp.B), dim3((unsigned)((sp.Q + 63) / 64 * 64)), 0, static_cast<hipStream_t>(stream),
+                     sp, logits, boxes, dets, counts);
+  LAUNCH_CHECK("gsr_setdet_postprocess");
   return GSR_OK;
 }
 

@@ -33,4 +33,8 @@ def __getattr__(name):
     if name in ("composite_over", "bbox_from_alpha", "benign_bboxes"):
         from . import attack
         return getattr(attack, name)
+    # both sides of a set-prediction (DETR-style) detector
+    if name in ("SetDetectorLoss", "SetDetectorOutput", "make_set_loss_fn"):
+        from . import set_detector
+        return getattr(set_detector, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -721,15 +721,117 @@ int gsr_detloss_workspace_bytes(const GsrDetLossSpec* spec, int64_t* bytes);
 int gsr_detloss(const GsrDetLossSpec* spec, const float* pred, const float* gt_boxes, const int32_t* gt_cls, void* ws,
                 int64_t ws_bytes, float* loss, float* grad_pred, int32_t* tgt, float* ts, void* stream);
 
+/* ---- Set-prediction (DETR-style) detector stage: matching, set criterion, output ------------------------------------------
+ * The reference's second detector family (detectors/detr_detector.py) emits Q queries per image, each with C + 1 logits
+ * whose LAST entry is "no object" and a box (cx, cy, w, h) normalised to the image.  Its infer() hands DETR's set
+ * criterion to backward() (:98-115): a one-to-one match of ground-truth rows to queries, then weighted cross-entropy, L1
+ * and GIoU; its success test is a softmax, a threshold and an IoU, without NMS (:186-243).  gsr_setdet_loss computes the
+ * match, the loss and its gradients in four launches, gsr_setdet_postprocess the detections in one.  The formulas below
+ * are the specification (written from the published DETR HungarianMatcher, SetCriterion and box_ops.generalized_box_iou;
+ * INTEGRATION.md lists the stated deviations); csrc/gsr_setdet.h holds the arithmetic, compiled for the kernels and for a
+ * host harness alike.  All arithmetic is float32, every operation rounded on its own; index-valued results are int32.
+ *
+ * Inputs.  logits [B, Q, C + 1] (channel C: no object); boxes [B, Q, 4] (cx, cy, w, h) normalised, what the head emits
+ * after its sigmoid; gt_boxes [B, M, 4]: x1 y1 x2 y2 in pixels of a frame of size (img_w, img_h) -- gsr_detloss's box
+ * format; gt_cls [B, M] int32.  A row is PRESENT iff 0 <= gt_cls < C (gt_cls lives in device memory, so another value
+ * cannot be refused without a device read: the row is absent).  Ground truth is normalised by the stage:
+ *     cx = (x1 + x2) * 0.5f / img_w    w = (x2 - x1) / img_w    (cy, h alike with img_h)
+ * 1 <= B <= 65535, 1 <= Q <= 1024, 1 <= C <= 1024, 1 <= M <= 32, Q >= M.
+ *
+ * xyxy(b) = (cx - 0.5f*w, cy - 0.5f*h, cx + 0.5f*w, cy + 0.5f*h).
+ * GIoU(a, b) on xyxy, no epsilon (as published):
+ *     area = (x2 - x1) * (y2 - y1)
+ *     inter = max(min(x2s) - max(x1s), 0) * max(min(y2s) - max(y1s), 0)
+ *     union = area_a + area_b - inter;   iou = inter / union
+ *     encl = max(max(x2s) - min(x1s), 0) * max(max(y2s) - min(y1s), 0)
+ *     giou = iou - (encl - union) / encl
+ *
+ * Cost, per image, query q and present row m, with p = softmax(logits[q]) (max-subtracted, p_c = exp(x_c - max) / sum):
+ *     cost[m,q] = -c_class * p[cls_m] + c_l1 * sum_4 |box_q - gt_m| + -c_giou * GIoU(xyxy(box_q), xyxy(gt_m))
+ * (DETR: c_class = 1, c_l1 = 5, c_giou = 2.)
+ *
+ * Match (nothing here is differentiated): every present row gets a distinct query such that the sum of cost is minimal,
+ * by shortest augmenting paths with dual potentials.  Columns are 1..Q (column j is query j - 1) and a virtual column 0,
+ * rows 1..M.  u[0..M] = 0, v[0..Q] = 0, p[0..Q] = 0 (the row held by a column, 0: free).  For every present row i in
+ * ascending order:
+ *     p[0] = i; j0 = 0; minv[j] = +inf, way[j] = 0, all columns unmarked
+ *     repeat:  mark j0; i0 = p[j0]
+ *              for every unmarked column j = 1..Q:  cur = (cost[i0,j] - u[i0]) - v[j];
+ *                  if cur < minv[j]: minv[j] = cur, way[j] = j0
+ *              (delta, j1) = the smallest minv[j] over the unmarked columns, the LOWEST j among equal values
+ *              if no minv[j] compares below +inf: j1 = the lowest unmarked column, delta = 0
+ *              marked columns j: u[p[j]] += delta, v[j] -= delta;   unmarked: minv[j] -= delta
+ *              j0 = j1
+ *     until p[j0] == 0 (at most M + 1 passes: every pass marks one more column, and marked columns hold rows)
+ *     then, at most M + 1 times while j0 != 0:  j1 = way[j0]; p[j0] = p[j1]; j0 = j1
+ * This fixes the result among assignments of equal cost, where scipy.optimize.linear_sum_assignment leaves it open.
+ * match[b,m] = the query of row m, -1 for an absent row; tgt[b,q] = the row of query q, -1 for an unmatched one.  Every
+ * loop is bounded by M and Q alone: with non-finite costs the result is unspecified, but every index stays in range and
+ * every loop ends.
+ *
+ * Loss.  t(b,q) = the class of the matched row, C for an unmatched query; wt = 1 for every class, eos_coef for C (DETR:
+ * 0.1); n = max(number of present rows in the batch, 1); W = sum_{b,q} wt[t], taken as
+ * (float)matched + eos_coef * (float)(B*Q - matched).
+ *     ce    = sum_{b,q} wt[t] * -(x_t - max - log(sum)) / W
+ *     l1    = sum_matched sum_4 |box_q - gt_m| / n
+ *     giou  = sum_matched (1 - GIoU(xyxy(box_q), xyxy(gt_m))) / n
+ *     total = w_ce*ce + w_l1*l1 + w_giou*giou                   (DETR: 1, 5, 2)
+ * loss[4] = (ce, l1, giou, total), the first three unweighted.  eos_coef = 0 with no present row divides 0 by 0, as the
+ * published code does.
+ *
+ * Backward (hand-written).  grad_logits [B,Q,C+1] = d total / d logits = (w_ce / W * wt[t]) * (p_c - [c == t]);
+ * grad_boxes [B,Q,4] = d total / d boxes: sign(0) = 0; a max or min of two equal arguments shares its gradient in halves;
+ * a clamp at 0 passes it where its argument is >= 0, as torch does; unmatched queries get zeros.  Either may be NULL (the
+ * loss bits are the same either way); when given, every element is written exactly once.  match [B,M] and tgt [B,Q] are
+ * optional outputs.
+ *
+ * Determinism.  Every sum is taken in an order fixed by the sizes alone -- per-thread runs, wave butterflies, LDS trees,
+ * per-block partials added by one block -- and there are no float atomics: two calls on the same input give the same
+ * bits, on any stream and from any host thread (each with its own workspace).  No allocation, no copy, no host
+ * synchronisation: capturable.
+ *   ws: gsr_setdet_workspace_bytes(spec) bytes of device memory, 16-byte aligned, scratch for the duration of the call's
+ *   kernels.
+ *
+ * gsr_setdet_postprocess (detr_detector.py:186-202): per query p = softmax(logits); the class is the first maximum of p_c
+ * over c < C (lowest index on ties; a NaN is never the maximum), the score that maximum; the query is kept iff
+ * score > conf_thr, so a NaN score is dropped.  Box: x1 = (cx - 0.5f*w) * img_w, x2 = (cx + 0.5f*w) * img_w, y alike with
+ * img_h.  Kept queries are written in QUERY ORDER (the reference does not sort and its argmax takes the first best IoU);
+ * no NMS.  dets [B,max_det,6] (x1 y1 x2 y2 score class-as-float) and counts [B,2] (kept = min(above_thr, max_det),
+ * above_thr), the layout gsr_det_postprocess writes; rows beyond the count are zero.  gsr_det_verdict on them gives the
+ * reference's verdict (:216-243).  One launch, no workspace.  M and the loss weights are checked but not used.
+ *
+ * All entries: every tensor argument is a DEVICE pointer.  A size out of range, Q < M, max_det outside 1..1024, a
+ * non-finite or negative c_* / w_* / eos_coef, a frame size that is not finite and > 0, non-zero flags, a workspace that
+ * is too small or misaligned, a NULL required pointer, a tensor that is not 4-byte aligned or more than 2^31 - 1 logits
+ * return GSR_ERR_INVALID with a gsr_last_error text before any device call. */
+typedef struct GsrSetDetSpec {
+  int32_t B, Q, C, M;        /* images, queries per image (1..1024), classes without "no object" (1..1024), gt rows (1..32) */
+  float   img_w, img_h;      /* the frame gt_boxes and dets are in */
+  float   c_class, c_l1, c_giou; /* matching cost; DETR: 1, 5, 2 */
+  float   w_ce, w_l1, w_giou;    /* loss weights; DETR: 1, 5, 2 */
+  float   eos_coef;          /* weight of the no-object class; DETR: 0.1 */
+  float   conf_thr;          /* gsr_setdet_postprocess; the reference: 0.7 */
+  int32_t max_det;           /* gsr_setdet_postprocess: rows of dets per image, 1..1024 */
+  uint32_t flags;            /* 0 */
+} GsrSetDetSpec;
+int gsr_setdet_workspace_bytes(const GsrSetDetSpec* spec, int64_t* bytes);
+int gsr_setdet_loss(const GsrSetDetSpec* spec, const float* logits, const float* boxes, const float* gt_boxes,
+                    const int32_t* gt_cls, void* ws, int64_t ws_bytes, float* loss, float* grad_logits, float* grad_boxes,
+                    int32_t* match, int32_t* tgt, void* stream);
+int gsr_setdet_postprocess(const GsrSetDetSpec* spec, const float* logits, const float* boxes, float* dets, int32_t* counts,
+                           void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
  * (gsr_image_resample, gsr_image_resample_backward, gsr_image_to_u8); GSR_CAP_DETECT = the detector output stage
  * (gsr_det_workspace_bytes, gsr_det_postprocess, gsr_det_nms, gsr_det_box_iou, gsr_det_verdict); GSR_CAP_DETLOSS = the
- * detector loss stage (gsr_detloss_workspace_bytes, gsr_detloss). */
+ * detector loss stage (gsr_detloss_workspace_bytes, gsr_detloss); GSR_CAP_SETDET = the set-prediction detector stage
+ * (gsr_setdet_workspace_bytes, gsr_setdet_loss, gsr_setdet_postprocess). */
 #define GSR_CAP_IMAGE 1
 #define GSR_CAP_DETECT 2
 #define GSR_CAP_DETLOSS 4
+#define GSR_CAP_SETDET 8
 int gsr_query(int32_t what, int64_t* out);
 
 /* Per-context numbers for roofline accounting: what 0 = num_rendered (N; waits for the forward's count if it was
