@@ -507,6 +507,11 @@ struct GsrCtx {
   bool aux = false;
   float *aux_depth_out = nullptr, *aux_alpha_out = nullptr;
   const float *aux_gd = nullptr, *aux_ga = nullptr;
+  // which size-gated variants of the binning front end this forward took (gsr_ctx_info 6-9)
+  int depth_passes = 0;           // 3 | 4
+  int tile_rounds = 0;            // 8 | 16: chunk rounds of k_emit and the tile sort; 0: no pairs
+  int scan_items = 0;             // 8 | 16: items per thread of the rank-order scan
+  bool group_sums = false;        // K2 read K1's sums through k_bout_group_sum
 };
 
 // Host copy of the forward's device-side scalars: waits for the (early) copy if it has not landed yet.
@@ -838,6 +843,7 @@ static int forward_impl(const FwdCall& f) {
   const int depth_passes = depth_passes_env ? depth_passes_env : (Pp >= (size_t(3) << 20) ? 4 : 3);
   const bool group_sums = nk1 > K1_GROUP_MIN;                              // K2 reads K1's sums through group sums (k_bout_group_sum)
   const uint32_t ngroups = (nk1 + K1_GROUP - 1) / K1_GROUP;
+  c->depth_passes = depth_passes; c->group_sums = group_sums; c->scan_items = scan_items_for((uint32_t)Pv);
   SlabPlan sp;
   sp.add<uint32_t>(Pp); sp.add<uint32_t>(Pp); sp.add<uint32_t>(Pp); sp.add<uint32_t>(Pp); sp.add<uint32_t>(Pp);   // dkey, k1, vtmp, v2, tcnt
   sp.add<uint32_t>((size_t)RS_BINS_DEV * nbP); sp.add<uint32_t>(RS_BINS_DEV);
@@ -1033,6 +1039,7 @@ static int forward_impl(const FwdCall& f) {
   if (nbound == 0 && P > 0) F_TRY("init", hipMemsetAsync(c->off, 0, sizeof(uint32_t), st));
   if (nbound > 0) {
     const int rounds = radix_rounds_for(nbound);
+    c->tile_rounds = rounds;
     const uint32_t chunkN = (uint32_t)rs_chunk(rounds);
     const uint32_t nbN = (nbound + chunkN - 1) / chunkN;
     const uint32_t tblN = RS_BINS * nbN;
@@ -1828,6 +1835,10 @@ int gsr_ctx_info(const GsrCtx* c, int32_t what, int64_t* out) {
     case 3: *out = (int64_t)c->nbound; return GSR_OK;
     case 4: *out = (int64_t)c->B; return GSR_OK;
     case 5: *out = (int64_t)c->Ppad; return GSR_OK;
+    case 6: *out = (int64_t)c->depth_passes; return GSR_OK;
+    case 7: *out = (int64_t)c->tile_rounds; return GSR_OK;
+    case 8: *out = (int64_t)c->scan_items; return GSR_OK;
+    case 9: *out = c->group_sums ? 1 : 0; return GSR_OK;
     default: return set_err(GSR_ERR_INVALID, "gsr_ctx_info: unknown item %d", what);
   }
 }
@@ -2610,6 +2621,52 @@ int gsr_test_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t n, int32_t begi
   uint32_t* table = v1 + n;
   uint32_t* sums = table + tbl;
   const int res = radix_sort_pairs(keys, vals, k1, v1, n, nullptr, begin_bit, end_bit, iota != 0, table, sums, st);
+  if (res) {
+    (void)hipMemcpyAsync(keys, k1, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(vals, v1, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, st);
+  }
+  pool_free(dev, blk);
+  LAUNCH_CHECK("test sort");
+  return GSR_OK;
+}
+
+int gsr_test_scan_ex(const uint32_t* in, uint32_t* out, uint32_t n, const uint32_t* n_dev, uint32_t* chunk_first,
+                     uint32_t chunk_len, uint32_t chunk_cap, void* stream) {
+  if (!in || !out) return set_err(GSR_ERR_INVALID, "gsr_test_scan_ex: null argument");
+  if (chunk_first && chunk_len == 0u) return set_err(GSR_ERR_INVALID, "gsr_test_scan_ex: chunk_first needs chunk_len > 0");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int dev = cur_dev();
+  void* blk = pool_alloc(dev, sizeof(uint32_t) * ((size_t)n / 2048 + 2), st);
+  if (!blk) return set_err(GSR_ERR_NOMEM, "gsr_test_scan_ex: allocation failed");
+  scan_exclusive_u32(in, out, n, n_dev, static_cast<uint32_t*>(blk), st, chunk_first, chunk_first ? chunk_len : 1u,
+                     chunk_first ? chunk_cap : 0u);
+  pool_free(dev, blk);
+  LAUNCH_CHECK("test scan");
+  return GSR_OK;
+}
+
+int gsr_test_sort_pairs_ex(uint32_t* keys, uint32_t* vals, uint32_t n, const uint32_t* n_dev, int32_t begin_bit,
+                           int32_t end_bit, int32_t iota, int32_t rounds, uint32_t* key_ranges, uint32_t key_limit,
+                           void* stream) {
+  if (!keys || !vals) return set_err(GSR_ERR_INVALID, "gsr_test_sort_pairs_ex: null argument");
+  if (rounds != 0 && rounds != RS_ROUNDS_MIN && rounds != RS_ROUNDS_MAX)
+    return set_err(GSR_ERR_INVALID, "gsr_test_sort_pairs_ex: rounds %d (0 = automatic, 8 or 16)", rounds);
+  if (begin_bit < 0 || end_bit > 32 || end_bit < begin_bit)
+    return set_err(GSR_ERR_INVALID, "gsr_test_sort_pairs_ex: bad bit range [%d, %d)", begin_bit, end_bit);
+  if (key_ranges && begin_bit != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_test_sort_pairs_ex: key_ranges need begin_bit 0 (a sort on the whole key), got %d", begin_bit);
+  if (n == 0) return GSR_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int dev = cur_dev();
+  const uint32_t tbl = radix_table_words(n);
+  void* blk = pool_alloc(dev, sizeof(uint32_t) * ((size_t)2 * n + tbl + RS_BINS), st);
+  if (!blk) return set_err(GSR_ERR_NOMEM, "gsr_test_sort_pairs_ex: allocation failed");
+  uint32_t* k1 = static_cast<uint32_t*>(blk);
+  uint32_t* v1 = k1 + n;
+  uint32_t* table = v1 + n;
+  uint32_t* sums = table + tbl;
+  const int res = radix_sort_pairs(keys, vals, k1, v1, n, n_dev, begin_bit, end_bit, iota != 0, table, sums, st, false,
+                                   key_ranges, key_limit, rounds);
   if (res) {
     (void)hipMemcpyAsync(keys, k1, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, st);
     (void)hipMemcpyAsync(vals, v1, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, st);

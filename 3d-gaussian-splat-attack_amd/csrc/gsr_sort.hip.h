@@ -181,12 +181,15 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_apply_carry(const uint32_
   if (b == nb - 1 && threadIdx.x == 0) out[n] = carry + total;
 }
 
+// items per thread of the scan of n words: 8 (2048 per block) up to 2 M, 16 (4096) above
+inline int scan_items_for(uint32_t n) { return n <= (2u << 20) ? 8 : 16; }
+
 // out may alias in; out holds n + 1 words (out[n_live] = total).  sums: ceil(n / 2048) words.
 inline void scan_exclusive_u32(const uint32_t* in, uint32_t* out, uint32_t n, const uint32_t* n_dev, uint32_t* sums,
                                hipStream_t st, uint32_t* chunk_first = nullptr, uint32_t chunk_len = 1,
                                uint32_t chunk_cap = 0) {
   if (n == 0) { (void)hipMemsetAsync(out, 0, sizeof(uint32_t), st); return; }
-  if (n <= (2u << 20)) {
+  if (scan_items_for(n) == 8) {
     const uint32_t nb = (n + 2047) / 2048;
     hipLaunchKernelGGL((k_scan_partial<8>), dim3(nb), dim3(SCAN_THREADS), 0, st, in, n, n_dev, sums);
     hipLaunchKernelGGL((k_scan_apply_carry<8>), dim3(nb), dim3(SCAN_THREADS), 0, st, in, out, n, n_dev, (const uint32_t*)sums,
@@ -507,14 +510,16 @@ inline void radix_pass(const uint32_t* ki, const uint32_t* vi, uint32_t* ko, uin
 // key_ranges != nullptr (and begin_bit == 0, end_bit covering every key below key_limit): the last pass also leaves the
 // span [start, end) of every key value below key_limit in key_ranges[2 key .. 2 key + 1], which the caller has set to
 // (0xFFFFFFFF, 0).
+// rounds: 8 or 16 64-element rounds per wave (2048- or 4096-element chunks); 0 = radix_rounds_for(n).
 // table: radix_table_words(n) words; sums: at least 256 words.
 inline int radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, const uint32_t* n_dev,
                             int begin_bit, int end_bit, bool iota_first, uint32_t* table, uint32_t* sums, hipStream_t st,
-                            bool first_hist_done = false, uint32_t* key_ranges = nullptr, uint32_t key_limit = 0) {
+                            bool first_hist_done = false, uint32_t* key_ranges = nullptr, uint32_t key_limit = 0,
+                            int rounds = 0) {
   if (n == 0 || end_bit <= begin_bit) return 0;
   const int bits = end_bit - begin_bit;
   const int passes = (bits + 7) / 8;
-  const int rounds = radix_rounds_for(n);
+  if (rounds == 0) rounds = radix_rounds_for(n);
   int cur = 0, bit = begin_bit;
   for (int p = 0; p < passes; ++p) {
     // spread the bits evenly over the passes (13 bits -> 7 + 6): longer digit runs per block

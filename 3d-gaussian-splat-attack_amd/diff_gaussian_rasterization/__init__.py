@@ -193,6 +193,11 @@ def _load():
     lib.gsr_test_scan.argtypes = [vp, vp, ctypes.c_uint32, vp]
     lib.gsr_test_sort_pairs.restype = ctypes.c_int
     lib.gsr_test_sort_pairs.argtypes = [vp, vp, ctypes.c_uint32, i32, i32, i32, vp]
+    if hasattr(lib, "gsr_test_scan_ex"):                   # (absent from older builds selected through GSR_LIBRARY for A/B runs)
+        lib.gsr_test_scan_ex.restype = ctypes.c_int
+        lib.gsr_test_scan_ex.argtypes = [vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp]
+        lib.gsr_test_sort_pairs_ex.restype = ctypes.c_int
+        lib.gsr_test_sort_pairs_ex.argtypes = [vp, vp, ctypes.c_uint32, vp, i32, i32, i32, i32, vp, ctypes.c_uint32, vp]
     lib.gsr_last_error.restype = ctypes.c_char_p
     lib.gsr_last_error.argtypes = []
     _lib = lib

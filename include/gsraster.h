@@ -842,6 +842,15 @@ int gsr_query(int32_t what, int64_t* out);
  * 4 KB: 50-190 MB at N = 3-10 M pairs.  num_rendered counts the pairs of the TIGHTENED tile rects (the tiles the
  * alpha >= 1/255 footprint's bounding box touches); under GSR_FLAG_NO_CULL it is the reference's count. */
 int gsr_ctx_info(const GsrCtx* ctx, int32_t what, int64_t* out);   /* also: 4 = views of the context's batch (1: an ordinary forward), 5 = Ppad */
+/* Items 6-9: which of the size-gated variants of the binning front end the context's forward took (tests assert them):
+ * 6 = passes of the depth sort: 3 (digits of <= 11 bits, 2048-bin kernels) or 4 (<= 8 bits, 256-bin kernels; from 3 << 20
+ *     virtual Gaussians on, or GSR_DEPTH_PASSES=4 in the environment),
+ * 7 = 64-element rounds per wave of the pair emission and the tile sort: 8 (2048-element chunks) or 16 (4096; above 4 << 20
+ *     pairs of capacity -- item 3 -- or GSR_RS_ROUNDS=16); 0 when the forward had no pairs.  Under 4 depth passes, passes
+ *     1-3 of the depth sort use the rounds the same rule gives for the number of virtual Gaussians,
+ * 8 = items per thread of the rank-order scan: 8, or 16 above 2 << 20 virtual Gaussians,
+ * 9 = 1 when the storage-order scan read the preprocess workgroups' sums through group sums (more than 4096 * 256
+ *     virtual Gaussians), else 0. */
 
 /* Copies one internal array of a context into a caller DEVICE buffer (tests / diagnostics):
  * what 0 = tile ranges [T][2] u32, 1 = sorted pair list [N] u32 (Gaussian index | strip mask << 28, tile by tile, depth
@@ -896,6 +905,24 @@ int gsr_debug_wave_clock_fwd(unsigned long long* buf);
 int gsr_test_scan(const uint32_t* in, uint32_t* out, uint32_t n, void* stream);
 int gsr_test_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t n, int32_t begin_bit, int32_t end_bit, int32_t iota,
                         void* stream);
+/* The same primitives with every argument the forward uses.
+ * gsr_test_scan_ex: n_dev (device, may be NULL): the live count is min(n, *n_dev); out[0..live) are the prefix sums and
+ *   out[live] the total, words behind it are not written.  out == in is allowed.  chunk_first (device, may be NULL): the
+ *   scanned values are run lengths of output slots (element r owns [out[r], out[r] + in[r])), and chunk_first[c] receives the
+ *   element that owns slot c * chunk_len, for every c < chunk_cap with c * chunk_len below the total; other entries are
+ *   not written.  chunk_len must be > 0 when chunk_first is given.
+ * gsr_test_sort_pairs_ex: n_dev as above (positions at and behind the live count hold nothing meaningful afterwards);
+ *   rounds: 64-element rounds per wave, 8 or 16 (chunks of 2048 / 4096 elements), 0 = what the library picks for n;
+ *   key_ranges (device, may be NULL; needs begin_bit == 0 and [0, end_bit) covering every key): 2 * key_limit words the
+ *   caller has set to (0xFFFFFFFF, 0); the last pass leaves [first, last + 1) of the run of every key < key_limit that is
+ *   present, in positions of the sorted output.
+ * Both return GSR_ERR_INVALID before any launch for NULL in / out / keys / vals, rounds outside {0, 8, 16}, a bit range
+ * outside [0, 32], and key_ranges with begin_bit != 0. */
+int gsr_test_scan_ex(const uint32_t* in, uint32_t* out, uint32_t n, const uint32_t* n_dev, uint32_t* chunk_first,
+                     uint32_t chunk_len, uint32_t chunk_cap, void* stream);
+int gsr_test_sort_pairs_ex(uint32_t* keys, uint32_t* vals, uint32_t n, const uint32_t* n_dev, int32_t begin_bit,
+                           int32_t end_bit, int32_t iota, int32_t rounds, uint32_t* key_ranges, uint32_t key_limit,
+                           void* stream);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,27 @@ def test_version_and_argument_validation_without_device(lib):
     assert b"columns" in lib.gsr_last_error()
 
 
+def test_wide_test_hooks_validate_before_any_launch(lib):
+    """gsr_test_scan_ex / gsr_test_sort_pairs_ex: NULL buffers, rounds outside {0, 8, 16}, a bad bit range and key ranges
+    with begin_bit != 0 are refused before the device is touched."""
+    one = ctypes.c_void_p(8)
+    assert lib.gsr_test_scan_ex(None, one, 4, None, None, 0, 0, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_test_scan_ex(one, None, 4, None, None, 0, 0, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_test_scan_ex(one, one, 4, None, one, 0, 4, None) == 1 and b"chunk_len" in lib.gsr_last_error()
+    assert lib.gsr_test_sort_pairs_ex(None, one, 4, None, 0, 8, 0, 0, None, 0, None) == 1 and b"null" in lib.gsr_last_error()
+    assert lib.gsr_test_sort_pairs_ex(one, None, 4, None, 0, 8, 0, 0, None, 0, None) == 1 and b"null" in lib.gsr_last_error()
+    for rounds in (-8, 1, 4, 12, 32):
+        assert lib.gsr_test_sort_pairs_ex(one, one, 4, None, 0, 8, 0, rounds, None, 0, None) == 1
+        assert b"rounds" in lib.gsr_last_error()
+    for lo, hi in ((-1, 8), (0, 33), (9, 3)):
+        assert lib.gsr_test_sort_pairs_ex(one, one, 4, None, lo, hi, 0, 8, None, 0, None) == 1
+        assert b"bit range" in lib.gsr_last_error()
+    assert lib.gsr_test_sort_pairs_ex(one, one, 4, None, 3, 9, 0, 16, one, 4, None) == 1
+    assert b"key_ranges" in lib.gsr_last_error()
+    for rounds in (0, 8, 16):                                  # nothing to sort: accepted, nothing launched
+        assert lib.gsr_test_sort_pairs_ex(one, one, 0, None, 0, 8, 0, rounds, one, 4, None) == 0
+
+
 def test_package_has_no_cpu_path():
     import diff_gaussian_rasterization as D
     st = D.GaussianRasterizationSettings(16, 16, 0.5, 0.5, torch.zeros(3), 1.0, torch.eye(4), torch.eye(4), 3,

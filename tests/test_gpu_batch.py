@@ -229,7 +229,13 @@ def test_fullsize_batch_of_four_equals_single_views():
     model, cams, _ = make_scene("nyc-1M", device=dev, n_views=8)
     g = torch.Generator().manual_seed(99)
     gcs = [torch.randn(3, 1080, 1920, generator=g).to(dev) for _ in range(4)]
-    _check_equal(model, [cams[i] for i in (0, 3, 5, 6)], gcs)
+    out, _ = _check_equal(model, [cams[i] for i in (0, 3, 5, 6)], gcs)
+    # what this test covers of the binning front end's size-gated variants (gsr_ctx_info 6-9): 4 x 1 M virtual Gaussians take
+    # the four-pass depth sort and the group sums; the chunk rounds follow the pair capacity the forward sized its buffers for
+    h = out["render"].grad_fn.holder
+    assert h.info(4) == 4 and h.info(6) == 4 and h.info(9) == 1
+    assert h.info(7) == (16 if h.info(3) > (4 << 20) else 8)
+    assert h.info(8) == (16 if 4 * h.info(5) > (2 << 20) else 8)
 
 
 def test_pgd_attack_batched_matches_per_view_loop():

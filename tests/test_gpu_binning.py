@@ -1,5 +1,7 @@
 """The binning stage as integers: tile lists against oracle_r.build_tile_lists, the depth order against a stable argsort for
-every shape of depth distribution, scan chunks, empty and nearly empty scenes, the asynchronous pair count."""
+every shape of depth distribution, scan chunks, empty and nearly empty scenes, live counts at the depth sort's chunk edges,
+the two scans of tiles touched against a bincount of the pair list, the asynchronous pair count.  The case helpers are shared
+with tests/binning_child.py, which runs them under the forced variants of the front end."""
 import math
 import pytest
 import torch
@@ -107,6 +109,154 @@ def _check_lists_against_stable_argsort(D, out):
     assert int(lens.sum()) > 0
 
 
+DEPTH_DISTS = ["constant", "two-values", "cluster+outliers", "shell-16-buckets", "shell-40-buckets", "narrow", "uniform",
+               "log-uniform"]
+WIDEST = "widest-digits"          # view depths 0.25 .. 3e5: the key range spans 30+ bits
+
+
+def _depth_scene(dist, P):
+    """(xyz, log scale) of P Gaussians ~1.7 px wide on screen whose view depths follow `dist` (one of DEPTH_DISTS, or
+    WIDEST), with exact ties at every 9th (WIDEST: 7th) Gaussian."""
+    widest = dist == WIDEST
+    g = torch.Generator().manual_seed(7 if widest else 11)
+    u = torch.rand(P, generator=g)
+    if widest:
+        z = torch.exp(u * (math.log(3e5) - math.log(0.25)) + math.log(0.25))
+    elif dist == "constant":
+        z = torch.full((P,), 5.0)
+    elif dist == "two-values":
+        z = torch.where(u < 0.3, torch.tensor(2.0), torch.tensor(7.5))
+    elif dist == "cluster+outliers":
+        z = 10.0 + (u - 0.5) * 1e-3
+        z[::20] = torch.exp(torch.rand(len(z[::20]), generator=g) * math.log(400.0)) * 0.3      # 0.3 .. 120
+    elif dist.startswith("shell"):
+        # outliers 0.3 .. 120 make the key range ~27 bits; the shell is 16 (or 40) runs of 2^16 float32 steps deep
+        z = 8.0 + u * (1.0 if dist == "shell-16-buckets" else 2.5)
+        z[::20] = torch.exp(torch.rand(len(z[::20]), generator=g) * math.log(400.0)) * 0.3
+    elif dist == "narrow":
+        z = 5.0 + torch.floor(u * 700.0) * 4.76837158203125e-07                           # 700 adjacent float32 values
+    elif dist == "uniform":
+        z = 1.0 + u * 30.0
+    else:
+        assert dist == "log-uniform", dist
+        z = torch.exp(u * math.log(1000.0)) * 0.3
+    if widest:
+        z[::7] = z[3]                                       # exact ties: stability
+    else:
+        z[::9] = z[4]
+    xy = (torch.rand(P, 2, generator=g) - 0.5) * 0.6
+    xyz = torch.cat([xy * z[:, None], z[:, None]], dim=1)
+    scale = torch.log(0.01 * z)[:, None].expand(P, 3).contiguous()      # ~1.7 px on screen whatever the depth
+    return xyz, scale
+
+
+# gsr_ctx_info items 6-9: which size-gated variants of the front end a forward took
+INFO_DEPTH_PASSES, INFO_TILE_ROUNDS, INFO_SCAN_ITEMS, INFO_GROUP_SUMS = 6, 7, 8, 9
+DV_N, DV_V, DV_W = 0, 1, 3
+GID_MASK = (1 << 28) - 1
+
+
+def _variants(img):
+    h = img.grad_fn.holder
+    return dict(passes=h.info(INFO_DEPTH_PASSES), rounds=h.info(INFO_TILE_ROUNDS), scan_items=h.info(INFO_SCAN_ITEMS),
+                group_sums=h.info(INFO_GROUP_SUMS))
+
+
+def _check_order_is_stable_argsort(D, out):
+    """order[:V] == the visible Gaussians in the order of the stable argsort of their float32 depths; -> V."""
+    img = out["render"]
+    order = D.export_state(img, "order").long()
+    depth = D.export_state(img, "G").view(-1, 12)[:, 9]
+    ids = torch.nonzero(out["radii"] > 0).flatten()
+    assert int(D.export_state(img, "dv")[DV_V]) == ids.numel() == order.numel()
+    assert torch.equal(order, ids[torch.argsort(depth[ids], stable=True)])
+    return int(ids.numel())
+
+
+def _check_pair_prefixes(D, out):
+    """The two scans of tiles touched against a bincount of the pair list's Gaussian ids (on the CPU): off in depth-rank
+    order (off[r + 1] - off[r] = pairs of the Gaussian of rank r: what the last depth pass gathered, through the byte array
+    or, for counts of 255 and more, the 32-bit one), offg in storage order; both end on the pair count.  -> the counts."""
+    img = out["render"]
+    P = int(out["radii"].numel())
+    N = D.last_num_rendered(img)
+    ids = (D.export_state(img, "pair_rank").long().cpu() & GID_MASK)
+    assert ids.numel() == N
+    cnt = torch.bincount(ids, minlength=P)
+    order = D.export_state(img, "order").long().cpu()
+    off = D.export_state(img, "off").long().cpu() & 0xFFFFFFFF
+    offg = D.export_state(img, "offg").long().cpu() & 0xFFFFFFFF
+    assert off.numel() == order.numel() + 1 and offg.numel() == P + 1
+    assert int(off[0]) == 0 and int(off[-1]) == N and int(offg[P]) == N
+    assert torch.equal(off[1:] - off[:-1], cnt[order])
+    assert torch.equal(offg, torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(cnt, 0)]))
+    assert int((cnt > 0).sum()) == order.numel()           # every Gaussian with pairs is ranked, and no other
+    return cnt
+
+
+def _depth_order_case(D, dev, dist, P=6000):
+    """One depth distribution: the exported depth order and every tile's list against the stable argsort; -> out."""
+    xyz, scale = _depth_scene(dist, P)
+    out = _raw_render(D, dev, xyz, scale, torch.zeros(P, 1), flags=D.FLAG_NO_CULL, grad=False)[2]
+    assert _check_order_is_stable_argsort(D, out) > P // 2
+    _check_lists_against_stable_argsort(D, out)
+    return out
+
+
+LIVE_COUNTS = [0, 1, 2047, 2048, 2049, 4096, 4097]         # around one and two 2048-key chunks of the depth sort
+
+
+def _live_count_case(D, dev, V, P=9000):
+    """Exactly V of P Gaussians in front of the camera, scattered through the storage order; the others lie behind it and
+    get the dropped key.  The live count, the depth order, the end of the rank-order scan; -> out."""
+    g = torch.Generator().manual_seed(100 + V)
+    front = torch.sort(torch.randperm(P, generator=g)[:V]).values
+    z = -(torch.rand(P, generator=g) * 5.0 + 0.5)
+    zf = torch.rand(V, generator=g) * 9.0 + 1.0
+    zf[::5] = zf[:1].clone()                                # exact ties: stability
+    z[front] = zf
+    xy = (torch.rand(P, 2, generator=g) - 0.5) * 0.6
+    xyz = torch.cat([xy * z.abs()[:, None], z[:, None]], dim=1)
+    scale = torch.log(0.01 * z.abs())[:, None].expand(P, 3).contiguous()
+    out = _raw_render(D, dev, xyz, scale, torch.full((P, 1), 2.0), grad=False)[2]
+    img = out["render"]
+    assert torch.equal(torch.nonzero(out["radii"] > 0).flatten().cpu(), front)
+    assert int(D.export_state(img, "dv")[DV_V]) == V
+    assert _check_order_is_stable_argsort(D, out) == V
+    off = D.export_state(img, "off").long() & 0xFFFFFFFF
+    assert off.numel() == V + 1 and int(off[V]) == D.last_num_rendered(img)
+    if V == 0:
+        bg = torch.tensor([0.2, 0.4, 0.6], device=dev)
+        assert D.last_num_rendered(img) == 0 and torch.equal(img, bg[:, None, None].expand_as(img))
+    else:
+        assert D.last_num_rendered(img) >= V
+        _check_pair_prefixes(D, out)
+        _check_lists_against_stable_argsort(D, out)
+    return out
+
+
+def _tiles_per_rank_case(D, dev):
+    """320 x 320 (400 tiles): 2000 small splats and, scattered among them, 8 that cover the whole image -- more tiles than
+    the byte array of tiles touched can hold, so the depth sort's last pass looks their count up in the 32-bit array.  -> out."""
+    P, big = 2008, torch.arange(8) * 251 + 100
+    g = torch.Generator().manual_seed(21)
+    z = torch.rand(P, generator=g) * 8.0 + 1.0
+    z[::6] = z[2]
+    xy = (torch.rand(P, 2, generator=g) - 0.5) * 0.9
+    xy[big] *= 0.2
+    xyz = torch.cat([xy * z[:, None], z[:, None]], dim=1)
+    scale = torch.log(0.01 * z)[:, None].expand(P, 3).contiguous()
+    scale[big] = math.log(5.0) + torch.log(z[big])[:, None]
+    out = _raw_render(D, dev, xyz, scale, torch.full((P, 1), 2.0), W=320, H=320, grad=False)[2]
+    cnt = _check_pair_prefixes(D, out)
+    assert bool((cnt[big] > 255).all()) and int(cnt[big].max()) <= 400, cnt[big].tolist()
+    small = torch.ones(P, dtype=torch.bool)
+    small[big] = False
+    assert 0 < int(cnt[small].max()) < 255 and int((cnt[small] > 0).sum()) > 1500
+    _check_order_is_stable_argsort(D, out)
+    return out
+
+
 def _small_scene(n_views=3, P=20000, w=320, h=192):
     from gsplat_attack.scenes import make_scene
     dev = torch.device("cuda:0")
@@ -177,12 +327,7 @@ def test_depth_range_that_needs_the_widest_digits_sorts_exactly():
     D = _hip()
     dev = torch.device("cuda:0")
     P = 40000
-    g = torch.Generator().manual_seed(7)
-    z = torch.exp(torch.rand(P, generator=g) * (math.log(3e5) - math.log(0.25)) + math.log(0.25))
-    z[::7] = z[3]                                           # exact ties: stability
-    xy = (torch.rand(P, 2, generator=g) - 0.5) * 0.6
-    xyz = torch.cat([xy * z[:, None], z[:, None]], dim=1)
-    scale = torch.log(0.01 * z)[:, None].expand(P, 3).contiguous()      # ~1.7 px on screen whatever the depth
+    xyz, scale = _depth_scene(WIDEST, P)
     model, cam, out = _raw_render(D, dev, xyz, scale, torch.zeros(P, 1), flags=D.FLAG_NO_CULL)
     dv = D.export_state(out["render"], "dv")
     assert int(dv[3]) >= 10, f"digit width {int(dv[3])}"
@@ -193,8 +338,7 @@ def test_depth_range_that_needs_the_widest_digits_sorts_exactly():
     _check_lists_against_stable_argsort(D, out)
 
 
-@pytest.mark.parametrize("dist", ["constant", "two-values", "cluster+outliers", "shell-16-buckets", "shell-40-buckets", "narrow",
-                                  "uniform", "log-uniform"])
+@pytest.mark.parametrize("dist", DEPTH_DISTS)
 def test_depth_order_is_the_stable_argsort_whatever_the_depth_distribution(dist):
     """The depth sort (three counting passes whose digit width follows the keys' range) on distributions that stress a
     sort by depth: every key equal, two values, 95 % of the Gaussians in a shell 1e-3 thick with outliers stretching the
@@ -204,32 +348,28 @@ def test_depth_order_is_the_stable_argsort_whatever_the_depth_distribution(dist)
     D = _hip()
     dev = torch.device("cuda:0")
     P = 60000
-    g = torch.Generator().manual_seed(11)
-    u = torch.rand(P, generator=g)
-    if dist == "constant":
-        z = torch.full((P,), 5.0)
-    elif dist == "two-values":
-        z = torch.where(u < 0.3, torch.tensor(2.0), torch.tensor(7.5))
-    elif dist == "cluster+outliers":
-        z = 10.0 + (u - 0.5) * 1e-3
-        z[::20] = torch.exp(torch.rand(P // 20, generator=g) * math.log(400.0)) * 0.3      # 0.3 .. 120
-    elif dist.startswith("shell"):
-        # outliers 0.3 .. 120 make the key range ~27 bits; the shell is 16 (or 40) runs of 2^16 float32 steps deep
-        z = 8.0 + u * (1.0 if dist == "shell-16-buckets" else 2.5)
-        z[::20] = torch.exp(torch.rand(P // 20, generator=g) * math.log(400.0)) * 0.3
-    elif dist == "narrow":
-        z = 5.0 + torch.floor(u * 700.0) * 4.76837158203125e-07                           # 700 adjacent float32 values
-    elif dist == "uniform":
-        z = 1.0 + u * 30.0
-    else:
-        z = torch.exp(u * math.log(1000.0)) * 0.3
-    z[::9] = z[4]                                           # exact ties: stability
-    xy = (torch.rand(P, 2, generator=g) - 0.5) * 0.6
-    xyz = torch.cat([xy * z[:, None], z[:, None]], dim=1)
-    scale = torch.log(0.01 * z)[:, None].expand(P, 3).contiguous()
+    xyz, scale = _depth_scene(dist, P)
     model, cam, out = _raw_render(D, dev, xyz, scale, torch.zeros(P, 1), flags=D.FLAG_NO_CULL, grad=False)
     assert int((out["radii"] > 0).sum()) > P // 2
     _check_lists_against_stable_argsort(D, out)
+
+
+@pytest.mark.parametrize("V", LIVE_COUNTS)
+def test_live_count_at_the_depth_sort_chunk_edges(V):
+    """V visible Gaussians scattered among 9000, V on both sides of one and two chunks of the depth sort: the device-side
+    live count, the depth order, the end of the rank-order scan, the background when nothing is visible."""
+    D = _hip()
+    out = _live_count_case(D, torch.device("cuda:0"), V)
+    v = _variants(out["render"])
+    print(f"V={V}: {v}")
+    assert v["scan_items"] == 8 and v["group_sums"] == 0 and v["rounds"] in ((0,) if V == 0 else (8, 16))
+
+
+def test_tiles_per_rank_gather_with_counts_beyond_a_byte():
+    """off (depth-rank order) and offg (storage order) against a bincount of the pair list, on a scene whose largest splats
+    touch all 400 tiles."""
+    D = _hip()
+    _tiles_per_rank_case(D, torch.device("cuda:0"))
 
 
 def test_more_gaussians_than_the_small_scan_chunk_handles():
@@ -246,6 +386,10 @@ def test_more_gaussians_than_the_small_scan_chunk_handles():
     b = _raw_render(D, dev, xyz, scale, opac, W=256, H=160, grad=False, flags=D.FLAG_NO_CULL)[2]
     assert int((a["radii"] > 0).sum()) > 100000
     assert torch.equal(a["radii"], b["radii"]) and torch.equal(a["render"], b["render"])
+    for o in (a, b):
+        v = _variants(o["render"])
+        assert v["scan_items"] == 16 and v["group_sums"] == 1, v
+    _check_pair_prefixes(D, a)
 
 
 def test_asynchronous_pair_count_matches_and_reports_overflow():
