@@ -21,6 +21,8 @@ from typing import NamedTuple, Optional
 import torch
 from torch import nn
 
+from ._signatures import CHUNK_FN as _CHUNK_FN, SIGNATURES
+
 NUM_OBJECTS = 16
 _LIB_NAME = "libgsraster.so"
 _lib = None
@@ -72,9 +74,6 @@ def extra_flags(flags: int):
 GSR_STAGES = ("preprocess", "depth_sort", "bin", "tile_sort", "render_fwd", "render_bwd", "preprocess_bwd")
 
 
-_CHUNK_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64)   # gsr_chunk_fn
-
-
 class _CSettings(ctypes.Structure):
     # field order and types mirror `struct GsrSettings` in include/gsraster.h
     _fields_ = [
@@ -111,100 +110,17 @@ def _load():
             f"`make -C {os.path.join(os.path.dirname(os.path.dirname(path)), 'csrc')}` (hipcc, gfx950); "
             "there is no CPU or PyTorch fallback for the raster path.")
     lib = ctypes.CDLL(path)
-    vp, i32, i64p = ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)
-    lib.gsr_forward.restype = ctypes.c_int
-    lib.gsr_forward.argtypes = [ctypes.POINTER(_CSettings), i32, i32] + [vp] * 8 + [vp, vp, vp,
-                                ctypes.POINTER(vp), i64p, vp]
-    lib.gsr_backward.restype = ctypes.c_int
-    lib.gsr_backward.argtypes = [vp] * 13
-    lib.gsr_forward_raw.restype = ctypes.c_int
-    lib.gsr_forward_raw.argtypes = [ctypes.POINTER(_CSettings), i32] + [vp] * 7 + [vp, vp, vp, ctypes.POINTER(vp), i64p, vp]
-    lib.gsr_backward_raw.restype = ctypes.c_int
-    lib.gsr_backward_raw.argtypes = [vp] * 12
-    lib.gsr_backward_raw_into.restype = ctypes.c_int
-    lib.gsr_backward_raw_into.argtypes = [vp] * 11 + [i32, vp]
-    lib.gsr_backward_raw_chunked.restype = ctypes.c_int
-    lib.gsr_backward_raw_chunked.argtypes = [vp] * 11 + [i32, i32, _CHUNK_FN, vp, vp]
-    lib.gsr_forward_raw2.restype = ctypes.c_int
-    lib.gsr_forward_raw2.argtypes = [ctypes.POINTER(_CSettings), i32] + [vp] * 7 + [i32] + [vp] * 7 + [vp, vp, vp, i64p, vp]
-    lib.gsr_forward_raw2_keep.restype = ctypes.c_int
-    lib.gsr_forward_raw2_keep.argtypes = ([ctypes.POINTER(_CSettings), i32] + [vp] * 7 + [i32] + [vp] * 7
-                                          + [vp, vp, vp, ctypes.POINTER(vp), i64p, vp])
-    if hasattr(lib, "gsr_forward_raw_batch"):              # (absent from older builds selected through GSR_LIBRARY for A/B runs)
-        lib.gsr_forward_raw_batch.restype = ctypes.c_int
-        lib.gsr_forward_raw_batch.argtypes = ([ctypes.POINTER(_CSettings), i32, i32] + [vp] * 6 + [vp, vp, ctypes.POINTER(vp), i64p, vp])
-        lib.gsr_backward_raw_batch_into.restype = ctypes.c_int
-        lib.gsr_backward_raw_batch_into.argtypes = [vp] * 9 + [i32, vp]
-        lib.gsr_backward_raw_batch_views.restype = ctypes.c_int
-        lib.gsr_backward_raw_batch_views.argtypes = [vp] * 9 + [ctypes.c_int64, vp]
-    if hasattr(lib, "gsr_forward_raw_batch_obj"):          # (C ABI 602)
-        lib.gsr_forward_raw_batch_obj.restype = ctypes.c_int
-        lib.gsr_forward_raw_batch_obj.argtypes = ([ctypes.POINTER(_CSettings), i32, i32] + [vp] * 7
-                                                  + [vp, vp, vp, ctypes.POINTER(vp), i64p, vp])
-        lib.gsr_forward_raw2_batch_obj.restype = ctypes.c_int
-        lib.gsr_forward_raw2_batch_obj.argtypes = ([ctypes.POINTER(_CSettings), i32, i32] + [vp] * 7 + [i32] + [vp] * 7
-                                                   + [vp, vp, vp, ctypes.POINTER(vp), i64p, vp])
-        lib.gsr_backward_raw_batch_obj_into.restype = ctypes.c_int
-        lib.gsr_backward_raw_batch_obj_into.argtypes = [vp] * 11 + [i32, vp]
-        lib.gsr_backward_raw_batch_obj_views.restype = ctypes.c_int
-        lib.gsr_backward_raw_batch_obj_views.argtypes = [vp] * 11 + [ctypes.c_int64, vp]
-    if hasattr(lib, "gsr_forward_raw2_batch"):
-        lib.gsr_forward_raw2_batch.restype = ctypes.c_int
-        lib.gsr_forward_raw2_batch.argtypes = ([ctypes.POINTER(_CSettings), i32, i32] + [vp] * 6 + [i32] + [vp] * 6
-                                               + [vp, vp, ctypes.POINTER(vp), i64p, vp])
-    if hasattr(lib, "gsr_forward_aux"):                # 0.6.4: depth / alpha maps
-        lib.gsr_forward_aux.restype = ctypes.c_int
-        lib.gsr_forward_aux.argtypes = list(lib.gsr_forward.argtypes[:-1]) + [vp, vp, vp]
-        lib.gsr_forward_raw_aux.restype = ctypes.c_int
-        lib.gsr_forward_raw_aux.argtypes = list(lib.gsr_forward_raw.argtypes[:-1]) + [vp, vp, vp]
-        lib.gsr_forward_raw_batch_aux.restype = ctypes.c_int
-        lib.gsr_forward_raw_batch_aux.argtypes = list(lib.gsr_forward_raw_batch.argtypes[:-1]) + [vp, vp, vp]
-        lib.gsr_ctx_set_aux_grads.restype = ctypes.c_int
-        lib.gsr_ctx_set_aux_grads.argtypes = [vp, vp, vp]
-    lib.gsr_ctx_rerender.restype = ctypes.c_int
-    lib.gsr_ctx_rerender.argtypes = [vp] * 8 + [ctypes.c_uint32, vp]
-    lib.gsr_ctx_free.restype = None
-    lib.gsr_ctx_free.argtypes = [vp]
-    lib.gsr_mark_visible.restype = ctypes.c_int
-    lib.gsr_mark_visible.argtypes = [ctypes.POINTER(_CSettings), i32, vp, vp, vp]
-    lib.gsr_query.restype = ctypes.c_int
-    lib.gsr_query.argtypes = [i32, i64p]
-    lib.gsr_ctx_info.restype = ctypes.c_int
-    lib.gsr_ctx_info.argtypes = [vp, i32, i64p]
-    lib.gsr_ctx_export.restype = ctypes.c_int
-    lib.gsr_ctx_export.argtypes = [vp, i32, vp, ctypes.c_int64, vp]
-    lib.gsr_trim_pool.restype = None
-    lib.gsr_trim_pool.argtypes = []
-    lib.gsr_profile.restype = None
-    lib.gsr_profile.argtypes = [i32]
-    lib.gsr_profile_read.restype = ctypes.c_int
-    lib.gsr_profile_read.argtypes = [ctypes.POINTER(ctypes.c_float), i64p]
-    if hasattr(lib, "gsr_ctx_request_sumsq"):              # (absent from older builds selected through GSR_LIBRARY for A/B runs)
-        lib.gsr_ctx_request_sumsq.restype = ctypes.c_int
-        lib.gsr_ctx_request_sumsq.argtypes = [vp, vp]
-        lib.gsr_pgd_step_normed.restype = ctypes.c_int
-        lib.gsr_pgd_step_normed.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_float, vp, vp]
-        lib.gsr_pgd_step_multi.restype = ctypes.c_int
-        lib.gsr_pgd_step_multi.argtypes = [ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp]
-    lib.gsr_pgd_step.restype = ctypes.c_int
-    lib.gsr_pgd_step.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
-                                 ctypes.c_int32, vp]
-    lib.gsr_test_scan.restype = ctypes.c_int
-    lib.gsr_test_scan.argtypes = [vp, vp, ctypes.c_uint32, vp]
-    lib.gsr_test_sort_pairs.restype = ctypes.c_int
-    lib.gsr_test_sort_pairs.argtypes = [vp, vp, ctypes.c_uint32, i32, i32, i32, vp]
-    if hasattr(lib, "gsr_test_scan_ex"):                   # (absent from older builds selected through GSR_LIBRARY for A/B runs)
-        lib.gsr_test_scan_ex.restype = ctypes.c_int
-        lib.gsr_test_scan_ex.argtypes = [vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp]
-        lib.gsr_test_sort_pairs_ex.restype = ctypes.c_int
-        lib.gsr_test_sort_pairs_ex.argtypes = [vp, vp, ctypes.c_uint32, vp, i32, i32, i32, i32, vp, ctypes.c_uint32, vp]
-    lib.gsr_last_error.restype = ctypes.c_char_p
-    lib.gsr_last_error.argtypes = []
+    # one declarative table (name -> restype, argtypes), applied to what this build exports: a library chosen through
+    # GSR_LIBRARY for A/B runs may lack the newer entry points and still loads
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = lib
     return lib
 
 
-GSR_ERR_OVERFLOW = 5          # include/gsraster.h
+GSR_ERR_INVALID, GSR_ERR_OVERFLOW = 1, 5          # include/gsraster.h
 
 
 class PairCapacityExceeded(RuntimeError):
@@ -215,6 +131,14 @@ class PairCapacityExceeded(RuntimeError):
 def _err(lib) -> str:
     msg = lib.gsr_last_error()
     return msg.decode("utf-8", "replace") if msg else "unknown error"
+
+
+def _rc_error(lib, rc: int, note: str = "", invalid=Exception) -> Exception:
+    """The exception of a non-zero return code: GSR_ERR_INVALID -> `invalid` (the forwards have always raised a plain
+    Exception for refused arguments and the backwards a RuntimeError: callers match on both), GSR_ERR_OVERFLOW ->
+    PairCapacityExceeded, anything else -> RuntimeError; the text is gsr_last_error() plus `note`."""
+    kind = invalid if rc == GSR_ERR_INVALID else PairCapacityExceeded if rc == GSR_ERR_OVERFLOW else RuntimeError
+    return kind(_err(lib) + note)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -243,6 +167,27 @@ def _f32c(t: torch.Tensor, device) -> torch.Tensor:
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+
+
+def _prep(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
+    """What the library is handed for an input: detached, dense float32 on `device`; None for an absent or empty one."""
+    return None if t is None or t.numel() == 0 else _f32c(t.detach(), device)
+
+
+def _hip_device(t: torch.Tensor):
+    if not t.is_cuda:
+        raise RuntimeError(f"diff_gaussian_rasterization: tensors must live on a HIP device (got {t.device}); "
+                           "there is no CPU path")
+    return t.device
+
+
+def _check_sh_storage(P: int, features_dc, features_rest) -> None:
+    if tuple(features_dc.shape) != (P, 1, 3) or tuple(features_rest.shape) != (P, 15, 3):
+        raise ValueError("fused path needs _features_dc [P,1,3] and _features_rest [P,15,3] (SH degree 3 storage)")
+
+
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 _SMALL = {}      # (id(tensor), device) -> (weakref to it, its _version, dense float32 device copy, copy event, stream)
@@ -330,8 +275,13 @@ def _check_versions(tensors, versions):
                                f"backward ran (version {t._version}, expected {v}); clone it or step after backward()")
 
 
-def _empty_like_or_none(t):
-    return None if t is None else torch.empty_like(t)
+def _empty_if(cond, shape, device):
+    """A gradient buffer for the backward to fill, or None when that gradient is not wanted."""
+    return torch.empty(shape, dtype=torch.float32, device=device) if cond else None
+
+
+def _shaped(t, shape, wanted=True):
+    return None if (t is None or not wanted) else t.reshape(shape)
 
 
 _ZERO = {}
@@ -397,22 +347,30 @@ def _arm_aux_grads(lib, holder, grad_depth, grad_alpha, shape, device):
     return (gd, ga)
 
 
+class _CallOpts(NamedTuple):
+    """Everything a render's autograd.Function is told besides its tensors, as ONE argument of .apply -- its last, so every
+    backward returns one gradient per tensor input plus the same fixed tail, whatever options exist.  A new option is a
+    new member here (with a default), read as `opts.<name>`; a new tensor input is a new position of .apply."""
+    keep: bool = True               # keep backward state (decided by the caller of apply(): see _wants_backward)
+    aux: bool = False               # also return the depth and alpha maps
+    bucket: object = None           # GradBucket / GradBucketSet the attribute gradients are written into
+    norms: Optional["GradNorms"] = None
+    cache_slot: Optional[tuple] = None      # (RenderCache, key)
+    color_only: bool = False        # no geometry gradient can be asked for: a re-render keeps no geometry backward state
+    settings_list: tuple = ()       # (batch) the views' GaussianRasterizationSettings
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, keep=True, aux=False):
+                raster_settings, opts):
         lib = _load()
-        ctx.aux = bool(aux)
-        if not means3D.is_cuda:
-            raise RuntimeError("diff_gaussian_rasterization: tensors must live on a HIP device (got "
-                               f"{means3D.device}); there is no CPU path")
-        device = means3D.device
+        keep, aux = opts.keep, opts.aux
+        ctx.aux = aux
+        device = _hip_device(means3D)
         P = int(means3D.shape[0])
-
-        def prep(t):
-            return None if t is None or t.numel() == 0 else _f32c(t.detach(), device)
-        m3, shc, shoc, colc = prep(means3D), prep(sh), prep(sh_objs), prep(colors_precomp)
-        opc, scc, roc, covc = prep(opacities), prep(scales), prep(rotations), prep(cov3Ds_precomp)
+        m3, shc, shoc, colc = (_prep(t, device) for t in (means3D, sh, sh_objs, colors_precomp))
+        opc, scc, roc, covc = (_prep(t, device) for t in (opacities, scales, rotations, cov3Ds_precomp))
         # all-zero object features composite to exactly zero: the forward runs without them and hands back a broadcast
         # zero; the context keeps the features, so a backward that IS given dL/dobjects still produces dL/dsh_objs
         obj_zero = shoc is not None and shoc.numel() == P * NUM_OBJECTS and _objects_all_zero(shoc, sh_objs)
@@ -440,37 +398,28 @@ class _RasterizeGaussians(torch.autograd.Function):
         # True for a requires_grad tensor even under torch.no_grad()): a forward-only call keeps no backward state
         # (segment boundaries, d colour / d direction)
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            head = (ctypes.byref(pack.c), P, K, _ptr(m3), _ptr(shc), _ptr(shoc), _ptr(colc), _ptr(opc), _ptr(scc), _ptr(roc),
+                    _ptr(covc), _ptr(color), _ptr(objects) if with_obj else None, _ptr(radii),
+                    ctypes.byref(handle) if keep else None, ctypes.byref(nren))
             if aux:
                 depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
                 alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
-                rc = lib.gsr_forward_aux(ctypes.byref(pack.c), P, K, _ptr(m3), _ptr(shc), _ptr(shoc), _ptr(colc), _ptr(opc),
-                                         _ptr(scc), _ptr(roc), _ptr(covc), _ptr(color), _ptr(objects) if with_obj else None,
-                                         _ptr(radii), ctypes.byref(handle) if keep else None, ctypes.byref(nren),
-                                         _ptr(depth), _ptr(alpha), stream)
+                rc = lib.gsr_forward_aux(*head, _ptr(depth), _ptr(alpha), _stream(device))
             else:
-                rc = lib.gsr_forward(ctypes.byref(pack.c), P, K, _ptr(m3), _ptr(shc), _ptr(shoc), _ptr(colc), _ptr(opc),
-                                     _ptr(scc), _ptr(roc), _ptr(covc), _ptr(color), _ptr(objects) if with_obj else None,
-                                     _ptr(radii),
-                                     ctypes.byref(handle) if keep else None, ctypes.byref(nren), stream)
+                rc = lib.gsr_forward(*head, _stream(device))
         if rc != 0:
-            msg = _err(lib)
+            note = ""
             if raster_settings.debug:
                 torch.save({"means3D": m3, "sh": shc, "sh_objs": shoc, "colors_precomp": colc, "opacities": opc,
                             "scales": scc, "rotations": roc, "cov3D_precomp": covc,
                             "settings": raster_settings._asdict()}, "snapshot_fw.dump")
-                msg += " (inputs saved to snapshot_fw.dump)"
-            if rc == 1:
-                raise Exception(msg)
-            raise RuntimeError(msg)
+                note = " (inputs saved to snapshot_fw.dump)"
+            raise _rc_error(lib, rc, note)
         ctx.holder = _CtxHolder(lib, handle) if keep else None
         ctx.pack = pack
         ctx._nren = nren.value
-        ctx.shapes = (means3D.shape, means2D.shape if means2D is not None else None,
-                      None if sh is None else sh.shape, None if sh_objs is None else sh_objs.shape,
-                      None if colors_precomp is None else colors_precomp.shape, opacities.shape,
-                      None if scales is None else scales.shape, None if rotations is None else rotations.shape,
-                      None if cov3Ds_precomp is None else cov3Ds_precomp.shape)
+        ctx.shapes = tuple(None if t is None else t.shape for t in (means3D, means2D, sh, sh_objs, colors_precomp, opacities,
+                                                                     scales, rotations, cov3Ds_precomp))
         # the library reads these again in backward: keep the exact (contiguous fp32) buffers alive, and remember
         # their versions -- an in-place edit between forward and backward must raise, as a saved tensor would
         ctx.kept = (m3, shc, shoc, colc, opc, scc, roc, covc)
@@ -494,41 +443,36 @@ class _RasterizeGaussians(torch.autograd.Function):
         gcol = _f32c(grad_color, device)
         gobj = None if (grad_objects is None or shoc is None) else _f32c(grad_objects, device)
         need = ctx.needs_input_grad
-
-        def out(cond, *shape):
-            return torch.empty(*shape, dtype=torch.float32, device=device) if cond else None
-        d_m3 = out(need[0], P, 3)
-        d_m2 = out(need[1], P, 3)
-        d_sh = out(need[2] and shc is not None, *(shc.shape if shc is not None else (0,)))
-        d_obj = out(need[3] and shoc is not None, P, NUM_OBJECTS)
-        d_col = out(need[4] and colc is not None, P, 3)
-        d_op = out(need[5], P)
-        d_sc = out(need[6] and scc is not None, P, 3)
-        d_ro = out(need[7] and roc is not None, P, 4)
-        d_cov = out(need[8] and covc is not None, P, 6)
+        # (input given?, its gradient's shape) per tensor input, in .apply's order -- which is gsr_backward's too
+        outs = ((True, (P, 3)),                                                 # means3D
+                (True, (P, 3)),                                                 # means2D
+                (shc is not None, shc.shape if shc is not None else (0,)),      # sh
+                (shoc is not None, (P, NUM_OBJECTS)),                           # sh_objs
+                (colc is not None, (P, 3)),                                     # colors_precomp
+                (True, (P,)),                                                   # opacities
+                (scc is not None, (P, 3)),                                      # scales
+                (roc is not None, (P, 4)),                                      # rotations
+                (covc is not None, (P, 6)))                                     # cov3Ds_precomp
+        grads = [_empty_if(wanted and given, shape, device) for wanted, (given, shape) in zip(need, outs)]
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             # (the maps reach geometry and opacity only: with none of those gradients wanted theirs are not handed over)
             geo = need[0] or need[1] or need[5] or need[6] or need[7] or need[8]
             aux_keep = _arm_aux_grads(lib, ctx.holder, grad_depth, grad_alpha, (H, W), device) if (ctx.aux and P > 0 and geo) else ()
-            rc = lib.gsr_backward(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_m3), _ptr(d_m2), _ptr(d_sh),
-                                  _ptr(d_obj), _ptr(d_col), _ptr(d_op), _ptr(d_sc), _ptr(d_ro), _ptr(d_cov), stream)
+            rc = lib.gsr_backward(ctx.holder.handle, _ptr(gcol), _ptr(gobj), *[_ptr(g) for g in grads], _stream(device))
         if rc != 0:
-            msg = _err(lib)
+            note = ""
             if ctx.pack.c.debug:
                 torch.save({"grad_color": gcol, "grad_objects": gobj}, "snapshot_bw.dump")
-                msg += " (gradients saved to snapshot_bw.dump)"
-            raise (PairCapacityExceeded if rc == 5 else RuntimeError)(msg)
+                note = " (gradients saved to snapshot_bw.dump)"
+            raise _rc_error(lib, rc, note, invalid=RuntimeError)
         if P == 0:
-            for t in (d_m3, d_m2, d_sh, d_obj, d_col, d_op, d_sc, d_ro, d_cov):
+            for t in grads:
                 if t is not None:
                     t.zero_()
-        s = ctx.shapes
+        return tuple(_shaped(g, s) for g, s in zip(grads, ctx.shapes)) + _NO_GRAD
 
-        def shaped(t, shape):
-            return None if t is None else t.reshape(shape)
-        return (shaped(d_m3, s[0]), shaped(d_m2, s[1]), shaped(d_sh, s[2]), shaped(d_obj, s[3]), shaped(d_col, s[4]),
-                shaped(d_op, s[5]), shaped(d_sc, s[6]), shaped(d_ro, s[7]), shaped(d_cov, s[8]), None, None, None)
+
+_NO_GRAD = (None, None)       # the two non-tensor arguments a single-view .apply ends with: the settings, the _CallOpts
 
 
 class _RenderToken:
@@ -640,6 +584,105 @@ def _entry_leave(entry: _CacheEntry, device):
     entry.stream = cur.cuda_stream
 
 
+def _views_sig(geo, views, kind: str, obj):
+    """(signature, tensors to hold weak references to) of a render of `views` (one GaussianRasterizationSettings per view;
+    a single-view render has one) over the geometry tensors `geo`.  `kind` names the context's kind -- "view", "batch",
+    "pair", "pair-batch": a key never re-renders a context of another kind -- and `obj` how it treats the object channels.
+    The later views add their field of view and camera tensor versions to view 0's signature; every view's camera tensors
+    are identity-checked besides: a new camera object that happens to get the id, the addresses and the versions of a dead
+    one is never mistaken for it."""
+    extra = [kind, len(views), obj]
+    for rs in views[1:]:
+        extra += [float(rs.tanfovx), float(rs.tanfovy)]
+        for t in (rs.viewmatrix, rs.projmatrix, rs.campos):
+            extra += [t.data_ptr(), t._version]
+    refs = tuple(geo) + tuple(t for rs in views for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
+    return _cache_sig(geo, views[0], extra=extra), refs
+
+
+def _cache_probe(cache: RenderCache, key, geo, used, views, kind: str, obj, honour_busy: bool):
+    """-> (entry to re-render or None, signature to store the coming forward's context under or None, refs).
+    `geo` are the caller's geometry tensors and `used` the dense forms the library is handed: a context is kept only when
+    they are the same storage (the address of a temporary copy says nothing about the caller's tensor).  `honour_busy`:
+    an entry waiting for its backward is left alone and nothing is stored (RenderCache); the forward-only pair renders,
+    whose contexts have no backward, pass False."""
+    if not all(a is None or a.data_ptr() == b.data_ptr() for a, b in zip(geo, used)):
+        return None, None, None
+    sig, refs = _views_sig(geo, views, kind, obj)
+    entry, may_store = cache._lookup(key, sig, refs)
+    if honour_busy and not may_store:
+        sig = None                      # the key's context is waiting for a backward: plain forward, not stored
+    return entry, sig, refs
+
+
+def _cache_rerender(lib, cache: RenderCache, key, entry: _CacheEntry, device, dc, rest, dc_b, rest_b, bg, color, objects,
+                    flags: int):
+    """Renders through the kept context of a hit: colour kernel + compositor only (gsr_ctx_rerender).
+    -> (rc, entry); entry is None when the kept context's forward (GSR_FLAG_ASYNC_COUNT) turned out to have overflowed its
+    guessed pair capacity: it can never be re-rendered.  The entry is dropped, and the caller takes the full forward in
+    this very call (which counts synchronously after an overflow) instead of poisoning the key."""
+    _entry_enter(entry, device)
+    rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(dc), _ptr(rest), _ptr(dc_b), _ptr(rest_b), _ptr(bg), _ptr(color),
+                              _ptr(objects), flags, _stream(device))
+    entry.gen += 1
+    if rc == GSR_ERR_OVERFLOW:
+        cache.entries.pop(key, None)
+        cache.dropped_overflow += 1
+        return rc, None
+    return rc, entry
+
+
+def _cache_store(cache: RenderCache, key, holder: _CtxHolder, sig, refs, pack, nren: int) -> _CacheEntry:
+    """Keeps a forward's context under `key`.  `pack` is what the context's pointers point into plus the radii of this
+    render: the kept context does not recompute them, later renders of the key return these."""
+    entry = _CacheEntry(holder, sig, tuple(weakref.ref(t) if t is not None else (lambda: None) for t in refs), pack, nren)
+    cache._store(key, entry)
+    return entry
+
+
+def _cache_leave(entry: _CacheEntry, device, node=None, keep: bool = False) -> None:
+    """After a render through `entry` has been enqueued: records the entry's last use and, for a differentiable path, ties
+    its autograd `node` to this generation of the entry (`keep`: a backward may come, so the entry is busy until then).
+    The forward-only pair renders have no node."""
+    _entry_leave(entry, device)
+    if node is not None:
+        node.entry, node.entry_gen = entry, entry.gen
+        if keep:
+            node.token = _RenderToken()
+            entry.token = weakref.ref(node.token)
+
+
+def _cache_backward_enter(node, device, what: str) -> None:
+    if node.entry is not None:
+        if node.entry.gen != node.entry_gen:
+            raise RuntimeError(f"diff_gaussian_rasterization: this {what}'s kept context (RenderCache) was rendered again "
+                               "before its backward ran; call backward() first, or render without the cache")
+        _entry_enter(node.entry, device)
+
+
+def _cache_backward_leave(node, device) -> None:
+    if node.entry is not None:
+        _entry_leave(node.entry, device)
+        node.token.done = True
+
+
+def _coeff_sig(src_dc, src_rest, dc, rest):
+    """Storage and version of the second model's two coefficient tensors (a pair render's frozen background, reference
+    attack.py:513-530), or None when the library was handed temporary dense copies of them."""
+    if src_dc.data_ptr() != dc.data_ptr() or src_rest.data_ptr() != rest.data_ptr():
+        return None
+    return tuple((t.data_ptr(), t._version) for t in (src_dc, src_rest))
+
+
+def _pair_rerender_args(kept, b_sig, dc_b, rest_b):
+    """-> (features_dc_b, features_rest_b, flags) of a pair context's gsr_ctx_rerender: while the second model's
+    coefficient tensors are the ones of the entry's last render, unmodified, the colour kernel runs over the first model's
+    Gaussians only (flag 2).  `kept` (the entry's pack) remembers this render's for the next."""
+    same = b_sig is not None and kept.b_sig == b_sig
+    kept.b_sig = b_sig
+    return (None, None, 1 | 2) if same else (dc_b, rest_b, 1)
+
+
 class GradNorms:
     """The six sums of squares the reference's L2 steps divide by (attack.py:53-119, 138-173: one global norm per raw
     attribute tensor, _features_dc and _features_rest separately), taken from the raster backward that WRITES the
@@ -696,9 +739,13 @@ class GradBucket:
     def reset(self):
         self.fresh, self.used = True, False
 
+    @staticmethod
+    def carve(flat: torch.Tensor, P: int):
+        """The six attribute pieces of a flat buffer of 59 P floats."""
+        return [flat[c0 * P:c1 * P] for c0, c1 in zip(GradBucket.CUTS[:-1], GradBucket.CUTS[1:])]
+
     def slices(self):
-        P = self.P
-        return [self.flat[c0 * P:c1 * P] for c0, c1 in zip(self.CUTS[:-1], self.CUTS[1:])]
+        return self.carve(self.flat, self.P)
 
     def range_slices(self, g_begin: int, g_end: int):
         """The six pieces of the flat buffer that hold the gradients of Gaussians [g_begin, g_end)."""
@@ -751,32 +798,149 @@ class GradBucketSet:
         return b
 
 
+class _GradPlan(NamedTuple):
+    """Where a raw backward writes the six attribute gradients (xyz, f_dc, f_rest, opacity, scaling, rotation)."""
+    bufs: list                  # one tensor per attribute, None = not wanted
+    bucket: object              # the caller's GradBucket / GradBucketSet when `bufs` are its slices, else None
+    per_view: bool              # ... a GradBucketSet: `bufs` are view 0's bucket, view v's lie 59 P floats further
+    chunked: bool               # the bucket asked for the per-Gaussian stage in ranges (GradBucket.chunks)
+    overwrites: bool            # the backward overwrites `bufs` with ONE summed gradient (what GradNorms can describe)
+
+
+def _plan_attr_grads(want, P: int, device, bucket=None, B: int = 1) -> _GradPlan:
+    """`want`: is the gradient of (xyz, the SH coefficients, opacity, scaling, rotation) needed?  A caller's bucket is used
+    only when all of them are: it then receives the 59 attribute gradients directly (overwritten by the first backward
+    after reset(), added to by the others) and autograd gets no gradient for those inputs."""
+    w_x, w_sh, w_op, w_sc, w_ro = want
+    if not (w_x and w_sh and w_op and w_sc and w_ro):
+        wanted = (w_x, w_sh, w_sh, w_op, w_sc, w_ro)
+        shapes = ((P, 3), (P, 1, 3), (P, 15, 3), (P,), (P, 3), (P, 4))
+        return _GradPlan([_empty_if(w, shp, device) for w, shp in zip(wanted, shapes)], None, False, False, True)
+    if isinstance(bucket, GradBucketSet):
+        if bucket.P != P or bucket.B < B or bucket.flat.device != device:
+            raise ValueError("grad bucket set does not match the batch (views, P or device)")
+        return _GradPlan(bucket.bucket(0).slices(), bucket, True, False, False)
+    if bucket is not None:
+        if bucket.P != P or bucket.flat.device != device:
+            raise ValueError("grad bucket does not match the model (P or device)")
+        chunked = bucket.chunks > 1
+        return _GradPlan(bucket.slices(), bucket, False, chunked, bucket.fresh and not chunked)
+    # All 59 attack-relevant floats per Gaussian are wanted (the normal case): carve them out of ONE flat buffer, in the
+    # order xyz | f_dc | f_rest | opacity | scaling | rotation.  autograd hands these views to .grad as they are, so a
+    # data-parallel caller can sum the whole gradient with a single collective
+    # (gsplat_attack.dist.allreduce_attribute_grads) instead of one per tensor.
+    flat = torch.empty(59 * P, dtype=torch.float32, device=device)
+    return _GradPlan(GradBucket.carve(flat, P), None, False, False, True)
+
+
+def _autograd_attr_grads(plan: _GradPlan):
+    """The six attribute gradients as autograd gets them after the backward ran: none when they went into the caller's
+    bucket, which is marked written."""
+    if plan.bucket is None:
+        return plan.bufs
+    if not plan.per_view:
+        plan.bucket.fresh, plan.bucket.used = False, True
+    return (None,) * 6
+
+
+def _arm_norms(lib, norms: GradNorms, holder: _CtxHolder, plan: _GradPlan, want, strict: bool) -> None:
+    """Asks the coming backward for the sums of squares of what it writes (gsr_ctx_request_sumsq), if it is the first since
+    norms.begin() and overwrites its outputs with one summed gradient.  When the library refuses: `strict` raises (the
+    single-view backward); otherwise the norms are invalidated and the step sums the gradient itself (the batch
+    backward: a build or a mode that cannot serve it)."""
+    norms.writes += 1
+    if norms.writes == 1 and plan.overwrites:
+        if lib.gsr_ctx_request_sumsq(holder.handle, ctypes.c_void_p(norms.sumsq.data_ptr())) != 0:
+            if strict:
+                raise RuntimeError(_err(lib))
+            norms.invalidate()
+            return
+        w_x, w_sh, w_op, w_sc, w_ro = want
+        norms.names = tuple(n for n, w in zip(GradNorms.NAMES, (w_x, w_sh, w_sh, w_op, w_sc, w_ro)) if w)
+    elif not plan.overwrites:
+        norms.invalidate()
+
+
+def _chunk_trampoline(bucket: GradBucket):
+    """-> (the gsr_chunk_fn that calls the bucket's one-shot on_chunk hook, the list its exception lands in): an exception
+    must not unwind through the C frames, so the caller raises it after the library has returned."""
+    hook, bucket.on_chunk = bucket.on_chunk, None
+    errs = []
+
+    def _done(_user, chunk, g0, g1):
+        try:
+            if hook is not None:
+                hook(int(chunk), int(g0), int(g1))
+        except BaseException as e:
+            errs.append(e)
+    return _CHUNK_FN(_done), errs
+
+
+# Which entry point a raw backward calls.  Key: (batch context, per-view bucket set, object channels, chunked, into a
+# bucket); value: (name, does it take grad_objects and dobjects_dc, what follows the gradient pointers).  Exactly the
+# combinations the two backwards can reach: the entry points refuse other context kinds under their own names.
+_BWD_PICK = {
+    (False, False, False, False, False): ("gsr_backward_raw", True, ""),
+    (False, False, True, False, False): ("gsr_backward_raw", True, ""),
+    (False, False, False, False, True): ("gsr_backward_raw_into", True, "accumulate"),
+    (False, False, True, False, True): ("gsr_backward_raw_into", True, "accumulate"),
+    (False, False, False, True, True): ("gsr_backward_raw_chunked", True, "chunks"),
+    (False, False, True, True, True): ("gsr_backward_raw_chunked", True, "chunks"),
+    (True, False, False, False, False): ("gsr_backward_raw_batch_into", False, "accumulate"),
+    (True, False, False, False, True): ("gsr_backward_raw_batch_into", False, "accumulate"),
+    (True, False, True, False, False): ("gsr_backward_raw_batch_obj_into", True, "accumulate"),
+    (True, False, True, False, True): ("gsr_backward_raw_batch_obj_into", True, "accumulate"),
+    # the per-Gaussian stage in ranges, each announced as soon as its launch is enqueued (all-reduce overlap)
+    (True, False, False, True, True): ("gsr_backward_raw_chunked", True, "chunks"),
+    (True, False, True, True, True): ("gsr_backward_raw_chunked", True, "chunks"),
+    (True, True, False, False, True): ("gsr_backward_raw_batch_views", False, "view_stride"),
+    (True, True, True, False, True): ("gsr_backward_raw_batch_obj_views", True, "view_stride"),
+}
+
+
+def _call_raw_backward(lib, batch: bool, with_obj: bool, holder: _CtxHolder, plan: _GradPlan, gcol, gobj, d_m2, d_obj,
+                       P: int, device) -> int:
+    """The one C call of a raw backward, picked from _BWD_PICK.  -> its return code."""
+    name, obj_args, tail = _BWD_PICK[(batch, plan.per_view, with_obj, plan.chunked, plan.bucket is not None)]
+    fn = getattr(lib, name)
+    d_x, d_dc, d_rest, d_op, d_sc, d_ro = (_ptr(t) for t in plan.bufs)
+    if obj_args:
+        args = (holder.handle, _ptr(gcol), _ptr(gobj), d_x, _ptr(d_m2), d_dc, d_rest, _ptr(d_obj), d_op, d_sc, d_ro)
+    else:
+        args = (holder.handle, _ptr(gcol), d_x, _ptr(d_m2), d_dc, d_rest, d_op, d_sc, d_ro)
+    bucket, stream = plan.bucket, _stream(device)
+    if tail == "":
+        return fn(*args, stream)
+    if tail == "view_stride":
+        return fn(*args, 59 * P, stream)
+    accumulate = 0 if (bucket is None or bucket.fresh) else 1
+    if tail == "accumulate":
+        return fn(*args, accumulate, stream)
+    cb, errs = _chunk_trampoline(bucket)
+    rc = fn(*args, accumulate, int(bucket.chunks), cb, None, stream)
+    bucket.chunks = 1
+    if errs:
+        raise errs[0]
+    return rc
+
+
 class _RasterizeGaussiansRaw(torch.autograd.Function):
     """Same path with the activation getters fused into the kernels (gsr_forward_raw / gsr_backward_raw): takes the
     RAW parameter tensors of a reference-style GaussianModel."""
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation, raster_settings,
-                keep=True, bucket=None, cache_slot=None, color_only=False, norms=None, aux=False):
+                opts):
         lib = _load()
-        ctx.aux = bool(aux)
-        if aux:
-            cache_slot = None                 # a kept context is never re-rendered with maps: aux renders bypass the cache
-        ctx.bucket = bucket
-        ctx.norms = norms
+        keep, aux = opts.keep, opts.aux
+        cache_slot = None if aux else opts.cache_slot   # a kept context is never re-rendered with maps: aux bypasses the cache
+        ctx.opts = opts
         ctx.entry = None
-        if not xyz.is_cuda:
-            raise RuntimeError("diff_gaussian_rasterization: tensors must live on a HIP device (got "
-                               f"{xyz.device}); there is no CPU path")
-        device = xyz.device
+        device = _hip_device(xyz)
         P = int(xyz.shape[0])
-        if tuple(features_dc.shape) != (P, 1, 3) or tuple(features_rest.shape) != (P, 15, 3):
-            raise ValueError("fused path needs _features_dc [P,1,3] and _features_rest [P,15,3] (SH degree 3 storage)")
-
-        def prep(t):
-            return None if t is None or t.numel() == 0 else _f32c(t.detach(), device)
-        x, dc, rest, obj = prep(xyz), prep(features_dc), prep(features_rest), prep(objects_dc)
-        op, sc, ro = prep(opacity), prep(scaling), prep(rotation)
+        _check_sh_storage(P, features_dc, features_rest)
+        x, dc, rest, obj = (_prep(t, device) for t in (xyz, features_dc, features_rest, objects_dc))
+        op, sc, ro = (_prep(t, device) for t in (opacity, scaling, rotation))
         if obj is not None and obj.numel() != P * NUM_OBJECTS:
             raise ValueError(f"objects_dc must hold P*{NUM_OBJECTS} values, got {tuple(obj.shape)}")
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
@@ -791,76 +955,47 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             pack.c.flags |= FLAG_OBJECTS_FOR_BACKWARD_ONLY
         objects = (torch.empty(NUM_OBJECTS, H, W, dtype=torch.float32, device=device) if with_obj
                    else _zero_scalar(device).expand(NUM_OBJECTS, H, W))
-        radii = None
         handle = ctypes.c_void_p(None)
         nren = ctypes.c_int64(0)
-        entry = None
+        entry = sig = refs = None
         if cache_slot is not None and P > 0:
             cache, key = cache_slot
             geo = (xyz, opacity, scaling, rotation, objects_dc if obj is not None else None)
-            dense = all(a is None or a.data_ptr() == b.data_ptr() for a, b in zip(geo, (x, op, sc, ro, obj)))
-            sig = _cache_sig(geo, raster_settings, extra=(obj_zero,)) if dense else None
-            # identity (weak references) of the geometry AND the camera tensors: a new camera object that happens to get
-            # the id, the addresses and the versions of a dead one is never mistaken for it
-            geo = geo + (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
-            if dense:
-                entry, may_store = cache._lookup(key, sig, geo)
-                if not may_store:
-                    sig = None                      # the key's context is waiting for a backward: plain forward, not stored
+            entry, sig, refs = _cache_probe(cache, key, geo, (x, op, sc, ro, obj), [raster_settings], "view", obj_zero, True)
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             if entry is not None:
-                # the geometry of this key is what its kept context was built from: colour kernel + compositor only
-                _entry_enter(entry, device)
+                # the geometry of this key is what its kept context was built from
                 radii = entry.pack.radii.detach()      # geometry is unchanged: so are the radii of the key's first render
-                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(dc), _ptr(rest), None, None, _ptr(pack.bg), _ptr(color),
-                                          _ptr(objects) if with_obj else None, 1 if color_only else 0, stream)
-                entry.gen += 1
                 nren.value = entry.nren
-                if rc == GSR_ERR_OVERFLOW:
-                    # the kept context's forward (GSR_FLAG_ASYNC_COUNT) turned out to have overflowed its guessed pair
-                    # capacity: it can never be re-rendered.  Drop the entry and take the full forward in this very call
-                    # (which counts synchronously after an overflow) instead of poisoning the key.
-                    cache.entries.pop(key, None)
-                    cache.dropped_overflow += 1
-                    entry = None
+                rc, entry = _cache_rerender(lib, cache, key, entry, device, dc, rest, None, None, pack.bg, color,
+                                            objects if with_obj else None, 1 if opts.color_only else 0)
             if entry is None:
-                want_ctx = keep or (cache_slot is not None and P > 0 and sig is not None)
                 radii = torch.empty(P, dtype=torch.int32, device=device)
+                head = (ctypes.byref(pack.c), P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op), _ptr(sc), _ptr(ro),
+                        _ptr(color), _ptr(objects) if with_obj else None, _ptr(radii),
+                        ctypes.byref(handle) if (keep or sig is not None) else None, ctypes.byref(nren))
                 if aux:
                     depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
                     alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
-                    rc = lib.gsr_forward_raw_aux(ctypes.byref(pack.c), P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op),
-                                                 _ptr(sc), _ptr(ro), _ptr(color), _ptr(objects) if with_obj else None,
-                                                 _ptr(radii), ctypes.byref(handle) if want_ctx else None, ctypes.byref(nren),
-                                                 _ptr(depth), _ptr(alpha), stream)
+                    rc = lib.gsr_forward_raw_aux(*head, _ptr(depth), _ptr(alpha), _stream(device))
                 else:
-                    rc = lib.gsr_forward_raw(ctypes.byref(pack.c), P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op), _ptr(sc),
-                                             _ptr(ro), _ptr(color), _ptr(objects) if with_obj else None, _ptr(radii),
-                                             ctypes.byref(handle) if want_ctx else None,
-                                             ctypes.byref(nren), stream)
+                    rc = lib.gsr_forward_raw(*head, _stream(device))
         if rc != 0:
-            msg = _err(lib)
+            note = ""
             if raster_settings.debug:
                 torch.save({"xyz": x, "features_dc": dc, "features_rest": rest, "objects_dc": obj, "opacity": op,
                             "scaling": sc, "rotation": ro, "settings": raster_settings._asdict()}, "snapshot_fw.dump")
-                msg += " (raw parameters saved to snapshot_fw.dump)"
-            raise Exception(msg) if rc == 1 else (PairCapacityExceeded if rc == GSR_ERR_OVERFLOW else RuntimeError)(msg)
+                note = " (raw parameters saved to snapshot_fw.dump)"
+            raise _rc_error(lib, rc, note)
         if entry is not None:
             ctx.holder = entry.holder
         else:
             ctx.holder = _CtxHolder(lib, handle) if handle.value else None
-            if cache_slot is not None and P > 0 and sig is not None and ctx.holder is not None:
-                pack.radii = radii         # the kept context does not recompute them: later renders of the key return these
-                entry = _CacheEntry(ctx.holder, sig, tuple(weakref.ref(t) if t is not None else (lambda: None) for t in geo),
-                                    pack, nren.value)
-                cache._store(key, entry)
+            if sig is not None and ctx.holder is not None:
+                pack.radii = radii
+                entry = _cache_store(cache, key, ctx.holder, sig, refs, pack, nren.value)
         if entry is not None:
-            _entry_leave(entry, device)
-            ctx.entry, ctx.entry_gen = entry, entry.gen
-            if keep:
-                ctx.token = _RenderToken()
-                entry.token = weakref.ref(ctx.token)
+            _cache_leave(entry, device, ctx, keep)
         if not keep:
             ctx.holder = None
         ctx.pack = pack
@@ -881,104 +1016,33 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         _check_versions(ctx.kept, ctx.versions)
         x, dc, rest, obj, op, sc, ro = ctx.kept
         device = x.device
-        if ctx.entry is not None:
-            if ctx.entry.gen != ctx.entry_gen:
-                raise RuntimeError("diff_gaussian_rasterization: this render's kept context (RenderCache) was rendered again "
-                                   "before its backward ran; call backward() first, or render without the cache")
-            _entry_enter(ctx.entry, device)
+        _cache_backward_enter(ctx, device, "render")
         P = int(x.shape[0])
         H, W = ctx.pack.c.image_height, ctx.pack.c.image_width
         if grad_color is None:
             grad_color = torch.zeros(3, H, W, dtype=torch.float32, device=device)
         gcol = _f32c(grad_color, device)
         gobj = None if (grad_objects is None or obj is None) else _f32c(grad_objects, device)
+        # inputs: xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation
         need = ctx.needs_input_grad
-
-        def out(cond, *shape):
-            return torch.empty(*shape, dtype=torch.float32, device=device) if cond else None
-        want_sh = need[2] or need[3]
-        all59 = need[0] and want_sh and need[5] and need[6] and need[7]
-        bucket = ctx.bucket if all59 else None
-        if bucket is not None:
-            # the caller's bucket receives the 59 attribute gradients directly (overwritten by the first backward after
-            # reset(), added to by the others); autograd gets no gradient for those inputs
-            if bucket.P != P or bucket.flat.device != device:
-                raise ValueError("grad bucket does not match the model (P or device)")
-            d_x, d_dc, d_rest, d_op, d_sc, d_ro = bucket.slices()
-        elif all59:
-            # All 59 attack-relevant floats per Gaussian are wanted (the normal case): carve them out of ONE flat
-            # buffer, in the order xyz | f_dc | f_rest | opacity | scaling | rotation.  autograd hands these views to
-            # .grad as they are, so a data-parallel caller can sum the whole gradient with a single collective
-            # (gsplat_attack.dist.allreduce_attribute_grads) instead of one per tensor.
-            flat = torch.empty(59 * P, dtype=torch.float32, device=device)
-            cuts = [0, 3 * P, 6 * P, 51 * P, 52 * P, 55 * P, 59 * P]
-            d_x, d_dc, d_rest, d_op, d_sc, d_ro = (flat[cuts[i]:cuts[i + 1]] for i in range(6))
-        else:
-            d_x = out(need[0], P, 3)
-            d_dc = out(want_sh, P, 1, 3)
-            d_rest = out(want_sh, P, 15, 3)
-            d_op = out(need[5], P)
-            d_sc = out(need[6], P, 3)
-            d_ro = out(need[7], P, 4)
-        d_m2 = out(need[1], P, 3)
-        d_obj = out(need[4] and obj is not None, P, NUM_OBJECTS)
-        norms = getattr(ctx, "norms", None)
-        if norms is not None:
-            norms.writes += 1
-            overwrites = (bucket is None or bucket.fresh) and not (bucket is not None and bucket.chunks > 1)
-            if norms.writes == 1 and overwrites and P > 0:
-                if lib.gsr_ctx_request_sumsq(ctx.holder.handle, ctypes.c_void_p(norms.sumsq.data_ptr())) != 0:
-                    raise RuntimeError(_err(lib))
-                norms.names = tuple(n for n, w in zip(GradNorms.NAMES, (need[0], want_sh, want_sh, need[5], need[6], need[7])) if w)
-            elif not overwrites:
-                norms.invalidate()
-        if P > 0:
-            with torch.cuda.device(device):
-                stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-                # (the maps reach geometry and opacity only: with none of those gradients wanted theirs are not handed over)
-                geo = need[0] or need[1] or need[5] or need[6] or need[7]
-                aux_keep = _arm_aux_grads(lib, ctx.holder, grad_depth, grad_alpha, (H, W), device) if (ctx.aux and geo) else ()
-                if bucket is not None and bucket.chunks > 1:
-                    hook, bucket.on_chunk = bucket.on_chunk, None
-                    errs = []
-
-                    def _done(_user, chunk, g0, g1):
-                        try:
-                            if hook is not None:
-                                hook(int(chunk), int(g0), int(g1))
-                        except BaseException as e:       # an exception must not unwind through the C frames
-                            errs.append(e)
-                    cb = _CHUNK_FN(_done)
-                    rc = lib.gsr_backward_raw_chunked(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2),
-                                                      _ptr(d_dc), _ptr(d_rest), _ptr(d_obj), _ptr(d_op), _ptr(d_sc), _ptr(d_ro),
-                                                      0 if bucket.fresh else 1, int(bucket.chunks), cb, None, stream)
-                    bucket.chunks = 1
-                    if errs:
-                        raise errs[0]
-                elif bucket is not None:
-                    rc = lib.gsr_backward_raw_into(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2), _ptr(d_dc),
-                                                   _ptr(d_rest), _ptr(d_obj), _ptr(d_op), _ptr(d_sc), _ptr(d_ro),
-                                                   0 if bucket.fresh else 1, stream)
-                else:
-                    rc = lib.gsr_backward_raw(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2), _ptr(d_dc),
-                                              _ptr(d_rest), _ptr(d_obj), _ptr(d_op), _ptr(d_sc), _ptr(d_ro), stream)
-            if rc != 0:
-                raise (PairCapacityExceeded if rc == 5 else RuntimeError)(_err(lib))
-        if ctx.entry is not None:
-            _entry_leave(ctx.entry, device)
-            ctx.token.done = True
-        if bucket is not None:
-            bucket.fresh, bucket.used = False, True
-            s = ctx.shapes
-            return (None, None if d_m2 is None else d_m2.reshape(s[1]), None, None,
-                    None if d_obj is None else d_obj.reshape(s[4]), None, None, None, None, None, None, None, None, None, None)
+        want = (need[0], need[2] or need[3], need[5], need[6], need[7])
+        plan = _plan_attr_grads(want, P, device, ctx.opts.bucket)
+        d_m2 = _empty_if(need[1], (P, 3), device)
+        d_obj = _empty_if(need[4] and obj is not None, (P, NUM_OBJECTS), device)
+        if ctx.opts.norms is not None:
+            _arm_norms(lib, ctx.opts.norms, ctx.holder, plan, want, strict=True)
+        with torch.cuda.device(device):
+            # (the maps reach geometry and opacity only: with none of those gradients wanted theirs are not handed over)
+            geo = need[0] or need[1] or need[5] or need[6] or need[7]
+            aux_keep = _arm_aux_grads(lib, ctx.holder, grad_depth, grad_alpha, (H, W), device) if (ctx.opts.aux and geo) else ()
+            rc = _call_raw_backward(lib, False, obj is not None, ctx.holder, plan, gcol, gobj, d_m2, d_obj, P, device)
+        if rc != 0:
+            raise _rc_error(lib, rc, invalid=RuntimeError)
+        _cache_backward_leave(ctx, device)
         s = ctx.shapes
-
-        def shaped(t, shape, wanted=True):
-            return None if (t is None or not wanted) else t.reshape(shape)
-        return (shaped(d_x, s[0]), shaped(d_m2, s[1]), shaped(d_dc, s[2], need[2]), shaped(d_rest, s[3], need[3]),
-                shaped(d_obj, s[4]), shaped(d_op, s[5]), shaped(d_sc, s[6]), shaped(d_ro, s[7]), None, None, None, None, None, None,
-                None)
+        d_x, d_dc, d_rest, d_op, d_sc, d_ro = _autograd_attr_grads(plan)
+        return (_shaped(d_x, s[0]), _shaped(d_m2, s[1]), _shaped(d_dc, s[2], need[2]), _shaped(d_rest, s[3], need[3]),
+                _shaped(d_obj, s[4]), _shaped(d_op, s[5]), _shaped(d_sc, s[6]), _shaped(d_ro, s[7])) + _NO_GRAD
 
 
 MAX_BATCH = 16                # views per gsr_forward_raw_batch call (csrc/gsr_kernels.hip.h)
@@ -996,6 +1060,27 @@ class _BatchPack:
         self.bgt = None
         self.b_sig = self.last_inputs = None      # (pair batches: the second model's coefficient versions, the inputs in flight)
 
+    def background(self, packs):
+        """What a re-render of the kept context is handed as background: None while the views' background tensors are the
+        forward's own, else (and from then on) their values restacked as one [B,3] tensor."""
+        ptrs = tuple(pk.bg.data_ptr() for pk in packs)
+        if ptrs == self.bg_src and self.bgt is None:
+            return None
+        self.bgt, self.bg_src = torch.stack([pk.bg[:3] for pk in packs]).contiguous(), ptrs
+        return self.bgt                         # (self.packs stays: the context's camera pointers point into them)
+
+
+def _view_packs(settings_list, device):
+    """-> (the views' settings packs, the same as the C array `const GsrSettings[B]` a batch entry point takes)."""
+    B = len(settings_list)
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"a batch holds 1..{MAX_BATCH} views, got {B}")
+    packs = [_SettingsPack(rs, device) for rs in settings_list]
+    carr = (_CSettings * B)()
+    for v, pk in enumerate(packs):
+        carr[v] = pk.c
+    return packs, carr
+
 
 class _RasterizeGaussiansRawBatch(torch.autograd.Function):
     """B views of one set of RAW parameters through ONE launch chain (gsr_forward_raw_batch / gsr_backward_raw_batch_into):
@@ -1005,129 +1090,81 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
     features' gradient is the view-ordered sum of the single-view ones."""
 
     @staticmethod
-    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, settings_list, keep=True,
-                bucket=None, norms=None, cache_slot=None, color_only=False, objects_dc=None, aux=False):
+    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, objects_dc, opts):
         lib = _load()
-        ctx.aux = bool(aux)
-        if aux:
-            cache_slot = None                 # aux renders bypass the cache (see _RasterizeGaussiansRaw)
-            if objects_dc is not None:
-                raise ValueError("rasterize_gaussians_raw_batch: aux=True with objects_dc is not supported (render the object "
-                                 "channels in a batch of their own)")
-        ctx.bucket = bucket
-        ctx.norms = norms
-        ctx.entry = None
-        if not xyz.is_cuda:
-            raise RuntimeError("diff_gaussian_rasterization: tensors must live on a HIP device (got "
-                               f"{xyz.device}); there is no CPU path")
-        device = xyz.device
-        P = int(xyz.shape[0])
-        B = len(settings_list)
-        if not 1 <= B <= MAX_BATCH:
-            raise ValueError(f"a batch holds 1..{MAX_BATCH} views, got {B}")
-        if tuple(features_dc.shape) != (P, 1, 3) or tuple(features_rest.shape) != (P, 15, 3):
-            raise ValueError("fused path needs _features_dc [P,1,3] and _features_rest [P,15,3] (SH degree 3 storage)")
-
-        def prep(t):
-            return None if t is None or t.numel() == 0 else _f32c(t.detach(), device)
-        x, dc, rest = prep(xyz), prep(features_dc), prep(features_rest)
-        op, sc, ro = prep(opacity), prep(scaling), prep(rotation)
+        keep, aux, settings_list = opts.keep, opts.aux, opts.settings_list
+        cache_slot = None if aux else opts.cache_slot     # aux renders bypass the cache (see _RasterizeGaussiansRaw)
         with_obj = objects_dc is not None
-        obj = prep(objects_dc) if with_obj else None
+        if aux and with_obj:
+            raise ValueError("rasterize_gaussians_raw_batch: aux=True with objects_dc is not supported (render the object "
+                             "channels in a batch of their own)")
+        ctx.opts = opts
+        ctx.entry = None
+        device = _hip_device(xyz)
+        P = int(xyz.shape[0])
+        packs, carr = _view_packs(settings_list, device)
+        B = len(packs)
+        _check_sh_storage(P, features_dc, features_rest)
+        x, dc, rest = (_prep(t, device) for t in (xyz, features_dc, features_rest))
+        op, sc, ro = (_prep(t, device) for t in (opacity, scaling, rotation))
+        obj = _prep(objects_dc, device)
         if obj is not None and obj.numel() != P * NUM_OBJECTS:
             raise ValueError(f"objects_dc must hold P*{NUM_OBJECTS} values, got {tuple(objects_dc.shape)}")
         H, W = int(settings_list[0].image_height), int(settings_list[0].image_width)
-        packs = [_SettingsPack(rs, device) for rs in settings_list]
-        carr = (_CSettings * B)()
-        for v, pk in enumerate(packs):
-            carr[v] = pk.c
         color = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
-        radii = torch.empty(B, P, dtype=torch.int32, device=device)
         objects = torch.empty(B, NUM_OBJECTS, H, W, dtype=torch.float32, device=device) if with_obj else None
         handle = ctypes.c_void_p(None)
         nren = ctypes.c_int64(0)
         # a kept batch context (RenderCache): the key's geometry tensors and ALL its views' camera tensors unchanged since the
         # key's last render -> the batch's colour kernel + one compositor launch over the kept lists (gsr_ctx_rerender)
-        entry, sig, refs = None, None, None
+        entry = sig = refs = None
         if cache_slot is not None and P > 0:
             cache, key = cache_slot
-            geo = (xyz, opacity, scaling, rotation)
-            used = (x, op, sc, ro)
-            if with_obj and obj is not None:       # (the context reads the object features through the forward's pointer)
-                geo, used = geo + (objects_dc,), used + (obj,)
-            if all(a.data_ptr() == b.data_ptr() for a, b in zip(geo, used)):
-                extra = [B] + (["obj"] if with_obj else [])
-                for rs in settings_list[1:]:
-                    extra += [float(rs.tanfovx), float(rs.tanfovy)]
-                    for t in (rs.viewmatrix, rs.projmatrix, rs.campos):
-                        extra += [t.data_ptr(), t._version]
-                sig = _cache_sig(geo, settings_list[0], extra=extra)
-                refs = geo + tuple(t for rs in settings_list for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
-                entry, may_store = cache._lookup(key, sig, refs)
-                if not may_store:
-                    sig = None                      # the key's context is waiting for a backward: plain forward, not stored
+            # (the object features belong to the geometry: the context reads them through the forward's pointer)
+            geo = (xyz, opacity, scaling, rotation, objects_dc if obj is not None else None)
+            entry, sig, refs = _cache_probe(cache, key, geo, (x, op, sc, ro, obj), settings_list, "batch", with_obj, True)
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             if entry is not None:
-                _entry_enter(entry, device)
-                bp = entry.pack
-                radii = bp.radii.detach()              # geometry is unchanged: so are the radii of the key's first render
-                ptrs = tuple(pk.bg.data_ptr() for pk in packs)
-                bgt = None
-                if ptrs != bp.bg_src or bp.bgt is not None:
-                    # other background tensors than the context's forward saw: their values as one [B,3] tensor
-                    bgt = torch.stack([pk.bg[:3] for pk in packs]).contiguous()
-                    bp.bgt, bp.bg_src = bgt, ptrs       # (bp.packs stays: the context's camera pointers point into them)
-                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(dc), _ptr(rest), None, None, _ptr(bgt), _ptr(color),
-                                          _ptr(objects), 1 if color_only else 0, stream)
-                entry.gen += 1
+                radii = entry.pack.radii.detach()      # geometry is unchanged: so are the radii of the key's first render
                 nren.value = entry.nren
-                if rc == GSR_ERR_OVERFLOW:             # (see _RasterizeGaussiansRaw: the entry can never be re-rendered)
-                    cache.entries.pop(key, None)
-                    cache.dropped_overflow += 1
-                    entry = None
+                rc, entry = _cache_rerender(lib, cache, key, entry, device, dc, rest, None, None, entry.pack.background(packs),
+                                            color, objects, 1 if opts.color_only else 0)
             if entry is None:
-                want_ctx = keep or sig is not None
+                radii = torch.empty(B, P, dtype=torch.int32, device=device)
+                want_ctx = ctypes.byref(handle) if (keep or sig is not None) else None
                 if with_obj:
                     rc = lib.gsr_forward_raw_batch_obj(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(obj), _ptr(op), _ptr(sc),
-                                                       _ptr(ro), _ptr(color), _ptr(objects), _ptr(radii),
-                                                       ctypes.byref(handle) if want_ctx else None, ctypes.byref(nren), stream)
-                elif aux:
-                    depth = torch.empty(B, 1, H, W, dtype=torch.float32, device=device)
-                    alpha = torch.empty(B, 1, H, W, dtype=torch.float32, device=device)
-                    rc = lib.gsr_forward_raw_batch_aux(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(op), _ptr(sc), _ptr(ro),
-                                                       _ptr(color), _ptr(radii), ctypes.byref(handle) if want_ctx else None,
-                                                       ctypes.byref(nren), _ptr(depth), _ptr(alpha), stream)
+                                                       _ptr(ro), _ptr(color), _ptr(objects), _ptr(radii), want_ctx,
+                                                       ctypes.byref(nren), _stream(device))
                 else:
-                    rc = lib.gsr_forward_raw_batch(carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(op), _ptr(sc), _ptr(ro),
-                                                   _ptr(color), _ptr(radii), ctypes.byref(handle) if want_ctx else None,
-                                                   ctypes.byref(nren), stream)
+                    head = (carr, B, P, _ptr(x), _ptr(dc), _ptr(rest), _ptr(op), _ptr(sc), _ptr(ro), _ptr(color), _ptr(radii),
+                            want_ctx, ctypes.byref(nren))
+                    if aux:
+                        depth = torch.empty(B, 1, H, W, dtype=torch.float32, device=device)
+                        alpha = torch.empty(B, 1, H, W, dtype=torch.float32, device=device)
+                        rc = lib.gsr_forward_raw_batch_aux(*head, _ptr(depth), _ptr(alpha), _stream(device))
+                    else:
+                        rc = lib.gsr_forward_raw_batch(*head, _stream(device))
         if rc != 0:
-            raise Exception(_err(lib)) if rc == 1 else (PairCapacityExceeded if rc == GSR_ERR_OVERFLOW else RuntimeError)(_err(lib))
+            raise _rc_error(lib, rc)
         if entry is not None:
             ctx.holder = entry.holder
         else:
             ctx.holder = _CtxHolder(lib, handle) if handle.value else None
             if sig is not None and ctx.holder is not None:
-                bp = _BatchPack(packs, radii)
-                entry = _CacheEntry(ctx.holder, sig, tuple(weakref.ref(t) for t in refs), bp, nren.value)
-                cache_slot[0]._store(cache_slot[1], entry)
+                entry = _cache_store(cache, key, ctx.holder, sig, refs, _BatchPack(packs, radii), nren.value)
         if entry is not None:
-            _entry_leave(entry, device)
-            ctx.entry, ctx.entry_gen = entry, entry.gen
-            if keep:
-                ctx.token = _RenderToken()
-                entry.token = weakref.ref(ctx.token)
+            _cache_leave(entry, device, ctx, keep)
         if not keep:
             ctx.holder = None
         ctx.packs = packs
         ctx.pack = packs[0]
         ctx.B = B
         ctx._nren = nren.value
-        ctx.shapes = (xyz.shape, None if means2D is None else means2D.shape, features_dc.shape, features_rest.shape,
-                      opacity.shape, scaling.shape, rotation.shape, None if objects_dc is None else objects_dc.shape)
+        ctx.shapes = tuple(None if t is None else t.shape for t in (xyz, means2D, features_dc, features_rest, opacity, scaling,
+                                                                     rotation, objects_dc))
         ctx.kept = (x, dc, rest, op, sc, ro)
-        ctx.obj, ctx.with_obj = obj, with_obj
+        ctx.obj = obj
         ctx.versions = _versions(ctx.kept + (obj,))
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
@@ -1138,156 +1175,66 @@ class _RasterizeGaussiansRawBatch(torch.autograd.Function):
         return color, radii
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_objects=None, grad_alpha=None):
-        grad_depth = None
-        if ctx.aux:                                    # outputs (color, radii, depth, alpha)
-            grad_depth, grad_objects = grad_objects, None
-            res = _RasterizeGaussiansRawBatch._backward(ctx, grad_color, grad_objects, grad_depth, grad_alpha)
-            return res[:13] + (None, None)             # (objects_dc = None and aux: no gradients)
-        return _RasterizeGaussiansRawBatch._backward(ctx, grad_color, grad_objects, None, None)
-
-    @staticmethod
-    def _backward(ctx, grad_color, grad_objects, grad_depth, grad_alpha):
+    def backward(ctx, grad_color, grad_radii, *grad_maps):
+        # outputs: (color, radii), (color, radii, objects) with objects_dc, (color, radii, depth, alpha) with aux
+        grad_objects = grad_depth = grad_alpha = None
+        if ctx.opts.aux:
+            grad_depth, grad_alpha = grad_maps
+        elif grad_maps:
+            grad_objects, = grad_maps
         _check_versions(ctx.kept + (ctx.obj,), ctx.versions)
         x, dc, rest, op, sc, ro = ctx.kept
+        # inputs: xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, objects_dc; then the _CallOpts
+        need = ctx.needs_input_grad
+        s = ctx.shapes
         if x is None:                                  # an empty scene: empty gradients
-            need = ctx.needs_input_grad
-            s = ctx.shapes
             dev0 = ctx.packs[0].device
-            z = lambda i, shp: torch.zeros(shp, dtype=torch.float32, device=dev0) if (need[i] and shp is not None) else None
-            res = (z(0, s[0]), z(1, s[1]), z(2, s[2]), z(3, s[3]), z(4, s[4]), z(5, s[5]), z(6, s[6]), None, None, None, None,
-                   None, None, z(13, s[7]) if ctx.with_obj else None)
-            return res if ctx.with_obj else res[:13]
+            return tuple(torch.zeros(shp, dtype=torch.float32, device=dev0) if (need[i] and shp is not None) else None
+                         for i, shp in enumerate(s)) + (None,)
         lib = ctx.holder.lib
         device = x.device
-        if ctx.entry is not None:
-            if ctx.entry.gen != ctx.entry_gen:
-                raise RuntimeError("diff_gaussian_rasterization: this batch's kept context (RenderCache) was rendered again "
-                                   "before its backward ran; call backward() first, or render without the cache")
-            _entry_enter(ctx.entry, device)
+        _cache_backward_enter(ctx, device, "batch")
         P, B = int(x.shape[0]), ctx.B
         H, W = ctx.pack.c.image_height, ctx.pack.c.image_width
         if grad_color is None:
             grad_color = torch.zeros(B, 3, H, W, dtype=torch.float32, device=device)
         gcol = _f32c(grad_color, device)
-        need = ctx.needs_input_grad
-
-        def out(cond, *shape):
-            return torch.empty(*shape, dtype=torch.float32, device=device) if cond else None
-        want_sh = need[2] or need[3]
-        all59 = need[0] and want_sh and need[4] and need[5] and need[6]
-        bucket = ctx.bucket if all59 else None
-        bset = bucket if isinstance(bucket, GradBucketSet) else None
-        if bset is not None:
-            # per-view gradients: the pointers are view 0's bucket, view v's lie 59 P floats further
-            if bset.P != P or bset.B < B or bset.flat.device != device:
-                raise ValueError("grad bucket set does not match the batch (views, P or device)")
-            d_x, d_dc, d_rest, d_op, d_sc, d_ro = bset.bucket(0).slices()
-        elif bucket is not None:
-            if bucket.P != P or bucket.flat.device != device:
-                raise ValueError("grad bucket does not match the model (P or device)")
-            d_x, d_dc, d_rest, d_op, d_sc, d_ro = bucket.slices()
-        elif all59:
-            flat = torch.empty(59 * P, dtype=torch.float32, device=device)
-            cuts = [0, 3 * P, 6 * P, 51 * P, 52 * P, 55 * P, 59 * P]
-            d_x, d_dc, d_rest, d_op, d_sc, d_ro = (flat[cuts[i]:cuts[i + 1]] for i in range(6))
-        else:
-            d_x = out(need[0], P, 3)
-            d_dc = out(want_sh, P, 1, 3)
-            d_rest = out(want_sh, P, 15, 3)
-            d_op = out(need[4], P)
-            d_sc = out(need[5], P, 3)
-            d_ro = out(need[6], P, 4)
-        d_m2 = out(need[1], B, P, 3)
+        want = (need[0], need[2] or need[3], need[4], need[5], need[6])
+        plan = _plan_attr_grads(want, P, device, ctx.opts.bucket, B)
+        d_m2 = _empty_if(need[1], (B, P, 3), device)
         # object channels: dL/dobjects [B,16,H,W] (or None: the segmented composite of the no-object batch runs) and the
         # object features' gradient [P,16], always written (zeros without dL/dobjects)
-        with_obj = ctx.with_obj
+        with_obj = s[7] is not None
         gobj = _f32c(grad_objects, device) if (with_obj and grad_objects is not None and ctx.obj is not None) else None
-        d_obj = out(with_obj and need[13], P, NUM_OBJECTS)
-        norms = getattr(ctx, "norms", None)
-        if norms is not None:
+        d_obj = _empty_if(with_obj and need[7], (P, NUM_OBJECTS), device)
+        # a bucket set receives per-view object gradients [B,P,16], summed below in view order (autograd's association)
+        d_objv = _empty_if(plan.per_view and d_obj is not None, (B, P, NUM_OBJECTS), device)
+        if ctx.opts.norms is not None:
             # the batch's ONE backward writes the summed gradient: its sums of squares are the L2 steps' norms (GradNorms)
-            norms.writes += 1
-            overwrites = bset is None and (bucket is None or bucket.fresh) and not (bucket is not None and bucket.chunks > 1)
-            if norms.writes == 1 and overwrites and P > 0:
-                if lib.gsr_ctx_request_sumsq(ctx.holder.handle, ctypes.c_void_p(norms.sumsq.data_ptr())) != 0:
-                    norms.invalidate()              # (a build or a mode that cannot serve it: the step sums the gradient itself)
-                else:
-                    norms.names = tuple(n for n, w in zip(GradNorms.NAMES, (need[0], want_sh, want_sh, need[4], need[5], need[6])) if w)
-            elif not overwrites:
-                norms.invalidate()
-        if P > 0:
-            with torch.cuda.device(device):
-                stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-                acc = 1 if (bucket is not None and bset is None and not bucket.fresh) else 0
-                geo = need[0] or need[1] or need[4] or need[5] or need[6]
-                aux_keep = _arm_aux_grads(lib, ctx.holder, grad_depth, grad_alpha, (B, H, W), device) if (ctx.aux and geo) else ()
-                if bset is not None and with_obj:
-                    # per-view object gradients [B,P,16], summed here in view order (autograd's association)
-                    d_objv = out(d_obj is not None, B, P, NUM_OBJECTS)
-                    rc = lib.gsr_backward_raw_batch_obj_views(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2),
-                                                              _ptr(d_dc), _ptr(d_rest), _ptr(d_objv), _ptr(d_op), _ptr(d_sc),
-                                                              _ptr(d_ro), 59 * P, stream)
-                    bset.used = B
-                    if rc == 0 and d_objv is not None:
-                        d_obj.copy_(d_objv[0])
-                        for v in range(1, B):
-                            d_obj.add_(d_objv[v])
-                elif bset is not None:
-                    rc = lib.gsr_backward_raw_batch_views(ctx.holder.handle, _ptr(gcol), _ptr(d_x), _ptr(d_m2), _ptr(d_dc),
-                                                          _ptr(d_rest), _ptr(d_op), _ptr(d_sc), _ptr(d_ro), 59 * P, stream)
-                    bset.used = B
-                elif bucket is not None and bucket.chunks > 1:
-                    # the per-Gaussian stage in ranges, each announced as soon as its launch is enqueued (all-reduce overlap)
-                    hook, bucket.on_chunk = bucket.on_chunk, None
-                    errs = []
+            _arm_norms(lib, ctx.opts.norms, ctx.holder, plan, want, strict=False)
+        with torch.cuda.device(device):
+            geo = need[0] or need[1] or need[4] or need[5] or need[6]
+            aux_keep = _arm_aux_grads(lib, ctx.holder, grad_depth, grad_alpha, (B, H, W), device) if (ctx.opts.aux and geo) else ()
+            rc = _call_raw_backward(lib, True, with_obj, ctx.holder, plan, gcol, gobj, d_m2,
+                                    d_objv if plan.per_view else d_obj, P, device)
+            if plan.per_view:
+                plan.bucket.used = B
+                if rc == 0 and d_objv is not None:
+                    d_obj.copy_(d_objv[0])
+                    for v in range(1, B):
+                        d_obj.add_(d_objv[v])
+        if rc != 0:
+            raise _rc_error(lib, rc, invalid=RuntimeError)
+        _cache_backward_leave(ctx, device)
+        d_x, d_dc, d_rest, d_op, d_sc, d_ro = _autograd_attr_grads(plan)
+        return (_shaped(d_x, s[0]), _shaped(d_m2, s[1]), _shaped(d_dc, s[2], need[2]), _shaped(d_rest, s[3], need[3]),
+                _shaped(d_op, s[4]), _shaped(d_sc, s[5]), _shaped(d_ro, s[6]), _shaped(d_obj, s[7]), None)
 
-                    def _done(_user, chunk, g0, g1):
-                        try:
-                            if hook is not None:
-                                hook(int(chunk), int(g0), int(g1))
-                        except BaseException as e:       # an exception must not unwind through the C frames
-                            errs.append(e)
-                    cb = _CHUNK_FN(_done)
-                    rc = lib.gsr_backward_raw_chunked(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2),
-                                                      _ptr(d_dc), _ptr(d_rest), _ptr(d_obj), _ptr(d_op), _ptr(d_sc), _ptr(d_ro),
-                                                      acc, int(bucket.chunks), cb, None, stream)
-                    bucket.chunks = 1
-                    if errs:
-                        raise errs[0]
-                elif with_obj:
-                    rc = lib.gsr_backward_raw_batch_obj_into(ctx.holder.handle, _ptr(gcol), _ptr(gobj), _ptr(d_x), _ptr(d_m2),
-                                                             _ptr(d_dc), _ptr(d_rest), _ptr(d_obj), _ptr(d_op), _ptr(d_sc),
-                                                             _ptr(d_ro), acc, stream)
-                else:
-                    rc = lib.gsr_backward_raw_batch_into(ctx.holder.handle, _ptr(gcol), _ptr(d_x), _ptr(d_m2), _ptr(d_dc),
-                                                         _ptr(d_rest), _ptr(d_op), _ptr(d_sc), _ptr(d_ro), acc, stream)
-            if rc != 0:
-                raise (PairCapacityExceeded if rc == 5 else RuntimeError)(_err(lib))
-        else:
-            for t in (d_x, d_dc, d_rest, d_op, d_sc, d_ro, d_m2):
-                if t is not None and bucket is None:
-                    t.zero_()
-            if d_obj is not None:
-                d_obj.zero_()
-        if ctx.entry is not None:
-            _entry_leave(ctx.entry, device)
-            ctx.token.done = True
-        s = ctx.shapes
-        # (one gradient per input: the 14th, objects_dc, only when it was passed)
-        g_obj = (None if d_obj is None else d_obj.reshape(s[7]),) if with_obj else ()
-        if bset is not None:
-            return (None, None if d_m2 is None else d_m2.reshape(s[1]), None, None, None, None, None, None, None, None, None,
-                    None, None) + g_obj
-        if bucket is not None:
-            bucket.fresh, bucket.used = False, True
-            return (None, None if d_m2 is None else d_m2.reshape(s[1]), None, None, None, None, None, None, None, None, None,
-                    None, None) + g_obj
 
-        def shaped(t, shape, wanted=True):
-            return None if (t is None or not wanted) else t.reshape(shape)
-        return (shaped(d_x, s[0]), shaped(d_m2, s[1]), shaped(d_dc, s[2], need[2]), shaped(d_rest, s[3], need[3]),
-                shaped(d_op, s[4]), shaped(d_sc, s[5]), shaped(d_ro, s[6]), None, None, None, None, None, None) + g_obj
+def _wants_backward(*tensors) -> bool:
+    """A forward keeps backward state only if autograd can reach it: grad mode on and an input that requires grad.
+    Decided here, before Function.apply (inside forward() grad mode is off and needs_input_grad ignores no_grad())."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
 def rasterize_gaussians_raw_batch(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, settings_list,
@@ -1303,27 +1250,15 @@ def rasterize_gaussians_raw_batch(xyz, means2D, features_dc, features_rest, opac
     gradients summed in view order (a GradBucket or GradBucketSet does not hold it).
     aux=True (not with objects_dc): -> (color, radii, depth[B,1,H,W], alpha[B,1,H,W]), both differentiable; every map bit for
     bit rasterize_gaussians_raw(..., aux=True)'s for that view; the render cache is bypassed."""
-    if aux:
-        keep = _wants_backward(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation)
-        return _RasterizeGaussiansRawBatch.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                                 list(settings_list), keep, grad_bucket, grad_norms, None, False, objects_dc, True)
-    keep = _wants_backward(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, objects_dc)
     # `cache` (a RenderCache) + `cache_key` (one per tuple of cameras): a batch whose geometry inputs and cameras are unchanged
     # since the key's last render re-uses that render's binning for all B views (gsr_ctx_rerender on the batch context)
-    slot = (cache, cache_key) if cache is not None else None
-    color_only = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad
-                                                       for t in (xyz, means2D, opacity, scaling, rotation)))
-    if objects_dc is None:
-        return _RasterizeGaussiansRawBatch.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                                 list(settings_list), keep, grad_bucket, grad_norms, slot, color_only)
-    return _RasterizeGaussiansRawBatch.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                             list(settings_list), keep, grad_bucket, grad_norms, slot, color_only, objects_dc)
-
-
-def _wants_backward(*tensors) -> bool:
-    """A forward keeps backward state only if autograd can reach it: grad mode on and an input that requires grad.
-    Decided here, before Function.apply (inside forward() grad mode is off and needs_input_grad ignores no_grad())."""
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+    opts = _CallOpts(keep=_wants_backward(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, objects_dc),
+                     aux=bool(aux), bucket=grad_bucket, norms=grad_norms,
+                     cache_slot=(cache, cache_key) if cache is not None else None,
+                     color_only=not _wants_backward(xyz, means2D, opacity, scaling, rotation),
+                     settings_list=tuple(settings_list))
+    return _RasterizeGaussiansRawBatch.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, objects_dc,
+                                             opts)
 
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation,
@@ -1335,18 +1270,14 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, objects_dc
     aux=True: -> (color, radii, objects, depth[1,H,W], alpha[1,H,W]) -- alpha = 1 - final transmittance, depth = sum of
     z_i alpha_i T_i (not divided by alpha; depth / alpha is the expected depth of the covered part) -- both differentiable
     w.r.t. xyz, opacity, scaling and rotation; the render cache is bypassed."""
-    if aux:
-        keep = _wants_backward(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation)
-        return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation,
-                                            raster_settings, keep, grad_bucket, None, False, grad_norms, True)
-    keep = _wants_backward(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation)
     # `cache` (a RenderCache) + `cache_key` (one per camera): a render whose geometry inputs are unchanged since the key's
     # last render re-uses that render's binning (gsr_ctx_rerender)
-    slot = (cache, cache_key) if cache is not None else None
-    color_only = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad
-                                                       for t in (xyz, means2D, opacity, scaling, rotation)))
+    opts = _CallOpts(keep=_wants_backward(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation),
+                     aux=bool(aux), bucket=grad_bucket, norms=grad_norms,
+                     cache_slot=(cache, cache_key) if cache is not None else None,
+                     color_only=not _wants_backward(xyz, means2D, opacity, scaling, rotation))
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, objects_dc, opacity, scaling, rotation,
-                                        raster_settings, keep, grad_bucket, slot, color_only, grad_norms)
+                                        raster_settings, opts)
 
 
 @torch.no_grad()
@@ -1358,19 +1289,13 @@ def rasterize_gaussians_raw2(params_a, params_b, raster_settings, objects: bool 
     tensors for this).  -> (color[3,H,W], radii[Pa+Pb], objects[16,H,W]); bitwise equal to rasterize_gaussians_raw on
     the concatenated tensors.  Not differentiable (the reference never calls backward on this render)."""
     lib = _load()
-    xa = params_a[0]
-    if not xa.is_cuda:
-        raise RuntimeError("diff_gaussian_rasterization: tensors must live on a HIP device; there is no CPU path")
-    device = xa.device
-
-    def prep(t):
-        return None if t is None or t.numel() == 0 else _f32c(t.detach(), device)
-    a = [prep(t) for t in params_a]
-    b = [prep(t) for t in params_b]
+    device = _hip_device(params_a[0])
+    a = [_prep(t, device) for t in params_a]
+    b = [_prep(t, device) for t in params_b]
     Pa, Pb = int(params_a[0].shape[0]), int(params_b[0].shape[0])
-    for P, (x, dc, rest, obj, op, sc, ro) in ((Pa, a), (Pb, b)):
-        if P and (tuple(dc.shape) != (P, 1, 3) or tuple(rest.shape) != (P, 15, 3)):
-            raise ValueError("fused path needs _features_dc [P,1,3] and _features_rest [P,15,3] (SH degree 3 storage)")
+    for P, params in ((Pa, params_a), (Pb, params_b)):
+        if P:
+            _check_sh_storage(P, params[1], params[2])
     with_obj = objects and (Pa == 0 or a[3] is not None) and (Pb == 0 or b[3] is not None)
     H, W = int(raster_settings.image_height), int(raster_settings.image_width)
     pack = _SettingsPack(raster_settings, device)
@@ -1382,60 +1307,34 @@ def rasterize_gaussians_raw2(params_a, params_b, raster_settings, objects: bool 
         a[3] = b[3] = None
     # cache: with both models' geometry unchanged since the key's last render, only the colour kernel and the compositor
     # run (gsr_ctx_rerender on a context kept by gsr_forward_raw2_keep) -- the success re-render of a colour attack
-    entry = sig = None
-    geo = ()
+    entry = sig = refs = b_sig = None
     if cache is not None and Pa > 0 and Pb > 0:
         geo = tuple(params_a[i] for i in (0, 4, 5, 6)) + tuple(params_b[i] for i in (0, 4, 5, 6)) + \
             ((params_a[3], params_b[3]) if with_obj else (None, None))
         used = (a[0], a[4], a[5], a[6], b[0], b[4], b[5], b[6], a[3], b[3])
-        if all(t is None or t.data_ptr() == u.data_ptr() for t, u in zip(geo, used)):
-            sig = _cache_sig(geo, raster_settings, extra=("pair", with_obj))
-            geo = geo + (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
-            entry, _ = cache._lookup(cache_key, sig, geo)        # forward-only contexts are never busy
+        entry, sig, refs = _cache_probe(cache, cache_key, geo, used, [raster_settings], "pair", with_obj, False)
+        b_sig = _coeff_sig(params_b[1], params_b[2], b[1], b[2])
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         if entry is not None:
-            _entry_enter(entry, device)
             radii = entry.pack.radii.detach()
-            # the second model is the frozen background (reference attack.py:513-530): while its coefficient tensors are the
-            # ones of the entry's last render, unmodified, the colour kernel runs over the first model's Gaussians only
-            b_sig = tuple((t.data_ptr(), t._version) for t in (params_b[1], params_b[2]))
-            b_same = (entry.pack.b_sig == b_sig and params_b[1].data_ptr() == b[1].data_ptr()
-                      and params_b[2].data_ptr() == b[2].data_ptr())
-            if b_same:
-                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(a[1]), _ptr(a[2]), None, None, _ptr(pack.bg),
-                                          _ptr(color), _ptr(objs) if with_obj else None, 1 | 2, stream)
-            else:
-                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(a[1]), _ptr(a[2]), _ptr(b[1]), _ptr(b[2]), _ptr(pack.bg),
-                                          _ptr(color), _ptr(objs) if with_obj else None, 1, stream)
-            entry.pack.b_sig = b_sig if (params_b[1].data_ptr() == b[1].data_ptr()
-                                         and params_b[2].data_ptr() == b[2].data_ptr()) else None
-            entry.gen += 1
+            dc_b, rest_b, flags = _pair_rerender_args(entry.pack, b_sig, b[1], b[2])
             # the context reads the coefficient tensors of THIS call on the stream: they stay referenced until the next render
             entry.pack.last_inputs = (a, b, pack)
-            if rc == GSR_ERR_OVERFLOW:                 # see _RasterizeGaussiansRaw.forward: drop the entry, full forward now
-                cache.entries.pop(cache_key, None)
-                cache.dropped_overflow += 1
-                entry = None
+            rc, entry = _cache_rerender(lib, cache, cache_key, entry, device, a[1], a[2], dc_b, rest_b, pack.bg, color,
+                                        objs if with_obj else None, flags)
         if entry is None:
             radii = torch.empty(Pa + Pb, dtype=torch.int32, device=device)
             handle = ctypes.c_void_p(None)
             rc = lib.gsr_forward_raw2_keep(ctypes.byref(pack.c), Pa, *[_ptr(t) for t in a], Pb, *[_ptr(t) for t in b],
                                            _ptr(color), _ptr(objs) if with_obj else None, _ptr(radii),
-                                           ctypes.byref(handle) if sig is not None else None, ctypes.byref(nren), stream)
+                                           ctypes.byref(handle) if sig is not None else None, ctypes.byref(nren), _stream(device))
             if rc == 0 and handle.value:
-                pack.radii = radii
-                pack.last_inputs = (a, b)
-                pack.b_sig = (tuple((t.data_ptr(), t._version) for t in (params_b[1], params_b[2]))
-                              if (params_b[1].data_ptr() == b[1].data_ptr() and params_b[2].data_ptr() == b[2].data_ptr())
-                              else None)
-                entry = _CacheEntry(_CtxHolder(lib, handle), sig,
-                                    tuple(weakref.ref(t) if t is not None else (lambda: None) for t in geo), pack, nren.value)
-                cache._store(cache_key, entry)
+                pack.radii, pack.last_inputs, pack.b_sig = radii, (a, b), b_sig
+                entry = _cache_store(cache, cache_key, _CtxHolder(lib, handle), sig, refs, pack, nren.value)
         if entry is not None and rc == 0:
-            _entry_leave(entry, device)
+            _cache_leave(entry, device)
     if rc != 0:
-        raise (Exception if rc == 1 else PairCapacityExceeded if rc == GSR_ERR_OVERFLOW else RuntimeError)(_err(lib))
+        raise _rc_error(lib, rc)
     return color, radii, objs
 
 
@@ -1452,21 +1351,16 @@ def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Opt
     objects_dc = (objects_dc_a [Pa,16], objects_dc_b [Pb,16]) (gsr_forward_raw2_batch_obj): -> (color, radii,
     objects[B,16,H,W]), every object map bit for bit rasterize_gaussians_raw2's for that view."""
     lib = _load()
-    xa = params_a[0]
-    if not xa.is_cuda:
-        raise RuntimeError("diff_gaussian_rasterization: tensors must live on a HIP device; there is no CPU path")
-    device = xa.device
-    B = len(settings_list)
-    if not 1 <= B <= MAX_BATCH:
-        raise ValueError(f"a batch holds 1..{MAX_BATCH} views, got {B}")
-    a = [_f32c(t.detach(), device) for t in params_a]
-    b = [_f32c(t.detach(), device) for t in params_b]
-    Pa, Pb = int(a[0].shape[0]), int(b[0].shape[0])
+    device = _hip_device(params_a[0])
+    packs, carr = _view_packs(settings_list, device)
+    B = len(packs)
+    Pa, Pb = int(params_a[0].shape[0]), int(params_b[0].shape[0])
     if Pa == 0 or Pb == 0:
         raise ValueError("rasterize_gaussians_raw2_batch needs two non-empty models")
-    for P, (x, dc, rest, op, sc, ro) in ((Pa, a), (Pb, b)):
-        if tuple(dc.shape) != (P, 1, 3) or tuple(rest.shape) != (P, 15, 3):
-            raise ValueError("fused path needs _features_dc [P,1,3] and _features_rest [P,15,3] (SH degree 3 storage)")
+    a = [_prep(t, device) for t in params_a]
+    b = [_prep(t, device) for t in params_b]
+    _check_sh_storage(Pa, params_a[1], params_a[2])
+    _check_sh_storage(Pb, params_b[1], params_b[2])
     with_obj = objects_dc is not None
     oa = ob = None
     if with_obj:
@@ -1474,10 +1368,6 @@ def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Opt
         if oa.numel() != Pa * NUM_OBJECTS or ob.numel() != Pb * NUM_OBJECTS:
             raise ValueError(f"objects_dc must hold Pa*{NUM_OBJECTS} and Pb*{NUM_OBJECTS} values")
     H, W = int(settings_list[0].image_height), int(settings_list[0].image_width)
-    packs = [_SettingsPack(rs, device) for rs in settings_list]
-    carr = (_CSettings * B)()
-    for v, pk in enumerate(packs):
-        carr[v] = pk.c
     color = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
     objs = torch.empty(B, NUM_OBJECTS, H, W, dtype=torch.float32, device=device) if with_obj else None
     nren = ctypes.c_int64(0)
@@ -1487,64 +1377,36 @@ def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Opt
         used = (a[0], a[3], a[4], a[5], b[0], b[3], b[4], b[5])
         if with_obj:                                # (the context reads the object features through the forward's pointers)
             geo, used = geo + tuple(objects_dc), used + (oa, ob)
-        if all(t.data_ptr() == u.data_ptr() for t, u in zip(geo, used)):
-            extra = ["pair-batch", B] + (["obj"] if with_obj else [])
-            for rs in settings_list[1:]:
-                extra += [float(rs.tanfovx), float(rs.tanfovy)]
-                for t in (rs.viewmatrix, rs.projmatrix, rs.campos):
-                    extra += [t.data_ptr(), t._version]
-            sig = _cache_sig(geo, settings_list[0], extra=extra)
-            refs = geo + tuple(t for rs in settings_list for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
-            entry, _ = cache._lookup(cache_key, sig, refs)       # forward-only contexts are never busy
-    b_dense = params_b[1].data_ptr() == b[1].data_ptr() and params_b[2].data_ptr() == b[2].data_ptr()
-    b_sig = tuple((t.data_ptr(), t._version) for t in (params_b[1], params_b[2])) if b_dense else None
+        entry, sig, refs = _cache_probe(cache, cache_key, geo, used, settings_list, "pair-batch", with_obj, False)
+    b_sig = _coeff_sig(params_b[1], params_b[2], b[1], b[2])
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         if entry is not None:
-            _entry_enter(entry, device)
             bp = entry.pack
             radii = bp.radii.detach()
-            ptrs = tuple(pk.bg.data_ptr() for pk in packs)
-            bgt = None
-            if ptrs != bp.bg_src or bp.bgt is not None:
-                bgt = torch.stack([pk.bg[:3] for pk in packs]).contiguous()
-                bp.bgt, bp.bg_src = bgt, ptrs
-            # the second model is the frozen background: while its coefficient tensors are those of the entry's last render,
-            # unmodified, the colour kernel covers the first model's Gaussians only
-            if b_sig is not None and bp.b_sig == b_sig:
-                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(a[1]), _ptr(a[2]), None, None, _ptr(bgt), _ptr(color),
-                                          _ptr(objs), 1 | 2, stream)
-            else:
-                rc = lib.gsr_ctx_rerender(entry.holder.handle, _ptr(a[1]), _ptr(a[2]), _ptr(b[1]), _ptr(b[2]), _ptr(bgt),
-                                          _ptr(color), _ptr(objs), 1, stream)
-            bp.b_sig = b_sig
+            dc_b, rest_b, flags = _pair_rerender_args(bp, b_sig, b[1], b[2])
             bp.last_inputs = (a, b, packs, oa, ob)     # read on the stream: referenced until the next render
-            entry.gen += 1
-            if rc == GSR_ERR_OVERFLOW:
-                cache.entries.pop(cache_key, None)
-                cache.dropped_overflow += 1
-                entry = None
+            rc, entry = _cache_rerender(lib, cache, cache_key, entry, device, a[1], a[2], dc_b, rest_b, bp.background(packs),
+                                        color, objs, flags)
         if entry is None:
             radii = torch.empty(B, Pa + Pb, dtype=torch.int32, device=device)
             handle = ctypes.c_void_p(None)
+            want_ctx = ctypes.byref(handle) if sig is not None else None
             if with_obj:
                 rc = lib.gsr_forward_raw2_batch_obj(carr, B, Pa, *[_ptr(t) for t in a[:3]], _ptr(oa), *[_ptr(t) for t in a[3:]],
                                                     Pb, *[_ptr(t) for t in b[:3]], _ptr(ob), *[_ptr(t) for t in b[3:]],
-                                                    _ptr(color), _ptr(objs), _ptr(radii),
-                                                    ctypes.byref(handle) if sig is not None else None, ctypes.byref(nren), stream)
+                                                    _ptr(color), _ptr(objs), _ptr(radii), want_ctx, ctypes.byref(nren),
+                                                    _stream(device))
             else:
                 rc = lib.gsr_forward_raw2_batch(carr, B, Pa, *[_ptr(t) for t in a], Pb, *[_ptr(t) for t in b], _ptr(color),
-                                                _ptr(radii), ctypes.byref(handle) if sig is not None else None,
-                                                ctypes.byref(nren), stream)
+                                                _ptr(radii), want_ctx, ctypes.byref(nren), _stream(device))
             if rc == 0 and handle.value:
                 bp = _BatchPack(packs, radii)
                 bp.b_sig, bp.last_inputs = b_sig, (a, b, packs, oa, ob)
-                entry = _CacheEntry(_CtxHolder(lib, handle), sig, tuple(weakref.ref(t) for t in refs), bp, nren.value)
-                cache._store(cache_key, entry)
+                entry = _cache_store(cache, cache_key, _CtxHolder(lib, handle), sig, refs, bp, nren.value)
         if entry is not None and rc == 0:
-            _entry_leave(entry, device)
+            _cache_leave(entry, device)
     if rc != 0:
-        raise (Exception if rc == 1 else PairCapacityExceeded if rc == GSR_ERR_OVERFLOW else RuntimeError)(_err(lib))
+        raise _rc_error(lib, rc)
     if with_obj:
         return color, radii, objs
     return color, radii
@@ -1553,11 +1415,8 @@ def rasterize_gaussians_raw2_batch(params_a, params_b, settings_list, cache: Opt
 def rasterize_gaussians(means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, aux: bool = False):
     keep = _wants_backward(means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-    if aux:
-        return _RasterizeGaussians.apply(means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, raster_settings, keep, True)
     return _RasterizeGaussians.apply(means3D, means2D, sh, sh_objs, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, keep)
+                                     cov3Ds_precomp, raster_settings, _CallOpts(keep=keep, aux=bool(aux)))
 
 
 class GaussianRasterizer(nn.Module):
@@ -1576,8 +1435,7 @@ class GaussianRasterizer(nn.Module):
             pack = _SettingsPack(self.raster_settings, device)
             present = torch.empty(pos.shape[0], dtype=torch.uint8, device=device)
             with torch.cuda.device(device):
-                stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-                rc = lib.gsr_mark_visible(ctypes.byref(pack.c), int(pos.shape[0]), _ptr(pos), _ptr(present), stream)
+                rc = lib.gsr_mark_visible(ctypes.byref(pack.c), int(pos.shape[0]), _ptr(pos), _ptr(present), _stream(device))
             if rc != 0:
                 raise RuntimeError(_err(lib))
             return present.bool()
@@ -1632,8 +1490,7 @@ def export_state(output: torch.Tensor, name: str) -> torch.Tensor:
         # only the Gaussians that emit pairs are ranked: dv[1] = V of them (order[:V], off[:V + 1] are meaningful)
         live = int(export_state(output, "dv")[1].item()) + (1 if name == "off" else 0)
     dst = torch.empty(max(n, 1), dtype=dt, device=output.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(output.device).cuda_stream)
-    if holder.lib.gsr_ctx_export(holder.handle, what, dst.data_ptr(), dst.numel() * 4, stream) != 0:
+    if holder.lib.gsr_ctx_export(holder.handle, what, dst.data_ptr(), dst.numel() * 4, _stream(output.device)) != 0:
         raise RuntimeError(_err(holder.lib))
     return dst[:n if live is None else live]
 

@@ -48,23 +48,7 @@ class _CDetSpec(ctypes.Structure):
                 ("ox", ctypes.c_float), ("oy", ctypes.c_float), ("sx", ctypes.c_float), ("sy", ctypes.c_float)]
 
 
-def _lib():
-    lib = _load()
-    if not hasattr(lib, "_detect_ready"):
-        vp, i32, i64, f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        sp = ctypes.POINTER(_CDetSpec)
-        lib.gsr_det_workspace_bytes.restype = ctypes.c_int
-        lib.gsr_det_workspace_bytes.argtypes = [sp, ctypes.POINTER(i64)]
-        lib.gsr_det_postprocess.restype = ctypes.c_int
-        lib.gsr_det_postprocess.argtypes = [sp, vp, vp, i64, vp, vp, vp]
-        lib.gsr_det_nms.restype = ctypes.c_int
-        lib.gsr_det_nms.argtypes = [i32, i32, vp, vp, vp, vp, f, i32, vp, i64, vp, vp, vp]
-        lib.gsr_det_box_iou.restype = ctypes.c_int
-        lib.gsr_det_box_iou.argtypes = [vp, i32, vp, i32, vp, vp]
-        lib.gsr_det_verdict.restype = ctypes.c_int
-        lib.gsr_det_verdict.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, f, vp, vp, vp]
-        lib._detect_ready = True
-    return lib
+_lib = _load              # (the entry points' signatures are declared in _signatures.py, applied by _load)
 
 
 def available() -> bool:

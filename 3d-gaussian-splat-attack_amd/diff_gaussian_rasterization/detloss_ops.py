@@ -44,17 +44,7 @@ class _CDetLossSpec(ctypes.Structure):
                 ("w_box", ctypes.c_float), ("w_cls", ctypes.c_float), ("w_dfl", ctypes.c_float), ("flags", ctypes.c_uint32)]
 
 
-def _lib():
-    lib = _load()
-    if not hasattr(lib, "_detloss_ready"):
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        sp = ctypes.POINTER(_CDetLossSpec)
-        lib.gsr_detloss_workspace_bytes.restype = ctypes.c_int
-        lib.gsr_detloss_workspace_bytes.argtypes = [sp, ctypes.POINTER(i64)]
-        lib.gsr_detloss.restype = ctypes.c_int
-        lib.gsr_detloss.argtypes = [sp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
-        lib._detloss_ready = True
-    return lib
+_lib = _load              # (the entry points' signatures are declared in _signatures.py, applied by _load)
 
 
 def available() -> bool:

@@ -14,28 +14,13 @@ from typing import NamedTuple, Sequence
 import numpy as np
 import torch
 
-from . import _err, _load
+from . import _err, _load, _stream
 
 MAX_CLASSES = 1024
 GSR_ERR_NOMEM = 3
 
 
-def _lib():
-    lib = _load()
-    if not hasattr(lib, "_groups_ready"):
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        lib.gsr_group_classify.restype = ctypes.c_int
-        lib.gsr_group_classify.argtypes = [vp, i32, vp, vp, i32, vp, i32, ctypes.c_float, vp, vp, vp]
-        lib.gsr_convex_hull_planes.restype = ctypes.c_int
-        lib.gsr_convex_hull_planes.argtypes = [vp, i64, vp, i64, ctypes.POINTER(i64), vp]
-        lib.gsr_points_in_hull.restype = ctypes.c_int
-        lib.gsr_points_in_hull.argtypes = [vp, i32, vp, i32, vp, ctypes.c_double, vp, vp, vp]
-        lib._groups_ready = True
-    return lib
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_lib = _load              # (the entry points' signatures are declared in _signatures.py, applied by _load)
 
 
 def _device_f32(t: torch.Tensor, device, name: str) -> torch.Tensor:

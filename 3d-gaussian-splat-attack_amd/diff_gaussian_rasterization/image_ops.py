@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional, Sequence
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _err, _load
+from . import _err, _load, _stream
 
 GSR_RESAMPLE_CLAMP01 = 1
 GSR_CAP_IMAGE = 1
@@ -47,19 +47,7 @@ class _CResample(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
-def _lib():
-    lib = _load()
-    if not hasattr(lib, "_image_ready"):
-        vp, i32 = ctypes.c_void_p, ctypes.c_int32
-        rp = ctypes.POINTER(_CResample)
-        lib.gsr_image_resample.restype = ctypes.c_int
-        lib.gsr_image_resample.argtypes = [rp, vp, vp, vp]
-        lib.gsr_image_resample_backward.restype = ctypes.c_int
-        lib.gsr_image_resample_backward.argtypes = [rp, vp, vp, vp, i32, vp]
-        lib.gsr_image_to_u8.restype = ctypes.c_int
-        lib.gsr_image_to_u8.argtypes = [vp, i32, i32, i32, vp, vp]
-        lib._image_ready = True
-    return lib
+_lib = _load              # (the entry points' signatures are declared in _signatures.py, applied by _load)
 
 
 def available() -> bool:
@@ -67,10 +55,6 @@ def available() -> bool:
     lib = _load()
     out = ctypes.c_int64(0)
     return lib.gsr_query(3, ctypes.byref(out)) == 0 and bool(out.value & GSR_CAP_IMAGE)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _need_device(t, fn: str, name: str) -> None:

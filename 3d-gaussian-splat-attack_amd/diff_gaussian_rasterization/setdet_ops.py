@@ -50,19 +50,7 @@ class _CSetDetSpec(ctypes.Structure):
                 ("eos_coef", ctypes.c_float), ("conf_thr", ctypes.c_float), ("max_det", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
-def _lib():
-    lib = _load()
-    if not hasattr(lib, "_setdet_ready"):
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        sp = ctypes.POINTER(_CSetDetSpec)
-        lib.gsr_setdet_workspace_bytes.restype = ctypes.c_int
-        lib.gsr_setdet_workspace_bytes.argtypes = [sp, ctypes.POINTER(i64)]
-        lib.gsr_setdet_loss.restype = ctypes.c_int
-        lib.gsr_setdet_loss.argtypes = [sp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
-        lib.gsr_setdet_postprocess.restype = ctypes.c_int
-        lib.gsr_setdet_postprocess.argtypes = [sp, vp, vp, vp, vp, vp]
-        lib._setdet_ready = True
-    return lib
+_lib = _load              # (the entry points' signatures are declared in _signatures.py, applied by _load)
 
 
 def available() -> bool:

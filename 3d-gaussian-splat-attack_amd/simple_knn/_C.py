@@ -5,8 +5,6 @@ On a HIP device it calls ``gsr_knn_dist2`` of libgsraster.so (uniform-grid exact
 -- which the reference never passes, its name says so -- get a chunked torch.cdist evaluation of the same definition,
 so that a GaussianModel-style container can be exercised in CPU-only unit tests; that branch is not on the raster path.
 """
-import ctypes
-
 import torch
 
 
@@ -29,17 +27,12 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
         return _dist2_torch(pts)
     import diff_gaussian_rasterization as D
     lib = D._load()
-    if not hasattr(lib, "_knn_ready"):
-        lib.gsr_knn_dist2.restype = ctypes.c_int
-        lib.gsr_knn_dist2.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-        lib._knn_ready = True
     P = int(pts.shape[0])
     out = torch.empty(P, dtype=torch.float32, device=pts.device)
     if P == 0:
         return out
     with torch.cuda.device(pts.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(pts.device).cuda_stream)
-        rc = lib.gsr_knn_dist2(pts.data_ptr(), P, out.data_ptr(), stream)
+        rc = lib.gsr_knn_dist2(pts.data_ptr(), P, out.data_ptr(), D._stream(pts.device))
     if rc != 0:
         raise RuntimeError(D._err(lib))
     return out

@@ -342,3 +342,34 @@ def test_overflowed_async_forward_does_not_poison_its_cache_key():
     with torch.no_grad():
         want = render(cam, model, plain, bg, 4.0)["render"].clone()       # counted synchronously, no cache: the right image
     assert torch.equal(second, want) and torch.equal(third, want)
+
+
+def test_overflowed_async_batch_forward_does_not_poison_its_cache_key():
+    """The same sequence through render_batch with B = 2: the batch forward shares the drop-and-take-the-full-forward step
+    with the single-view one, and its kept context is a batch context."""
+    import diff_gaussian_rasterization as D
+    from diff_gaussian_rasterization import RenderCache
+    from gsplat_attack.renderer import PipelineParams, render_batch
+    dev, model, cams, bg = _scene(50000, 640, 360, n_views=2, key="nyc-1M")
+    plain = PipelineParams(skip_objects=True)
+    with torch.no_grad():
+        small = render_batch(cams, model, plain, bg)["render"].clone()    # seeds the capacity table for this batch
+    assert torch.isfinite(small).all()
+    cache = RenderCache()
+    cached = PipelineParams(skip_objects=True, render_cache=cache)
+    try:
+        D.set_flags(D.FLAG_ASYNC_COUNT)
+        with torch.no_grad():
+            first = render_batch(cams, model, cached, bg, 4.0)["render"].clone()
+            assert torch.isnan(first).all() and len(cache.entries) == 1
+            second = render_batch(cams, model, cached, bg, 4.0)["render"].clone()   # hit -> overflow -> dropped -> full forward
+            assert cache.dropped_overflow == 1 and len(cache.entries) == 1
+            assert torch.isfinite(second).all()
+            hits = cache.hits
+            third = render_batch(cams, model, cached, bg, 4.0)["render"].clone()    # an ordinary hit on the replaced entry
+        assert cache.dropped_overflow == 1 and cache.hits == hits + 1
+    finally:
+        D.set_flags(0)
+    with torch.no_grad():
+        want = render_batch(cams, model, plain, bg, 4.0)["render"].clone()
+    assert torch.equal(second, want) and torch.equal(third, want)
