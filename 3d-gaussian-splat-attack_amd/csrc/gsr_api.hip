@@ -31,6 +31,7 @@
 #include "gsr_detect.hip.h"
 #include "gsr_detloss.hip.h"
 #include "gsr_setdet.hip.h"
+#include "gsr_rcnn.hip.h"
 
 using namespace gsr;
 
@@ -1818,7 +1819,8 @@ int gsr_query(int32_t what, int64_t* out) {
       *out = (int64_t)pl.total;
       return GSR_OK;
     }
-    case 3: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS | GSR_CAP_SETDET; return GSR_OK;     // capability bits
+    case 3: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS | GSR_CAP_SETDET; return GSR_OK;     // capability bits 0..3: closed
+    case 4: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS | GSR_CAP_SETDET | GSR_CAP_RCNN; return GSR_OK;     // every capability bit
     default: return set_err(GSR_ERR_INVALID, "gsr_query: unknown item %d", what);
   }
 }
@@ -2582,6 +2584,265 @@ int gsr_setdet_postprocess(const GsrSetDetSpec* d, const float* logits, const fl
   hipLaunchKernelGGL(gsr_setdet::k_setdet_post, dim3((unsigned)sp.B), dim3((unsigned)((sp.Q + 63) / 64 * 64)), 0, static_cast<hipStream_t>(stream),
                      sp, logits, boxes, dets, counts);
   LAUNCH_CHECK("gsr_setdet_postprocess");
+  return GSR_OK;
+}
+
+// ---- two-stage detector stage (gsr_rcnn.h / gsr_rcnn.hip.h): no allocation, no copy, no host wait; every entry checks the
+// members of the spec it uses on the host before the first launch.  Workspace, each region rounded up to 256 bytes:
+// [nrows 1 i32][slab blocks*2 f32] for the loss; [boxes B*R*4 f32][score B*R f32][cls B*R i32][ncand B i32]
+// [keep B*max_det i32][nkept B i32][the NMS walk's own workspace] for the output stage; the two share the start.
+struct RcnnWs {
+  size_t nrows, slab, loss_bytes;
+  size_t boxes, score, cls, ncand, keep, nkept, nms, post_bytes;
+};
+
+static bool rcnn_pos_finite(float v) { return v > 0.0f && v <= 3.0e38f; }
+static bool rcnn_nonneg_finite(float v) { return v >= 0.0f && v <= 3.0e38f; }
+
+static unsigned rcnn_row_blocks(long long B, long long S) {
+  return (unsigned)((B * S + gsr_rcnn::ROW_WAVES - 1) / gsr_rcnn::ROW_WAVES);
+}
+
+static RcnnWs rcnn_layout(const GsrRcnnSpec* d, bool loss, bool post) {
+  RcnnWs w{};
+  if (loss) {
+    w.nrows = 0;
+    w.slab = det_round(4);
+    w.loss_bytes = w.slab + det_round((size_t)rcnn_row_blocks(d->B, d->S) * 2 * 4);
+  }
+  if (post) {
+    const size_t BR = (size_t)d->B * (size_t)d->R;
+    w.boxes = 0;
+    w.score = w.boxes + det_round(BR * 4 * 4);
+    w.cls = w.score + det_round(BR * 4);
+    w.ncand = w.cls + det_round(BR * 4);
+    w.keep = w.ncand + det_round((size_t)d->B * 4);
+    w.nkept = w.keep + det_round((size_t)d->B * (size_t)d->max_det * 4);
+    w.nms = w.nkept + det_round((size_t)d->B * 4);
+    w.post_bytes = w.nms + det_layout(d->B, d->R, d->R).bytes;
+  }
+  return w;
+}
+
+static void rcnn_copy_spec(const GsrRcnnSpec* d, gsr_rcnn::Spec& sp) {
+  sp.B = d->B; sp.R = d->R; sp.M = d->M; sp.S = d->S; sp.C = d->C; sp.max_pos = d->max_pos; sp.append_gt = d->append_gt != 0 ? 1 : 0;
+  sp.seed = d->seed; sp.fg_iou = d->fg_iou; sp.Cf = d->Cf; sp.Hf = d->Hf; sp.Wf = d->Wf; sp.PH = d->PH; sp.PW = d->PW;
+  sp.spatial_scale = d->spatial_scale; sp.sampling_ratio = d->sampling_ratio; sp.bw_x = d->bw_x; sp.bw_y = d->bw_y;
+  sp.bw_w = d->bw_w; sp.bw_h = d->bw_h; sp.beta = d->beta; sp.w_cls = d->w_cls; sp.w_box = d->w_box; sp.conf_thr = d->conf_thr;
+  sp.iou_thr = d->iou_thr; sp.max_det = d->max_det; sp.img_w = d->img_w; sp.img_h = d->img_h; sp.flags = d->flags;
+}
+
+static int rcnn_common(const char* fn, const GsrRcnnSpec* d) {
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->B > 65535) return set_err(GSR_ERR_INVALID, "%s: B=%d images (1..65535)", fn, d->B);
+  if (d->flags & ~GSR_RCNN_CLASS_AGNOSTIC) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
+  return GSR_OK;
+}
+
+static int rcnn_sample_spec(const char* fn, const GsrRcnnSpec* d) {
+  if (int rc = rcnn_common(fn, d)) return rc;
+  if (d->M < 1 || d->M > gsr_rcnn::MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: M=%d gt rows per image (1..%d)", fn, d->M, gsr_rcnn::MAX_ROWS);
+  if (d->S < 1 || d->S > gsr_rcnn::MAX_SAMPLE) return set_err(GSR_ERR_INVALID, "%s: S=%d RoIs per image (1..%d)", fn, d->S, gsr_rcnn::MAX_SAMPLE);
+  if (d->C < 1 || d->C > gsr_rcnn::MAX_CLASSES) return set_err(GSR_ERR_INVALID, "%s: C=%d classes (1..%d)", fn, d->C, gsr_rcnn::MAX_CLASSES);
+  if (d->R < 1 || (long long)d->R + (long long)d->M > gsr_rcnn::MAX_CAND)
+    return set_err(GSR_ERR_INVALID, "%s: R=%d proposals with M=%d rows (R >= 1, R + M <= %d)", fn, d->R, d->M, gsr_rcnn::MAX_CAND);
+  if (d->max_pos < 0 || d->max_pos > d->S) return set_err(GSR_ERR_INVALID, "%s: max_pos=%d (0..S=%d)", fn, d->max_pos, d->S);
+  if (!rcnn_nonneg_finite(d->fg_iou)) return set_err(GSR_ERR_INVALID, "%s: fg_iou must be finite and >= 0", fn);
+  return GSR_OK;
+}
+
+static int rcnn_roi_spec(const char* fn, const GsrRcnnSpec* d, unsigned long long& pooled_elems) {
+  if (int rc = rcnn_common(fn, d)) return rc;
+  if (d->S < 1 || d->S > gsr_rcnn::MAX_SAMPLE) return set_err(GSR_ERR_INVALID, "%s: S=%d RoIs per image (1..%d)", fn, d->S, gsr_rcnn::MAX_SAMPLE);
+  if (d->Cf < 1 || d->Hf < 1 || d->Wf < 1) return set_err(GSR_ERR_INVALID, "%s: the feature map is %d x %d x %d (sizes >= 1)", fn, d->Cf, d->Hf, d->Wf);
+  if (d->Cf > 65535) return set_err(GSR_ERR_INVALID, "%s: Cf=%d channels (1..65535)", fn, d->Cf);
+  if (d->PH < 1 || d->PH > gsr_rcnn::MAX_POOL || d->PW < 1 || d->PW > gsr_rcnn::MAX_POOL)
+    return set_err(GSR_ERR_INVALID, "%s: the pooled size is %d x %d (1..%d each)", fn, d->PH, d->PW, gsr_rcnn::MAX_POOL);
+  if (d->sampling_ratio < 0) return set_err(GSR_ERR_INVALID, "%s: sampling_ratio=%d (>= 0)", fn, d->sampling_ratio);
+  if (!rcnn_pos_finite(d->spatial_scale)) return set_err(GSR_ERR_INVALID, "%s: spatial_scale must be finite and > 0", fn);
+  const unsigned long long feat = (unsigned long long)d->B * (unsigned long long)d->Cf * (unsigned long long)d->Hf * (unsigned long long)d->Wf;
+  pooled_elems = (unsigned long long)d->B * (unsigned long long)d->S * (unsigned long long)d->Cf * (unsigned long long)(d->PH * d->PW);
+  if ((unsigned long long)d->Hf * (unsigned long long)d->Wf > 0x7fffffffull || feat > 0x7fffffffull || pooled_elems > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in features or pooled", fn);
+  return GSR_OK;
+}
+
+static int rcnn_head_spec(const char* fn, const GsrRcnnSpec* d, long long rows_per_image) {
+  if (int rc = rcnn_common(fn, d)) return rc;
+  if (d->C < 1 || d->C > gsr_rcnn::MAX_CLASSES) return set_err(GSR_ERR_INVALID, "%s: C=%d classes (1..%d)", fn, d->C, gsr_rcnn::MAX_CLASSES);
+  if (!rcnn_pos_finite(d->bw_x) || !rcnn_pos_finite(d->bw_y) || !rcnn_pos_finite(d->bw_w) || !rcnn_pos_finite(d->bw_h))
+    return set_err(GSR_ERR_INVALID, "%s: bw_x, bw_y, bw_w, bw_h must be finite and > 0", fn);
+  if ((unsigned long long)d->B * (unsigned long long)rows_per_image * 4ull * (unsigned long long)d->C > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in scores or deltas", fn);
+  return GSR_OK;
+}
+
+static int rcnn_loss_spec(const char* fn, const GsrRcnnSpec* d) {
+  if (int rc = rcnn_common(fn, d)) return rc;
+  if (d->S < 1 || d->S > gsr_rcnn::MAX_SAMPLE) return set_err(GSR_ERR_INVALID, "%s: S=%d RoIs per image (1..%d)", fn, d->S, gsr_rcnn::MAX_SAMPLE);
+  if (d->M < 1 || d->M > gsr_rcnn::MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: M=%d gt rows per image (1..%d)", fn, d->M, gsr_rcnn::MAX_ROWS);
+  if (int rc = rcnn_head_spec(fn, d, d->S)) return rc;
+  if (!rcnn_nonneg_finite(d->beta) || !rcnn_nonneg_finite(d->w_cls) || !rcnn_nonneg_finite(d->w_box))
+    return set_err(GSR_ERR_INVALID, "%s: beta, w_cls, w_box must be finite and >= 0", fn);
+  return GSR_OK;
+}
+
+static int rcnn_post_spec(const char* fn, const GsrRcnnSpec* d) {
+  if (int rc = rcnn_common(fn, d)) return rc;
+  if (d->R < 1 || d->R > gsr_rcnn::MAX_CAND) return set_err(GSR_ERR_INVALID, "%s: R=%d proposals per image (1..%d)", fn, d->R, gsr_rcnn::MAX_CAND);
+  if (int rc = rcnn_head_spec(fn, d, d->R)) return rc;
+  if (d->max_det < 1 || d->max_det > d->R) return set_err(GSR_ERR_INVALID, "%s: max_det=%d (1..R=%d)", fn, d->max_det, d->R);
+  if (!rcnn_nonneg_finite(d->conf_thr) || !rcnn_nonneg_finite(d->iou_thr))
+    return set_err(GSR_ERR_INVALID, "%s: conf_thr, iou_thr must be finite and >= 0", fn);
+  if (!rcnn_pos_finite(d->img_w) || !rcnn_pos_finite(d->img_h))
+    return set_err(GSR_ERR_INVALID, "%s: the frame is %g x %g (finite sizes > 0)", fn, (double)d->img_w, (double)d->img_h);
+  return GSR_OK;
+}
+
+int gsr_rcnn_sample(const GsrRcnnSpec* d, const float* proposals, const int32_t* n_prop, const float* gt_boxes, const int32_t* gt_cls,
+                    int32_t* idx, float* rois, int32_t* labels, int32_t* gt_row, int32_t* counts, void* stream) {
+  if (int rc = rcnn_sample_spec("gsr_rcnn_sample", d)) return rc;
+  if (!proposals || !gt_boxes || !gt_cls || !idx || !rois || !labels || !gt_row || !counts)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_sample: null proposals / gt_boxes / gt_cls / idx / rois / labels / gt_row / counts");
+  if ((((uintptr_t)proposals | (uintptr_t)n_prop | (uintptr_t)gt_boxes | (uintptr_t)gt_cls | (uintptr_t)idx | (uintptr_t)rois |
+        (uintptr_t)labels | (uintptr_t)gt_row | (uintptr_t)counts) & 3) != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_sample: every tensor must be 4-byte aligned");
+  gsr_rcnn::SampleArgs ar;
+  rcnn_copy_spec(d, ar.sp);
+  ar.proposals = proposals; ar.n_prop = n_prop; ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls;
+  ar.idx = idx; ar.rois = rois; ar.labels = labels; ar.gt_row = gt_row; ar.counts = counts;
+  hipLaunchKernelGGL(gsr_rcnn::k_rcnn_sample, dim3((unsigned)d->B), dim3(gsr_rcnn::SAMP_THREADS), 0, static_cast<hipStream_t>(stream), ar);
+  LAUNCH_CHECK("gsr_rcnn_sample");
+  return GSR_OK;
+}
+
+int gsr_roi_align(const GsrRcnnSpec* d, const float* features, const float* rois, const int32_t* n_roi, int32_t n_roi_stride,
+                  float* pooled, void* stream) {
+  unsigned long long total = 0;
+  if (int rc = rcnn_roi_spec("gsr_roi_align", d, total)) return rc;
+  if (!features || !rois || !pooled) return set_err(GSR_ERR_INVALID, "gsr_roi_align: null features / rois / pooled");
+  if (n_roi && n_roi_stride < 1) return set_err(GSR_ERR_INVALID, "gsr_roi_align: n_roi_stride=%d (>= 1)", n_roi_stride);
+  if ((((uintptr_t)features | (uintptr_t)rois | (uintptr_t)n_roi | (uintptr_t)pooled) & 3) != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_roi_align: every tensor must be 4-byte aligned");
+  gsr_rcnn::RoiArgs ar{};
+  rcnn_copy_spec(d, ar.sp);
+  ar.features = features; ar.rois = rois; ar.n_roi = n_roi; ar.n_roi_stride = n_roi ? n_roi_stride : 0; ar.pooled = pooled;
+  const unsigned long long per_roi = (unsigned long long)d->Cf * (unsigned long long)(d->PH * d->PW);
+  hipLaunchKernelGGL(gsr_rcnn::k_roi_align, dim3((unsigned)(d->B * d->S), (unsigned)((per_roi + gsr_rcnn::RA_THREADS - 1) / gsr_rcnn::RA_THREADS)),
+                     dim3(gsr_rcnn::RA_THREADS), 0, static_cast<hipStream_t>(stream), ar);
+  LAUNCH_CHECK("gsr_roi_align");
+  return GSR_OK;
+}
+
+int gsr_roi_align_backward(const GsrRcnnSpec* d, const float* rois, const int32_t* n_roi, int32_t n_roi_stride, const float* grad_pooled,
+                           float* grad_features, int32_t accumulate, void* stream) {
+  unsigned long long total = 0;
+  if (int rc = rcnn_roi_spec("gsr_roi_align_backward", d, total)) return rc;
+  if (!rois || !grad_pooled || !grad_features) return set_err(GSR_ERR_INVALID, "gsr_roi_align_backward: null rois / grad_pooled / grad_features");
+  if (n_roi && n_roi_stride < 1) return set_err(GSR_ERR_INVALID, "gsr_roi_align_backward: n_roi_stride=%d (>= 1)", n_roi_stride);
+  if ((((uintptr_t)rois | (uintptr_t)n_roi | (uintptr_t)grad_pooled | (uintptr_t)grad_features) & 3) != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_roi_align_backward: every tensor must be 4-byte aligned");
+  const unsigned long long tiles = (unsigned long long)((d->Hf + gsr_rcnn::RB_TILE - 1) / gsr_rcnn::RB_TILE) *
+                                   (unsigned long long)((d->Wf + gsr_rcnn::RB_TILE - 1) / gsr_rcnn::RB_TILE);
+  if (tiles > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "gsr_roi_align_backward: more than 2^31 - 1 tiles");
+  gsr_rcnn::RoiArgs ar{};
+  rcnn_copy_spec(d, ar.sp);
+  ar.rois = rois; ar.n_roi = n_roi; ar.n_roi_stride = n_roi ? n_roi_stride : 0; ar.grad_pooled = grad_pooled;
+  ar.grad_features = grad_features; ar.accumulate = accumulate != 0 ? 1 : 0;
+  hipLaunchKernelGGL(gsr_rcnn::k_roi_align_bwd,
+                     dim3((unsigned)tiles, (unsigned)((d->Cf + gsr_rcnn::RB_CHUNK - 1) / gsr_rcnn::RB_CHUNK), (unsigned)d->B),
+                     dim3(gsr_rcnn::RB_THREADS), 0, static_cast<hipStream_t>(stream), ar);
+  LAUNCH_CHECK("gsr_roi_align_backward");
+  return GSR_OK;
+}
+
+int gsr_rcnn_workspace_bytes(const GsrRcnnSpec* d, int64_t* bytes) {
+  if (int rc = rcnn_common("gsr_rcnn_workspace_bytes", d)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_rcnn_workspace_bytes: null bytes");
+  const bool loss = d->S >= 1 && d->S <= gsr_rcnn::MAX_SAMPLE;
+  const bool post = d->R >= 1 && d->R <= gsr_rcnn::MAX_CAND && d->max_det >= 1 && d->max_det <= d->R;
+  if (!loss && !post)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_workspace_bytes: neither S=%d (1..%d) nor R=%d (1..%d) with max_det=%d (1..R) is in range",
+                   d->S, gsr_rcnn::MAX_SAMPLE, d->R, gsr_rcnn::MAX_CAND, d->max_det);
+  const RcnnWs w = rcnn_layout(d, loss, post);
+  *bytes = (int64_t)std::max(w.loss_bytes, w.post_bytes);
+  return GSR_OK;
+}
+
+int gsr_rcnn_loss(const GsrRcnnSpec* d, const float* scores, const float* deltas, const float* rois, const int32_t* labels,
+                  const int32_t* gt_row, const float* gt_boxes, void* ws, int64_t ws_bytes, float* loss, float* grad_scores,
+                  float* grad_deltas, void* stream) {
+  if (int rc = rcnn_loss_spec("gsr_rcnn_loss", d)) return rc;
+  if (!scores || !deltas || !rois || !labels || !gt_row || !gt_boxes || !ws || !loss)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_loss: null scores / deltas / rois / labels / gt_row / gt_boxes / ws / loss");
+  const RcnnWs w = rcnn_layout(d, true, false);
+  if (ws_bytes < (int64_t)w.loss_bytes)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_loss: workspace of %lld bytes, %zu needed (gsr_rcnn_workspace_bytes)", (long long)ws_bytes, w.loss_bytes);
+  if (((uintptr_t)ws & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_rcnn_loss: the workspace must be 16-byte aligned");
+  if ((((uintptr_t)scores | (uintptr_t)deltas | (uintptr_t)rois | (uintptr_t)labels | (uintptr_t)gt_row | (uintptr_t)gt_boxes |
+        (uintptr_t)loss | (uintptr_t)grad_scores | (uintptr_t)grad_deltas) & 3) != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_loss: every tensor must be 4-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  gsr_rcnn::LossArgs ar;
+  rcnn_copy_spec(d, ar.sp);
+  ar.scores = scores; ar.deltas = deltas; ar.rois = rois; ar.labels = labels; ar.gt_row = gt_row; ar.gt_boxes = gt_boxes;
+  ar.nrows = reinterpret_cast<int32_t*>(base + w.nrows);
+  ar.slab = reinterpret_cast<float*>(base + w.slab);
+  ar.loss = loss; ar.grad_scores = grad_scores; ar.grad_deltas = grad_deltas;
+  const unsigned blocks = rcnn_row_blocks(d->B, d->S);
+  hipLaunchKernelGGL(gsr_rcnn::k_rcnn_count, dim3(1), dim3(gsr_rcnn::FIN_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rcnn_loss (count)");
+  hipLaunchKernelGGL(gsr_rcnn::k_rcnn_rows, dim3(blocks), dim3(gsr_rcnn::ROW_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rcnn_loss (rows)");
+  hipLaunchKernelGGL(gsr_rcnn::k_rcnn_final, dim3(1), dim3(gsr_rcnn::FIN_THREADS), 0, st, ar, blocks);
+  LAUNCH_CHECK("gsr_rcnn_loss (final)");
+  return GSR_OK;
+}
+
+int gsr_rcnn_postprocess(const GsrRcnnSpec* d, const float* scores, const float* deltas, const float* proposals, const int32_t* n_prop,
+                         void* ws, int64_t ws_bytes, float* dets, int32_t* counts, void* stream) {
+  if (int rc = rcnn_post_spec("gsr_rcnn_postprocess", d)) return rc;
+  if (!scores || !deltas || !proposals || !ws || !dets || !counts)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_postprocess: null scores / deltas / proposals / ws / dets / counts");
+  const RcnnWs w = rcnn_layout(d, false, true);
+  if (ws_bytes < (int64_t)w.post_bytes)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_postprocess: workspace of %lld bytes, %zu needed (gsr_rcnn_workspace_bytes)", (long long)ws_bytes,
+                   w.post_bytes);
+  if (((uintptr_t)ws & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_rcnn_postprocess: the workspace must be 16-byte aligned");
+  if ((((uintptr_t)scores | (uintptr_t)deltas | (uintptr_t)proposals | (uintptr_t)n_prop | (uintptr_t)dets | (uintptr_t)counts) & 3) != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_rcnn_postprocess: every tensor must be 4-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  gsr_rcnn::PostArgs ar;
+  rcnn_copy_spec(d, ar.sp);
+  ar.scores = scores; ar.deltas = deltas; ar.proposals = proposals; ar.n_prop = n_prop;
+  ar.boxes = reinterpret_cast<float*>(base + w.boxes);
+  ar.score = reinterpret_cast<float*>(base + w.score);
+  ar.cls = reinterpret_cast<int32_t*>(base + w.cls);
+  ar.ncand = reinterpret_cast<int32_t*>(base + w.ncand);
+  int32_t* keep = reinterpret_cast<int32_t*>(base + w.keep);
+  int32_t* nkept = reinterpret_cast<int32_t*>(base + w.nkept);
+  ar.keep = keep; ar.nkept = nkept; ar.dets = dets; ar.counts = counts;
+  hipLaunchKernelGGL(gsr_rcnn::k_rcnn_post, dim3((unsigned)d->B), dim3(gsr_rcnn::POST_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rcnn_postprocess (candidates)");
+  // gsr_det_nms's two launches on the compacted candidates: entries at or beyond ncand[b] do not take part
+  const DetWs nw = det_layout(d->B, d->R, d->R);
+  int32_t* order = reinterpret_cast<int32_t*>(base + w.nms + nw.order);
+  int32_t* nsel = reinterpret_cast<int32_t*>(base + w.nms + nw.ncand);
+  hipLaunchKernelGGL(gsr_detect::k_det_select_sort, dim3((unsigned)d->B), dim3(gsr_detect::SEL_THREADS), 0, st, d->R, d->R,
+                     (const float*)ar.score, 0, 0.0f, (const int32_t*)ar.ncand, order, nsel, (int32_t*)nullptr, 0);
+  LAUNCH_CHECK("gsr_rcnn_postprocess (select)");
+  gsr_detect::NmsArgs na;
+  na.sp = gsr_detect::Spec{};
+  na.sp.B = d->B; na.sp.A = d->R; na.sp.C = 1; na.sp.box_format = 1; na.sp.iou_thr = d->iou_thr; na.sp.max_candidates = d->R;
+  na.sp.max_det = d->max_det; na.sp.flags = 0u;
+  na.pred = nullptr; na.score = ar.score; na.cls = ar.cls; na.boxes = ar.boxes; na.order = order; na.ncand = nsel;
+  na.dets = nullptr; na.keep = keep; na.counts = nkept;
+  hipLaunchKernelGGL((gsr_detect::k_det_nms<false>), dim3((unsigned)d->B), dim3(gsr_detect::NMS_THREADS), 0, st, na);
+  LAUNCH_CHECK("gsr_rcnn_postprocess (nms)");
+  hipLaunchKernelGGL(gsr_rcnn::k_rcnn_gather, dim3((unsigned)d->B), dim3(256), 0, st, ar);
+  LAUNCH_CHECK("gsr_rcnn_postprocess (gather)");
   return GSR_OK;
 }
 

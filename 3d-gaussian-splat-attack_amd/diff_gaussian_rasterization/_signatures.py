@@ -78,6 +78,13 @@ SIGNATURES = {
     "gsr_setdet_workspace_bytes": (INT, _p(2)),
     "gsr_setdet_loss": (INT, _p(6) + (I64,) + _p(6)),
     "gsr_setdet_postprocess": (INT, _p(6)),
+    # ---- two-stage detector: sampler, RoIAlign, box-head loss, output
+    "gsr_rcnn_sample": (INT, _p(11)),
+    "gsr_roi_align": (INT, _p(4) + (I32,) + _p(2)),
+    "gsr_roi_align_backward": (INT, _p(3) + (I32,) + _p(2) + (I32, PTR)),
+    "gsr_rcnn_workspace_bytes": (INT, _p(2)),
+    "gsr_rcnn_loss": (INT, _p(8) + (I64,) + _p(4)),
+    "gsr_rcnn_postprocess": (INT, _p(6) + (I64,) + _p(3)),
     # ---- library state, profiling, test hooks
     "gsr_query": (INT, (I32, PTR)),
     "gsr_trim_pool": (None, ()),

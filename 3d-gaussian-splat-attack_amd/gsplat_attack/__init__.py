@@ -37,4 +37,8 @@ def __getattr__(name):
     if name in ("SetDetectorLoss", "SetDetectorOutput", "make_set_loss_fn"):
         from . import set_detector
         return getattr(set_detector, name)
+    # both sides of a two-stage (R-CNN-style) detector
+    if name in ("ProposalSampler", "RoIHeadLoss", "RoIHeadOutput", "make_roi_loss_fn"):
+        from . import roi_detector
+        return getattr(roi_detector, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

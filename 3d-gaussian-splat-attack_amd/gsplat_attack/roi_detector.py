@@ -1,0 +1,160 @@
+"""Both sides of a two-stage (R-CNN-style) detector, on the two-stage stage's HIP kernels
+(diff_gaussian_rasterization.rcnn_ops).  Such a detector runs a backbone to one feature map, takes proposals from a region
+proposer, pools every proposal with RoIAlign and hands the pooled features to a box head that emits C + 1 class scores
+(the last: background) and 4 box deltas per class for every RoI.
+
+The reference's default detector is Detectron2's Faster R-CNN in its C4 form (detectors/detectron2_detector.py): its
+infer() descends on loss_cls of 512 RoIs per image drawn by a host randperm, through a RoIAlign whose backward scatters
+with float atomics.  Here the sample is a keyed, fixed draw, RoIAlign's backward is a gather and the loss a fixed-order
+sum, so that a PGD step is bitwise reproducible from the loss back to the Gaussian parameters.  include/gsraster.h holds
+the formulas; INTEGRATION.md lists the stated deviations.
+
+  ProposalSampler   .sample(proposals, gt_boxes, gt_cls, seed=...) -> rcnn_ops.Sample
+  roi_align         (features, rois, counts, ...) -> pooled [B,S,Cf,PH,PW], differentiable with respect to the features
+  RoIHeadLoss       .loss(scores, deltas, sample, gt_boxes) -> (total, items[2] = cls, box)
+  RoIHeadOutput     .detect(scores, deltas, proposals) -> (dets, counts); .verdicts(...) on gsr_det_verdict
+  make_roi_loss_fn  renders -> detector_input -> backbone -> proposer (detached) -> sample -> roi_align -> box_head -> loss
+                    as pgd_attack's loss_fn; it takes the global view indices of the renders (loss_fn.takes_view_index)
+"""
+from __future__ import annotations
+
+from typing import Callable, Optional, Sequence, Tuple, Union
+
+import torch
+
+from diff_gaussian_rasterization import detect_ops, rcnn_ops
+from diff_gaussian_rasterization.rcnn_ops import RcnnSpec, Sample
+
+
+def _gt(gt_boxes, gt_cls, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[B,M,4] / [B,M], or [B,4] / [B]: one row per image; a row holding a NaN is absent."""
+    gb = torch.as_tensor(gt_boxes, dtype=torch.float32).to(device)
+    gc = torch.as_tensor(gt_cls).to(device=device, dtype=torch.int32)
+    if gb.dim() == 2:
+        gb, gc = gb[:, None, :], gc.reshape(-1, 1)
+    gc = torch.where(torch.isnan(gb).any(-1), torch.full_like(gc, -1), gc)
+    return torch.nan_to_num(gb, nan=0.0), gc
+
+
+class ProposalSampler:
+    """nc classes; per_image RoIs per image of which at most positive_fraction are foreground (Detectron2: 512, 0.25);
+    fg_iou: the IoU from which a candidate is foreground; append_gt: the ground-truth boxes are candidates too."""
+
+    def __init__(self, nc: int, per_image: int = 512, positive_fraction: float = 0.25, fg_iou: float = 0.5, append_gt: bool = True,
+                 seed: int = 0):
+        if not 1 <= nc <= rcnn_ops.MAX_CLASSES:
+            raise ValueError(f"ProposalSampler: nc must be 1..{rcnn_ops.MAX_CLASSES}")
+        if not 1 <= per_image <= rcnn_ops.MAX_SAMPLE:
+            raise ValueError(f"ProposalSampler: per_image must be 1..{rcnn_ops.MAX_SAMPLE}")
+        if not 0.0 <= positive_fraction <= 1.0:
+            raise ValueError("ProposalSampler: positive_fraction must be in [0, 1]")
+        self.nc = int(nc)
+        self.seed = int(seed)
+        self.spec = RcnnSpec(S=int(per_image), max_pos=int(per_image * positive_fraction), append_gt=bool(append_gt),
+                             fg_iou=float(fg_iou))
+
+    def sample(self, proposals: torch.Tensor, gt_boxes, gt_cls, seed: Optional[int] = None,
+               n_prop: Optional[torch.Tensor] = None) -> Sample:
+        """proposals [B,R,4] x1 y1 x2 y2 in pixels, in the proposer's order; gt_boxes [B,M,4] (or [B,4]); gt_cls [B,M] (or [B]),
+        negative: absent.  The same seed gives the same sample; pass a new one for a fresh draw."""
+        gb, gc = _gt(gt_boxes, gt_cls, proposals.device)
+        spec = self.spec._replace(seed=self.seed if seed is None else int(seed))
+        return rcnn_ops.sample(proposals, gb, gc, self.nc, spec, n_prop=n_prop)
+
+
+def roi_align(features: torch.Tensor, rois: torch.Tensor, counts: Optional[torch.Tensor] = None, output_size=(14, 14),
+              spatial_scale: float = 1.0 / 16.0, sampling_ratio: int = 0) -> torch.Tensor:
+    """Detectron2's ROIAlignV2 (aligned): features [B,Cf,Hf,Wf], rois [B,S,4] in image pixels, counts: a Sample's counts
+    (or int32 [B], or None: every row) -> pooled [B,S,Cf,PH,PW]; rows beyond the count are zero."""
+    ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
+    spec = RcnnSpec(PH=int(ph), PW=int(pw), spatial_scale=float(spatial_scale), sampling_ratio=int(sampling_ratio))
+    return rcnn_ops.roi_align(features, rois, counts, spec)
+
+
+class RoIHeadLoss:
+    """nc classes (the head emits nc + 1 scores per RoI); cls, box: the weights of the two terms -- the reference descends on
+    the classification term alone (1, 0); Detectron2's own sum is (1, 1)."""
+
+    def __init__(self, nc: int, cls: float = 1.0, box: float = 0.0, box_weights=(10.0, 10.0, 5.0, 5.0), beta: float = 0.0,
+                 class_agnostic: bool = False):
+        if not 1 <= nc <= rcnn_ops.MAX_CLASSES:
+            raise ValueError(f"RoIHeadLoss: nc must be 1..{rcnn_ops.MAX_CLASSES}")
+        vals = (cls, box, beta)
+        if not all(float(v) >= 0 and float(v) < float("inf") for v in vals):
+            raise ValueError("RoIHeadLoss: the weights and beta must be finite and >= 0")
+        self.nc = int(nc)
+        self.spec = RcnnSpec(w_cls=float(cls), w_box=float(box), box_weights=tuple(float(v) for v in box_weights), beta=float(beta),
+                             class_agnostic=bool(class_agnostic))
+
+    def loss(self, scores: torch.Tensor, deltas: torch.Tensor, sample: Sample, gt_boxes) -> Tuple[torch.Tensor, torch.Tensor]:
+        """scores [B,S,nc+1]; deltas [B,S,4*nc] (or [B,S,4]); sample: what ProposalSampler.sample returned; gt_boxes as given
+        to it -> (total, items[2] = cls, box unweighted)."""
+        if scores.dim() != 3 or scores.shape[2] != self.nc + 1:
+            raise ValueError(f"RoIHeadLoss: scores must be [B,S,{self.nc + 1}], got {tuple(scores.shape)}")
+        gb = torch.as_tensor(gt_boxes, dtype=torch.float32).to(scores.device)
+        if gb.dim() == 2:
+            gb = gb[:, None, :]
+        gb = torch.nan_to_num(gb, nan=0.0)
+        return rcnn_ops.rcnn_loss(scores, deltas, sample.rois, sample.labels, sample.gt_row, gb, self.spec)
+
+
+class RoIHeadOutput:
+    """frame = (img_w, img_h): the boxes are clipped to it; conf: the score a proposal must exceed (the reference: 0.5);
+    iou: the NMS threshold; max_det: rows per image (Detectron2: 100)."""
+
+    def __init__(self, frame: Tuple[float, float], conf: float = 0.5, iou: float = 0.5, max_det: int = 100,
+                 box_weights=(10.0, 10.0, 5.0, 5.0), class_agnostic: bool = False):
+        w, h = float(frame[0]), float(frame[1])
+        if not (w > 0 and h > 0):
+            raise ValueError("frame must be (img_w, img_h) with both > 0")
+        if not 1 <= max_det <= rcnn_ops.MAX_CAND:
+            raise ValueError(f"RoIHeadOutput: max_det must be 1..{rcnn_ops.MAX_CAND}")
+        self.spec = RcnnSpec(conf_thr=float(conf), iou_thr=float(iou), max_det=int(max_det), img_w=w, img_h=h,
+                             box_weights=tuple(float(v) for v in box_weights), class_agnostic=bool(class_agnostic))
+
+    def detect(self, scores: torch.Tensor, deltas: torch.Tensor, proposals: torch.Tensor,
+               n_prop: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (dets [B,min(max_det,R),6]: x1 y1 x2 y2 score class of the kept boxes, best first, zero rows beyond; counts int32
+        [B,2]: kept, candidates), both on the scores' device."""
+        return rcnn_ops.postprocess(scores, deltas, proposals, self.spec, n_prop=n_prop)
+
+    def verdicts(self, scores: torch.Tensor, deltas: torch.Tensor, proposals: torch.Tensor, gt_bboxes: Optional[torch.Tensor],
+                 target: int, untarget: Optional[int] = None, is_targeted: bool = True, iou_match: float = 0.5,
+                 n_prop: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """gt_bboxes [B,4] (x1 y1 x2 y2 in the frame; None or a NaN row: no box for that view)
+        -> (flags int32 [B] on the device: bit 0 success, bit 1 target_exists, bit 2 untarget_absent;
+            best [B,4]: iou, score, class, row of the detection closest to the gt box, -1 where there is none)."""
+        dets, counts = self.detect(scores, deltas, proposals, n_prop=n_prop)
+        gt = None if gt_bboxes is None else torch.as_tensor(gt_bboxes, dtype=torch.float32).to(dets.device)
+        return detect_ops.verdict(dets, counts, gt, target, untarget, is_targeted, iou_match)
+
+
+def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable, detector_input: Optional[Callable],
+                     sampler: ProposalSampler, head_loss: RoIHeadLoss, gt_bboxes, target: Union[int, Sequence[int]],
+                     output_size=(14, 14), spatial_scale: float = 1.0 / 16.0, sampling_ratio: int = 0) -> Callable:
+    """-> loss_fn(renders [B,3,H,W], idx=None) -> total, for pgd_attack(loss_fn=...).  backbone(images) -> features
+    [B,Cf,Hf,Wf]; proposer(features) -> proposals [B,R,4] in image pixels (taken detached, as Detectron2 does);
+    box_head(pooled [B*S,Cf,PH,PW]) -> (scores [B*S,nc+1], deltas [B*S,4*nc or 4]); gt_bboxes [V,4]: every view's box in the
+    frame of the detector's input; target: the class the loss pulls towards, one int or one per view; idx: the views the
+    renders show (default 0..B-1).  The sampler's seed is its own: every step draws the same RoIs for the same proposals."""
+    gt_all = torch.as_tensor(gt_bboxes, dtype=torch.float32)
+    tg_all = torch.as_tensor(target, dtype=torch.int32)
+
+    def loss_fn(renders: torch.Tensor, idx: Optional[Sequence[int]] = None) -> torch.Tensor:
+        x = renders[None] if renders.dim() == 3 else renders
+        ids = list(range(int(x.shape[0]))) if idx is None else [int(i) for i in idx]
+        if len(ids) != int(x.shape[0]):
+            raise ValueError(f"loss_fn: {len(ids)} view indices for {int(x.shape[0])} renders")
+        features = backbone(detector_input(x) if detector_input is not None else x)
+        with torch.no_grad():
+            proposals = proposer(features.detach())
+        gt = gt_all[ids]
+        cls = tg_all.expand(gt_all.shape[0])[ids] if tg_all.dim() == 0 else tg_all[ids]
+        smp = sampler.sample(proposals, gt, cls)
+        pooled = roi_align(features, smp.rois, smp.counts, output_size, spatial_scale, sampling_ratio)
+        B, S = int(pooled.shape[0]), int(pooled.shape[1])
+        scores, deltas = box_head(pooled.reshape(B * S, *pooled.shape[2:]))
+        return head_loss.loss(scores.reshape(B, S, -1), deltas.reshape(B, S, -1), smp, gt)[0]
+
+    loss_fn.takes_view_index = True
+    return loss_fn

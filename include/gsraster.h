@@ -821,17 +821,145 @@ int gsr_setdet_loss(const GsrSetDetSpec* spec, const float* logits, const float*
 int gsr_setdet_postprocess(const GsrSetDetSpec* spec, const float* logits, const float* boxes, float* dets, int32_t* counts,
                            void* stream);
 
+/* ---- Two-stage (R-CNN-style) detector stage: proposal sampler, RoIAlign, box-head loss, output ------------------------------
+ * The reference's default detector is Detectron2's Faster R-CNN in its C4 form (detectors/detectron2_detector.py with
+ * Base-RCNN-C4.yaml): Res5ROIHeads on one stride-16 feature map, a 14 x 14 aligned RoIAlign with adaptive sampling, and
+ * infer() descends on loss_cls alone.  Five entries carry what sits around the network's own layers: gsr_rcnn_sample
+ * (label_and_sample_proposals, made deterministic), gsr_roi_align and gsr_roi_align_backward (ROIAlignV2, the backward a
+ * gather), gsr_rcnn_loss (FastRCNNOutputLayers.losses with its gradient) and gsr_rcnn_postprocess (fast_rcnn_inference).
+ * The formulas below are the specification (written from the published Detectron2 sources; INTEGRATION.md lists the stated
+ * deviations); csrc/gsr_rcnn.h holds the arithmetic, compiled for the kernels and for a host harness alike.  All
+ * arithmetic is float32, every operation rounded on its own; index-valued results are int32.  One GsrRcnnSpec serves all
+ * entries; each checks the members it names below and ignores the others.  Proposals are an input: the RPN's own proposal
+ * generation, the RPN losses, FPN level assignment and masks are not part of this stage.
+ *
+ * gsr_rcnn_sample (members B, R, M, S, C, max_pos, append_gt, seed, fg_iou).  proposals [B,R,4]: x1 y1 x2 y2 in pixels, in
+ * the proposer's order; n_prop [B] int32 or NULL (= R; clamped to 0..R); gt_boxes [B,M,4]; gt_cls [B,M] int32, a row being
+ * PRESENT iff 0 <= gt_cls < C as in the other stages.  1 <= M <= 32, 1 <= S <= 1024 (Detectron2: 512), 0 <= max_pos <= S
+ * (Detectron2: 128), R >= 1, R + M <= 4096, 1 <= C <= 1024.
+ *   Candidates.  Candidate i < R is proposal i, valid iff i < n_prop[b]; with append_gt != 0 (Detectron2: on) candidate
+ *   R + m is ground-truth row m, valid iff the row is present.
+ *   IoU of a candidate against row m (Detectron2's pairwise_iou): areas and intersection as in gsr_det_box_iou,
+ *       iou = inter > 0 ? inter / ((area_a + area_b) - inter) : 0
+ *   Match: the first maximum over the present rows in ascending m (the lowest m wins ties; a NaN is never the maximum).  The
+ *   candidate is FOREGROUND iff that maximum is >= fg_iou (non-strict, as Matcher is; Detectron2: 0.5) and then has its
+ *   row's class; every other valid candidate -- all of them when no row is present -- is BACKGROUND, class C.
+ *   Quota.  n_pos = min(#foreground, max_pos);  n_neg = min(#background, S - n_pos).
+ *   Choice.  Where Detectron2 draws a randperm, each kind is ordered by (key, i) ascending and its first n_pos / n_neg taken:
+ *       mix32(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16        (uint32)
+ *       key(b, i) = mix32(mix32(seed ^ (uint32)b * 0x9E3779B9) + (uint32)i)
+ *   The same seed gives the same sample on every run; a caller who wants a fresh draw per step changes seed.
+ *   Outputs, the taken candidates in ASCENDING CANDIDATE INDEX: idx [B,S] (-1 beyond the count), rois [B,S,4] (the gathered
+ *   boxes, zero rows beyond), labels [B,S] (the class, C for background, -1 beyond), gt_row [B,S] (the matched row, -1 for
+ *   background and beyond), counts [B,2] = (taken, foreground taken).  Every element of every output is written.  With NaN
+ *   boxes the result is unspecified, but every index stays in range and every loop ends.  One launch, one workgroup per image.
+ *
+ * gsr_roi_align (members B, S, Cf, Hf, Wf, PH, PW, spatial_scale, sampling_ratio): ROIAlignV2, aligned = True.
+ * features [B,Cf,Hf,Wf]; rois [B,S,4] in image pixels; n_roi: NULL (= S) or int32, image b's count at
+ * n_roi[b * n_roi_stride] (clamped to 0..S; gsr_rcnn_sample's counts with stride 2); pooled [B,S,Cf,PH,PW].
+ * 1 <= B, Cf <= 65535, 1 <= S <= 1024, 1 <= PH, PW <= 14, sampling_ratio >= 0, spatial_scale finite and > 0 (the C4 model:
+ * 1/16).  Per axis (x shown):
+ *       start = x1 * scale - 0.5f;  end = x2 * scale - 0.5f;  len = end - start  (no clamp to 1);  bin = len / PW
+ *       grid = sampling_ratio > 0 ? sampling_ratio : ceil(len / PW), clamped to 0..16
+ *   count = max(grid_h * grid_w, 1).  Sample (iy, ix) of bin (ph, pw): y = start_h + ph * bin_h + (iy + 0.5f) * bin_h / grid_h,
+ *   x alike.  The bilinear read is 0 when y < -1 || y > Hf || x < -1 || x > Wf; otherwise y = max(y, 0), y_low = (int)y; if
+ *   y_low >= Hf - 1 both rows are Hf - 1 and y = y_low; ly = y - y_low, hy = 1 - ly (x alike) and the value is
+ *   hy*hx*v1 + hy*lx*v2 + ly*hx*v3 + ly*lx*v4.  pooled = (the sum over the bin's samples in (iy, ix) order) / count.  Rows
+ *   at or beyond n_roi[b] and RoIs holding a non-finite coordinate give zeros; every element of pooled is written.  The
+ *   clamp of grid at 16 is a stated deviation (reached only by a RoI longer than 16 * PW feature cells).  One launch.
+ *
+ * gsr_roi_align_backward: grad_features [B,Cf,Hf,Wf] from grad_pooled [B,S,Cf,PH,PW]; nothing flows to the RoIs (Detectron2
+ * detaches proposals).  A gather, no float atomics: with wy[ph][y] = the sum, in sample order, of the shares hy / ly that
+ * the samples of bin ph give row y (wx alike),
+ *       grad_features[b,c,y,x] = sum over RoIs s ascending of
+ *                                (sum over ph ascending, then pw ascending, of (wy[ph][y] * wx[pw][x]) * grad_pooled[b,s,c,ph,pw]) / count_s
+ *   an order fixed by the sizes and the RoI values alone: two calls on the same input give the same bits, on any stream.
+ *   Every element is written exactly once; with accumulate != 0 the sum is added to what is there, as
+ *   gsr_image_resample_backward does.  One launch.
+ *
+ * gsr_rcnn_loss (members B, S, C, M, bw_*, beta, w_cls, w_box, flags).  scores [B,S,C+1] (channel C: background);
+ * deltas [B,S,4*C], or [B,S,4] with GSR_RCNN_CLASS_AGNOSTIC; rois, labels, gt_row as the sampler wrote them; gt_boxes
+ * [B,M,4].  Rows with label -1 take no part (a label above C counts as -1); n = max(rows with label >= 0 in the batch, 1).
+ *       cls = sum_rows -(x_t - max - log(sum exp(x - max))) / n
+ *       target deltas of a foreground row (label < C, 0 <= gt_row < M; Box2BoxTransform.get_deltas, src = roi, dst = gt):
+ *           sw = x2 - x1, scx = x1 + 0.5f * sw (dst alike);  tx = bw_x * (dcx - scx) / sw;  tw = bw_w * log(dw / sw);  y, h alike
+ *       box = sum_fg sum_4 smooth_l1(delta[4*cls + k] - t_k, beta) / n
+ *             beta = 0 (Detectron2): |x| with sign(0) = 0;  beta > 0: 0.5 x^2 / beta where |x| < beta, |x| - 0.5 beta elsewhere
+ *       total = w_cls * cls + w_box * box                        (Detectron2: bw = 10, 10, 5, 5; the reference descends on cls)
+ *   loss[3] = (cls, box, total), the first two unweighted.  grad_scores = (w_cls / n) * (p_c - [c == t]), zero on rows that
+ *   take no part; grad_deltas is zero except in the four channels of a foreground row's class, (w_box / n) * smooth_l1'.
+ *   Either may be NULL (the loss bits are the same either way); when given, every element is written exactly once.  A
+ *   foreground row has IoU >= fg_iou > 0 with its box, hence sw, sh > 0.  Sums: per-row terms, four rows per block, the
+ *   blocks' partials added by one block in index order (per-thread runs, an LDS tree).  ws: gsr_rcnn_workspace_bytes(spec)
+ *   bytes of device memory, 16-byte aligned.  Three launches.
+ *
+ * gsr_rcnn_postprocess (members B, R, C, bw_*, conf_thr, iou_thr, max_det, img_w, img_h, flags): fast_rcnn_inference.
+ * scores [B,R,C+1], deltas [B,R,4*C] (or [B,R,4]), proposals [B,R,4], n_prop as above; 1 <= R <= 4096, 1 <= max_det <= R.
+ * Per proposal p = softmax(scores); the class is the first maximum of p_c over c < C (a NaN is never the maximum), the score
+ * that maximum; the proposal is a candidate iff score > conf_thr (the reference: 0.5; a softmax has at most one entry above
+ * 0.5, so from 0.5 up this is Detectron2's per-class filter; below, one label per proposal is a stated deviation).  Box
+ * (Box2BoxTransform.apply_deltas on the class's four deltas, w = x2 - x1, cx = x1 + 0.5f * w of the proposal):
+ *       dx = d0 / bw_x;  dw = min(d2 / bw_w, log(1000 / 16));  pcx = dx * w + cx;  pw = exp(dw) * w
+ *       x1' = pcx - 0.5f * pw, x2' = pcx + 0.5f * pw, clipped to [0, img_w]; y alike with [0, img_h]
+ * A candidate with a non-finite box is dropped.  counts[b,1] = the candidates.  They are compacted in proposal order and
+ * walked by gsr_det_nms's kernels (class-aware, iou_thr -- Detectron2: 0.5 --, max_det -- 100): score descending, then
+ * proposal order.  dets [B,max_det,6] (x1 y1 x2 y2 score class-as-float, zero rows beyond) and counts [B,2] (kept,
+ * candidates): the layout gsr_det_verdict reads.  ws as above.  Four launches.
+ *
+ * All entries: every tensor argument is a DEVICE pointer.  A size out of range, a non-finite or negative weight, beta, fg_iou
+ * or threshold, box weights or a frame that are not finite and > 0, unknown flags, a workspace that is too small or
+ * misaligned, a NULL required pointer, a tensor that is not 4-byte aligned or more than 2^31 - 1 elements in a tensor
+ * return GSR_ERR_INVALID with a gsr_last_error text before any device call.  No allocation, no copy, no host
+ * synchronisation: everything is enqueued on `stream`; capturable and re-entrant (each caller with its own workspace). */
+#define GSR_RCNN_CLASS_AGNOSTIC 1u
+typedef struct GsrRcnnSpec {
+  int32_t B, R, M, S, C;     /* images, proposals per image, gt rows (1..32), sampled RoIs (1..1024), classes without background */
+  int32_t max_pos;           /* sampler: foreground quota, 0..S; Detectron2: 128 */
+  int32_t append_gt;         /* sampler: ground-truth rows are candidates; Detectron2: 1 */
+  uint32_t seed;             /* sampler */
+  float   fg_iou;            /* sampler; Detectron2: 0.5 */
+  int32_t Cf, Hf, Wf;        /* RoIAlign: the feature map */
+  int32_t PH, PW;            /* RoIAlign: 1..14 */
+  float   spatial_scale;     /* RoIAlign; the C4 model: 1/16 */
+  int32_t sampling_ratio;    /* RoIAlign: 0 = adaptive */
+  float   bw_x, bw_y, bw_w, bw_h; /* Box2BoxTransform weights; Detectron2: 10, 10, 5, 5 */
+  float   beta;              /* loss: smooth-L1 beta; Detectron2: 0 */
+  float   w_cls, w_box;      /* loss weights; the reference descends on cls alone: 1, 0 */
+  float   conf_thr, iou_thr; /* output; the reference: 0.5, 0.5 */
+  int32_t max_det;           /* output: rows of dets per image, 1..R; Detectron2: 100 */
+  float   img_w, img_h;      /* output: boxes are clipped to this frame */
+  uint32_t flags;            /* GSR_RCNN_CLASS_AGNOSTIC */
+} GsrRcnnSpec;
+int gsr_rcnn_sample(const GsrRcnnSpec* spec, const float* proposals, const int32_t* n_prop, const float* gt_boxes,
+                    const int32_t* gt_cls, int32_t* idx, float* rois, int32_t* labels, int32_t* gt_row, int32_t* counts,
+                    void* stream);
+int gsr_roi_align(const GsrRcnnSpec* spec, const float* features, const float* rois, const int32_t* n_roi,
+                  int32_t n_roi_stride, float* pooled, void* stream);
+int gsr_roi_align_backward(const GsrRcnnSpec* spec, const float* rois, const int32_t* n_roi, int32_t n_roi_stride,
+                           const float* grad_pooled, float* grad_features, int32_t accumulate, void* stream);
+int gsr_rcnn_workspace_bytes(const GsrRcnnSpec* spec, int64_t* bytes);
+int gsr_rcnn_loss(const GsrRcnnSpec* spec, const float* scores, const float* deltas, const float* rois, const int32_t* labels,
+                  const int32_t* gt_row, const float* gt_boxes, void* ws, int64_t ws_bytes, float* loss, float* grad_scores,
+                  float* grad_deltas, void* stream);
+int gsr_rcnn_postprocess(const GsrRcnnSpec* spec, const float* scores, const float* deltas, const float* proposals,
+                         const int32_t* n_prop, void* ws, int64_t ws_bytes, float* dets, int32_t* counts, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
  * (gsr_image_resample, gsr_image_resample_backward, gsr_image_to_u8); GSR_CAP_DETECT = the detector output stage
  * (gsr_det_workspace_bytes, gsr_det_postprocess, gsr_det_nms, gsr_det_box_iou, gsr_det_verdict); GSR_CAP_DETLOSS = the
  * detector loss stage (gsr_detloss_workspace_bytes, gsr_detloss); GSR_CAP_SETDET = the set-prediction detector stage
- * (gsr_setdet_workspace_bytes, gsr_setdet_loss, gsr_setdet_postprocess). */
+ * (gsr_setdet_workspace_bytes, gsr_setdet_loss, gsr_setdet_postprocess).  Item 3 is closed at these four bits: callers
+ * compare its value as a whole, so a build with later stages still reports 15 there;
+ * 4 every capability bit of this build: the four above and the later ones.  GSR_CAP_RCNN = the two-stage detector stage
+ * (gsr_rcnn_sample, gsr_roi_align, gsr_roi_align_backward, gsr_rcnn_workspace_bytes, gsr_rcnn_loss, gsr_rcnn_postprocess).
+ * A library that predates item 4 answers it with GSR_ERR_INVALID: no later stage. */
 #define GSR_CAP_IMAGE 1
 #define GSR_CAP_DETECT 2
 #define GSR_CAP_DETLOSS 4
 #define GSR_CAP_SETDET 8
+#define GSR_CAP_RCNN 16
 int gsr_query(int32_t what, int64_t* out);
 
 /* Per-context numbers for roofline accounting: what 0 = num_rendered (N; waits for the forward's count if it was
