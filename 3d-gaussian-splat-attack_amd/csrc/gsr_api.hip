@@ -2032,24 +2032,8 @@ int gsr_knn_dist2(const float* points, int32_t P, float* mean_dist2, void* strea
   pool_free(dev, bb_blk);
   if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "gsr_knn_dist2: bounding box: %s", hipGetErrorString(e));
   // ---- grid: about three points per cell, at most 256 cells per axis ---------------------------------------------
-  double ext[3], vol = 1.0, emax = 0.0;
-  for (int a = 0; a < 3; ++a) { ext[a] = (double)host_bb[3 + a] - (double)host_bb[a]; emax = std::max(emax, ext[a]); }
-  if (!(emax > 0.0)) emax = 1.0;                       // all points coincide
-  for (int a = 0; a < 3; ++a) { ext[a] = std::max(ext[a], 1e-6 * emax); vol *= ext[a]; }
-  const double cell = std::cbrt(vol * 3.0 / (double)P);
-  KnnGrid g;
-  int dims[3];
-  float inv[3], size[3];
-  for (int a = 0; a < 3; ++a) {
-    dims[a] = (int)std::min(256.0, std::max(1.0, std::ceil(ext[a] / cell)));
-    const double c = ext[a] / dims[a];
-    inv[a] = (float)(1.0 / c);
-    size[a] = (float)c;
-  }
-  g.minx = host_bb[0]; g.miny = host_bb[1]; g.minz = host_bb[2];
-  g.inv_cx = inv[0]; g.inv_cy = inv[1]; g.inv_cz = inv[2];
-  g.sx = size[0]; g.sy = size[1]; g.sz = size[2]; g.dx = dims[0]; g.dy = dims[1]; g.dz = dims[2];
-  const uint32_t ncells = (uint32_t)dims[0] * dims[1] * dims[2];
+  const KnnGrid g = knn_make_grid(host_bb, P);   // gsr_knn.h
+  const uint32_t ncells = (uint32_t)g.dx * g.dy * g.dz;
   // ---- workspace -----------------------------------------------------------------------------------------------
   const size_t words = (size_t)4 * n + tbl + RS_BINS + 2 * (size_t)ncells + 64;
   void* blk = pool_alloc(dev, sizeof(uint32_t) * words, st);

@@ -4,6 +4,8 @@ scene/gaussian_model.py:17; called at :144 in create_from_pcd to seed the initia
 On a HIP device it calls ``gsr_knn_dist2`` of libgsraster.so (uniform-grid exact 3-NN, csrc/gsr_knn.hip.h).  CPU tensors
 -- which the reference never passes, its name says so -- get a chunked torch.cdist evaluation of the same definition,
 so that a GaussianModel-style container can be exercised in CPU-only unit tests; that branch is not on the raster path.
+With fewer than 4 points both branches follow the kernel's contract (csrc/gsr_knn.h): a missing neighbour counts as FLT_MAX,
+summed and divided in float32 -- +inf for P <= 2, FLT_MAX / 3 for P = 3 -- so create_from_pcd gives the same scales on either.
 """
 import torch
 
@@ -16,7 +18,11 @@ def _dist2_torch(pts: torch.Tensor) -> torch.Tensor:
     for s in range(0, P, chunk):
         d2 = torch.cdist(pts[s:s + chunk], pts).square_()
         near = torch.topk(d2, k, dim=1, largest=False).values[:, 1:]
-        out[s:s + chunk] = near.mean(dim=1) if near.shape[1] else 0.0
+        if k < 4:   # the kernel's contract (csrc/gsr_knn.h): a missing neighbour counts as FLT_MAX, summed and divided in float32
+            near = torch.cat([near, near.new_full((near.shape[0], 4 - k), torch.finfo(torch.float32).max)], dim=1)
+            out[s:s + chunk] = (near[:, 0] + near[:, 1] + near[:, 2]) / 3.0
+        else:
+            out[s:s + chunk] = near.mean(dim=1)
     return out
 
 

@@ -480,7 +480,11 @@ int gsr_pgd_step_multi(int32_t n, float* const* x, const float* const* grad, con
 /* Mean squared distance of every point to its 3 nearest other points (exact): replaces the reference's second native
  * import, simple_knn._C.distCUDA2 (reference scene/gaussian_model.py:17, called at :144 to seed the initial scales).
  * points [P,3] float32 device, mean_dist2 [P] float32 device.  Synchronises the stream once (scene set-up routine, not
- * part of the per-view path).  With fewer than 4 points the missing neighbours count as FLT_MAX, like the original. */
+ * part of the per-view path).  With fewer than 4 points the missing neighbours count as FLT_MAX, like the original:
+ * the sum and the division are float32, so P <= 2 gives +inf and P = 3 gives (d0 + d1 + FLT_MAX) / 3.  A point with a
+ * NaN or an infinite coordinate gets +inf and is no neighbour of any other point (csrc/gsr_knn.h).  Known limit: the
+ * grid is uniform over the bounding box, so one far (or infinite) point puts the rest into a few cells and the search
+ * turns quadratic in the points that share a cell; exact still, run time not measured. */
 int gsr_knn_dist2(const float* points, int32_t P, float* mean_dist2, void* stream);
 
 /* ---- groups set-up (C ABI 603) -----------------------------------------------------------------------------------
