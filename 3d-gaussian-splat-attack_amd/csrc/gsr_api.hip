@@ -1944,7 +1944,7 @@ int gsr_pgd_step(float* x, const float* grad, const float* x0, int64_t rows, int
     hipLaunchKernelGGL((k_pgd_step<false>), dim3(blocks), dim3(64), 0, st, x, grad, x0, (size_t)rows, cols, alpha, epsilon,
                        (const double*)nullptr, 0);
   } else {
-    const int nb = (int)std::min<size_t>((n + 4095) / 4096, 1024);
+    const int nb = pgd_sumsq_blocks(n);
     void* blk = pool_alloc(dev, sizeof(double) * (size_t)nb, st);
     if (!blk) return set_err(GSR_ERR_NOMEM, "gsr_pgd_step: allocation failed");
     double* partial = static_cast<double*>(blk);
@@ -1983,7 +1983,7 @@ int gsr_pgd_step_multi(int32_t n, float* const* x, const float* const* grad, con
     if (l2 && rows[t] > 0) {
       if (sumsq && sumsq[t]) { m.partial[t] = sumsq[t]; m.nb[t] = 1; }
       else {
-        m.nb[t] = (int)std::min<size_t>(((size_t)rows[t] * (size_t)cols[t] + 4095) / 4096, 1024);
+        m.nb[t] = pgd_sumsq_blocks((size_t)rows[t] * (size_t)cols[t]);
         need += (size_t)m.nb[t];
       }
     }

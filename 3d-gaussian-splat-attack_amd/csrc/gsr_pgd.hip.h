@@ -12,14 +12,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace gsr {
+#include "gsr_pgd.h"   // the scalar source (shared with tests/host_math/pgd_host.cpp) and the non-finite / range contract
 
-constexpr int PGD_MAX_COLS = 48;
-// Rows per wave: 64 for narrow rows; 32 for rows wider than PGD_NARROW floats, so that a wave's deltas take 6 KB of LDS
-// instead of 12 and 16 waves fit a CU where 12 did (the kernel is bandwidth-bound: more waves = more loads in flight).
-constexpr int PGD_NARROW = 24;
-constexpr int PGD_LDS_FLOATS = 64 * PGD_NARROW > 32 * PGD_MAX_COLS ? 64 * PGD_NARROW : 32 * PGD_MAX_COLS;
-__host__ __device__ inline int pgd_rows_per_wave(int cols) { return cols > PGD_NARROW ? 32 : 64; }
+namespace gsr {
 
 // per-block partial sums of squares (float per thread, double across the block: the order is fixed => reproducible).
 // 16-byte loads when the tensor starts on a 16-byte boundary (n / 4 float4 + a scalar tail), 4-byte loads otherwise.
@@ -59,25 +54,22 @@ __device__ __forceinline__ void pgd_step_wave(float* __restrict__ x, const float
   const size_t base = r0 * (size_t)cols;
   const int n = nr * cols;
   const bool vec = nr == rpw && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x0)) & 15u) == 0u;
-  float scale = 0.f;                            // alpha / ||g||  (0 when the gradient is zero: no step)
+  float scale = 0.f;                            // alpha / ||g||  (0 when the norm is zero or NaN: no step)
   if (L2) {
     double t = 0.0;
     for (int i = lane; i < nb; i += 64) t += partial[i];
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) t += __shfl_xor(t, s, 64);
-    const float nrm = sqrtf((float)t);
-    scale = nrm > 0.f ? alpha / nrm : 0.f;
+    scale = pgd_l2_scale(t, alpha);
   }
   auto upd = [&](float xv, float gv, float ov, float& dlt) -> float {
     if (L2) {
-      const float xn = fmaf(-scale, gv, xv);
+      const float xn = pgd_l2_move(xv, gv, scale);
       dlt = xn - ov;
       return xn;
     }
-    const float sg = gv > 0.f ? 1.f : (gv < 0.f ? -1.f : 0.f);        // torch.sign (NaN -> NaN is not reproduced: 0)
-    const float xn = fmaf(-alpha, sg, xv);
     dlt = 0.f;
-    return fminf(fmaxf(xn - ov, -eps), eps) + ov;
+    return pgd_linf_update(xv, gv, ov, alpha, eps);
   };
   if (vec) {
     const int n4 = n >> 2;                      // 16 * cols
@@ -107,9 +99,8 @@ __device__ __forceinline__ void pgd_step_wave(float* __restrict__ x, const float
   float f = 1.f;
   if (lane < nr) {
     float ss = 0.f;
-    for (int c = 0; c < cols; ++c) { const float d = sd[lane * cols + c]; ss = fmaf(d, d, ss); }
-    const float nrm = sqrtf(ss);
-    if (nrm > eps) f = eps / (nrm + 1e-7f);
+    for (int c = 0; c < cols; ++c) ss = pgd_row_accum(sd[lane * cols + c], ss);
+    f = pgd_row_factor(sqrtf(ss), eps);
   }
   // Row r's factor is parked in LDS and read per element.  (A cross-lane read of lane r's register inside the loop
   // below would return 0 for rows whose owner lane has already left the loop in the last, partial iteration:
@@ -127,14 +118,14 @@ __device__ __forceinline__ void pgd_step_wave(float* __restrict__ x, const float
       const float4 ov = o4[i], d = sd4[i];
       const int e = 4 * i;
       float4 r;
-      r.x = fmaf(d.x, sf[e / cols], ov.x); r.y = fmaf(d.y, sf[(e + 1) / cols], ov.y);
-      r.z = fmaf(d.z, sf[(e + 2) / cols], ov.z); r.w = fmaf(d.w, sf[(e + 3) / cols], ov.w);
+      r.x = pgd_l2_result(d.x, sf[e / cols], ov.x); r.y = pgd_l2_result(d.y, sf[(e + 1) / cols], ov.y);
+      r.z = pgd_l2_result(d.z, sf[(e + 2) / cols], ov.z); r.w = pgd_l2_result(d.w, sf[(e + 3) / cols], ov.w);
       xo4[i] = r;
     }
   } else {
     for (int i = lane; i < n; i += 64) {
       const int r = i / cols;
-      x[base + i] = fmaf(sd[i], sf[r], x0[base + i]);
+      x[base + i] = pgd_l2_result(sd[i], sf[r], x0[base + i]);
     }
   }
 }
@@ -150,7 +141,6 @@ __global__ void __launch_bounds__(64) k_pgd_step(float* __restrict__ x, const fl
 // iteration, each a bandwidth-bound launch of a few tens of microseconds whose tail and whose successor's ramp-up are
 // not covered by anything on the stream.  Workgroup b belongs to the tensor t with first[t] <= b < first[t + 1]; the
 // arithmetic per tensor is pgd_step_wave's, so the result is bit for bit that of the per-tensor launches.
-constexpr int PGD_MAX_TENSORS = 8;
 struct PgdMulti {
   float* x[PGD_MAX_TENSORS];
   const float* g[PGD_MAX_TENSORS];
@@ -167,9 +157,7 @@ struct PgdMulti {
 
 template <bool L2>
 __global__ void __launch_bounds__(64) k_pgd_step_multi(PgdMulti m) {
-  int t = 0;
-#pragma unroll
-  for (int i = 1; i < PGD_MAX_TENSORS; ++i) t += (i < m.n && blockIdx.x >= m.first[i]) ? 1 : 0;
+  const int t = pgd_tensor_of_block(m.first, m.n, blockIdx.x);
   pgd_step_wave<L2>(m.x[t], m.g[t], m.x0[t], (size_t)m.rows[t], m.cols[t], m.alpha[t], m.eps[t], m.partial[t], m.nb[t],
                     blockIdx.x - m.first[t]);
 }

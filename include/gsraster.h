@@ -446,6 +446,16 @@ int gsr_mark_visible(const GsrSettings* settings, int32_t P, const float* means3
  * [P,45] and once for _features_dc [P,3]).  l2 == 0: x += -alpha*sign(grad); x = clamp(x - x0, -eps, eps) + x0.
  * l2 != 0: x += -alpha*grad/||grad||_2 with the norm over the whole tensor (no step when it is 0), then every ROW of
  * x - x0 longer than eps is scaled by eps/(norm + 1e-7) (torch.renorm(p=2, dim=0, maxnorm=eps)).  cols <= 48.
+ * A row exactly eps long is not scaled.  Only x is written; grad and x0 are read.
+ * Non-finite and out-of-range inputs follow the tensor formulation (gsplat_attack/pgd.py on the CPU; csrc/gsr_pgd.h has
+ * the full list): sign(NaN) = 0; a NaN in x or x0 comes out NaN at that element under both rules, and under L2 its row
+ * is not scaled; an infinite x or x0 element gives x0 +- eps resp. +-inf under L-inf, and under L2 NaN at that element
+ * and x0 in the rest of its row.  L2: a NaN gradient element or a NaN sum of squares means NO step for the whole tensor
+ * (the projection still runs); an infinite gradient element means no step at the finite elements and NaN at that one.
+ * The norm is a float32 and the squares are summed in float32 per thread: gradients of magnitude <= 1e-23 (every square
+ * underflows) or >= 1e19 on 12 elements or more (the sum overflows) lose the L2 step, x stays finite; squares that are
+ * float32 denormals (|grad| below about 1e-19) make the step's length approximate.  A sum handed in as a double
+ * (gsr_pgd_step_normed, sumsq[] of gsr_pgd_step_multi) is used down to a norm of FLT_MIN.  eps = 0 returns x0.
  */
 int gsr_pgd_step(float* x, const float* grad, const float* x0, int64_t rows, int32_t cols, float alpha, float epsilon,
                  int32_t l2, void* stream);
