@@ -1718,6 +1718,79 @@ static int backward_impl(GsrCtx* c, const BwdCall& b) {
   return done(GSR_OK);
 }
 
+// ---- what the four detector stages' entries (further down) share.  A stage states the regions of its workspace once, as a run of take()
+// calls on a Carve: with no base that run is the sizing pass (off ends as the bytes needed), with the caller's workspace
+// it hands out the pointers -- so *_workspace_bytes and the entry point cannot drift apart.
+static inline size_t det_round(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct Carve {
+  char* base;
+  size_t off = 0;
+  explicit Carve(void* ws = nullptr) : base(static_cast<char*>(ws)) {}
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += det_round(count * sizeof(T));
+    return p;
+  }
+};
+
+// the caller's workspace holds `need` bytes and starts on an `align`-byte boundary; sizer: the call that gives `need`
+static int check_workspace(const char* fn, const void* ws, int64_t ws_bytes, size_t need, unsigned align, const char* sizer) {
+  if (ws_bytes < (int64_t)need)
+    return set_err(GSR_ERR_INVALID, "%s: workspace of %lld bytes, %zu needed (%s)", fn, (long long)ws_bytes, need, sizer);
+  if (((uintptr_t)ws & (uintptr_t)(align - 1)) != 0)
+    return set_err(GSR_ERR_INVALID, "%s: the workspace must be %u-byte aligned", fn, align);
+  return GSR_OK;
+}
+
+// null pointers (optional tensors) pass
+template <class... P>
+static int check_aligned4(const char* fn, const P*... p) {
+  if (((... | (uintptr_t)p) & 3) != 0) return set_err(GSR_ERR_INVALID, "%s: every tensor must be 4-byte aligned", fn);
+  return GSR_OK;
+}
+
+static bool finite_pos(float v) { return v > 0.0f && v <= 3.0e38f; }       // false for a NaN
+static bool finite_nonneg(float v) { return v >= 0.0f && v <= 3.0e38f; }
+static bool all_finite_nonneg(std::initializer_list<float> v) { return std::all_of(v.begin(), v.end(), finite_nonneg); }
+
+struct DetWs {
+  float* score;
+  int32_t *cls, *order, *ncand;
+};
+
+static DetWs det_regions(Carve& c, long long B, long long A, long long maxc) {
+  DetWs w;
+  w.score = c.take<float>((size_t)(B * A));
+  w.cls = c.take<int32_t>((size_t)(B * A));
+  w.order = c.take<int32_t>((size_t)(B * maxc));
+  w.ncand = c.take<int32_t>((size_t)B);
+  return w;
+}
+
+// The NMS walk over B rows of n boxes (x1 y1 x2 y2): the select-sort by score of the rows below n_valid[b] (NULL: all n),
+// then the greedy walk writes keep [B, max_det] and counts.  w: det_regions(B, n, n); fn: the entry, for the error text.
+static int launch_nms_walk(const char* fn, int32_t B, int32_t n, const float* boxes, const float* scores, const int32_t* classes,
+                           const int32_t* n_valid, float iou_thr, int32_t max_det, const DetWs& w, int32_t* keep, int32_t* counts,
+                           hipStream_t st) {
+  char stage[64];
+  hipLaunchKernelGGL(gsr_detect::k_det_select_sort, dim3((unsigned)B), dim3(gsr_detect::SEL_THREADS), 0, st, n, n, scores, 0, 0.0f,
+                     n_valid, w.order, w.ncand, (int32_t*)nullptr, 0);
+  snprintf(stage, sizeof(stage), "%s (select)", fn);
+  LAUNCH_CHECK(stage);
+  gsr_detect::NmsArgs na;
+  na.sp = gsr_detect::Spec{};
+  na.sp.B = B; na.sp.A = n; na.sp.C = 1; na.sp.box_format = 1; na.sp.iou_thr = iou_thr; na.sp.max_candidates = n; na.sp.max_det = max_det;
+  na.sp.flags = classes ? 0u : gsr_detect::CLASS_AGNOSTIC;
+  na.pred = nullptr; na.score = scores; na.cls = classes; na.boxes = boxes; na.order = w.order; na.ncand = w.ncand;
+  na.dets = nullptr; na.keep = keep; na.counts = counts;
+  hipLaunchKernelGGL((gsr_detect::k_det_nms<false>), dim3((unsigned)B), dim3(gsr_detect::NMS_THREADS), 0, st, na);
+  snprintf(stage, sizeof(stage), "%s (nms)", fn);
+  LAUNCH_CHECK(stage);
+  return GSR_OK;
+}
+
 extern "C" {
 
 int gsr_backward(GsrCtx* c, const float* grad_color, const float* grad_objects, float* dmeans3D, float* dmeans2D,
@@ -2213,22 +2286,6 @@ int gsr_image_to_u8(const float* src, int32_t B, int32_t H, int32_t W, uint8_t* 
 // ---- detector output stage (gsr_detect.h / gsr_detect.hip.h): no allocation, no copy, no host wait; everything is
 // checked on the host before the first launch.  Workspace: [score B*A f32][class B*A i32][order B*maxc i32][ncand B i32],
 // each region rounded up to 256 bytes.
-static inline size_t det_round(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct DetWs {
-  size_t score, cls, order, ncand, bytes;
-};
-
-static DetWs det_layout(long long B, long long A, long long maxc) {
-  DetWs w;
-  w.score = 0;
-  w.cls = w.score + det_round((size_t)(B * A) * 4);
-  w.order = w.cls + det_round((size_t)(B * A) * 4);
-  w.ncand = w.order + det_round((size_t)(B * maxc) * 4);
-  w.bytes = w.ncand + det_round((size_t)B * 4);
-  return w;
-}
-
 static int det_spec(const char* fn, const GsrDetSpec* d, gsr_detect::Spec& sp) {
   if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
   if (d->B < 1 || d->A < 1 || d->C < 1) return set_err(GSR_ERR_INVALID, "%s: sizes must be >= 1 (B=%d A=%d C=%d)", fn, d->B, d->A, d->C);
@@ -2254,7 +2311,9 @@ int gsr_det_workspace_bytes(const GsrDetSpec* d, int64_t* bytes) {
   gsr_detect::Spec sp;
   if (int rc = det_spec("gsr_det_workspace_bytes", d, sp)) return rc;
   if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_det_workspace_bytes: null bytes");
-  *bytes = (int64_t)det_layout(sp.B, sp.A, sp.max_candidates).bytes;
+  Carve c;
+  det_regions(c, sp.B, sp.A, sp.max_candidates);
+  *bytes = (int64_t)c.off;
   return GSR_OK;
 }
 
@@ -2263,31 +2322,25 @@ int gsr_det_postprocess(const GsrDetSpec* d, const float* pred, void* ws, int64_
   gsr_detect::Spec sp;
   if (int rc = det_spec("gsr_det_postprocess", d, sp)) return rc;
   if (!pred || !ws || !dets || !counts) return set_err(GSR_ERR_INVALID, "gsr_det_postprocess: null pred / ws / dets / counts");
-  const DetWs w = det_layout(sp.B, sp.A, sp.max_candidates);
-  if (ws_bytes < (int64_t)w.bytes)
-    return set_err(GSR_ERR_INVALID, "gsr_det_postprocess: workspace of %lld bytes, %zu needed (gsr_det_workspace_bytes)", (long long)ws_bytes, w.bytes);
-  if (((uintptr_t)ws & 7) != 0) return set_err(GSR_ERR_INVALID, "gsr_det_postprocess: the workspace must be 8-byte aligned");
+  Carve c(ws);
+  const DetWs w = det_regions(c, sp.B, sp.A, sp.max_candidates);
+  if (int rc = check_workspace("gsr_det_postprocess", ws, ws_bytes, c.off, 8, "gsr_det_workspace_bytes")) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  float* score = reinterpret_cast<float*>(base + w.score);
-  int32_t* cls = reinterpret_cast<int32_t*>(base + w.cls);
-  int32_t* order = reinterpret_cast<int32_t*>(base + w.order);
-  int32_t* ncand = reinterpret_cast<int32_t*>(base + w.ncand);
   const unsigned long long anchors = (unsigned long long)sp.B * (unsigned long long)sp.A;
   if (sp.layout == 1) {
     const unsigned blocks = (unsigned)((anchors + gsr_detect::SCORE_THREADS - 1) / gsr_detect::SCORE_THREADS);
-    hipLaunchKernelGGL((gsr_detect::k_det_score<1>), dim3(blocks), dim3(gsr_detect::SCORE_THREADS), 0, st, sp, pred, score, cls);
+    hipLaunchKernelGGL((gsr_detect::k_det_score<1>), dim3(blocks), dim3(gsr_detect::SCORE_THREADS), 0, st, sp, pred, w.score, w.cls);
   } else {
     const unsigned per = gsr_detect::SCORE_THREADS / 16;
     const unsigned blocks = (unsigned)((anchors + per - 1) / per);
-    hipLaunchKernelGGL((gsr_detect::k_det_score<0>), dim3(blocks), dim3(gsr_detect::SCORE_THREADS), 0, st, sp, pred, score, cls);
+    hipLaunchKernelGGL((gsr_detect::k_det_score<0>), dim3(blocks), dim3(gsr_detect::SCORE_THREADS), 0, st, sp, pred, w.score, w.cls);
   }
   LAUNCH_CHECK("gsr_det_postprocess (score)");
   hipLaunchKernelGGL(gsr_detect::k_det_select_sort, dim3((unsigned)sp.B), dim3(gsr_detect::SEL_THREADS), 0, st, sp.A,
-                     sp.max_candidates, (const float*)score, 1, sp.conf_thr, (const int32_t*)nullptr, order, ncand, counts + 1, 2);
+                     sp.max_candidates, (const float*)w.score, 1, sp.conf_thr, (const int32_t*)nullptr, w.order, w.ncand, counts + 1, 2);
   LAUNCH_CHECK("gsr_det_postprocess (select)");
   gsr_detect::NmsArgs na;
-  na.sp = sp; na.pred = pred; na.score = score; na.cls = cls; na.boxes = nullptr; na.order = order; na.ncand = ncand;
+  na.sp = sp; na.pred = pred; na.score = w.score; na.cls = w.cls; na.boxes = nullptr; na.order = w.order; na.ncand = w.ncand;
   na.dets = dets; na.keep = nullptr; na.counts = counts;
   hipLaunchKernelGGL((gsr_detect::k_det_nms<true>), dim3((unsigned)sp.B), dim3(gsr_detect::NMS_THREADS), 0, st, na);
   LAUNCH_CHECK("gsr_det_postprocess (nms)");
@@ -2302,27 +2355,11 @@ int gsr_det_nms(int32_t B, int32_t n, const float* boxes, const float* scores, c
   if ((unsigned long long)B * (unsigned long long)n * 4ull > 0x7fffffffull)
     return set_err(GSR_ERR_INVALID, "gsr_det_nms: more than 2^31 - 1 elements in boxes");
   if (!boxes || !scores || !ws || !keep || !counts) return set_err(GSR_ERR_INVALID, "gsr_det_nms: null boxes / scores / ws / keep / counts");
-  const DetWs w = det_layout(B, n, n);
-  if (ws_bytes < (int64_t)w.bytes)
-    return set_err(GSR_ERR_INVALID, "gsr_det_nms: workspace of %lld bytes, %zu needed (gsr_det_workspace_bytes with A = max_candidates = n)",
-                   (long long)ws_bytes, w.bytes);
-  if (((uintptr_t)ws & 7) != 0) return set_err(GSR_ERR_INVALID, "gsr_det_nms: the workspace must be 8-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  int32_t* order = reinterpret_cast<int32_t*>(base + w.order);
-  int32_t* ncand = reinterpret_cast<int32_t*>(base + w.ncand);
-  hipLaunchKernelGGL(gsr_detect::k_det_select_sort, dim3((unsigned)B), dim3(gsr_detect::SEL_THREADS), 0, st, n, n, scores, 0, 0.0f,
-                     n_valid, order, ncand, (int32_t*)nullptr, 0);
-  LAUNCH_CHECK("gsr_det_nms (select)");
-  gsr_detect::NmsArgs na;
-  na.sp = gsr_detect::Spec{};
-  na.sp.B = B; na.sp.A = n; na.sp.C = 1; na.sp.box_format = 1; na.sp.iou_thr = iou_thr; na.sp.max_candidates = n; na.sp.max_det = max_det;
-  na.sp.flags = classes ? 0u : gsr_detect::CLASS_AGNOSTIC;
-  na.pred = nullptr; na.score = scores; na.cls = classes; na.boxes = boxes; na.order = order; na.ncand = ncand;
-  na.dets = nullptr; na.keep = keep; na.counts = counts;
-  hipLaunchKernelGGL((gsr_detect::k_det_nms<false>), dim3((unsigned)B), dim3(gsr_detect::NMS_THREADS), 0, st, na);
-  LAUNCH_CHECK("gsr_det_nms (nms)");
-  return GSR_OK;
+  Carve c(ws);
+  const DetWs w = det_regions(c, B, n, n);
+  if (int rc = check_workspace("gsr_det_nms", ws, ws_bytes, c.off, 8, "gsr_det_workspace_bytes with A = max_candidates = n")) return rc;
+  return launch_nms_walk("gsr_det_nms", B, n, boxes, scores, classes, n_valid, iou_thr, max_det, w, keep, counts,
+                         static_cast<hipStream_t>(stream));
 }
 
 int gsr_det_box_iou(const float* a, int32_t n, const float* b, int32_t m, float* iou, void* stream) {
@@ -2352,10 +2389,6 @@ int gsr_det_verdict(const float* dets, const int32_t* counts, int32_t B, int32_t
 // everything is checked on the host before the first launch.  Workspace: [ov B*M*A f32][metric B*M*A f32][tgt B*A i32]
 // [ts B*A f32][ts_sum B f32][slab blocks*3 f32], each region rounded up to 256 bytes; the slab is sized for one anchor
 // per lane (the most blocks either path launches).
-struct DetLossWs {
-  size_t ov, metric, tgt, ts, ts_sum, slab, bytes;
-};
-
 static unsigned detloss_tiles(long long A, int v) {
   const long long per = (long long)gsr_dloss::TERM_THREADS * v;
   return (unsigned)((A + per - 1) / per);
@@ -2363,18 +2396,16 @@ static unsigned detloss_tiles(long long A, int v) {
 
 static unsigned detloss_chunks(int C) { return 1u + (unsigned)((C + gsr_dloss::CLS_CHUNK - 1) / gsr_dloss::CLS_CHUNK); }
 
-static DetLossWs detloss_layout(const gsr_dloss::Spec& sp) {
+static void detloss_regions(Carve& c, gsr_dloss::Args& ar) {
+  const gsr_dloss::Spec& sp = ar.sp;
   const size_t BA = (size_t)sp.B * (size_t)sp.A, BMA = BA * (size_t)sp.M;
   const size_t blocks = (size_t)detloss_tiles(sp.A, 1) * (size_t)detloss_chunks(sp.C) * (size_t)sp.B;
-  DetLossWs w;
-  w.ov = 0;
-  w.metric = w.ov + det_round(BMA * 4);
-  w.tgt = w.metric + det_round(BMA * 4);
-  w.ts = w.tgt + det_round(BA * 4);
-  w.ts_sum = w.ts + det_round(BA * 4);
-  w.slab = w.ts_sum + det_round((size_t)sp.B * 4);
-  w.bytes = w.slab + det_round(blocks * 3 * 4);
-  return w;
+  ar.ov = c.take<float>(BMA);
+  ar.metric = c.take<float>(BMA);
+  ar.tgt = c.take<int32_t>(BA);
+  ar.ts = c.take<float>(BA);
+  ar.ts_sum = c.take<float>((size_t)sp.B);
+  ar.slab = c.take<float>(blocks * 3);
 }
 
 static int detloss_spec(const char* fn, const GsrDetLossSpec* d, gsr_dloss::Spec& sp) {
@@ -2385,13 +2416,11 @@ static int detloss_spec(const char* fn, const GsrDetLossSpec* d, gsr_dloss::Spec
   if (d->reg_max != gsr_dloss::REG_MAX) return set_err(GSR_ERR_INVALID, "%s: reg_max=%d (only %d is built)", fn, d->reg_max, gsr_dloss::REG_MAX);
   if (d->topk < 1 || d->topk > gsr_dloss::MAX_TOPK) return set_err(GSR_ERR_INVALID, "%s: topk=%d (1..%d)", fn, d->topk, gsr_dloss::MAX_TOPK);
   if (d->flags != 0u) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
-  const float fl[5] = {d->alpha, d->beta, d->w_box, d->w_cls, d->w_dfl};
-  for (int i = 0; i < 5; ++i)
-    if (!(fl[i] >= 0.0f) || !(fl[i] <= 3.0e38f))
-      return set_err(GSR_ERR_INVALID, "%s: alpha, beta, w_box, w_cls, w_dfl must be finite and >= 0", fn);
+  if (!all_finite_nonneg({d->alpha, d->beta, d->w_box, d->w_cls, d->w_dfl}))
+    return set_err(GSR_ERR_INVALID, "%s: alpha, beta, w_box, w_cls, w_dfl must be finite and >= 0", fn);
   unsigned long long total = 0;
   for (int i = 0; i < d->nl; ++i) {
-    if (d->level_h[i] < 1 || d->level_w[i] < 1 || !(d->level_stride[i] > 0.0f) || !(d->level_stride[i] <= 3.0e38f))
+    if (d->level_h[i] < 1 || d->level_w[i] < 1 || !finite_pos(d->level_stride[i]))
       return set_err(GSR_ERR_INVALID, "%s: level %d is %d x %d with stride %g (sizes >= 1, a finite stride > 0)", fn, i,
                      d->level_h[i], d->level_w[i], (double)d->level_stride[i]);
     sp.h[i] = d->level_h[i]; sp.w[i] = d->level_w[i]; sp.stride[i] = d->level_stride[i];
@@ -2414,36 +2443,28 @@ static int detloss_spec(const char* fn, const GsrDetLossSpec* d, gsr_dloss::Spec
 }
 
 int gsr_detloss_workspace_bytes(const GsrDetLossSpec* d, int64_t* bytes) {
-  gsr_dloss::Spec sp;
-  if (int rc = detloss_spec("gsr_detloss_workspace_bytes", d, sp)) return rc;
+  gsr_dloss::Args ar;
+  if (int rc = detloss_spec("gsr_detloss_workspace_bytes", d, ar.sp)) return rc;
   if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_detloss_workspace_bytes: null bytes");
-  *bytes = (int64_t)detloss_layout(sp).bytes;
+  Carve c;
+  detloss_regions(c, ar);
+  *bytes = (int64_t)c.off;
   return GSR_OK;
 }
 
 int gsr_detloss(const GsrDetLossSpec* d, const float* pred, const float* gt_boxes, const int32_t* gt_cls, void* ws,
                 int64_t ws_bytes, float* loss, float* grad_pred, int32_t* tgt, float* ts, void* stream) {
-  gsr_dloss::Spec sp;
-  if (int rc = detloss_spec("gsr_detloss", d, sp)) return rc;
+  gsr_dloss::Args ar;
+  if (int rc = detloss_spec("gsr_detloss", d, ar.sp)) return rc;
+  const gsr_dloss::Spec& sp = ar.sp;
   if (!pred || !gt_boxes || !gt_cls || !ws || !loss)
     return set_err(GSR_ERR_INVALID, "gsr_detloss: null pred / gt_boxes / gt_cls / ws / loss");
-  const DetLossWs w = detloss_layout(sp);
-  if (ws_bytes < (int64_t)w.bytes)
-    return set_err(GSR_ERR_INVALID, "gsr_detloss: workspace of %lld bytes, %zu needed (gsr_detloss_workspace_bytes)", (long long)ws_bytes, w.bytes);
-  if (((uintptr_t)ws & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_detloss: the workspace must be 16-byte aligned");
-  if ((((uintptr_t)pred | (uintptr_t)gt_boxes | (uintptr_t)gt_cls | (uintptr_t)loss | (uintptr_t)grad_pred | (uintptr_t)tgt |
-        (uintptr_t)ts) & 3) != 0)
-    return set_err(GSR_ERR_INVALID, "gsr_detloss: every tensor must be 4-byte aligned");
+  Carve c(ws);
+  detloss_regions(c, ar);
+  if (int rc = check_workspace("gsr_detloss", ws, ws_bytes, c.off, 16, "gsr_detloss_workspace_bytes")) return rc;
+  if (int rc = check_aligned4("gsr_detloss", pred, gt_boxes, gt_cls, loss, grad_pred, tgt, ts)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  gsr_dloss::Args ar;
-  ar.sp = sp; ar.pred = pred; ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls;
-  ar.ov = reinterpret_cast<float*>(base + w.ov);
-  ar.metric = reinterpret_cast<float*>(base + w.metric);
-  ar.tgt = reinterpret_cast<int32_t*>(base + w.tgt);
-  ar.ts = reinterpret_cast<float*>(base + w.ts);
-  ar.ts_sum = reinterpret_cast<float*>(base + w.ts_sum);
-  ar.slab = reinterpret_cast<float*>(base + w.slab);
+  ar.pred = pred; ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls;
   ar.loss = loss; ar.grad_pred = grad_pred; ar.tgt_out = tgt; ar.ts_out = ts;
   const unsigned long long anchors = (unsigned long long)sp.B * (unsigned long long)sp.A;
   hipLaunchKernelGGL(gsr_dloss::k_detloss_metrics, dim3((unsigned)((anchors + gsr_dloss::MET_THREADS - 1) / gsr_dloss::MET_THREADS)),
@@ -2467,25 +2488,19 @@ int gsr_detloss(const GsrDetLossSpec* d, const float* pred, const float* gt_boxe
 // ---- set-prediction detector stage (gsr_setdet.h / gsr_setdet.hip.h): four launches for the loss, one for the output
 // stage; no allocation, no copy, no host wait; everything is checked on the host before the first launch.  Workspace:
 // [stats B*Q*2 f32][cost B*M*Q f32][tgt B*Q i32][nmatch B i32][slab blocks*3 f32], each region rounded up to 256 bytes.
-struct SetDetWs {
-  size_t stats, cost, tgt, nmatch, slab, bytes;
-};
-
 static unsigned setdet_term_blocks(const gsr_setdet::Spec& sp) {
   const unsigned long long total = (unsigned long long)sp.B * (unsigned long long)sp.Q * (unsigned long long)(sp.C + 1);
   return (unsigned)((total + gsr_setdet::TERM_TILE - 1) / gsr_setdet::TERM_TILE);
 }
 
-static SetDetWs setdet_layout(const gsr_setdet::Spec& sp) {
+static void setdet_regions(Carve& c, gsr_setdet::Args& ar) {
+  const gsr_setdet::Spec& sp = ar.sp;
   const size_t BQ = (size_t)sp.B * (size_t)sp.Q;
-  SetDetWs w;
-  w.stats = 0;
-  w.cost = w.stats + det_round(BQ * 2 * 4);
-  w.tgt = w.cost + det_round(BQ * (size_t)sp.M * 4);
-  w.nmatch = w.tgt + det_round(BQ * 4);
-  w.slab = w.nmatch + det_round((size_t)sp.B * 4);
-  w.bytes = w.slab + det_round((size_t)setdet_term_blocks(sp) * 3 * 4);
-  return w;
+  ar.stats = c.take<float>(BQ * 2);
+  ar.cost = c.take<float>(BQ * (size_t)sp.M);
+  ar.tgt = c.take<int32_t>(BQ);
+  ar.nmatch = c.take<int32_t>((size_t)sp.B);
+  ar.slab = c.take<float>((size_t)setdet_term_blocks(sp) * 3);
 }
 
 static int setdet_spec(const char* fn, const GsrSetDetSpec* d, gsr_setdet::Spec& sp) {
@@ -2498,11 +2513,9 @@ static int setdet_spec(const char* fn, const GsrSetDetSpec* d, gsr_setdet::Spec&
   if (d->max_det < 1 || d->max_det > gsr_setdet::MAX_QUERIES)
     return set_err(GSR_ERR_INVALID, "%s: max_det=%d (1..%d)", fn, d->max_det, gsr_setdet::MAX_QUERIES);
   if (d->flags != 0u) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
-  const float fl[7] = {d->c_class, d->c_l1, d->c_giou, d->w_ce, d->w_l1, d->w_giou, d->eos_coef};
-  for (int i = 0; i < 7; ++i)
-    if (!(fl[i] >= 0.0f) || !(fl[i] <= 3.0e38f))
-      return set_err(GSR_ERR_INVALID, "%s: c_class, c_l1, c_giou, w_ce, w_l1, w_giou, eos_coef must be finite and >= 0", fn);
-  if (!(d->img_w > 0.0f) || !(d->img_w <= 3.0e38f) || !(d->img_h > 0.0f) || !(d->img_h <= 3.0e38f))
+  if (!all_finite_nonneg({d->c_class, d->c_l1, d->c_giou, d->w_ce, d->w_l1, d->w_giou, d->eos_coef}))
+    return set_err(GSR_ERR_INVALID, "%s: c_class, c_l1, c_giou, w_ce, w_l1, w_giou, eos_coef must be finite and >= 0", fn);
+  if (!finite_pos(d->img_w) || !finite_pos(d->img_h))
     return set_err(GSR_ERR_INVALID, "%s: the frame is %g x %g (finite sizes > 0)", fn, (double)d->img_w, (double)d->img_h);
   if ((unsigned long long)d->B * (unsigned long long)d->Q * (unsigned long long)(d->C + 1) > 0x7fffffffull)
     return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in logits", fn);
@@ -2513,36 +2526,29 @@ static int setdet_spec(const char* fn, const GsrSetDetSpec* d, gsr_setdet::Spec&
 }
 
 int gsr_setdet_workspace_bytes(const GsrSetDetSpec* d, int64_t* bytes) {
-  gsr_setdet::Spec sp;
-  if (int rc = setdet_spec("gsr_setdet_workspace_bytes", d, sp)) return rc;
+  gsr_setdet::Args ar;
+  if (int rc = setdet_spec("gsr_setdet_workspace_bytes", d, ar.sp)) return rc;
   if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_setdet_workspace_bytes: null bytes");
-  *bytes = (int64_t)setdet_layout(sp).bytes;
+  Carve c;
+  setdet_regions(c, ar);
+  *bytes = (int64_t)c.off;
   return GSR_OK;
 }
 
 int gsr_setdet_loss(const GsrSetDetSpec* d, const float* logits, const float* boxes, const float* gt_boxes, const int32_t* gt_cls,
                     void* ws, int64_t ws_bytes, float* loss, float* grad_logits, float* grad_boxes, int32_t* match, int32_t* tgt,
                     void* stream) {
-  gsr_setdet::Spec sp;
-  if (int rc = setdet_spec("gsr_setdet_loss", d, sp)) return rc;
+  gsr_setdet::Args ar;
+  if (int rc = setdet_spec("gsr_setdet_loss", d, ar.sp)) return rc;
+  const gsr_setdet::Spec& sp = ar.sp;
   if (!logits || !boxes || !gt_boxes || !gt_cls || !ws || !loss)
     return set_err(GSR_ERR_INVALID, "gsr_setdet_loss: null logits / boxes / gt_boxes / gt_cls / ws / loss");
-  const SetDetWs w = setdet_layout(sp);
-  if (ws_bytes < (int64_t)w.bytes)
-    return set_err(GSR_ERR_INVALID, "gsr_setdet_loss: workspace of %lld bytes, %zu needed (gsr_setdet_workspace_bytes)", (long long)ws_bytes, w.bytes);
-  if (((uintptr_t)ws & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_setdet_loss: the workspace must be 16-byte aligned");
-  if ((((uintptr_t)logits | (uintptr_t)boxes | (uintptr_t)gt_boxes | (uintptr_t)gt_cls | (uintptr_t)loss | (uintptr_t)grad_logits |
-        (uintptr_t)grad_boxes | (uintptr_t)match | (uintptr_t)tgt) & 3) != 0)
-    return set_err(GSR_ERR_INVALID, "gsr_setdet_loss: every tensor must be 4-byte aligned");
+  Carve c(ws);
+  setdet_regions(c, ar);
+  if (int rc = check_workspace("gsr_setdet_loss", ws, ws_bytes, c.off, 16, "gsr_setdet_workspace_bytes")) return rc;
+  if (int rc = check_aligned4("gsr_setdet_loss", logits, boxes, gt_boxes, gt_cls, loss, grad_logits, grad_boxes, match, tgt)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  gsr_setdet::Args ar;
-  ar.sp = sp; ar.logits = logits; ar.boxes = boxes; ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls;
-  ar.stats = reinterpret_cast<float*>(base + w.stats);
-  ar.cost = reinterpret_cast<float*>(base + w.cost);
-  ar.tgt = reinterpret_cast<int32_t*>(base + w.tgt);
-  ar.nmatch = reinterpret_cast<int32_t*>(base + w.nmatch);
-  ar.slab = reinterpret_cast<float*>(base + w.slab);
+  ar.logits = logits; ar.boxes = boxes; ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls;
   ar.loss = loss; ar.grad_logits = grad_logits; ar.grad_boxes = grad_boxes; ar.match_out = match; ar.tgt_out = tgt;
   const unsigned long long queries = (unsigned long long)sp.B * (unsigned long long)sp.Q;
   hipLaunchKernelGGL(gsr_setdet::k_setdet_cost, dim3((unsigned)((queries + gsr_setdet::COST_WAVES - 1) / gsr_setdet::COST_WAVES)),
@@ -2563,8 +2569,7 @@ int gsr_setdet_postprocess(const GsrSetDetSpec* d, const float* logits, const fl
   gsr_setdet::Spec sp;
   if (int rc = setdet_spec("gsr_setdet_postprocess", d, sp)) return rc;
   if (!logits || !boxes || !dets || !counts) return set_err(GSR_ERR_INVALID, "gsr_setdet_postprocess: null logits / boxes / dets / counts");
-  if ((((uintptr_t)logits | (uintptr_t)boxes | (uintptr_t)dets | (uintptr_t)counts) & 3) != 0)
-    return set_err(GSR_ERR_INVALID, "gsr_setdet_postprocess: every tensor must be 4-byte aligned");
+  if (int rc = check_aligned4("gsr_setdet_postprocess", logits, boxes, dets, counts)) return rc;
   hipLaunchKernelGGL(gsr_setdet::k_setdet_post, dim3((unsigned)sp.B), dim3((unsigned)((sp.Q + 63) / 64 * 64)), 0, static_cast<hipStream_t>(stream),
                      sp, logits, boxes, dets, counts);
   LAUNCH_CHECK("gsr_setdet_postprocess");
@@ -2575,37 +2580,25 @@ int gsr_setdet_postprocess(const GsrSetDetSpec* d, const float* logits, const fl
 // members of the spec it uses on the host before the first launch.  Workspace, each region rounded up to 256 bytes:
 // [nrows 1 i32][slab blocks*2 f32] for the loss; [boxes B*R*4 f32][score B*R f32][cls B*R i32][ncand B i32]
 // [keep B*max_det i32][nkept B i32][the NMS walk's own workspace] for the output stage; the two share the start.
-struct RcnnWs {
-  size_t nrows, slab, loss_bytes;
-  size_t boxes, score, cls, ncand, keep, nkept, nms, post_bytes;
-};
-
-static bool rcnn_pos_finite(float v) { return v > 0.0f && v <= 3.0e38f; }
-static bool rcnn_nonneg_finite(float v) { return v >= 0.0f && v <= 3.0e38f; }
-
 static unsigned rcnn_row_blocks(long long B, long long S) {
   return (unsigned)((B * S + gsr_rcnn::ROW_WAVES - 1) / gsr_rcnn::ROW_WAVES);
 }
 
-static RcnnWs rcnn_layout(const GsrRcnnSpec* d, bool loss, bool post) {
-  RcnnWs w{};
-  if (loss) {
-    w.nrows = 0;
-    w.slab = det_round(4);
-    w.loss_bytes = w.slab + det_round((size_t)rcnn_row_blocks(d->B, d->S) * 2 * 4);
-  }
-  if (post) {
-    const size_t BR = (size_t)d->B * (size_t)d->R;
-    w.boxes = 0;
-    w.score = w.boxes + det_round(BR * 4 * 4);
-    w.cls = w.score + det_round(BR * 4);
-    w.ncand = w.cls + det_round(BR * 4);
-    w.keep = w.ncand + det_round((size_t)d->B * 4);
-    w.nkept = w.keep + det_round((size_t)d->B * (size_t)d->max_det * 4);
-    w.nms = w.nkept + det_round((size_t)d->B * 4);
-    w.post_bytes = w.nms + det_layout(d->B, d->R, d->R).bytes;
-  }
-  return w;
+static void rcnn_loss_regions(Carve& c, const GsrRcnnSpec* d, gsr_rcnn::LossArgs& ar) {
+  ar.nrows = c.take<int32_t>(1);
+  ar.slab = c.take<float>((size_t)rcnn_row_blocks(d->B, d->S) * 2);
+}
+
+// keep / nkept: what the NMS walk writes and k_rcnn_gather reads; nms: the walk's own workspace
+static void rcnn_post_regions(Carve& c, const GsrRcnnSpec* d, gsr_rcnn::PostArgs& ar, int32_t*& keep, int32_t*& nkept, DetWs& nms) {
+  const size_t BR = (size_t)d->B * (size_t)d->R;
+  ar.boxes = c.take<float>(BR * 4);
+  ar.score = c.take<float>(BR);
+  ar.cls = c.take<int32_t>(BR);
+  ar.ncand = c.take<int32_t>((size_t)d->B);
+  ar.keep = keep = c.take<int32_t>((size_t)d->B * (size_t)d->max_det);
+  ar.nkept = nkept = c.take<int32_t>((size_t)d->B);
+  nms = det_regions(c, d->B, d->R, d->R);
 }
 
 static void rcnn_copy_spec(const GsrRcnnSpec* d, gsr_rcnn::Spec& sp) {
@@ -2631,7 +2624,7 @@ static int rcnn_sample_spec(const char* fn, const GsrRcnnSpec* d) {
   if (d->R < 1 || (long long)d->R + (long long)d->M > gsr_rcnn::MAX_CAND)
     return set_err(GSR_ERR_INVALID, "%s: R=%d proposals with M=%d rows (R >= 1, R + M <= %d)", fn, d->R, d->M, gsr_rcnn::MAX_CAND);
   if (d->max_pos < 0 || d->max_pos > d->S) return set_err(GSR_ERR_INVALID, "%s: max_pos=%d (0..S=%d)", fn, d->max_pos, d->S);
-  if (!rcnn_nonneg_finite(d->fg_iou)) return set_err(GSR_ERR_INVALID, "%s: fg_iou must be finite and >= 0", fn);
+  if (!finite_nonneg(d->fg_iou)) return set_err(GSR_ERR_INVALID, "%s: fg_iou must be finite and >= 0", fn);
   return GSR_OK;
 }
 
@@ -2643,7 +2636,7 @@ static int rcnn_roi_spec(const char* fn, const GsrRcnnSpec* d, unsigned long lon
   if (d->PH < 1 || d->PH > gsr_rcnn::MAX_POOL || d->PW < 1 || d->PW > gsr_rcnn::MAX_POOL)
     return set_err(GSR_ERR_INVALID, "%s: the pooled size is %d x %d (1..%d each)", fn, d->PH, d->PW, gsr_rcnn::MAX_POOL);
   if (d->sampling_ratio < 0) return set_err(GSR_ERR_INVALID, "%s: sampling_ratio=%d (>= 0)", fn, d->sampling_ratio);
-  if (!rcnn_pos_finite(d->spatial_scale)) return set_err(GSR_ERR_INVALID, "%s: spatial_scale must be finite and > 0", fn);
+  if (!finite_pos(d->spatial_scale)) return set_err(GSR_ERR_INVALID, "%s: spatial_scale must be finite and > 0", fn);
   const unsigned long long feat = (unsigned long long)d->B * (unsigned long long)d->Cf * (unsigned long long)d->Hf * (unsigned long long)d->Wf;
   pooled_elems = (unsigned long long)d->B * (unsigned long long)d->S * (unsigned long long)d->Cf * (unsigned long long)(d->PH * d->PW);
   if ((unsigned long long)d->Hf * (unsigned long long)d->Wf > 0x7fffffffull || feat > 0x7fffffffull || pooled_elems > 0x7fffffffull)
@@ -2654,7 +2647,7 @@ static int rcnn_roi_spec(const char* fn, const GsrRcnnSpec* d, unsigned long lon
 static int rcnn_head_spec(const char* fn, const GsrRcnnSpec* d, long long rows_per_image) {
   if (int rc = rcnn_common(fn, d)) return rc;
   if (d->C < 1 || d->C > gsr_rcnn::MAX_CLASSES) return set_err(GSR_ERR_INVALID, "%s: C=%d classes (1..%d)", fn, d->C, gsr_rcnn::MAX_CLASSES);
-  if (!rcnn_pos_finite(d->bw_x) || !rcnn_pos_finite(d->bw_y) || !rcnn_pos_finite(d->bw_w) || !rcnn_pos_finite(d->bw_h))
+  if (!finite_pos(d->bw_x) || !finite_pos(d->bw_y) || !finite_pos(d->bw_w) || !finite_pos(d->bw_h))
     return set_err(GSR_ERR_INVALID, "%s: bw_x, bw_y, bw_w, bw_h must be finite and > 0", fn);
   if ((unsigned long long)d->B * (unsigned long long)rows_per_image * 4ull * (unsigned long long)d->C > 0x7fffffffull)
     return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in scores or deltas", fn);
@@ -2666,7 +2659,7 @@ static int rcnn_loss_spec(const char* fn, const GsrRcnnSpec* d) {
   if (d->S < 1 || d->S > gsr_rcnn::MAX_SAMPLE) return set_err(GSR_ERR_INVALID, "%s: S=%d RoIs per image (1..%d)", fn, d->S, gsr_rcnn::MAX_SAMPLE);
   if (d->M < 1 || d->M > gsr_rcnn::MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: M=%d gt rows per image (1..%d)", fn, d->M, gsr_rcnn::MAX_ROWS);
   if (int rc = rcnn_head_spec(fn, d, d->S)) return rc;
-  if (!rcnn_nonneg_finite(d->beta) || !rcnn_nonneg_finite(d->w_cls) || !rcnn_nonneg_finite(d->w_box))
+  if (!finite_nonneg(d->beta) || !finite_nonneg(d->w_cls) || !finite_nonneg(d->w_box))
     return set_err(GSR_ERR_INVALID, "%s: beta, w_cls, w_box must be finite and >= 0", fn);
   return GSR_OK;
 }
@@ -2676,9 +2669,9 @@ static int rcnn_post_spec(const char* fn, const GsrRcnnSpec* d) {
   if (d->R < 1 || d->R > gsr_rcnn::MAX_CAND) return set_err(GSR_ERR_INVALID, "%s: R=%d proposals per image (1..%d)", fn, d->R, gsr_rcnn::MAX_CAND);
   if (int rc = rcnn_head_spec(fn, d, d->R)) return rc;
   if (d->max_det < 1 || d->max_det > d->R) return set_err(GSR_ERR_INVALID, "%s: max_det=%d (1..R=%d)", fn, d->max_det, d->R);
-  if (!rcnn_nonneg_finite(d->conf_thr) || !rcnn_nonneg_finite(d->iou_thr))
+  if (!finite_nonneg(d->conf_thr) || !finite_nonneg(d->iou_thr))
     return set_err(GSR_ERR_INVALID, "%s: conf_thr, iou_thr must be finite and >= 0", fn);
-  if (!rcnn_pos_finite(d->img_w) || !rcnn_pos_finite(d->img_h))
+  if (!finite_pos(d->img_w) || !finite_pos(d->img_h))
     return set_err(GSR_ERR_INVALID, "%s: the frame is %g x %g (finite sizes > 0)", fn, (double)d->img_w, (double)d->img_h);
   return GSR_OK;
 }
@@ -2688,9 +2681,7 @@ int gsr_rcnn_sample(const GsrRcnnSpec* d, const float* proposals, const int32_t*
   if (int rc = rcnn_sample_spec("gsr_rcnn_sample", d)) return rc;
   if (!proposals || !gt_boxes || !gt_cls || !idx || !rois || !labels || !gt_row || !counts)
     return set_err(GSR_ERR_INVALID, "gsr_rcnn_sample: null proposals / gt_boxes / gt_cls / idx / rois / labels / gt_row / counts");
-  if ((((uintptr_t)proposals | (uintptr_t)n_prop | (uintptr_t)gt_boxes | (uintptr_t)gt_cls | (uintptr_t)idx | (uintptr_t)rois |
-        (uintptr_t)labels | (uintptr_t)gt_row | (uintptr_t)counts) & 3) != 0)
-    return set_err(GSR_ERR_INVALID, "gsr_rcnn_sample: every tensor must be 4-byte aligned");
+  if (int rc = check_aligned4("gsr_rcnn_sample", proposals, n_prop, gt_boxes, gt_cls, idx, rois, labels, gt_row, counts)) return rc;
   gsr_rcnn::SampleArgs ar;
   rcnn_copy_spec(d, ar.sp);
   ar.proposals = proposals; ar.n_prop = n_prop; ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls;
@@ -2706,8 +2697,7 @@ int gsr_roi_align(const GsrRcnnSpec* d, const float* features, const float* rois
   if (int rc = rcnn_roi_spec("gsr_roi_align", d, total)) return rc;
   if (!features || !rois || !pooled) return set_err(GSR_ERR_INVALID, "gsr_roi_align: null features / rois / pooled");
   if (n_roi && n_roi_stride < 1) return set_err(GSR_ERR_INVALID, "gsr_roi_align: n_roi_stride=%d (>= 1)", n_roi_stride);
-  if ((((uintptr_t)features | (uintptr_t)rois | (uintptr_t)n_roi | (uintptr_t)pooled) & 3) != 0)
-    return set_err(GSR_ERR_INVALID, "gsr_roi_align: every tensor must be 4-byte aligned");
+  if (int rc = check_aligned4("gsr_roi_align", features, rois, n_roi, pooled)) return rc;
   gsr_rcnn::RoiArgs ar{};
   rcnn_copy_spec(d, ar.sp);
   ar.features = features; ar.rois = rois; ar.n_roi = n_roi; ar.n_roi_stride = n_roi ? n_roi_stride : 0; ar.pooled = pooled;
@@ -2724,8 +2714,7 @@ int gsr_roi_align_backward(const GsrRcnnSpec* d, const float* rois, const int32_
   if (int rc = rcnn_roi_spec("gsr_roi_align_backward", d, total)) return rc;
   if (!rois || !grad_pooled || !grad_features) return set_err(GSR_ERR_INVALID, "gsr_roi_align_backward: null rois / grad_pooled / grad_features");
   if (n_roi && n_roi_stride < 1) return set_err(GSR_ERR_INVALID, "gsr_roi_align_backward: n_roi_stride=%d (>= 1)", n_roi_stride);
-  if ((((uintptr_t)rois | (uintptr_t)n_roi | (uintptr_t)grad_pooled | (uintptr_t)grad_features) & 3) != 0)
-    return set_err(GSR_ERR_INVALID, "gsr_roi_align_backward: every tensor must be 4-byte aligned");
+  if (int rc = check_aligned4("gsr_roi_align_backward", rois, n_roi, grad_pooled, grad_features)) return rc;
   const unsigned long long tiles = (unsigned long long)((d->Hf + gsr_rcnn::RB_TILE - 1) / gsr_rcnn::RB_TILE) *
                                    (unsigned long long)((d->Wf + gsr_rcnn::RB_TILE - 1) / gsr_rcnn::RB_TILE);
   if (tiles > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "gsr_roi_align_backward: more than 2^31 - 1 tiles");
@@ -2748,8 +2737,14 @@ int gsr_rcnn_workspace_bytes(const GsrRcnnSpec* d, int64_t* bytes) {
   if (!loss && !post)
     return set_err(GSR_ERR_INVALID, "gsr_rcnn_workspace_bytes: neither S=%d (1..%d) nor R=%d (1..%d) with max_det=%d (1..R) is in range",
                    d->S, gsr_rcnn::MAX_SAMPLE, d->R, gsr_rcnn::MAX_CAND, d->max_det);
-  const RcnnWs w = rcnn_layout(d, loss, post);
-  *bytes = (int64_t)std::max(w.loss_bytes, w.post_bytes);
+  Carve cl, cp;                                  // the two share the start
+  gsr_rcnn::LossArgs la;
+  gsr_rcnn::PostArgs pa;
+  int32_t *keep, *nkept;
+  DetWs nms;
+  if (loss) rcnn_loss_regions(cl, d, la);
+  if (post) rcnn_post_regions(cp, d, pa, keep, nkept, nms);
+  *bytes = (int64_t)std::max(cl.off, cp.off);
   return GSR_OK;
 }
 
@@ -2759,20 +2754,14 @@ int gsr_rcnn_loss(const GsrRcnnSpec* d, const float* scores, const float* deltas
   if (int rc = rcnn_loss_spec("gsr_rcnn_loss", d)) return rc;
   if (!scores || !deltas || !rois || !labels || !gt_row || !gt_boxes || !ws || !loss)
     return set_err(GSR_ERR_INVALID, "gsr_rcnn_loss: null scores / deltas / rois / labels / gt_row / gt_boxes / ws / loss");
-  const RcnnWs w = rcnn_layout(d, true, false);
-  if (ws_bytes < (int64_t)w.loss_bytes)
-    return set_err(GSR_ERR_INVALID, "gsr_rcnn_loss: workspace of %lld bytes, %zu needed (gsr_rcnn_workspace_bytes)", (long long)ws_bytes, w.loss_bytes);
-  if (((uintptr_t)ws & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_rcnn_loss: the workspace must be 16-byte aligned");
-  if ((((uintptr_t)scores | (uintptr_t)deltas | (uintptr_t)rois | (uintptr_t)labels | (uintptr_t)gt_row | (uintptr_t)gt_boxes |
-        (uintptr_t)loss | (uintptr_t)grad_scores | (uintptr_t)grad_deltas) & 3) != 0)
-    return set_err(GSR_ERR_INVALID, "gsr_rcnn_loss: every tensor must be 4-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
   gsr_rcnn::LossArgs ar;
+  Carve c(ws);
+  rcnn_loss_regions(c, d, ar);
+  if (int rc = check_workspace("gsr_rcnn_loss", ws, ws_bytes, c.off, 16, "gsr_rcnn_workspace_bytes")) return rc;
+  if (int rc = check_aligned4("gsr_rcnn_loss", scores, deltas, rois, labels, gt_row, gt_boxes, loss, grad_scores, grad_deltas)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   rcnn_copy_spec(d, ar.sp);
   ar.scores = scores; ar.deltas = deltas; ar.rois = rois; ar.labels = labels; ar.gt_row = gt_row; ar.gt_boxes = gt_boxes;
-  ar.nrows = reinterpret_cast<int32_t*>(base + w.nrows);
-  ar.slab = reinterpret_cast<float*>(base + w.slab);
   ar.loss = loss; ar.grad_scores = grad_scores; ar.grad_deltas = grad_deltas;
   const unsigned blocks = rcnn_row_blocks(d->B, d->S);
   hipLaunchKernelGGL(gsr_rcnn::k_rcnn_count, dim3(1), dim3(gsr_rcnn::FIN_THREADS), 0, st, ar);
@@ -2789,42 +2778,23 @@ int gsr_rcnn_postprocess(const GsrRcnnSpec* d, const float* scores, const float*
   if (int rc = rcnn_post_spec("gsr_rcnn_postprocess", d)) return rc;
   if (!scores || !deltas || !proposals || !ws || !dets || !counts)
     return set_err(GSR_ERR_INVALID, "gsr_rcnn_postprocess: null scores / deltas / proposals / ws / dets / counts");
-  const RcnnWs w = rcnn_layout(d, false, true);
-  if (ws_bytes < (int64_t)w.post_bytes)
-    return set_err(GSR_ERR_INVALID, "gsr_rcnn_postprocess: workspace of %lld bytes, %zu needed (gsr_rcnn_workspace_bytes)", (long long)ws_bytes,
-                   w.post_bytes);
-  if (((uintptr_t)ws & 15) != 0) return set_err(GSR_ERR_INVALID, "gsr_rcnn_postprocess: the workspace must be 16-byte aligned");
-  if ((((uintptr_t)scores | (uintptr_t)deltas | (uintptr_t)proposals | (uintptr_t)n_prop | (uintptr_t)dets | (uintptr_t)counts) & 3) != 0)
-    return set_err(GSR_ERR_INVALID, "gsr_rcnn_postprocess: every tensor must be 4-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
   gsr_rcnn::PostArgs ar;
+  int32_t *keep, *nkept;
+  DetWs nms;
+  Carve c(ws);
+  rcnn_post_regions(c, d, ar, keep, nkept, nms);
+  if (int rc = check_workspace("gsr_rcnn_postprocess", ws, ws_bytes, c.off, 16, "gsr_rcnn_workspace_bytes")) return rc;
+  if (int rc = check_aligned4("gsr_rcnn_postprocess", scores, deltas, proposals, n_prop, dets, counts)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   rcnn_copy_spec(d, ar.sp);
   ar.scores = scores; ar.deltas = deltas; ar.proposals = proposals; ar.n_prop = n_prop;
-  ar.boxes = reinterpret_cast<float*>(base + w.boxes);
-  ar.score = reinterpret_cast<float*>(base + w.score);
-  ar.cls = reinterpret_cast<int32_t*>(base + w.cls);
-  ar.ncand = reinterpret_cast<int32_t*>(base + w.ncand);
-  int32_t* keep = reinterpret_cast<int32_t*>(base + w.keep);
-  int32_t* nkept = reinterpret_cast<int32_t*>(base + w.nkept);
-  ar.keep = keep; ar.nkept = nkept; ar.dets = dets; ar.counts = counts;
+  ar.dets = dets; ar.counts = counts;
   hipLaunchKernelGGL(gsr_rcnn::k_rcnn_post, dim3((unsigned)d->B), dim3(gsr_rcnn::POST_THREADS), 0, st, ar);
   LAUNCH_CHECK("gsr_rcnn_postprocess (candidates)");
   // gsr_det_nms's two launches on the compacted candidates: entries at or beyond ncand[b] do not take part
-  const DetWs nw = det_layout(d->B, d->R, d->R);
-  int32_t* order = reinterpret_cast<int32_t*>(base + w.nms + nw.order);
-  int32_t* nsel = reinterpret_cast<int32_t*>(base + w.nms + nw.ncand);
-  hipLaunchKernelGGL(gsr_detect::k_det_select_sort, dim3((unsigned)d->B), dim3(gsr_detect::SEL_THREADS), 0, st, d->R, d->R,
-                     (const float*)ar.score, 0, 0.0f, (const int32_t*)ar.ncand, order, nsel, (int32_t*)nullptr, 0);
-  LAUNCH_CHECK("gsr_rcnn_postprocess (select)");
-  gsr_detect::NmsArgs na;
-  na.sp = gsr_detect::Spec{};
-  na.sp.B = d->B; na.sp.A = d->R; na.sp.C = 1; na.sp.box_format = 1; na.sp.iou_thr = d->iou_thr; na.sp.max_candidates = d->R;
-  na.sp.max_det = d->max_det; na.sp.flags = 0u;
-  na.pred = nullptr; na.score = ar.score; na.cls = ar.cls; na.boxes = ar.boxes; na.order = order; na.ncand = nsel;
-  na.dets = nullptr; na.keep = keep; na.counts = nkept;
-  hipLaunchKernelGGL((gsr_detect::k_det_nms<false>), dim3((unsigned)d->B), dim3(gsr_detect::NMS_THREADS), 0, st, na);
-  LAUNCH_CHECK("gsr_rcnn_postprocess (nms)");
+  if (int rc = launch_nms_walk("gsr_rcnn_postprocess", d->B, d->R, ar.boxes, ar.score, ar.cls, ar.ncand, d->iou_thr, d->max_det, nms,
+                               keep, nkept, st))
+    return rc;
   hipLaunchKernelGGL(gsr_rcnn::k_rcnn_gather, dim3((unsigned)d->B), dim3(256), 0, st, ar);
   LAUNCH_CHECK("gsr_rcnn_postprocess (gather)");
   return GSR_OK;

@@ -15,9 +15,16 @@
 #include <stdint.h>
 
 #include "gsr_detect.h"   // score_key, composite
+#include "gsr_detmath.h"  // m_exp, m_log, dmax_da, dmin_da, present
 #include "gsr_math.h"     // GSR_HD, GSR_FP_STRICT
 
 namespace gsr_dloss {
+
+using gsr_detmath::dmax_da;
+using gsr_detmath::dmin_da;
+using gsr_detmath::m_exp;
+using gsr_detmath::m_log;
+using gsr_detmath::present;
 
 constexpr int MAX_LEVELS = 5;
 constexpr int MAX_ROWS = 32;     // gt rows per image
@@ -39,10 +46,6 @@ struct Box {
   T x1, y1, x2, y2;
 };
 
-GSR_HD float m_exp(float x) { return expf(x); }
-GSR_HD double m_exp(double x) { return exp(x); }
-GSR_HD float m_log(float x) { return logf(x); }
-GSR_HD double m_log(double x) { return log(x); }
 GSR_HD float m_log1p(float x) { return log1pf(x); }
 GSR_HD double m_log1p(double x) { return log1p(x); }
 GSR_HD float m_atan(float x) { return atanf(x); }
@@ -53,9 +56,6 @@ GSR_HD float m_floor(float x) { return floorf(x); }
 GSR_HD double m_floor(double x) { return floor(x); }
 
 GSR_HD int channels(const Spec& sp) { return BOX_CH + sp.C; }
-
-// a row is present iff its class is one of the head's
-GSR_HD bool present(int cls, int C) { return cls >= 0 && cls < C; }
 
 // anchor a -> its grid point (x + 0.5, y + 0.5) and the stride of its level (a in 0 .. A-1)
 GSR_HD void anchor_point(const Spec& sp, int a, float& gx, float& gy, float& stride) {
@@ -94,12 +94,6 @@ GSR_HD T softmax_expect(const T* bins, size_t step, T* p, T* lse) {
   if (lse) *lse = m + m_log(s);
   return d;
 }
-
-// d max(a, b) / d a and d min(a, b) / d a, a tie shared in halves (torch.maximum / torch.minimum)
-template <class T>
-GSR_HD T dmax_da(T a, T b) { return a > b ? (T)1 : (a == b ? (T)0.5 : (T)0); }
-template <class T>
-GSR_HD T dmin_da(T a, T b) { return a < b ? (T)1 : (a == b ? (T)0.5 : (T)0); }
 
 // ---- CIoU(b1, b2) of the contract; g (may be NULL): d ciou / d (b1.x1, b1.y1, b1.x2, b1.y2) with `a` held constant.
 // a_in (may be NULL): the value of `a` to use instead of this point's -- the function of b1 whose derivative g is, for

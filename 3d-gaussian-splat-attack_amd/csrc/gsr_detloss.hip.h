@@ -20,9 +20,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gsr_block.hip.h"
 #include "gsr_detloss.h"
 
 namespace gsr_dloss {
+
+using gsr_block::block_tree_sum;
+using gsr_block::slab_sum;
 
 constexpr int MET_THREADS = 128;
 constexpr int ASG_THREADS = 1024;
@@ -98,7 +102,7 @@ __global__ void __launch_bounds__(ASG_THREADS) k_detloss_assign(Args ar) {
   __shared__ float s_rov[MAX_ROWS], s_rmet[MAX_ROWS];
   __shared__ int32_t s_cls[MAX_ROWS];                // -1: absent
   __shared__ float s_gt[MAX_ROWS * 4];
-  __shared__ float s_red[ASG_THREADS];
+  __shared__ float s_red[1][ASG_THREADS];
   const Spec& sp = ar.sp;
   const int b = blockIdx.x, t = threadIdx.x, A = sp.A, M = sp.M, K = sp.topk;
   const int E = M * K;                               // <= 512
@@ -194,13 +198,9 @@ __global__ void __launch_bounds__(ASG_THREADS) k_detloss_assign(Args ar) {
 
   float acc = 0.0f;
   for (int a = t; a < A; a += ASG_THREADS) acc += ts[a];
-  s_red[t] = acc;
-  __syncthreads();
-  for (int s = ASG_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) s_red[t] += s_red[t + s];
-    __syncthreads();
-  }
-  if (t == 0) ar.ts_sum[b] = s_red[0];
+  s_red[0][t] = acc;
+  block_tree_sum(s_red);
+  if (t == 0) ar.ts_sum[b] = s_red[0][0];
 }
 
 // ---- (c) the loss terms and the gradient ------------------------------------------------------------------------------------
@@ -296,15 +296,7 @@ __global__ void __launch_bounds__(TERM_THREADS) k_detloss_terms(Args ar) {
   s_red[0][t] = acc_box;
   s_red[1][t] = acc_cls;
   s_red[2][t] = acc_dfl;
-  __syncthreads();
-  for (int s = TERM_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      s_red[0][t] += s_red[0][t + s];
-      s_red[1][t] += s_red[1][t + s];
-      s_red[2][t] += s_red[2][t + s];
-    }
-    __syncthreads();
-  }
+  block_tree_sum(s_red);
   if (t < 3) {
     const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     ar.slab[blk * 3 + (size_t)t] = s_red[t][0];
@@ -316,16 +308,7 @@ __global__ void __launch_bounds__(FIN_THREADS) k_detloss_final(Args ar, unsigned
   __shared__ float s_red[3][FIN_THREADS];
   const Spec& sp = ar.sp;
   const int t = threadIdx.x;
-  float acc[3] = {0.0f, 0.0f, 0.0f};
-  for (unsigned i = (unsigned)t; i < nblocks; i += FIN_THREADS)
-    for (int j = 0; j < 3; ++j) acc[j] += ar.slab[(size_t)i * 3 + (size_t)j];
-  for (int j = 0; j < 3; ++j) s_red[j][t] = acc[j];
-  __syncthreads();
-  for (int s = FIN_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s)
-      for (int j = 0; j < 3; ++j) s_red[j][t] += s_red[j][t + s];
-    __syncthreads();
-  }
+  slab_sum<3, FIN_THREADS>(ar.slab, nblocks, s_red);
   if (t == 0) {
     const float tss = detloss_tss(ar.ts_sum, sp.B);
     const float box = s_red[0][0] / tss, cls = s_red[1][0] / tss, dfl = s_red[2][0] / tss;

@@ -10,13 +10,18 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "gsr_detloss.h"   // m_exp, m_log
+#include "gsr_detmath.h"   // m_exp, m_log, present, is_finite, the softmax pieces
 #include "gsr_math.h"      // GSR_HD, GSR_FP_STRICT
 
 namespace gsr_rcnn {
 
-using gsr_dloss::m_exp;
-using gsr_dloss::m_log;
+using gsr_detmath::is_finite;
+using gsr_detmath::log_softmax;
+using gsr_detmath::m_exp;
+using gsr_detmath::m_log;
+using gsr_detmath::present;
+using gsr_detmath::softmax_prob;
+using gsr_detmath::softmax_stats;
 
 constexpr int MAX_ROWS = 32;         // gt rows per image
 constexpr int MAX_SAMPLE = 1024;     // RoIs per image
@@ -42,8 +47,6 @@ struct Spec {
   float img_w, img_h;
   uint32_t flags;
 };
-
-GSR_HD bool present(int cls, int C) { return cls >= 0 && cls < C; }
 
 // ---- the sampler ------------------------------------------------------------------------------------------------------
 GSR_HD uint32_t mix32(uint32_t x) {
@@ -110,9 +113,6 @@ GSR_HD void roi_axis(T lo, T hi, T scale, int P, int sampling_ratio, T& start, T
 }
 
 template <class T>
-GSR_HD bool is_finite(T v) { return v - v == (T)0; }
-
-template <class T>
 GSR_HD bool roi_finite(const T* r) { return is_finite(r[0]) && is_finite(r[1]) && is_finite(r[2]) && is_finite(r[3]); }
 
 // sample i of bin p
@@ -144,29 +144,6 @@ GSR_HD bool lerp_axis(T y, int n, int& lo, int& hi, T& wl, T& wh) {
 }
 
 // ---- the box head's loss --------------------------------------------------------------------------------------------------
-template <class T>
-GSR_HD void softmax_stats(const T* x, int n, T& mx, T& sum) {
-  GSR_FP_STRICT
-  T m = x[0];
-  for (int k = 1; k < n; ++k) m = x[k] > m ? x[k] : m;
-  T s = (T)0;
-  for (int k = 0; k < n; ++k) s = s + m_exp(x[k] - m);
-  mx = m;
-  sum = s;
-}
-
-template <class T>
-GSR_HD T softmax_prob(T x, T mx, T sum) {
-  GSR_FP_STRICT
-  return m_exp(x - mx) / sum;
-}
-
-template <class T>
-GSR_HD T log_softmax(T x, T mx, T sum) {
-  GSR_FP_STRICT
-  return (x - mx) - m_log(sum);
-}
-
 // Box2BoxTransform.get_deltas: src = the RoI, dst = the gt box, weights w[4] = wx wy ww wh
 template <class T>
 GSR_HD void target_deltas(const T* src, const T* dst, const T* w, T* t) {

@@ -25,9 +25,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gsr_block.hip.h"
 #include "gsr_rcnn.h"
 
 namespace gsr_rcnn {
+
+using gsr_block::block_scan;
+using gsr_block::block_tree_sum;
+using gsr_block::slab_sum;
+using gsr_block::wave_softmax_stats;
 
 constexpr int SAMP_THREADS = 1024;
 constexpr int SAMP_PER = MAX_CAND / SAMP_THREADS;     // 4
@@ -42,37 +48,6 @@ constexpr int ROW_WAVES = ROW_THREADS / 64;
 constexpr int FIN_THREADS = 256;
 constexpr int POST_THREADS = 1024;
 constexpr int POST_PER = MAX_CAND / POST_THREADS;     // 4
-
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float o = __shfl_xor(v, m);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-// a + b is the same bits as b + a, so every lane ends with the same sum
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);
-  return v;
-}
-
-// inclusive scan of one int per thread over the workgroup (blockDim.x = THREADS)
-template <int THREADS>
-__device__ __forceinline__ int block_scan(int32_t* s_scan, int mine) {
-  const int t = threadIdx.x;
-  s_scan[t] = mine;
-  __syncthreads();
-  for (int s = 1; s < THREADS; s <<= 1) {
-    const int add = t >= s ? s_scan[t - s] : 0;
-    __syncthreads();
-    s_scan[t] += add;
-    __syncthreads();
-  }
-  return s_scan[t];
-}
 
 // ---- the sampler --------------------------------------------------------------------------------------------------------
 struct SampleArgs {
@@ -156,7 +131,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) k_rcnn_sample(SampleArgs ar) {
     }
     if (take) { taken |= 1u << k; ++mine; }
   }
-  const int incl = block_scan<SAMP_THREADS>(s_scan, mine);
+  const int incl = block_scan(s_scan, mine, SAMP_THREADS);
   const int total = s_scan[SAMP_THREADS - 1];                            // = n_pos + n_neg <= S
   int pos = incl - mine;
   for (int k = 0; k < per; ++k) {
@@ -374,18 +349,14 @@ struct LossArgs {
 };
 
 __global__ void __launch_bounds__(FIN_THREADS) k_rcnn_count(LossArgs ar) {
-  __shared__ int s_cnt[FIN_THREADS];
+  __shared__ int s_cnt[1][FIN_THREADS];
   const int t = threadIdx.x;
   const long long rows = (long long)ar.sp.B * (long long)ar.sp.S;
   int n = 0;
   for (long long i = t; i < rows; i += FIN_THREADS) n += (ar.labels[i] >= 0 && ar.labels[i] <= ar.sp.C) ? 1 : 0;
-  s_cnt[t] = n;
-  __syncthreads();
-  for (int s = FIN_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) s_cnt[t] += s_cnt[t + s];
-    __syncthreads();
-  }
-  if (t == 0) ar.nrows[0] = s_cnt[0];
+  s_cnt[0][t] = n;
+  block_tree_sum(s_cnt);
+  if (t == 0) ar.nrows[0] = s_cnt[0][0];
 }
 
 __device__ __forceinline__ float norm_rows(int n) { return n > 1 ? (float)n : 1.0f; }
@@ -411,12 +382,8 @@ __global__ void __launch_bounds__(ROW_THREADS) k_rcnn_rows(LossArgs ar) {
     const float* x = ar.scores + (size_t)gq * (size_t)n1;
     float* gs = ar.grad_scores ? ar.grad_scores + (size_t)gq * (size_t)n1 : nullptr;
     if (label >= 0) {
-      float m = -INFINITY;
-      for (int k = lane; k < n1; k += 64) m = x[k] > m ? x[k] : m;
-      m = wave_max_f(m);
-      float sm = 0.0f;
-      for (int k = lane; k < n1; k += 64) sm = sm + m_exp(x[k] - m);
-      sm = wave_sum_f(sm);
+      float m, sm;
+      wave_softmax_stats(x, n1, lane, m, sm);
       ce = -log_softmax<float>(x[label], m, sm);
       if (gs)
         for (int k = lane; k < n1; k += 64) gs[k] = kc * (softmax_prob<float>(x[k], m, sm) - (k == label ? 1.0f : 0.0f));
@@ -463,16 +430,7 @@ __global__ void __launch_bounds__(FIN_THREADS) k_rcnn_final(LossArgs ar, unsigne
   __shared__ float s_red[2][FIN_THREADS];
   const Spec& sp = ar.sp;
   const int t = threadIdx.x;
-  float acc[2] = {0.0f, 0.0f};
-  for (unsigned i = (unsigned)t; i < nblocks; i += FIN_THREADS)
-    for (int j = 0; j < 2; ++j) acc[j] = acc[j] + ar.slab[(size_t)i * 2 + (size_t)j];
-  for (int j = 0; j < 2; ++j) s_red[j][t] = acc[j];
-  __syncthreads();
-  for (int s = FIN_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s)
-      for (int j = 0; j < 2; ++j) s_red[j][t] = s_red[j][t] + s_red[j][t + s];
-    __syncthreads();
-  }
+  slab_sum<2, FIN_THREADS>(ar.slab, nblocks, s_red);
   if (t == 0) {
     const float nr = norm_rows(ar.nrows[0]);
     const float cls = s_red[0][0] / nr, box = s_red[1][0] / nr;
@@ -543,7 +501,7 @@ __global__ void __launch_bounds__(POST_THREADS) k_rcnn_post(PostArgs ar) {
     cand |= 1u << k;
     ++mine;
   }
-  const int incl = block_scan<POST_THREADS>(s_scan, mine);
+  const int incl = block_scan(s_scan, mine, POST_THREADS);
   const int total = s_scan[POST_THREADS - 1];
   int pos = incl - mine;
 #pragma unroll

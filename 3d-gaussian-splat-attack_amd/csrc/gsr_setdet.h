@@ -15,15 +15,19 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "gsr_detloss.h"   // m_exp, m_log, dmax_da, dmin_da
+#include "gsr_detmath.h"   // m_exp, m_log, dmax_da, dmin_da, present, the softmax pieces
 #include "gsr_math.h"      // GSR_HD, GSR_FP_STRICT
 
 namespace gsr_setdet {
 
-using gsr_dloss::dmax_da;
-using gsr_dloss::dmin_da;
-using gsr_dloss::m_exp;
-using gsr_dloss::m_log;
+using gsr_detmath::dmax_da;
+using gsr_detmath::dmin_da;
+using gsr_detmath::log_softmax;
+using gsr_detmath::m_exp;
+using gsr_detmath::m_log;
+using gsr_detmath::present;
+using gsr_detmath::softmax_prob;
+using gsr_detmath::softmax_stats;   // of one query's n = C + 1 logits
 
 constexpr int MAX_ROWS = 32;       // gt rows per image
 constexpr int MAX_QUERIES = 1024;
@@ -38,9 +42,6 @@ struct Spec {
   float conf_thr;
   int32_t max_det;
 };
-
-// a row is present iff its class is one of the head's
-GSR_HD bool present(int cls, int C) { return cls >= 0 && cls < C; }
 
 template <class T>
 GSR_HD T m_inf() { return (T)INFINITY; }
@@ -98,30 +99,6 @@ GSR_HD T giou(const T* a, const T* b, T* g) {
     }
   }
   return iou - gap;
-}
-
-// ---- softmax statistics of one query's n = C + 1 logits: the maximum and sum exp(x - max), added in index order
-template <class T>
-GSR_HD void softmax_stats(const T* x, int n, T& mx, T& sum) {
-  GSR_FP_STRICT
-  T m = x[0];
-  for (int k = 1; k < n; ++k) m = x[k] > m ? x[k] : m;
-  T s = (T)0;
-  for (int k = 0; k < n; ++k) s = s + m_exp(x[k] - m);
-  mx = m;
-  sum = s;
-}
-
-template <class T>
-GSR_HD T softmax_prob(T x, T mx, T sum) {
-  GSR_FP_STRICT
-  return m_exp(x - mx) / sum;
-}
-
-template <class T>
-GSR_HD T log_softmax(T x, T mx, T sum) {
-  GSR_FP_STRICT
-  return (x - mx) - m_log(sum);
 }
 
 // ---- the matching cost of one (row, query): p_cls = softmax(logits_q)[cls_m]; box and gt normalised (cx, cy, w, h)

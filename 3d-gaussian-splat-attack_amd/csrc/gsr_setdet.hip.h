@@ -19,9 +19,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gsr_block.hip.h"
 #include "gsr_setdet.h"
 
 namespace gsr_setdet {
+
+using gsr_block::block_scan;
+using gsr_block::block_tree_sum;
+using gsr_block::slab_sum;
+using gsr_block::wave_softmax_stats;
 
 constexpr int COST_THREADS = 256;
 constexpr int COST_WAVES = COST_THREADS / 64;
@@ -50,33 +56,6 @@ struct Args {
   int32_t* match_out;         // [B, M] or NULL
   int32_t* tgt_out;           // [B, Q] or NULL
 };
-
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float o = __shfl_xor(v, m);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-// a + b is the same bits as b + a, so every lane ends with the same sum
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);
-  return v;
-}
-
-// the statistics of one query's row, by one wave
-__device__ __forceinline__ void wave_softmax_stats(const float* x, int n, int lane, float& mx, float& sum) {
-  float m = -INFINITY;
-  for (int k = lane; k < n; k += 64) m = x[k] > m ? x[k] : m;
-  m = wave_max_f(m);
-  float s = 0.0f;
-  for (int k = lane; k < n; k += 64) s = s + m_exp(x[k] - m);
-  mx = m;
-  sum = wave_sum_f(s);
-}
 
 // ---- (a) statistics and the cost matrix -----------------------------------------------------------------------------------
 __global__ void __launch_bounds__(COST_THREADS) k_setdet_cost(Args ar) {
@@ -223,22 +202,18 @@ __global__ void __launch_bounds__(MATCH_THREADS) k_setdet_match(Args ar) {
 // ---- (c) the loss terms and the gradients -------------------------------------------------------------------------------------
 // the batch's matched rows: integers, so any order gives the same number
 template <int THREADS>
-__device__ __forceinline__ long long block_matched(const int32_t* nmatch, int B, int* s_cnt) {
+__device__ __forceinline__ long long block_matched(const int32_t* nmatch, int B, int (&s_cnt)[1][THREADS]) {
   const int t = threadIdx.x;
   int n = 0;
   for (int i = t; i < B; i += THREADS) n += nmatch[i];
-  s_cnt[t] = n;
-  __syncthreads();
-  for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) s_cnt[t] += s_cnt[t + s];
-    __syncthreads();
-  }
-  return (long long)s_cnt[0];
+  s_cnt[0][t] = n;
+  block_tree_sum(s_cnt);
+  return (long long)s_cnt[0][0];
 }
 
 __global__ void __launch_bounds__(TERM_THREADS) k_setdet_terms(Args ar) {
   __shared__ float s_red[3][TERM_THREADS];
-  __shared__ int s_cnt[TERM_THREADS];
+  __shared__ int s_cnt[1][TERM_THREADS];
   const Spec& sp = ar.sp;
   const int t = threadIdx.x;
   const unsigned n1 = (unsigned)sp.C + 1u;
@@ -282,35 +257,18 @@ __global__ void __launch_bounds__(TERM_THREADS) k_setdet_terms(Args ar) {
   s_red[0][t] = acc_ce;
   s_red[1][t] = acc_l1;
   s_red[2][t] = acc_g;
-  __syncthreads();
-  for (int s = TERM_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      s_red[0][t] += s_red[0][t + s];
-      s_red[1][t] += s_red[1][t + s];
-      s_red[2][t] += s_red[2][t + s];
-    }
-    __syncthreads();
-  }
+  block_tree_sum(s_red);
   if (t < 3) ar.slab[(size_t)blockIdx.x * 3 + (size_t)t] = s_red[t][0];
 }
 
 // ---- (d) the slab -> loss[4] ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(FIN_THREADS) k_setdet_final(Args ar, unsigned nblocks) {
   __shared__ float s_red[3][FIN_THREADS];
-  __shared__ int s_cnt[FIN_THREADS];
+  __shared__ int s_cnt[1][FIN_THREADS];
   const Spec& sp = ar.sp;
   const int t = threadIdx.x;
   const long long matched = block_matched<FIN_THREADS>(ar.nmatch, sp.B, s_cnt);
-  float acc[3] = {0.0f, 0.0f, 0.0f};
-  for (unsigned i = (unsigned)t; i < nblocks; i += FIN_THREADS)
-    for (int j = 0; j < 3; ++j) acc[j] += ar.slab[(size_t)i * 3 + (size_t)j];
-  for (int j = 0; j < 3; ++j) s_red[j][t] = acc[j];
-  __syncthreads();
-  for (int s = FIN_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s)
-      for (int j = 0; j < 3; ++j) s_red[j][t] += s_red[j][t + s];
-    __syncthreads();
-  }
+  slab_sum<3, FIN_THREADS>(ar.slab, nblocks, s_red);
   if (t == 0) {
     const float nb = norm_boxes<float>(matched);
     const float wsum = norm_ce<float>(matched, (long long)sp.B * (long long)sp.Q, sp.eos_coef);
@@ -341,18 +299,11 @@ __global__ void __launch_bounds__(POST_THREADS) k_setdet_post(Spec sp, const flo
     }
   }
   const int mine = bp > sp.conf_thr ? 1 : 0;                            // false for a NaN score and for t >= Q
-  s_scan[t] = mine;
-  __syncthreads();
-  for (int s = 1; s < nt; s <<= 1) {
-    const int add = t >= s ? s_scan[t - s] : 0;
-    __syncthreads();
-    s_scan[t] += add;
-    __syncthreads();
-  }
+  const int incl = block_scan(s_scan, mine, nt);
   const int above = s_scan[nt - 1];
   const int kept = above < sp.max_det ? above : sp.max_det;
   float* out = dets + (size_t)b * (size_t)sp.max_det * 6;
-  const int pos = s_scan[t] - mine;
+  const int pos = incl - mine;
   if (mine && pos < sp.max_det) {
     float bx[4], o[4];
     for (int k = 0; k < 4; ++k) bx[k] = boxes[((size_t)b * (size_t)Q + (size_t)t) * 4 + (size_t)k];

@@ -17,7 +17,8 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _load
-from .image_ops import _need_device, _raise, _stream
+from . import _ops_common
+from ._ops_common import _f32, _i32, _need_device, _ptr, call, capability
 
 GSR_CAP_DETECT = 2
 GSR_DET_CLASS_AGNOSTIC = 1
@@ -53,13 +54,7 @@ _lib = _load              # (the entry points' signatures are declared in _signa
 
 def available() -> bool:
     """Bit 1 of gsr_query(3): the loaded library has the detector output stage."""
-    lib = _load()
-    out = ctypes.c_int64(0)
-    return lib.gsr_query(3, ctypes.byref(out)) == 0 and bool(out.value & GSR_CAP_DETECT)
-
-
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().to(torch.float32).contiguous()
+    return capability(3, GSR_CAP_DETECT)
 
 
 def c_spec(spec: DetSpec, B: int, A: int, C: int) -> _CDetSpec:
@@ -70,16 +65,7 @@ def c_spec(spec: DetSpec, B: int, A: int, C: int) -> _CDetSpec:
 
 
 def workspace_bytes(cs: _CDetSpec) -> int:
-    lib = _lib()
-    n = ctypes.c_int64(0)
-    rc = lib.gsr_det_workspace_bytes(ctypes.byref(cs), ctypes.byref(n))
-    if rc != 0:
-        _raise(lib, rc)
-    return int(n.value)
-
-
-def _workspace(cs: _CDetSpec, device) -> torch.Tensor:
-    return torch.empty(((workspace_bytes(cs) + 7) // 8,), dtype=torch.int64, device=device)
+    return _ops_common.workspace_bytes("gsr_det_workspace_bytes", cs)
 
 
 def postprocess(raw: torch.Tensor, spec: DetSpec) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -94,15 +80,11 @@ def postprocess(raw: torch.Tensor, spec: DetSpec) -> Tuple[torch.Tensor, torch.T
     if C < 1:
         raise ValueError(f"postprocess: {K} channels leave no class (4 box channels{' and objectness' if spec.has_obj else ''})")
     cs = c_spec(spec, B, A, C)
-    ws = _workspace(cs, x.device)
+    ws = _ops_common.workspace(workspace_bytes(cs), x.device)
     dets = torch.empty((B, int(spec.max_det), 6), dtype=torch.float32, device=x.device)
     counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
-    lib = _lib()
-    with torch.cuda.device(x.device):
-        rc = lib.gsr_det_postprocess(ctypes.byref(cs), x.data_ptr(), ws.data_ptr(), ws.numel() * 8, dets.data_ptr(),
-                                     counts.data_ptr(), _stream(x.device))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_det_postprocess", x.device, ctypes.byref(cs), x.data_ptr(), ws.data_ptr(), ws.numel() * 8, dets.data_ptr(),
+         counts.data_ptr())
     return dets, counts
 
 
@@ -115,33 +97,28 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_thr: float, max_det: int,
     if boxes.dim() != 3 or boxes.shape[2] != 4 or tuple(scores.shape) != tuple(boxes.shape[:2]):
         raise ValueError(f"nms: boxes must be [B,n,4] and scores [B,n], got {tuple(boxes.shape)} and {tuple(scores.shape)}")
     dev = boxes.device
-    bx, sc = _f32(boxes), _f32(scores).to(dev)
+    bx, sc = _f32(boxes), _f32(scores, dev)
     B, n = int(bx.shape[0]), int(bx.shape[1])
     cl = nv = None
     if classes is not None:
         _need_device(classes, "nms", "classes")
         if tuple(classes.shape) != (B, n):
             raise ValueError(f"nms: classes must be [B,n], got {tuple(classes.shape)}")
-        cl = classes.detach().to(device=dev, dtype=torch.int32).contiguous()
+        cl = _i32(classes, dev)
     if n_valid is not None:
         _need_device(n_valid, "nms", "n_valid")
         if tuple(n_valid.shape) != (B,):
             raise ValueError(f"nms: n_valid must be [B], got {tuple(n_valid.shape)}")
-        nv = n_valid.detach().to(device=dev, dtype=torch.int32).contiguous()
+        nv = _i32(n_valid, dev)
     if n < 1 or n > MAX_CANDIDATES:
         raise ValueError(f"nms: n={n} boxes per image (1..{MAX_CANDIDATES})")
     # the workspace of a spec with A = max_candidates = n (include/gsraster.h)
     cs = _CDetSpec(B, n, 1, 0, 0, 1, 0.0, float(iou_thr), n, 1, 0, 0.0, 0.0, 1.0, 1.0)
-    lib = _lib()
-    ws = _workspace(cs, dev)
+    ws = _ops_common.workspace(workspace_bytes(cs), dev)
     keep = torch.empty((B, int(max_det)), dtype=torch.int32, device=dev)
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gsr_det_nms(B, n, bx.data_ptr(), sc.data_ptr(), cl.data_ptr() if cl is not None else None,
-                             nv.data_ptr() if nv is not None else None, float(iou_thr), int(max_det), ws.data_ptr(),
-                             ws.numel() * 8, keep.data_ptr(), counts.data_ptr(), _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_det_nms", dev, B, n, bx.data_ptr(), sc.data_ptr(), _ptr(cl), _ptr(nv), float(iou_thr), int(max_det), ws.data_ptr(),
+         ws.numel() * 8, keep.data_ptr(), counts.data_ptr())
     return keep, counts
 
 
@@ -151,13 +128,9 @@ def box_iou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     _need_device(b, "box_iou", "b")
     if a.dim() != 2 or a.shape[1] != 4 or b.dim() != 2 or b.shape[1] != 4:
         raise ValueError(f"box_iou: a and b must be [n,4] and [m,4], got {tuple(a.shape)} and {tuple(b.shape)}")
-    x, y = _f32(a), _f32(b).to(a.device)
+    x, y = _f32(a), _f32(b, a.device)
     out = torch.empty((int(x.shape[0]), int(y.shape[0])), dtype=torch.float32, device=x.device)
-    lib = _lib()
-    with torch.cuda.device(x.device):
-        rc = lib.gsr_det_box_iou(x.data_ptr(), int(x.shape[0]), y.data_ptr(), int(y.shape[0]), out.data_ptr(), _stream(x.device))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_det_box_iou", x.device, x.data_ptr(), int(x.shape[0]), y.data_ptr(), int(y.shape[0]), out.data_ptr())
     return out
 
 
@@ -171,21 +144,16 @@ def verdict(dets: torch.Tensor, counts: torch.Tensor, gt: Optional[torch.Tensor]
         raise ValueError(f"verdict: dets must be [B,max_det,6] and counts [B,2], got {tuple(dets.shape)} and {tuple(counts.shape)}")
     dev = dets.device
     d = _f32(dets)
-    c = counts.detach().to(device=dev, dtype=torch.int32).contiguous()
+    c = _i32(counts, dev)
     B, max_det = int(d.shape[0]), int(d.shape[1])
     g = None
     if gt is not None:
         _need_device(gt, "verdict", "gt")
         if tuple(gt.shape) != (B, 4):
             raise ValueError(f"verdict: gt must be [B,4], got {tuple(gt.shape)}")
-        g = _f32(gt).to(dev)
+        g = _f32(gt, dev)
     bits = torch.empty((B,), dtype=torch.int32, device=dev)
     best = torch.empty((B, 4), dtype=torch.float32, device=dev)
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_det_verdict(d.data_ptr(), c.data_ptr(), B, max_det, g.data_ptr() if g is not None else None, int(target),
-                                 -1 if untarget is None else int(untarget), 1 if is_targeted else 0, float(iou_match),
-                                 bits.data_ptr(), best.data_ptr(), _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_det_verdict", dev, d.data_ptr(), c.data_ptr(), B, max_det, _ptr(g), int(target), -1 if untarget is None else int(untarget),
+         1 if is_targeted else 0, float(iou_match), bits.data_ptr(), best.data_ptr())
     return bits, best

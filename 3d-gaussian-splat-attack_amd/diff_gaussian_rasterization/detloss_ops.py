@@ -18,7 +18,8 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _load
-from .image_ops import _need_device, _raise, _stream
+from . import _ops_common
+from ._ops_common import _f32, _i32, _need_device, _ptr, call, capability
 
 GSR_CAP_DETLOSS = 4
 MAX_ROWS = 32
@@ -49,9 +50,7 @@ _lib = _load              # (the entry points' signatures are declared in _signa
 
 def available() -> bool:
     """Bit 2 of gsr_query(3): the loaded library has the detector loss stage."""
-    lib = _load()
-    out = ctypes.c_int64(0)
-    return lib.gsr_query(3, ctypes.byref(out)) == 0 and bool(out.value & GSR_CAP_DETLOSS)
+    return capability(3, GSR_CAP_DETLOSS)
 
 
 def c_spec(spec: DetLossSpec, levels: Sequence[Tuple[int, int, float]], B: int, C: int, M: int) -> _CDetLossSpec:
@@ -68,12 +67,7 @@ def c_spec(spec: DetLossSpec, levels: Sequence[Tuple[int, int, float]], B: int, 
 
 
 def workspace_bytes(cs: _CDetLossSpec) -> int:
-    lib = _lib()
-    n = ctypes.c_int64(0)
-    rc = lib.gsr_detloss_workspace_bytes(ctypes.byref(cs), ctypes.byref(n))
-    if rc != 0:
-        _raise(lib, rc)
-    return int(n.value)
+    return _ops_common.workspace_bytes("gsr_detloss_workspace_bytes", cs)
 
 
 def run(pred: torch.Tensor, levels: Sequence[Tuple[int, int, float]], gt_boxes: torch.Tensor, gt_cls: torch.Tensor,
@@ -89,24 +83,17 @@ def run(pred: torch.Tensor, levels: Sequence[Tuple[int, int, float]], gt_boxes: 
         raise ValueError(f"detloss: gt_boxes must be [B,M,4] and gt_cls [B,M] with B={B}, got {tuple(gt_boxes.shape)} and "
                          f"{tuple(gt_cls.shape)}")
     dev = pred.device
-    x = pred.detach().to(torch.float32).contiguous()
-    gb = gt_boxes.detach().to(device=dev, dtype=torch.float32).contiguous()
-    gc = gt_cls.detach().to(device=dev, dtype=torch.int32).contiguous()
+    x, gb, gc = _f32(pred), _f32(gt_boxes, dev), _i32(gt_cls, dev)
     cs = c_spec(spec, levels, B, K - 64, int(gb.shape[1]))
     if cs.A != A:
         raise ValueError(f"detloss: the levels hold {cs.A} anchors, pred has {A}")
-    ws = torch.empty(((workspace_bytes(cs) + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    ws = _ops_common.workspace(workspace_bytes(cs), dev)
     loss = torch.empty((4,), dtype=torch.float32, device=dev)
     grad = torch.empty_like(x) if want_grad else None
     tgt = torch.empty((B, A), dtype=torch.int32, device=dev) if want_assignment else None
     ts = torch.empty((B, A), dtype=torch.float32, device=dev) if want_assignment else None
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_detloss(ctypes.byref(cs), x.data_ptr(), gb.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                             loss.data_ptr(), grad.data_ptr() if grad is not None else None,
-                             tgt.data_ptr() if tgt is not None else None, ts.data_ptr() if ts is not None else None, _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_detloss", dev, ctypes.byref(cs), x.data_ptr(), gb.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+         loss.data_ptr(), _ptr(grad), _ptr(tgt), _ptr(ts))
     return loss, grad, tgt, ts
 
 

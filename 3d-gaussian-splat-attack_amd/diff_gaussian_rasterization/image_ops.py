@@ -16,7 +16,8 @@ from typing import NamedTuple, Optional, Sequence
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _err, _load, _stream
+from . import _load
+from ._ops_common import _need_device, call, capability
 
 GSR_RESAMPLE_CLAMP01 = 1
 GSR_CAP_IMAGE = 1
@@ -52,16 +53,7 @@ _lib = _load              # (the entry points' signatures are declared in _signa
 
 def available() -> bool:
     """Bit 0 of gsr_query(3): the loaded library has the image front end."""
-    lib = _load()
-    out = ctypes.c_int64(0)
-    return lib.gsr_query(3, ctypes.byref(out)) == 0 and bool(out.value & GSR_CAP_IMAGE)
-
-
-def _need_device(t, fn: str, name: str) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{fn}: {name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{fn}: {name} must live on a HIP device (got {t.device}); there is no CPU path")
+    return capability(3, GSR_CAP_IMAGE)
 
 
 def _channel_floats(v, C: int, fn: str, name: str):
@@ -85,19 +77,11 @@ def _c_spec(spec: ResampleSpec, shape, fn: str):
     return cs, (mean, inv_std)
 
 
-def _raise(lib, rc: int):
-    raise (ValueError if rc == 1 else RuntimeError)(_err(lib))
-
-
 def _forward(src: torch.Tensor, spec: ResampleSpec) -> torch.Tensor:
     dst = torch.empty((src.shape[0], src.shape[1], int(spec.out_h), int(spec.out_w)), dtype=torch.float32, device=src.device)
     cs, keep = _c_spec(spec, src.shape, "resample")
-    lib = _lib()
-    with torch.cuda.device(src.device):
-        rc = lib.gsr_image_resample(ctypes.byref(cs), src.data_ptr(), dst.data_ptr(), _stream(src.device))
+    call("gsr_image_resample", src.device, ctypes.byref(cs), src.data_ptr(), dst.data_ptr())
     del keep
-    if rc != 0:
-        _raise(lib, rc)
     return dst
 
 
@@ -128,13 +112,9 @@ def resample_backward(grad_dst: torch.Tensor, spec: ResampleSpec, src_shape, src
         if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
             raise ValueError("resample_backward: out must be a contiguous float32 tensor of the source's shape on grad_dst's device")
     cs, keep = _c_spec(spec, shape, "resample_backward")
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_image_resample_backward(ctypes.byref(cs), s.data_ptr() if s is not None else None, g.data_ptr(),
-                                             out.data_ptr(), 1 if accumulate else 0, _stream(dev))
+    call("gsr_image_resample_backward", dev, ctypes.byref(cs), s.data_ptr() if s is not None else None, g.data_ptr(), out.data_ptr(),
+         1 if accumulate else 0)
     del keep
-    if rc != 0:
-        _raise(lib, rc)
     return out
 
 
@@ -176,9 +156,5 @@ def to_uint8_hwc(images: torch.Tensor) -> torch.Tensor:
     x = x.to(torch.float32).contiguous()
     B, _, H, W = (int(s) for s in x.shape)
     out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=x.device)
-    lib = _lib()
-    with torch.cuda.device(x.device):
-        rc = lib.gsr_image_to_u8(x.data_ptr(), B, H, W, out.data_ptr(), _stream(x.device))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_image_to_u8", x.device, x.data_ptr(), B, H, W, out.data_ptr())
     return out[0] if single else out

@@ -22,7 +22,8 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _load
-from .image_ops import _need_device, _raise, _stream
+from . import _ops_common
+from ._ops_common import _f32, _i32, _need_device, _ptr, call, capability
 
 GSR_CAP_RCNN = 16
 GSR_RCNN_CLASS_AGNOSTIC = 1
@@ -84,9 +85,7 @@ _lib = _load              # (the entry points' signatures are declared in _signa
 def available() -> bool:
     """Bit 4 of gsr_query(4), the item that holds every capability bit (item 3 is closed at bits 0..3): the loaded library
     has the two-stage detector stage.  A library without item 4 refuses it: no stage."""
-    lib = _load()
-    out = ctypes.c_int64(0)
-    return lib.gsr_query(4, ctypes.byref(out)) == 0 and bool(out.value & GSR_CAP_RCNN)
+    return capability(4, GSR_CAP_RCNN)
 
 
 def c_spec(spec: RcnnSpec, B: int = 1, R: int = 1, M: int = 1, C: int = 1, Cf: int = 1, Hf: int = 1, Wf: int = 1,
@@ -102,28 +101,7 @@ def c_spec(spec: RcnnSpec, B: int = 1, R: int = 1, M: int = 1, C: int = 1, Cf: i
 
 
 def workspace_bytes(cs: _CRcnnSpec) -> int:
-    lib = _lib()
-    n = ctypes.c_int64(0)
-    rc = lib.gsr_rcnn_workspace_bytes(ctypes.byref(cs), ctypes.byref(n))
-    if rc != 0:
-        _raise(lib, rc)
-    return int(n.value)
-
-
-def _workspace(cs: _CRcnnSpec, dev) -> torch.Tensor:
-    return torch.empty(((workspace_bytes(cs) + 15) // 16 * 2,), dtype=torch.int64, device=dev)
-
-
-def _f32(t: torch.Tensor, dev) -> torch.Tensor:
-    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-
-def _i32(t: torch.Tensor, dev) -> torch.Tensor:
-    return t.detach().to(device=dev, dtype=torch.int32).contiguous()
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
+    return _ops_common.workspace_bytes("gsr_rcnn_workspace_bytes", cs)
 
 
 def sample(proposals: torch.Tensor, gt_boxes: torch.Tensor, gt_cls: torch.Tensor, nc: int, spec: RcnnSpec = RcnnSpec(),
@@ -152,12 +130,8 @@ def sample(proposals: torch.Tensor, gt_boxes: torch.Tensor, gt_cls: torch.Tensor
     out = Sample(torch.empty((B, S), dtype=torch.int32, device=dev), torch.empty((B, S, 4), dtype=torch.float32, device=dev),
                  torch.empty((B, S), dtype=torch.int32, device=dev), torch.empty((B, S), dtype=torch.int32, device=dev),
                  torch.empty((B, 2), dtype=torch.int32, device=dev))
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_rcnn_sample(ctypes.byref(cs), pr.data_ptr(), _ptr(npr), gb.data_ptr(), gc.data_ptr(), out.idx.data_ptr(),
-                                 out.rois.data_ptr(), out.labels.data_ptr(), out.gt_row.data_ptr(), out.counts.data_ptr(), _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_rcnn_sample", dev, ctypes.byref(cs), pr.data_ptr(), _ptr(npr), gb.data_ptr(), gc.data_ptr(), out.idx.data_ptr(),
+         out.rois.data_ptr(), out.labels.data_ptr(), out.gt_row.data_ptr(), out.counts.data_ptr())
     return out
 
 
@@ -183,11 +157,7 @@ def roi_align_forward(features: torch.Tensor, rois: torch.Tensor, counts: Option
     f, r = _f32(features, dev), _f32(rois, dev)
     cs = c_spec(spec, B=B, Cf=int(f.shape[1]), Hf=int(f.shape[2]), Wf=int(f.shape[3]), S=S)
     pooled = torch.empty((B, S, int(f.shape[1]), int(cs.PH), int(cs.PW)), dtype=torch.float32, device=dev)
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_roi_align(ctypes.byref(cs), f.data_ptr(), r.data_ptr(), _ptr(counts), stride, pooled.data_ptr(), _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_roi_align", dev, ctypes.byref(cs), f.data_ptr(), r.data_ptr(), _ptr(counts), stride, pooled.data_ptr())
     return pooled
 
 
@@ -209,12 +179,8 @@ def roi_align_backward(grad_pooled: torch.Tensor, rois: torch.Tensor, counts: Op
         out = torch.empty((B, Cf, Hf, Wf), dtype=torch.float32, device=dev)
     elif tuple(out.shape) != (B, Cf, Hf, Wf) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
         raise ValueError("roi_align_backward: `out` must be a contiguous float32 [B,Cf,Hf,Wf] on the gradient's device")
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_roi_align_backward(ctypes.byref(cs), r.data_ptr(), _ptr(counts), stride, g.data_ptr(), out.data_ptr(),
-                                        1 if accumulate else 0, _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_roi_align_backward", dev, ctypes.byref(cs), r.data_ptr(), _ptr(counts), stride, g.data_ptr(), out.data_ptr(),
+         1 if accumulate else 0)
     return out
 
 
@@ -271,16 +237,12 @@ def run_loss(scores: torch.Tensor, deltas: torch.Tensor, rois: torch.Tensor, lab
     lb, gr = _i32(labels, dev), _i32(gt_row, dev)
     cs = c_spec(spec, B=B, M=int(gb.shape[1]), C=C, S=S)
     cs.R, cs.max_det = 0, 0                                    # the workspace of the loss alone
-    ws = _workspace(cs, dev)
+    ws = _ops_common.workspace(workspace_bytes(cs), dev)
     loss = torch.empty((3,), dtype=torch.float32, device=dev)
     gs = torch.empty_like(x) if want_grad else None
     gd = torch.empty_like(d) if want_grad else None
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_rcnn_loss(ctypes.byref(cs), x.data_ptr(), d.data_ptr(), r.data_ptr(), lb.data_ptr(), gr.data_ptr(), gb.data_ptr(),
-                               ws.data_ptr(), ws.numel() * 8, loss.data_ptr(), _ptr(gs), _ptr(gd), _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_rcnn_loss", dev, ctypes.byref(cs), x.data_ptr(), d.data_ptr(), r.data_ptr(), lb.data_ptr(), gr.data_ptr(), gb.data_ptr(),
+         ws.data_ptr(), ws.numel() * 8, loss.data_ptr(), _ptr(gs), _ptr(gd))
     return loss, gs, gd
 
 
@@ -331,13 +293,9 @@ def postprocess(scores: torch.Tensor, deltas: torch.Tensor, proposals: torch.Ten
         npr = _i32(n_prop, dev)
     cs = c_spec(spec, B=B, R=R, C=C, S=0)
     cs.max_det = min(int(spec.max_det), R)
-    ws = _workspace(cs, dev)
+    ws = _ops_common.workspace(workspace_bytes(cs), dev)
     dets = torch.empty((B, int(cs.max_det), 6), dtype=torch.float32, device=dev)
     counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_rcnn_postprocess(ctypes.byref(cs), x.data_ptr(), d.data_ptr(), pr.data_ptr(), _ptr(npr), ws.data_ptr(),
-                                      ws.numel() * 8, dets.data_ptr(), counts.data_ptr(), _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_rcnn_postprocess", dev, ctypes.byref(cs), x.data_ptr(), d.data_ptr(), pr.data_ptr(), _ptr(npr), ws.data_ptr(),
+         ws.numel() * 8, dets.data_ptr(), counts.data_ptr())
     return dets, counts

@@ -20,7 +20,8 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _load
-from .image_ops import _need_device, _raise, _stream
+from . import _ops_common
+from ._ops_common import _f32, _i32, _need_device, _ptr, call, capability
 
 GSR_CAP_SETDET = 8
 MAX_ROWS = 32
@@ -55,9 +56,7 @@ _lib = _load              # (the entry points' signatures are declared in _signa
 
 def available() -> bool:
     """Bit 3 of gsr_query(3): the loaded library has the set-prediction detector stage."""
-    lib = _load()
-    out = ctypes.c_int64(0)
-    return lib.gsr_query(3, ctypes.byref(out)) == 0 and bool(out.value & GSR_CAP_SETDET)
+    return capability(3, GSR_CAP_SETDET)
 
 
 def c_spec(spec: SetDetSpec, B: int, Q: int, C: int, M: int) -> _CSetDetSpec:
@@ -67,12 +66,7 @@ def c_spec(spec: SetDetSpec, B: int, Q: int, C: int, M: int) -> _CSetDetSpec:
 
 
 def workspace_bytes(cs: _CSetDetSpec) -> int:
-    lib = _lib()
-    n = ctypes.c_int64(0)
-    rc = lib.gsr_setdet_workspace_bytes(ctypes.byref(cs), ctypes.byref(n))
-    if rc != 0:
-        _raise(lib, rc)
-    return int(n.value)
+    return _ops_common.workspace_bytes("gsr_setdet_workspace_bytes", cs)
 
 
 def _heads(fn: str, logits: torch.Tensor, boxes: torch.Tensor) -> Tuple[int, int, int]:
@@ -96,25 +90,17 @@ def run(logits: torch.Tensor, boxes: torch.Tensor, gt_boxes: torch.Tensor, gt_cl
         raise ValueError(f"setdet_loss: gt_boxes must be [B,M,4] and gt_cls [B,M] with B={B}, got {tuple(gt_boxes.shape)} and "
                          f"{tuple(gt_cls.shape)}")
     dev = logits.device
-    x = logits.detach().to(torch.float32).contiguous()
-    bx = boxes.detach().to(device=dev, dtype=torch.float32).contiguous()
-    gb = gt_boxes.detach().to(device=dev, dtype=torch.float32).contiguous()
-    gc = gt_cls.detach().to(device=dev, dtype=torch.int32).contiguous()
+    x, bx, gb, gc = _f32(logits), _f32(boxes, dev), _f32(gt_boxes, dev), _i32(gt_cls, dev)
     M = int(gb.shape[1])
     cs = c_spec(spec, B, Q, C, M)
-    ws = torch.empty(((workspace_bytes(cs) + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    ws = _ops_common.workspace(workspace_bytes(cs), dev)
     loss = torch.empty((4,), dtype=torch.float32, device=dev)
     gl = torch.empty_like(x) if want_grad else None
     gbx = torch.empty_like(bx) if want_grad else None
     match = torch.empty((B, M), dtype=torch.int32, device=dev) if want_matching else None
     tgt = torch.empty((B, Q), dtype=torch.int32, device=dev) if want_matching else None
-    lib = _lib()
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(dev):
-        rc = lib.gsr_setdet_loss(ctypes.byref(cs), x.data_ptr(), bx.data_ptr(), gb.data_ptr(), gc.data_ptr(), ws.data_ptr(),
-                                 ws.numel() * 8, loss.data_ptr(), ptr(gl), ptr(gbx), ptr(match), ptr(tgt), _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_setdet_loss", dev, ctypes.byref(cs), x.data_ptr(), bx.data_ptr(), gb.data_ptr(), gc.data_ptr(), ws.data_ptr(),
+         ws.numel() * 8, loss.data_ptr(), _ptr(gl), _ptr(gbx), _ptr(match), _ptr(tgt))
     return loss, gl, gbx, match, tgt
 
 
@@ -152,14 +138,9 @@ def postprocess(logits: torch.Tensor, boxes: torch.Tensor, spec: SetDetSpec = Se
     threshold)."""
     B, Q, C = _heads("setdet_postprocess", logits, boxes)
     dev = logits.device
-    x = logits.detach().to(torch.float32).contiguous()
-    bx = boxes.detach().to(device=dev, dtype=torch.float32).contiguous()
+    x, bx = _f32(logits), _f32(boxes, dev)
     cs = c_spec(spec, B, Q, C, 1)
     dets = torch.empty((B, int(cs.max_det), 6), dtype=torch.float32, device=dev)
     counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    lib = _lib()
-    with torch.cuda.device(dev):
-        rc = lib.gsr_setdet_postprocess(ctypes.byref(cs), x.data_ptr(), bx.data_ptr(), dets.data_ptr(), counts.data_ptr(), _stream(dev))
-    if rc != 0:
-        _raise(lib, rc)
+    call("gsr_setdet_postprocess", dev, ctypes.byref(cs), x.data_ptr(), bx.data_ptr(), dets.data_ptr(), counts.data_ptr())
     return dets, counts

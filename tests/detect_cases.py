@@ -12,10 +12,11 @@ empty boxes) use numbers on which float32 and float64 agree exactly and are exem
 """
 import ctypes
 import os
-import subprocess
 from typing import NamedTuple, Tuple
 
 import numpy as np
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HM = os.path.join(ROOT, "tests", "host_math")
@@ -288,12 +289,7 @@ def c_spec(c: Case) -> CSpec:
 
 
 def host_lib():
-    so = os.path.join(HM, "libdetecthost.so")
-    src = os.path.join(HM, "detect_host.cpp")
-    hdrs = [os.path.join(CSRC, "gsr_detect.h"), os.path.join(CSRC, "gsr_math.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = host_build.host_lib("detect")
     i, f, vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
     lib.dh_postprocess.restype = i
     lib.dh_postprocess.argtypes = [ctypes.POINTER(CSpec), vp, vp, vp]

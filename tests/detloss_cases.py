@@ -20,11 +20,12 @@ python tests/detloss_cases.py searches the seeds.
 import ctypes
 import math
 import os
-import subprocess
 from typing import NamedTuple, Tuple
 
 import numpy as np
 import torch
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HM = os.path.join(ROOT, "tests", "host_math")
@@ -295,12 +296,7 @@ def c_spec(levels, B, C, M, topk=TOPK, alpha=ALPHA, beta=BETA, w=(W_BOX, W_CLS, 
 
 
 def host_lib():
-    so = os.path.join(HM, "libdetlosshost.so")
-    src = os.path.join(HM, "detloss_host.cpp")
-    hdrs = [os.path.join(CSRC, n) for n in ("gsr_detloss.h", "gsr_detect.h", "gsr_math.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = host_build.host_lib("detloss")
     vp = ctypes.c_void_p
     for fn in (lib.dlh_run_f32, lib.dlh_run_f64):
         fn.restype = ctypes.c_int

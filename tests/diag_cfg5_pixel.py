@@ -8,7 +8,6 @@ alpha at one pixel -- and the pixel is composited in float64 from each of the th
 import ctypes
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -20,14 +19,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import oracle_r as O  # noqa: E402
 from util import settings_for  # noqa: E402
+import host_build  # noqa: E402
 from gsplat_attack.scenes import make_scene  # noqa: E402
 
 PX, PY = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (3484, 437)
-HM = os.path.join(ROOT, "tests", "host_math")
-so = os.path.join(HM, "libhostmath.so")
-subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "3d-gaussian-splat-attack_amd", "csrc"),
-                os.path.join(HM, "host_math.cpp"), "-o", so], check=True)
-lib = ctypes.CDLL(so)
+lib = host_build.host_lib("math")
 ref, cams, _ = make_scene("airport-4K", device="cpu", n_views=1)
 cam = cams[0]
 H, W = cam.image_height, cam.image_width

@@ -20,12 +20,13 @@ the clamped source).
 """
 import ctypes
 import os
-import subprocess
 from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HM = os.path.join(ROOT, "tests", "host_math")
@@ -93,12 +94,7 @@ GPU_EXTRA = [Case(1080, 1920, 360, 640, 640, 640, 140, 0, 114 / 255, B=2),
 
 
 def host_lib():
-    so = os.path.join(HM, "libimagehost.so")
-    src = os.path.join(HM, "image_host.cpp")
-    hdrs = [os.path.join(CSRC, "gsr_image.h"), os.path.join(CSRC, "gsr_math.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = host_build.host_lib("image")
     i, f, vp, u32 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32
     lib.ih_forward.restype = i
     lib.ih_forward.argtypes = [i] * 10 + [f, vp, vp, u32, vp, vp]

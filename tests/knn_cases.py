@@ -13,10 +13,11 @@ make at most 8 units of 2^-24, doubled.  Taking another neighbour among near-tie
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import torch
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "3d-gaussian-splat-attack_amd", "csrc")
@@ -263,11 +264,7 @@ def check(tag, name, got, ref):
 
 # ---- the host build -----------------------------------------------------------------------------------------------------------
 def host_lib():
-    so = os.path.join(HM, "libknnhost.so")
-    hdrs = [os.path.join(CSRC, n) for n in ("gsr_knn.h", "gsr_math.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in [SRC] + hdrs):
-        subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, SRC, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = host_build.host_lib("knn")
     lib.kh_dist2.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.kh_dist2.restype = ctypes.c_int
     return lib

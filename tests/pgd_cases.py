@@ -34,9 +34,10 @@ eps + u (||out||_2 + ||x0||_2 + eps); after an L-inf step |out - x0| <= eps + u 
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "3d-gaussian-splat-attack_amd", "csrc")
@@ -410,11 +411,7 @@ def check(tag, c: Case, rule, got, ref=None, no_step=None, quiet=False, norm_err
 
 # ---- the host build ----------------------------------------------------------------------------------------------------------
 def host_lib():
-    so = os.path.join(HM, "libpgdhost.so")
-    hdrs = [os.path.join(CSRC, n) for n in ("gsr_pgd.h", "gsr_math.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in [SRC] + hdrs):
-        subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, SRC, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = host_build.host_lib("pgd")
     lib.ph_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float,
                             ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]
     lib.ph_step.restype = ctypes.c_int

@@ -18,7 +18,6 @@ Decisions that a rounding could flip are kept away from their thresholds, and th
 import ctypes
 import math
 import os
-import subprocess
 from functools import lru_cache
 from typing import NamedTuple, Optional, Tuple
 
@@ -26,6 +25,7 @@ import numpy as np
 import torch
 
 import detloss_cases as DL
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "3d-gaussian-splat-attack_amd", "csrc")
@@ -640,12 +640,7 @@ def c_spec(**kw) -> CSpec:
 
 
 def host_lib():
-    so = os.path.join(HM, "librcnnhost.so")
-    src = os.path.join(HM, "rcnn_host.cpp")
-    hdrs = [os.path.join(CSRC, n) for n in ("gsr_rcnn.h", "gsr_detloss.h", "gsr_detect.h", "gsr_math.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = host_build.host_lib("rcnn")
     vp, sp = ctypes.c_void_p, ctypes.POINTER(CSpec)
     lib.rh_sample.argtypes = [sp] + [vp] * 9
     lib.rh_roi_align.argtypes = [sp, vp, vp, vp, ctypes.c_int32, vp]

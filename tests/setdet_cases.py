@@ -25,13 +25,13 @@ import ctypes
 import itertools
 import math
 import os
-import subprocess
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from detloss_cases import bound, err  # noqa: F401  (the project's bound, shared)
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HM = os.path.join(ROOT, "tests", "host_math")
@@ -341,16 +341,11 @@ def c_spec(B, Q, C, M, frame=FRAME, costs=(C_CLASS, C_L1, C_GIOU), w=(W_CE, W_L1
 
 
 def host_sources():
-    return os.path.join(HM, "setdet_host.cpp"), [os.path.join(CSRC, n) for n in ("gsr_setdet.h", "gsr_detloss.h", "gsr_detect.h",
-                                                                                   "gsr_math.h")]
+    return os.path.join(HM, "setdet_host.cpp"), [os.path.join(CSRC, n) for n in ("gsr_setdet.h", "gsr_detmath.h", "gsr_math.h")]
 
 
 def host_lib():
-    so = os.path.join(HM, "libsetdethost.so")
-    src, hdrs = host_sources()
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, src, "-o", so], check=True)
-    lib = ctypes.CDLL(so)
+    lib = host_build.host_lib("setdet")
     vp = ctypes.c_void_p
     for fn in (lib.sdh_run_f32, lib.sdh_run_f64):
         fn.restype = ctypes.c_int

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_build
 from gsplat_attack.cameras import look_at_camera
 from gsplat_attack.scenes import make_scene
 from oracle import oracle_r as O
@@ -21,13 +22,7 @@ HM = os.path.join(ROOT, "tests", "host_math")
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(HM, "libhostmath.so")
-    src = os.path.join(HM, "host_math.cpp")
-    hdr = os.path.join(ROOT, "3d-gaussian-splat-attack_amd", "csrc", "gsr_math.h")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.run(["g++", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.dirname(hdr), src, "-o", so],
-                       check=True)
-    return ctypes.CDLL(so)
+    return host_build.host_lib("math")
 
 
 def f32(x):
