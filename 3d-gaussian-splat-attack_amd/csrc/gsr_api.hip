@@ -32,6 +32,7 @@
 #include "gsr_detloss.hip.h"
 #include "gsr_setdet.hip.h"
 #include "gsr_rcnn.hip.h"
+#include "gsr_rpn.hip.h"
 
 using namespace gsr;
 
@@ -1718,7 +1719,7 @@ static int backward_impl(GsrCtx* c, const BwdCall& b) {
   return done(GSR_OK);
 }
 
-// ---- what the four detector stages' entries (further down) share.  A stage states the regions of its workspace once, as a run of take()
+// ---- what the five detector stages' entries (further down) share.  A stage states the regions of its workspace once, as a run of take()
 // calls on a Carve: with no base that run is the sizing pass (off ends as the bytes needed), with the caller's workspace
 // it hands out the pointers -- so *_workspace_bytes and the entry point cannot drift apart.
 static inline size_t det_round(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -1893,7 +1894,8 @@ int gsr_query(int32_t what, int64_t* out) {
       return GSR_OK;
     }
     case 3: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS | GSR_CAP_SETDET; return GSR_OK;     // capability bits 0..3: closed
-    case 4: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS | GSR_CAP_SETDET | GSR_CAP_RCNN; return GSR_OK;     // every capability bit
+    case 4: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS | GSR_CAP_SETDET | GSR_CAP_RCNN; return GSR_OK;     // bits 0..4: closed
+    case 5: *out = GSR_CAP_IMAGE | GSR_CAP_DETECT | GSR_CAP_DETLOSS | GSR_CAP_SETDET | GSR_CAP_RCNN | GSR_CAP_RPN; return GSR_OK;     // every capability bit
     default: return set_err(GSR_ERR_INVALID, "gsr_query: unknown item %d", what);
   }
 }
@@ -2797,6 +2799,103 @@ int gsr_rcnn_postprocess(const GsrRcnnSpec* d, const float* scores, const float*
     return rc;
   hipLaunchKernelGGL(gsr_rcnn::k_rcnn_gather, dim3((unsigned)d->B), dim3(256), 0, st, ar);
   LAUNCH_CHECK("gsr_rcnn_postprocess (gather)");
+  return GSR_OK;
+}
+
+// ---- RPN proposal stage (gsr_rpn.h / gsr_rpn.hip.h): no allocation, no copy, no host wait; every entry checks the members
+// of the spec it uses on the host before the first launch.  Workspace (gsr_rpn_nms alone), each region rounded up to 256
+// bytes: [order B*N i32][nvalid B i32].
+static void rpn_regions(Carve& c, const GsrRpnSpec* d, gsr_rpn::NmsArgs& ar) {
+  ar.order = c.take<int32_t>((size_t)d->B * (size_t)d->N);
+  ar.nvalid = c.take<int32_t>((size_t)d->B);
+}
+
+static void rpn_copy_spec(const GsrRpnSpec* d, gsr_rpn::Spec& sp) {
+  sp.B = d->B; sp.A = d->A; sp.Hf = d->Hf; sp.Wf = d->Wf; sp.stride = d->stride; sp.shift0 = d->shift0; sp.img_w = d->img_w;
+  sp.img_h = d->img_h; sp.min_size = d->min_size; sp.pre_topk = d->pre_topk; sp.level = d->level; sp.cand_offset = d->cand_offset;
+  sp.N = d->N; sp.post_topk = d->post_topk; sp.iou_thr = d->iou_thr; sp.flags = d->flags;
+}
+
+static int rpn_common(const char* fn, const GsrRpnSpec* d) {
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->B > 65535) return set_err(GSR_ERR_INVALID, "%s: B=%d images (1..65535)", fn, d->B);
+  if (d->flags != 0u) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
+  if (d->N < 1 || d->N > gsr_rpn::MAX_SLOTS) return set_err(GSR_ERR_INVALID, "%s: N=%d candidate slots per image (1..%d)", fn, d->N, gsr_rpn::MAX_SLOTS);
+  return GSR_OK;
+}
+
+static int rpn_select_spec(const char* fn, const GsrRpnSpec* d) {
+  if (int rc = rpn_common(fn, d)) return rc;
+  if (d->A < 1 || d->Hf < 1 || d->Wf < 1) return set_err(GSR_ERR_INVALID, "%s: the level is %d anchors on %d x %d cells (sizes >= 1)", fn, d->A, d->Hf, d->Wf);
+  const unsigned long long n_in = (unsigned long long)d->A * (unsigned long long)d->Hf * (unsigned long long)d->Wf;
+  if (n_in > 0x7fffffffull || (unsigned long long)d->B * n_in * 4ull > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in logits or deltas", fn);
+  if (d->stride < 1 || (long long)d->Hf * d->stride > (1ll << 24) || (long long)d->Wf * d->stride > (1ll << 24))
+    return set_err(GSR_ERR_INVALID, "%s: stride=%d (>= 1, Hf * stride and Wf * stride <= 2^24)", fn, d->stride);
+  if (!(d->shift0 >= -3.0e38f && d->shift0 <= 3.0e38f)) return set_err(GSR_ERR_INVALID, "%s: shift0 must be finite", fn);
+  if (!finite_pos(d->img_w) || !finite_pos(d->img_h))
+    return set_err(GSR_ERR_INVALID, "%s: the frame is %g x %g (finite sizes > 0)", fn, (double)d->img_w, (double)d->img_h);
+  if (!finite_nonneg(d->min_size)) return set_err(GSR_ERR_INVALID, "%s: min_size must be finite and >= 0", fn);
+  if (d->pre_topk < 1) return set_err(GSR_ERR_INVALID, "%s: pre_topk=%d (>= 1)", fn, d->pre_topk);
+  if (d->level < 0) return set_err(GSR_ERR_INVALID, "%s: level=%d (>= 0)", fn, d->level);
+  const long long n_l = (long long)std::min<unsigned long long>(n_in, (unsigned long long)d->pre_topk);
+  if (d->cand_offset < 0 || (long long)d->cand_offset + n_l > (long long)d->N)
+    return set_err(GSR_ERR_INVALID, "%s: cand_offset=%d with %lld slots of this level (cand_offset >= 0, cand_offset + min(pre_topk, A*Hf*Wf) <= N=%d)",
+                   fn, d->cand_offset, n_l, d->N);
+  return GSR_OK;
+}
+
+static int rpn_nms_spec(const char* fn, const GsrRpnSpec* d) {
+  if (int rc = rpn_common(fn, d)) return rc;
+  if (d->post_topk < 1 || d->post_topk > std::min(d->N, gsr_rpn::MAX_POST))
+    return set_err(GSR_ERR_INVALID, "%s: post_topk=%d (1..min(N=%d, %d))", fn, d->post_topk, d->N, gsr_rpn::MAX_POST);
+  if (!finite_nonneg(d->iou_thr)) return set_err(GSR_ERR_INVALID, "%s: iou_thr must be finite and >= 0", fn);
+  return GSR_OK;
+}
+
+int gsr_rpn_workspace_bytes(const GsrRpnSpec* d, int64_t* bytes) {
+  if (int rc = rpn_common("gsr_rpn_workspace_bytes", d)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_rpn_workspace_bytes: null bytes");
+  Carve c;
+  gsr_rpn::NmsArgs ar;
+  rpn_regions(c, d, ar);
+  *bytes = (int64_t)c.off;
+  return GSR_OK;
+}
+
+int gsr_rpn_select(const GsrRpnSpec* d, const float* logits, const float* deltas, const float* cell_anchors, float* cand_boxes,
+                   float* cand_scores, int32_t* cand_level, void* stream) {
+  if (int rc = rpn_select_spec("gsr_rpn_select", d)) return rc;
+  if (!logits || !deltas || !cell_anchors || !cand_boxes || !cand_scores || !cand_level)
+    return set_err(GSR_ERR_INVALID, "gsr_rpn_select: null logits / deltas / cell_anchors / cand_boxes / cand_scores / cand_level");
+  if (int rc = check_aligned4("gsr_rpn_select", logits, deltas, cell_anchors, cand_boxes, cand_scores, cand_level)) return rc;
+  gsr_rpn::SelectArgs ar;
+  rpn_copy_spec(d, ar.sp);
+  ar.logits = logits; ar.deltas = deltas; ar.cell_anchors = cell_anchors;
+  ar.cand_boxes = cand_boxes; ar.cand_scores = cand_scores; ar.cand_level = cand_level;
+  hipLaunchKernelGGL(gsr_rpn::k_rpn_select, dim3((unsigned)d->B), dim3(gsr_rpn::RPN_THREADS), 0, static_cast<hipStream_t>(stream), ar);
+  LAUNCH_CHECK("gsr_rpn_select");
+  return GSR_OK;
+}
+
+int gsr_rpn_nms(const GsrRpnSpec* d, const float* cand_boxes, const float* cand_scores, const int32_t* cand_level, void* ws,
+                int64_t ws_bytes, float* proposals, float* scores, int32_t* keep, int32_t* counts, void* stream) {
+  if (int rc = rpn_nms_spec("gsr_rpn_nms", d)) return rc;
+  if (!cand_boxes || !cand_scores || !cand_level || !ws || !proposals || !scores || !keep || !counts)
+    return set_err(GSR_ERR_INVALID, "gsr_rpn_nms: null cand_boxes / cand_scores / cand_level / ws / proposals / scores / keep / counts");
+  gsr_rpn::NmsArgs ar;
+  Carve c(ws);
+  rpn_regions(c, d, ar);
+  if (int rc = check_workspace("gsr_rpn_nms", ws, ws_bytes, c.off, 16, "gsr_rpn_workspace_bytes")) return rc;
+  if (int rc = check_aligned4("gsr_rpn_nms", cand_boxes, cand_scores, cand_level, proposals, scores, keep, counts)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rpn_copy_spec(d, ar.sp);
+  ar.cand_boxes = cand_boxes; ar.cand_scores = cand_scores; ar.cand_level = cand_level;
+  ar.proposals = proposals; ar.scores = scores; ar.keep = keep; ar.counts = counts;
+  hipLaunchKernelGGL(gsr_rpn::k_rpn_order, dim3((unsigned)d->B), dim3(gsr_rpn::RPN_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rpn_nms (order)");
+  hipLaunchKernelGGL(gsr_rpn::k_rpn_walk, dim3((unsigned)d->B), dim3(gsr_rpn::RPN_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rpn_nms (walk)");
   return GSR_OK;
 }
 

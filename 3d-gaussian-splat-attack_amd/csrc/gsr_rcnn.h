@@ -179,9 +179,9 @@ GSR_HD bool score_better(T pa, int ca, T pb, int cb) { return pa > pb || (pa == 
 template <class T>
 GSR_HD T clip(T v, T lo, T hi) { return v < lo ? lo : (v > hi ? hi : v); }   // a NaN stays a NaN
 
-// Box2BoxTransform.apply_deltas and a clip to the image
+// Box2BoxTransform.apply_deltas, before any clip (the proposal stage, gsr_rpn.h, tests this box for finiteness)
 template <class T>
-GSR_HD void apply_deltas(const T* roi, const T* d, const T* w, T img_w, T img_h, T* o) {
+GSR_HD void apply_deltas_raw(const T* roi, const T* d, const T* w, T* o) {
   GSR_FP_STRICT
   const T bw = roi[2] - roi[0], bh = roi[3] - roi[1];
   const T cx = roi[0] + (T)0.5 * bw, cy = roi[1] + (T)0.5 * bh;
@@ -192,10 +192,25 @@ GSR_HD void apply_deltas(const T* roi, const T* d, const T* w, T img_w, T img_h,
   dh = dh < lim ? dh : (dh == dh ? lim : dh);
   const T pcx = dx * bw + cx, pcy = dy * bh + cy;
   const T pw = m_exp(dw) * bw, ph = m_exp(dh) * bh;
-  o[0] = clip<T>(pcx - (T)0.5 * pw, (T)0, img_w);
-  o[1] = clip<T>(pcy - (T)0.5 * ph, (T)0, img_h);
-  o[2] = clip<T>(pcx + (T)0.5 * pw, (T)0, img_w);
-  o[3] = clip<T>(pcy + (T)0.5 * ph, (T)0, img_h);
+  o[0] = pcx - (T)0.5 * pw;
+  o[1] = pcy - (T)0.5 * ph;
+  o[2] = pcx + (T)0.5 * pw;
+  o[3] = pcy + (T)0.5 * ph;
+}
+
+template <class T>
+GSR_HD void clip_box(T* o, T img_w, T img_h) {
+  o[0] = clip<T>(o[0], (T)0, img_w);
+  o[1] = clip<T>(o[1], (T)0, img_h);
+  o[2] = clip<T>(o[2], (T)0, img_w);
+  o[3] = clip<T>(o[3], (T)0, img_h);
+}
+
+// ... and a clip to the image
+template <class T>
+GSR_HD void apply_deltas(const T* roi, const T* d, const T* w, T img_w, T img_h, T* o) {
+  apply_deltas_raw<T>(roi, d, w, o);
+  clip_box<T>(o, img_w, img_h);
 }
 
 }  // namespace gsr_rcnn

@@ -85,6 +85,9 @@ SIGNATURES = {
     "gsr_rcnn_workspace_bytes": (INT, _p(2)),
     "gsr_rcnn_loss": (INT, _p(8) + (I64,) + _p(4)),
     "gsr_rcnn_postprocess": (INT, _p(6) + (I64,) + _p(3)),
+    "gsr_rpn_workspace_bytes": (INT, _p(2)),
+    "gsr_rpn_select": (INT, _p(8)),
+    "gsr_rpn_nms": (INT, _p(5) + (I64,) + _p(5)),
     # ---- library state, profiling, test hooks
     "gsr_query": (INT, (I32, PTR)),
     "gsr_trim_pool": (None, ()),

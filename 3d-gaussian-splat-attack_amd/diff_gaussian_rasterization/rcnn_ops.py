@@ -83,7 +83,7 @@ _lib = _load              # (the entry points' signatures are declared in _signa
 
 
 def available() -> bool:
-    """Bit 4 of gsr_query(4), the item that holds every capability bit (item 3 is closed at bits 0..3): the loaded library
+    """Bit 4 of gsr_query(4), the item that holds bits 0..4 (item 3 is closed at bits 0..3, item 4 at these five): the loaded library
     has the two-stage detector stage.  A library without item 4 refuses it: no stage."""
     return capability(4, GSR_CAP_RCNN)
 

@@ -41,4 +41,8 @@ def __getattr__(name):
     if name in ("ProposalSampler", "RoIHeadLoss", "RoIHeadOutput", "make_roi_loss_fn"):
         from . import roi_detector
         return getattr(roi_detector, name)
+    # the region proposer in front of it
+    if name in ("RpnProposer", "Proposals", "cell_anchors"):
+        from . import proposals
+        return getattr(proposals, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

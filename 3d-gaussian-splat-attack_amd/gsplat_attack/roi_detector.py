@@ -13,7 +13,8 @@ the formulas; INTEGRATION.md lists the stated deviations.
   roi_align         (features, rois, counts, ...) -> pooled [B,S,Cf,PH,PW], differentiable with respect to the features
   RoIHeadLoss       .loss(scores, deltas, sample, gt_boxes) -> (total, items[2] = cls, box)
   RoIHeadOutput     .detect(scores, deltas, proposals) -> (dets, counts); .verdicts(...) on gsr_det_verdict
-  make_roi_loss_fn  renders -> detector_input -> backbone -> proposer (detached) -> sample -> roi_align -> box_head -> loss
+  make_roi_loss_fn  renders -> detector_input -> backbone -> proposer (detached; gsplat_attack.proposals.RpnProposer is one)
+                    -> sample -> roi_align -> box_head -> loss
                     as pgd_attack's loss_fn; it takes the global view indices of the renders (loss_fn.takes_view_index)
 """
 from __future__ import annotations
@@ -133,7 +134,9 @@ def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable,
                      sampler: ProposalSampler, head_loss: RoIHeadLoss, gt_bboxes, target: Union[int, Sequence[int]],
                      output_size=(14, 14), spatial_scale: float = 1.0 / 16.0, sampling_ratio: int = 0) -> Callable:
     """-> loss_fn(renders [B,3,H,W], idx=None) -> total, for pgd_attack(loss_fn=...).  backbone(images) -> features
-    [B,Cf,Hf,Wf]; proposer(features) -> proposals [B,R,4] in image pixels (taken detached, as Detectron2 does);
+    [B,Cf,Hf,Wf]; proposer(features) -> proposals [B,R,4] in image pixels (taken detached, as Detectron2 does), or
+    (proposals, n_prop int32 [B]) where only the first n_prop[b] rows of image b are proposals, as a
+    gsplat_attack.proposals.RpnProposer returns them;
     box_head(pooled [B*S,Cf,PH,PW]) -> (scores [B*S,nc+1], deltas [B*S,4*nc or 4]); gt_bboxes [V,4]: every view's box in the
     frame of the detector's input; target: the class the loss pulls towards, one int or one per view; idx: the views the
     renders show (default 0..B-1).  The sampler's seed is its own: every step draws the same RoIs for the same proposals."""
@@ -148,9 +151,12 @@ def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable,
         features = backbone(detector_input(x) if detector_input is not None else x)
         with torch.no_grad():
             proposals = proposer(features.detach())
+        n_prop = None
+        if not isinstance(proposals, torch.Tensor):                      # (proposals, n_prop): rows beyond the count are no candidates
+            proposals, n_prop = proposals
         gt = gt_all[ids]
         cls = tg_all.expand(gt_all.shape[0])[ids] if tg_all.dim() == 0 else tg_all[ids]
-        smp = sampler.sample(proposals, gt, cls)
+        smp = sampler.sample(proposals, gt, cls, n_prop=n_prop)
         pooled = roi_align(features, smp.rois, smp.counts, output_size, spatial_scale, sampling_ratio)
         B, S = int(pooled.shape[0]), int(pooled.shape[1])
         scores, deltas = box_head(pooled.reshape(B * S, *pooled.shape[2:]))

@@ -958,6 +958,70 @@ int gsr_rcnn_loss(const GsrRcnnSpec* spec, const float* scores, const float* del
 int gsr_rcnn_postprocess(const GsrRcnnSpec* spec, const float* scores, const float* deltas, const float* proposals,
                          const int32_t* n_prop, void* ws, int64_t ws_bytes, float* dets, int32_t* counts, void* stream);
 
+/* ---- RPN proposal stage (capability bit GSR_CAP_RPN of gsr_query(5)) -----------------------------------------------------
+ * The step in front of gsr_rcnn_sample: from the RPN head's objectness logits and anchor deltas to the proposals, as
+ * Detectron2's DefaultAnchorGenerator, Box2BoxTransform, find_top_rpn_proposals and batched_nms compute them (the reference
+ * runs its C4 Faster R-CNN in training mode: the best 12 000 of 15 * Hf * Wf anchors, NMS at 0.7, keep 2 000).  Two
+ * entries: gsr_rpn_select, once per feature level, fills that level's range of the candidate slots; gsr_rpn_nms walks all
+ * slots.  These are the formulas of record (INTEGRATION.md section 8i lists the deviations); csrc/gsr_rpn.h holds the
+ * arithmetic, compiled for the kernels and for a host harness alike.  All arithmetic is float32, every operation rounded
+ * on its own; index-valued results are int32.  One GsrRpnSpec serves both entries, each reading the members named with it.
+ *
+ * gsr_rpn_select (members B, A, Hf, Wf, stride, shift0, img_w, img_h, min_size, pre_topk, level, cand_offset, N).
+ * logits [B,A,Hf,Wf] and deltas [B,4A,Hf,Wf] are the RPN head's own layouts; delta k of anchor a is channel 4a + k.
+ * cell_anchors [A,4] (a device tensor): x1 y1 x2 y2 relative to a cell's shift.  The candidate index of anchor a at cell
+ * (x, y) is i = (y * Wf + x) * A + a, its anchor
+ *       cell_anchors[a] + ((float)(x * stride) + shift0, (float)(y * stride) + shift0)      added to both corners
+ * (shift0 = Detectron2's offset * stride).  The candidates are the first n_l = min(pre_topk, A * Hf * Wf) indices in the
+ * order (logit descending by float comparison, index ascending): +0.0 and -0.0 are equal, and a NaN logit is never a
+ * candidate (with fewer than n_l logits that are not NaN the last ranks stay unused).  The candidate of rank r is decoded
+ * (Box2BoxTransform.apply_deltas with weights 1, 1, 1, 1; w = x2 - x1, cx = x1 + 0.5f * w of the anchor):
+ *       dw = min(d2, log(1000 / 16));  pcx = d0 * w + cx;  pw = exp(dw) * w;  x1' = pcx - 0.5f * pw, x2' = pcx + 0.5f * pw
+ * and y alike.  It is dropped if any of the four unclipped coordinates is not finite; otherwise the box is clipped to
+ * [0, img_w] x [0, img_h] and dropped unless x2' - x1' > min_size and y2' - y1' > min_size.  A dropped candidate does not
+ * free its place for rank pre_topk (Detectron2 filters after its top-k as well).  Slot cand_offset + r of cand_boxes
+ * [B,N,4], cand_scores [B,N] and cand_level [B,N] receives the box, the logit and `level`; a dropped or unused rank
+ * receives zeros and level -1.  Every slot cand_offset .. cand_offset + n_l - 1 is written, no other.  1 <= N <= 16384,
+ * cand_offset >= 0, cand_offset + n_l <= N, level >= 0, pre_topk >= 1, stride >= 1 with Hf * stride, Wf * stride <= 2^24.
+ * One launch, one workgroup per image: a radix select of the n_l-th (logit, index) key, the survivors sorted in LDS.
+ *
+ * gsr_rpn_nms (members B, N, post_topk, iou_thr): 1 <= N <= 16384, 1 <= post_topk <= min(N, 4096).  The slots with
+ * level >= 0 (and a score that is not NaN) are walked in the order (score descending by float comparison with +-0 equal,
+ * slot ascending).  A box is suppressed iff an earlier KEPT box of the same level (levels compared as integers) has
+ * iou > iou_thr -- strict; a NaN IoU is inert; the IoU is gsr_det_nms's, operation by operation:
+ *       inter = max(min(ax2,bx2) - max(ax1,bx1), 0) * max(min(ay2,by2) - max(ay1,by1), 0)
+ *       iou = inter / ((area_a + area_b) - inter),   area = (x2 - x1) * (y2 - y1)
+ * The walk stops after post_topk keeps.  proposals [B,post_topk,4] and scores [B,post_topk] in walk order, zeros beyond
+ * the count; keep [B,post_topk]: the kept slots, -1 beyond; counts [B].  Every element is written.  ws:
+ * gsr_rpn_workspace_bytes(spec) bytes (members B, N) of device memory, 16-byte aligned; gsr_rpn_select needs none.  Two
+ * launches, one workgroup per image each: the order (an LDS sort), then the walk with the kept boxes in LDS.
+ *
+ * Both entries: every tensor argument is a DEVICE pointer.  A size out of range, a frame that is not finite and > 0, a
+ * shift0 that is not finite, a min_size or iou_thr that is not finite and >= 0, unknown flags (none are defined), a
+ * workspace that is too small or misaligned, a NULL required pointer, a tensor that is not 4-byte aligned or more than
+ * 2^31 - 1 elements in a tensor return GSR_ERR_INVALID with a gsr_last_error text before any device call.  No allocation,
+ * no copy, no host synchronisation, no float atomics: everything is enqueued on `stream`; capturable and re-entrant (each
+ * caller with its own workspace and candidate arrays). */
+typedef struct GsrRpnSpec {
+  int32_t B, A, Hf, Wf;      /* images, anchors per cell, the level's feature map */
+  int32_t stride;            /* select: pixels per cell */
+  float   shift0;            /* select: Detectron2's offset * stride */
+  float   img_w, img_h;      /* select: boxes are clipped to this frame */
+  float   min_size;          /* select: both sides must exceed it; Detectron2: 0 */
+  int32_t pre_topk;          /* select: candidates per level and image; Detectron2 in training: 12000 */
+  int32_t level;             /* select: what cand_level receives, >= 0 */
+  int32_t cand_offset;       /* select: the level's first slot */
+  int32_t N;                 /* candidate slots per image, 1..16384 */
+  int32_t post_topk;         /* nms: rows of proposals per image, 1..min(N, 4096); Detectron2 in training: 2000 */
+  float   iou_thr;           /* nms; Detectron2: 0.7 */
+  uint32_t flags;            /* none defined: 0 */
+} GsrRpnSpec;
+int gsr_rpn_workspace_bytes(const GsrRpnSpec* spec, int64_t* bytes);
+int gsr_rpn_select(const GsrRpnSpec* spec, const float* logits, const float* deltas, const float* cell_anchors,
+                   float* cand_boxes, float* cand_scores, int32_t* cand_level, void* stream);
+int gsr_rpn_nms(const GsrRpnSpec* spec, const float* cand_boxes, const float* cand_scores, const int32_t* cand_level, void* ws,
+                int64_t ws_bytes, float* proposals, float* scores, int32_t* keep, int32_t* counts, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
@@ -966,14 +1030,18 @@ int gsr_rcnn_postprocess(const GsrRcnnSpec* spec, const float* scores, const flo
  * detector loss stage (gsr_detloss_workspace_bytes, gsr_detloss); GSR_CAP_SETDET = the set-prediction detector stage
  * (gsr_setdet_workspace_bytes, gsr_setdet_loss, gsr_setdet_postprocess).  Item 3 is closed at these four bits: callers
  * compare its value as a whole, so a build with later stages still reports 15 there;
- * 4 every capability bit of this build: the four above and the later ones.  GSR_CAP_RCNN = the two-stage detector stage
+ * 4 the five bits up to GSR_CAP_RCNN: the four above and GSR_CAP_RCNN = the two-stage detector stage
  * (gsr_rcnn_sample, gsr_roi_align, gsr_roi_align_backward, gsr_rcnn_workspace_bytes, gsr_rcnn_loss, gsr_rcnn_postprocess).
- * A library that predates item 4 answers it with GSR_ERR_INVALID: no later stage. */
+ * A library that predates item 4 answers it with GSR_ERR_INVALID: no later stage.  Item 4 is closed at these five bits
+ * (31), for the same reason as item 3;
+ * 5 every capability bit of this build: the five above and GSR_CAP_RPN = the RPN proposal stage
+ * (gsr_rpn_workspace_bytes, gsr_rpn_select, gsr_rpn_nms).  A library that predates item 5 refuses it alike. */
 #define GSR_CAP_IMAGE 1
 #define GSR_CAP_DETECT 2
 #define GSR_CAP_DETLOSS 4
 #define GSR_CAP_SETDET 8
 #define GSR_CAP_RCNN 16
+#define GSR_CAP_RPN 32
 int gsr_query(int32_t what, int64_t* out);
 
 /* Per-context numbers for roofline accounting: what 0 = num_rendered (N; waits for the forward's count if it was
