@@ -181,23 +181,26 @@ void pool_retag(int dev, void* p, hipStream_t st) {
     if (b.p == p) { b.stream = st; return; }
 }
 
-// a slab = one pool block carved into 256-byte aligned pieces
+// A slab = one pool block carved into pieces that start on 256-byte boundaries.  A slab's regions are stated once, as a
+// run of take() calls in a function of their own (keep_regions, scratch_regions, seg_regions): on a Slab without a block
+// that run is the sizing pass (take hands out null and only advances; block_bytes() is what to ask of the pool), on a
+// Slab over the block it hands out the pointers -- so the size and the carving cannot drift apart.  A take that ends
+// beyond the block clears `ok`, which the caller turns into a refusal before anything is launched.
 struct Slab {
   char* base = nullptr;
   size_t cap = 0, cur = 0;
+  bool ok = true;
+  Slab() = default;
+  Slab(void* blk, size_t bytes) : base(static_cast<char*>(blk)), cap(bytes) {}
   template <typename T>
   T* take(size_t n) {
     cur = (cur + 255) & ~size_t(255);
-    T* r = reinterpret_cast<T*>(base + cur);
+    T* r = base ? reinterpret_cast<T*>(base + cur) : nullptr;
     cur += n * sizeof(T);
+    if (base && cur > cap) ok = false;
     return r;
   }
-};
-
-struct SlabPlan {
-  size_t bytes = 0;
-  template <typename T>
-  void add(size_t n) { bytes = ((bytes + 255) & ~size_t(255)) + n * sizeof(T); }
+  size_t block_bytes() const { return cur + 256; }
 };
 
 // Host-visible slot of ONE forward's pair count.  The kernel that computes the count (k_storage_scan_hist) stores it
@@ -308,9 +311,8 @@ bool side_stream_for(int dev, hipStream_t main, SideStream& out) {
   // lowest priority: its one kernel (SH -> RGB) has the whole binning chain's duration to finish in, and must not take
   // wave slots from the chain's short kernels, which sit on the view's critical path
   int least = 0, greatest = 0;
-  static const int prio_env = [] { const char* e = getenv("GSR_SIDE_PRIORITY"); return e ? atoi(e) : 1; }();
   if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = 0; }
-  if (hipStreamCreateWithPriority(&s.side, hipStreamNonBlocking, prio_env ? least : 0) != hipSuccess ||
+  if (hipStreamCreateWithPriority(&s.side, hipStreamNonBlocking, least) != hipSuccess ||
       hipEventCreateWithFlags(&s.fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&s.join, hipEventDisableTiming) != hipSuccess) {
     (void)hipGetLastError();
@@ -319,67 +321,6 @@ bool side_stream_for(int dev, hipStream_t main, SideStream& out) {
   g_sides.push_back(s);
   out = s;
   return true;
-}
-
-// EXPERIMENT (GSR_COMP_CUMASK=w0,w1,... hex words): the two VALU-bound compositors K6 / K7 of a caller
-// stream run on a companion stream restricted to the given compute units (hipExtStreamCreateWithCUMask), so that the
-// HBM- and latency-bound kernels of OTHER views' streams always find the remaining CUs free of compositor waves.
-// Two event hops per compositor launch.  Off unless the variable is set.
-struct CompStream { int dev; hipStream_t main, comp; hipEvent_t in, out; };
-std::mutex g_comp_mu;
-std::vector<CompStream> g_comps;
-static const std::vector<uint32_t>& comp_mask_env() {
-  static const std::vector<uint32_t> m = [] {
-    std::vector<uint32_t> v;
-    const char* e = getenv("GSR_COMP_CUMASK");
-    if (e) {
-      const char* p = e;
-      while (*p) {
-        char* end = nullptr;
-        const unsigned long w = strtoul(p, &end, 16);
-        if (end == p) break;
-        v.push_back((uint32_t)w);
-        p = (*end == ',') ? end + 1 : end;
-      }
-    }
-    return v;
-  }();
-  return m;
-}
-bool comp_stream_for(int dev, hipStream_t main, CompStream& out) {
-  const std::vector<uint32_t>& mask = comp_mask_env();
-  if (mask.empty()) return false;
-  std::lock_guard<std::mutex> lk(g_comp_mu);
-  for (const CompStream& s : g_comps)
-    if (s.dev == dev && s.main == main) { out = s; return true; }
-  CompStream s{dev, main, nullptr, nullptr, nullptr};
-  if (hipExtStreamCreateWithCUMask(&s.comp, (uint32_t)mask.size(), mask.data()) != hipSuccess ||
-      hipEventCreateWithFlags(&s.in, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s.out, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  g_comps.push_back(s);
-  out = s;
-  return true;
-}
-// hop onto the compositor stream (returns the stream to launch on) and back
-static hipStream_t comp_enter(int dev, hipStream_t st, CompStream& cs, bool& used) {
-  used = comp_stream_for(dev, st, cs);
-  if (!used) return st;
-  if (hipEventRecord(cs.in, st) != hipSuccess || hipStreamWaitEvent(cs.comp, cs.in, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    used = false;
-    return st;
-  }
-  return cs.comp;
-}
-// (false: the join failed -- the caller's stream is NOT ordered behind the compositor stream, which is an error to report)
-static bool comp_leave(hipStream_t st, const CompStream& cs, bool used) {
-  if (!used) return true;
-  const bool ok = hipEventRecord(cs.out, cs.comp) == hipSuccess && hipStreamWaitEvent(st, cs.out, 0) == hipSuccess;
-  if (!ok) (void)hipGetLastError();
-  return ok;
 }
 
 // Count slots of forwards whose context was released before the copy landed (forward-only calls with an asynchronous
@@ -675,11 +616,8 @@ static PreColorBatchArgs color_batch_args(const GsrCtx* c, uint32_t* tcnt) {
 
 // K6 of a context whose binning (pair list, tile ranges, schedule, boundary-record plan) and splat records are in place:
 // the last launch of a forward, and all that a re-render of a kept context needs behind the colour kernel.
-static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hipStream_t st_main) {
+static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hipStream_t st) {
   const GsrSettings* s = &c->st;
-  CompStream comp_s{};
-  bool comp_used = false;
-  hipStream_t st = comp_enter(c->dev, st_main, comp_s, comp_used);
   const int W = s->image_width, H = s->image_height, ntiles = c->ntiles;
   const size_t HW = (size_t)H * W;
   const float* sh_objs = out_objects ? c->sh_objs : nullptr;
@@ -713,17 +651,11 @@ static int launch_render_fwd(GsrCtx* c, float* out_color, float* out_objects, hi
   const bool obj = out_objects && sh_objs;
   if (out_objects && !obj) {
     hipError_t e = hipMemsetAsync(out_objects, 0, sizeof(float) * NUM_OBJ * HW * (size_t)c->B, st);   // (a batch: [B,16,H,W])
-    if (e != hipSuccess) {
-      (void)comp_leave(st_main, comp_s, comp_used);
-      return set_err(GSR_ERR_DEVICE, "objects: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "objects: %s", hipGetErrorString(e));
   }
   const RenderFwdPick k6 = pick_render_fwd(obj, fwd_npx, k6_shared, aux);
   hipLaunchKernelGGL(k6.kern, k6.wpb > 1 ? gridS : gridT, dim3(64 * k6.wpb), 0, st, ra);
-  hipError_t e = hipGetLastError();
-  const bool joined = comp_leave(st_main, comp_s, comp_used);
-  if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "render forward: launch failed: %s", hipGetErrorString(e));
-  if (!joined) return set_err(GSR_ERR_DEVICE, "render forward: joining the compositor stream failed");
+  LAUNCH_CHECK("render forward");
   return GSR_OK;
 }
 
@@ -747,12 +679,21 @@ struct FwdCall {
   void* stream = nullptr;
 };
 
-static int forward_impl(const FwdCall& f) {
+// ---------------------------------------------------------------------------------------------
+// The forward.  forward_impl (at the end of this section) is its table of contents: check, plan, allocate and carve,
+// then one member of FwdRun per pipeline stage.  A new buffer goes into ONE of the region functions (keep_regions,
+// scratch_regions, seg_regions); a new stage is one more `int FwdRun::x()` and one more line of forward_impl.
+// ---------------------------------------------------------------------------------------------
+static int tiles_across(int px) { return (px + TILE - 1) / TILE; }
+// a batch: B views as one virtual scene of B * Ppad Gaussians and B * tpv tiles (a batch of one is an ordinary forward)
+static int batch_views(const FwdCall& f) { return (f.nviews > 1 && f.P > 0) ? f.nviews : 1; }
+static int batch_pad(int32_t P, int B) { return B > 1 ? (int)(((size_t)P + BATCH_PAD - 1) / BATCH_PAD * BATCH_PAD) : P; }
+
+// every refusal of a forward's arguments: nothing has been allocated or launched
+static int check_forward(const FwdCall& f) {
   const GsrSettings* const s = f.s;
   const int32_t P = f.P, K = f.K;
-  const float* sh_objs = f.sh_objs;
   const bool want_aux = f.out_depth != nullptr || f.out_alpha != nullptr;
-  if (f.ctx_out) *f.ctx_out = nullptr;
   if (want_aux && s && (s->flags & GSR_FLAG_NEEDLE_DOUBLE))
     return set_err(GSR_ERR_INVALID, "gsr_forward_aux: depth / alpha maps are not available under GSR_FLAG_NEEDLE_DOUBLE");
   if (want_aux && (f.segb || f.fwd_only))
@@ -774,370 +715,451 @@ static int forward_impl(const FwdCall& f) {
                    s->sh_degree, (s->sh_degree + 1) * (s->sh_degree + 1), K);
   if (!s->bg || !s->viewmatrix || !s->projmatrix || !s->campos)
     return set_err(GSR_ERR_INVALID, "gsr_forward: settings tensors (bg, viewmatrix, projmatrix, campos) must be device pointers");
-  // objects not wanted -- unless the features are to be kept for the backward (GSR_FLAG_OBJECTS_FOR_BACKWARD_ONLY)
-  if (f.out_objects == nullptr && sh_objs != nullptr && !(s->flags & GSR_FLAG_OBJECTS_FOR_BACKWARD_ONLY)) sh_objs = nullptr;
-
-  hipStream_t st = static_cast<hipStream_t>(f.stream);
-  const int dev = cur_dev();
-  const int H = s->image_height, W = s->image_width;
-  const int gridx = (W + TILE - 1) / TILE, gridy = (H + TILE - 1) / TILE;
-  const int tpv = gridx * gridy;                                       // tiles per view
+  const int gridx = tiles_across(s->image_width), gridy = tiles_across(s->image_height);
   if (gridx > 4095 || gridy > 4095) return set_err(GSR_ERR_INVALID, "gsr_forward: image larger than 65520 px per side");
-  // a batch: B views as one virtual scene of B * Ppad Gaussians and B * tpv tiles (a batch of one is an ordinary forward)
-  const int B = (f.nviews > 1 && P > 0) ? f.nviews : 1;
-  const int Ppad = B > 1 ? (int)(((size_t)P + BATCH_PAD - 1) / BATCH_PAD * BATCH_PAD) : P;
-  if ((size_t)B * (size_t)Ppad > (size_t)RANK_MASK)
+  const int B = batch_views(f);
+  if ((size_t)B * (size_t)batch_pad(P, B) > (size_t)RANK_MASK)
     return set_err(GSR_ERR_INVALID, "gsr_forward: more than 2^28 Gaussians (times views of a batch)");
-  if ((size_t)B * (size_t)tpv >= (size_t)SCHED_TILE_MASK) return set_err(GSR_ERR_INVALID, "gsr_forward: more than 2^28 tiles in the batch");
-  const int Pv = B > 1 ? B * Ppad : P;                                 // virtual Gaussians
-  const int ntiles = B * tpv;                                          // virtual tiles
-  const size_t HW = (size_t)H * W * (size_t)B;                         // pixels of all views
+  if ((size_t)B * (size_t)(gridx * gridy) >= (size_t)SCHED_TILE_MASK) return set_err(GSR_ERR_INVALID, "gsr_forward: more than 2^28 tiles in the batch");
+  return GSR_OK;
+}
 
-  GsrCtx* c = new (std::nothrow) GsrCtx();
-  if (!c) return set_err(GSR_ERR_NOMEM, "gsr_forward: host allocation failed");
-  c->dev = dev; c->st = *s; c->P = P; c->K = K; c->gridx = gridx; c->gridy = gridy; c->ntiles = ntiles;
-  c->B = B; c->Ppad = Ppad; c->Pv = Pv; c->tpv = tpv;
-  if (B > 1) c->views.assign(s, s + B);
-  c->means3D = f.means3D; c->shs = f.shs; c->sh_objs = sh_objs; c->colors = f.colors_precomp; c->opac = f.opacities;
-  c->scales = f.scales; c->rots = f.rotations; c->cov3d = f.cov3D_precomp;
-  c->raw = f.raw; c->sh_dc = f.sh_dc;
-  c->fwd_only = f.fwd_only; c->objects_out = f.out_objects != nullptr && sh_objs != nullptr;
-  c->aux = want_aux; c->aux_depth_out = f.out_depth; c->aux_alpha_out = f.out_alpha;
-  if (f.segb) { c->has_b = true; c->b = *f.segb; }
+// The sizes of one forward and the variants it takes: host arithmetic on the call's arguments, plus the pair count an
+// earlier forward of the same (P, H, W) left behind.
+struct FwdPlan {
+  int32_t P = 0, K = 0;
+  int H = 0, W = 0, gridx = 0, gridy = 0;
+  int B = 1, Ppad = 0, Pv = 0, tpv = 0, ntiles = 0;   // GsrCtx has their meaning
+  size_t HW = 0;                    // pixels of all views
+  size_t Pp = 1;                    // max(Pv, 1): what the per-Gaussian regions are sized for
+  uint32_t nbP = 0;                 // chunks of the storage scan / depth sort
+  uint32_t nk1 = 0, nk1v = 0;       // workgroups of K1's geometry half: all views, per view
+  uint32_t nkc = 0;                 // ... of its colour half, per view
+  uint32_t ngroups = 0;
+  int depth_passes = 3;
+  bool group_sums = false;          // K2 reads K1's sums through group sums (k_bout_group_sum)
+  bool lanegroup = false, want_D = false, want_abc = false, needle_double = false;
+  int cull = 1;
+  bool async_count = false;
+  unsigned long long cap_pairs = MAX_PAIRS - 1;
+  const float* sh_objs = nullptr;   // the call's, or null where the object channels are not wanted
+};
 
-  const size_t Pp = (size_t)std::max(Pv, 1);
-  pending_harvest();
+static FwdPlan plan_forward(const FwdCall& f, int dev) {
+  const GsrSettings* const s = f.s;
+  FwdPlan p;
+  p.P = f.P; p.K = f.K;
+  // objects not wanted -- unless the features are to be kept for the backward (GSR_FLAG_OBJECTS_FOR_BACKWARD_ONLY)
+  p.sh_objs = (f.out_objects == nullptr && !(s->flags & GSR_FLAG_OBJECTS_FOR_BACKWARD_ONLY)) ? nullptr : f.sh_objs;
+  p.H = s->image_height; p.W = s->image_width;
+  p.gridx = tiles_across(p.W); p.gridy = tiles_across(p.H);
+  p.tpv = p.gridx * p.gridy;                                           // tiles per view
+  p.B = batch_views(f);
+  p.Ppad = batch_pad(p.P, p.B);
+  p.Pv = p.B > 1 ? p.B * p.Ppad : p.P;                                 // virtual Gaussians
+  p.ntiles = p.B * p.tpv;                                              // virtual tiles
+  p.HW = (size_t)p.H * p.W * (size_t)p.B;
+  p.Pp = (size_t)std::max(p.Pv, 1);
   // Asynchronous pair count (GSR_FLAG_ASYNC_COUNT, or GSR_ASYNC_COUNT=1 in the environment): the host does not wait
   // for the pair count; buffers and grids are sized from the count an earlier forward of the same (P, H, W) saw, with
   // head-room.  Without such an entry this forward counts synchronously (and leaves the entry behind).
   static const int async_env = [] { const char* e = getenv("GSR_ASYNC_COUNT"); return e ? atoi(e) : 0; }();
-  unsigned long long cap_pairs = MAX_PAIRS - 1;
-  bool async_count = false;
-  if (P > 0 && (async_env != 0 || (s->flags & GSR_FLAG_ASYNC_COUNT))) {
+  if (p.P > 0 && (async_env != 0 || (s->flags & GSR_FLAG_ASYNC_COUNT))) {
     unsigned long long seen = 0;
-    if (cap_lookup(CapKey{dev, Pv, H, W}, seen)) {
-      cap_pairs = std::min<unsigned long long>(seen + seen / 4 + 65536ull, MAX_PAIRS - 1);
-      async_count = true;
+    if (cap_lookup(CapKey{dev, p.Pv, p.H, p.W}, seen)) {
+      p.cap_pairs = std::min<unsigned long long>(seen + seen / 4 + 65536ull, MAX_PAIRS - 1);
+      p.async_count = true;
     }
   }
-  // ---- kept slab ---------------------------------------------------------------------------
-  SlabPlan kp;
-  kp.add<float4>(REC * Pp);   // G records (storage order)
-  kp.add<uint32_t>(Pp); kp.add<uint32_t>(Pp + 1); kp.add<uint32_t>(Pp + 1);   // order, off, offg
-  kp.add<uint2>(ntiles); kp.add<float>(HW); kp.add<uint32_t>(HW); kp.add<uint32_t>(DV_WORDS); kp.add<uint32_t>(ntiles);
   // the SH layouts the reference uses (and precomputed colours) take the lane-group kernels
-  c->lanegroup = f.raw || (f.shs && K == 16) || f.colors_precomp != nullptr;
-  const bool want_D = c->lanegroup && f.shs != nullptr && f.ctx_out != nullptr && !f.fwd_only;
-  if (want_D) kp.add<float>(9 * Pp);
-  const bool needle_double = (s->flags & GSR_FLAG_NEEDLE_DOUBLE) != 0u;
-  const bool want_abc = needle_double && c->lanegroup && f.ctx_out != nullptr && !f.fwd_only;
-  if (want_abc) kp.add<double>(Pp);
-  if (B > 1) kp.add<ViewDev>((size_t)B);
-  c->keep_bytes = kp.bytes + 256;
-  c->keep_blk = pool_alloc(dev, c->keep_bytes, st);
-  // ---- scratch slab (released at the end of forward) ----------------------------------------
-  const uint32_t nbP = (uint32_t)((Pp + DCHUNK - 1) / DCHUNK);             // chunks of the storage scan / depth sort
-  const uint32_t nk1 = (uint32_t)((Pp + PREG_BLOCK - 1) / PREG_BLOCK);     // workgroups of K1's geometry half (all views)
-  const uint32_t nk1v = B > 1 ? (uint32_t)(Ppad / PREG_BLOCK) : nk1;       // ... per view
-  const uint32_t nkc = (uint32_t)(((size_t)std::max(P, 1) + PREF_BLOCK - 1) / PREF_BLOCK);   // ... of its colour half, per view
+  p.lanegroup = f.raw || (f.shs && p.K == 16) || f.colors_precomp != nullptr;
+  p.want_D = p.lanegroup && f.shs != nullptr && f.ctx_out != nullptr && !f.fwd_only;
+  p.needle_double = (s->flags & GSR_FLAG_NEEDLE_DOUBLE) != 0u;
+  p.want_abc = p.needle_double && p.lanegroup && f.ctx_out != nullptr && !f.fwd_only;
+  p.cull = (s->flags & GSR_FLAG_NO_CULL) ? 0 : 1;
+  p.nbP = (uint32_t)((p.Pp + DCHUNK - 1) / DCHUNK);
+  p.nk1 = (uint32_t)((p.Pp + PREG_BLOCK - 1) / PREG_BLOCK);
+  p.nk1v = p.B > 1 ? (uint32_t)(p.Ppad / PREG_BLOCK) : p.nk1;
+  p.nkc = (uint32_t)(((size_t)std::max(p.P, 1) + PREF_BLOCK - 1) / PREF_BLOCK);
   // the depth sort: three passes of <= 11 bits (a latency-bound million keys) or four of <= 8 (several million: throughput)
   static const int depth_passes_env = [] { const char* e = getenv("GSR_DEPTH_PASSES"); int v = e ? atoi(e) : 0; return (v == 3 || v == 4) ? v : 0; }();
-  const int depth_passes = depth_passes_env ? depth_passes_env : (Pp >= (size_t(3) << 20) ? 4 : 3);
-  const bool group_sums = nk1 > K1_GROUP_MIN;                              // K2 reads K1's sums through group sums (k_bout_group_sum)
-  const uint32_t ngroups = (nk1 + K1_GROUP - 1) / K1_GROUP;
-  c->depth_passes = depth_passes; c->group_sums = group_sums; c->scan_items = scan_items_for((uint32_t)Pv);
-  SlabPlan sp;
-  sp.add<uint32_t>(Pp); sp.add<uint32_t>(Pp); sp.add<uint32_t>(Pp); sp.add<uint32_t>(Pp); sp.add<uint32_t>(Pp);   // dkey, k1, vtmp, v2, tcnt
-  sp.add<uint32_t>((size_t)RS_BINS_DEV * nbP); sp.add<uint32_t>(RS_BINS_DEV);
-  sp.add<uint4>(nk1); sp.add<uint32_t>(nbP + 2);
-  if (group_sums) sp.add<uint4>(ngroups);
-  sp.add<uint8_t>(Pp);
-  void* scratch_blk = pool_alloc(dev, sp.bytes + 256, st);
-  if (!c->keep_blk || !scratch_blk) {
-    pool_free(dev, scratch_blk);
-    gsr_ctx_free(c);
-    return set_err(GSR_ERR_NOMEM, "gsr_forward: workspace allocation failed (P=%d, %dx%d)", P, W, H);
-  }
-  Slab ks{static_cast<char*>(c->keep_blk), c->keep_bytes, 0};
-  c->G0 = ks.take<float4>(REC * Pp); c->G1 = c->G0 + 1; c->G2 = c->G0 + 2;   // interleaved records, REC float4 apart
-  c->order = ks.take<uint32_t>(Pp); c->off = ks.take<uint32_t>(Pp + 1); c->offg = ks.take<uint32_t>(Pp + 1);
-  c->ranges = ks.take<uint2>(ntiles); c->final_T = ks.take<float>(HW); c->n_contrib = ks.take<uint32_t>(HW);
-  c->dv = ks.take<uint32_t>(DV_WORDS);
-  c->sched = ks.take<uint32_t>(ntiles);
-  if (want_D) c->D = ks.take<float>(9 * Pp);
-  if (want_abc) c->abc = ks.take<double>(Pp);
-  if (B > 1) c->vpack = ks.take<ViewDev>((size_t)B);
-  Slab ss{static_cast<char*>(scratch_blk), sp.bytes + 256, 0};
-  uint32_t* dkey = ss.take<uint32_t>(Pp); uint32_t* k1 = ss.take<uint32_t>(Pp); uint32_t* vtmp = ss.take<uint32_t>(Pp);
-  uint32_t* v2 = ss.take<uint32_t>(Pp); uint32_t* tcnt = ss.take<uint32_t>(Pp);
-  uint32_t* table = ss.take<uint32_t>((size_t)RS_BINS_DEV * nbP); uint32_t* tsums = ss.take<uint32_t>(RS_BINS_DEV);
-  uint4* bout = ss.take<uint4>(nk1);
-  uint32_t* psums = ss.take<uint32_t>(nbP + 2);
-  uint4* gsum = group_sums ? ss.take<uint4>(ngroups) : nullptr;
-  uint8_t* tcnt8 = ss.take<uint8_t>(Pp);
+  p.depth_passes = depth_passes_env ? depth_passes_env : (p.Pp >= (size_t(3) << 20) ? 4 : 3);
+  p.group_sums = p.nk1 > K1_GROUP_MIN;
+  p.ngroups = (p.nk1 + K1_GROUP - 1) / K1_GROUP;
+  return p;
+}
 
-  void* pairs_blk[4] = {nullptr, nullptr, nullptr, nullptr};
-  void* tbl_blk = nullptr;
+// ---- the forward's three slabs: each region list stands here once (see Slab) -------------------------------------
+// the kept slab: what the context holds until gsr_ctx_free
+static void keep_regions(Slab& s, const FwdPlan& p, GsrCtx* c) {
+  c->G0 = s.take<float4>(REC * p.Pp);   // G records (storage order): interleaved, REC float4 apart
+  c->G1 = c->G0 ? c->G0 + 1 : nullptr; c->G2 = c->G0 ? c->G0 + 2 : nullptr;
+  c->order = s.take<uint32_t>(p.Pp); c->off = s.take<uint32_t>(p.Pp + 1); c->offg = s.take<uint32_t>(p.Pp + 1);
+  c->ranges = s.take<uint2>(p.ntiles); c->final_T = s.take<float>(p.HW); c->n_contrib = s.take<uint32_t>(p.HW);
+  c->dv = s.take<uint32_t>(DV_WORDS);
+  c->sched = s.take<uint32_t>(p.ntiles);
+  c->D = p.want_D ? s.take<float>(9 * p.Pp) : nullptr;
+  c->abc = p.want_abc ? s.take<double>(p.Pp) : nullptr;
+  c->vpack = p.B > 1 ? s.take<ViewDev>((size_t)p.B) : nullptr;
+}
+
+// the scratch slab: released at the end of the forward
+struct FwdScratch {
+  uint32_t *dkey = nullptr, *k1 = nullptr, *vtmp = nullptr, *v2 = nullptr, *tcnt = nullptr, *table = nullptr, *tsums = nullptr;
+  uint4* bout = nullptr;
+  uint32_t* psums = nullptr;
+  uint4* gsum = nullptr;            // null unless FwdPlan::group_sums
+  uint8_t* tcnt8 = nullptr;
+};
+
+static void scratch_regions(Slab& s, const FwdPlan& p, FwdScratch& w) {
+  w.dkey = s.take<uint32_t>(p.Pp); w.k1 = s.take<uint32_t>(p.Pp); w.vtmp = s.take<uint32_t>(p.Pp);
+  w.v2 = s.take<uint32_t>(p.Pp); w.tcnt = s.take<uint32_t>(p.Pp);
+  w.table = s.take<uint32_t>((size_t)RS_BINS_DEV * p.nbP); w.tsums = s.take<uint32_t>(RS_BINS_DEV);
+  w.bout = s.take<uint4>(p.nk1);
+  w.psums = s.take<uint32_t>(p.nbP + 2);
+  w.gsum = p.group_sums ? s.take<uint4>(p.ngroups) : nullptr;
+  w.tcnt8 = s.take<uint8_t>(p.Pp);
+}
+
+// the segment slab: boundary records of split tiles, for c->rec_cap records (kept with the context)
+static void seg_regions(Slab& s, GsrCtx* c) {
+  c->bnd = s.take<float4>((size_t)c->rec_cap * PXL * 64); c->rec_item = s.take<uint2>(c->rec_cap);
+  c->segoff = s.take<uint32_t>(c->ntiles);
+}
+
+// What one forward holds while it runs -- the context it is filling and everything transient -- and its stages, in the
+// order forward_impl runs them.
+struct FwdRun {
+  const FwdCall& f;
+  const FwdPlan& p;
+  int dev;
+  hipStream_t st;
+  GsrCtx* c = nullptr;
+  void* scratch_blk = nullptr;
+  FwdScratch w;
+  // The pair-proportional pool blocks of a forward with nbound > 0 pairs: (tile key, depth rank) arrays A and B for the
+  // tile sort to alternate between -- the rank array it ends in stays with the context -- and the sort's table, which
+  // also holds the sums and chunk_first (ngrain entries).
+  uint32_t *tileA = nullptr, *rankA = nullptr, *tileB = nullptr, *rankB = nullptr, *tableN = nullptr;
+  int rounds = 0, tile_bits = 0;
+  uint32_t nbN = 0, ngrain = 0;
+  uint32_t* tsumsN() const { return tableN + RS_BINS * nbN; }
+  uint32_t* chunk_first() const { return tsumsN() + RS_BINS; }
   SideStream side{};
   bool side_used = false;
-  auto fail = [&](int code) {
-    if (side_used) (void)hipStreamWaitEvent(st, side.join, 0);   // nothing of this forward may outlive its workspace
+
+  int allocate();            // the context, its kept slab, the scratch slab
+  int preprocess();          // P > 0: K1 (its colour half forked off: fork_color) and the storage scan
+  int fork_color();
+  int depth_sort();
+  int pair_count();
+  int empty_scene();         // P = 0, instead of the three above
+  int take_pair_buffers();   // nbound > 0: these three
+  int emit();
+  int tile_sort();
+  int render();              // joins the colour half; segments, tile schedule, K6
+  // the forward failed with `code`: nothing of it may outlive its workspace
+  int abandon(int code) {
+    if (side_used) (void)hipStreamWaitEvent(st, side.join, 0);
     pool_free(dev, scratch_blk);
-    pool_free(dev, tbl_blk);
-    for (void* b : pairs_blk) if (b && b != c->rank_blk) pool_free(dev, b);
+    for (void* b : {(void*)tableN, (void*)tileA, (void*)rankA, (void*)tileB, (void*)rankB})
+      if (!(c && b == c->rank_blk)) pool_free(dev, b);
     gsr_ctx_free(c);
     return code;
-  };
-#define F_TRY(stage, expr)                                                                                   \
-  do {                                                                                                       \
-    hipError_t _e = (expr);                                                                                  \
-    if (_e != hipSuccess) return fail(set_err(GSR_ERR_DEVICE, "%s: %s (%s)", stage, hipGetErrorString(_e), #expr)); \
-  } while (0)
-#define F_LAUNCH(stage)                                                                                            \
-  do {                                                                                                             \
-    hipError_t _e = hipGetLastError();                                                                             \
-    if (_e != hipSuccess) return fail(set_err(GSR_ERR_DEVICE, "%s: launch failed: %s", stage, hipGetErrorString(_e))); \
-  } while (0)
+  }
+};
 
-  const ViewArgs va = view_args(*s);
-  const dim3 blk(256);
-  const dim3 blkPre(PREG_BLOCK), gridPre(nk1v), blkCol(PREF_BLOCK), gridCol(nkc);
-  const int cull = (s->flags & GSR_FLAG_NO_CULL) ? 0 : 1;
-  uint32_t nbound = 0;
-  // K1's colour half: on the side stream unless the caller turned that off (GSR_FLAG_NO_SIDE_STREAM / GSR_SIDE_STREAM=0).
-  // GSR_FORK_LATE=1 (experiment) starts it behind the depth sort instead of behind the geometry half.
-  PreArgs color_pa[MAX_BATCH] = {};
-  bool want_color = false;
-  static const int fork_late = [] { const char* e = getenv("GSR_FORK_LATE"); return e ? atoi(e) : 0; }();
-  auto launch_color = [&]() -> int {
-    static const int side_env = [] { const char* e = getenv("GSR_SIDE_STREAM"); return e ? atoi(e) : 1; }();
-    hipStream_t cs = st;
-    if (side_env != 0 && !(s->flags & GSR_FLAG_NO_SIDE_STREAM) && side_stream_for(dev, st, side)) {
-      F_TRY("side stream", hipEventRecord(side.fork, st));
-      F_TRY("side stream", hipStreamWaitEvent(side.side, side.fork, 0));
-      cs = side.side;
-      side_used = true;
-    }
-    // beside the chain: a thin grid (GSR_COLOR_BLOCKS workgroups looping over the chunks); alone: one per chunk
-    static const int col_blocks = [] { const char* e = getenv("GSR_COLOR_BLOCKS"); int v = e ? atoi(e) : 512; return v > 0 ? v : 512; }();
-    const dim3 gridC(side_used ? std::min<unsigned>(gridCol.x, (unsigned)col_blocks) : gridCol.x);
-    // a batch of views: ONE launch reads every SH row once for all the views that see the Gaussian (GSR_BATCH_COLOR=0:
-    // the single-view kernel once per view -- the A/B form)
-    static const int batch_color_env = [] { const char* e = getenv("GSR_BATCH_COLOR"); return e ? atoi(e) : 1; }();
-    if (B > 1 && f.raw && batch_color_env != 0) {
-      hipLaunchKernelGGL(k_pre_color_batch, gridC, blkCol, 0, cs, color_batch_args(c, tcnt));
-    } else {
-      for (int v = 0; v < B; ++v) {
-        hipLaunchKernelGGL(f.raw ? k_pre_color<true> : k_pre_color<false>, gridC, blkCol, 0, cs, color_pa[v]);
-      }
-    }
-    if (side_used) F_TRY("side stream", hipEventRecord(side.join, side.side));
-    return GSR_OK;
-  };
-  if (P > 0) {
-    {
-      StageTimer t(GSR_STAGE_PREPROCESS, st);
-      PreBlockOut bo;
-      bo.bout = bout;
-      bo.ranges = P >= tpv ? c->ranges : nullptr;         // the tile ranges are cleared by K1's first threads
-      bo.ntiles = tpv;
-      if (!bo.ranges) {                                   // fewer Gaussians than tiles: spans (0xFFFFFFFF, 0) by two fills
-        F_TRY("ranges", hipMemset2DAsync(c->ranges, sizeof(uint2), 0xFF, sizeof(uint32_t), ntiles, st));
-        F_TRY("ranges", hipMemset2DAsync(reinterpret_cast<char*>(c->ranges) + sizeof(uint32_t), sizeof(uint2), 0, sizeof(uint32_t), ntiles, st));
-      }
-      if (B > 1) launch_pack_views(c, st);
-      if (c->lanegroup) {
-        // (a batch: one launch per view over that view's padded range of the virtual scene -- the same kernels, their
-        // per-Gaussian arrays offset by v * Ppad; everything behind K1 then runs once over the B * Ppad virtual Gaussians)
-        // (a batch: ONE launch of the geometry kernel over the B views' padded ranges -- view = workgroup / workgroups per
-        // view; everything behind K1 then runs once over the B * Ppad virtual Gaussians.  The colour kernel still runs once
-        // per view, its per-Gaussian arrays offset by v * Ppad.)
-        PreArgs pa = color_args(c, tcnt);      // what the colour half reads; the geometry half adds:
-        pa.Pfill = B > 1 ? Ppad : P; pa.vpack = B > 1 ? c->vpack : nullptr; pa.bpv = (int)nk1v;
-        pa.scales = f.scales; pa.rots = f.rotations; pa.cov3d = f.cov3D_precomp; pa.opac = f.opacities;
-        pa.colors = f.colors_precomp; pa.radii = f.radii; pa.dkey = dkey; pa.tcnt8 = tcnt8; pa.abc = c->abc;
-        pa.scales_b = f.segb ? f.segb->scaling : nullptr; pa.rots_b = f.segb ? f.segb->rotation : nullptr;
-        pa.opac_b = f.segb ? f.segb->opacity : nullptr;
-        pa.cull = cull; pa.bo = bo;
-        hipLaunchKernelGGL(pick_pre_geom(f.raw, needle_double), dim3(nk1), blkPre, 0, st, pa);
-        for (int v = 0; v < B; ++v) {          // the colour kernel, view by view: its per-Gaussian arrays offset by v * Ppad
-          const size_t o = (size_t)v * (size_t)Ppad;
-          color_pa[v] = color_args(c, tcnt + o);
-          color_pa[v].va = view_args(s[v]);
-          color_pa[v].G0 += REC * o; color_pa[v].G1 += REC * o; color_pa[v].G2 += REC * o;
-          if (c->D) color_pa[v].D += 9 * o;
-        }
-        want_color = !f.colors_precomp;
-        if (want_color && !fork_late) { const int rcol = launch_color(); if (rcol != GSR_OK) return rcol; }
-      } else
-        hipLaunchKernelGGL(k_preprocess, gridPre, blkPre, 0, st, P, K, va, (cull ? 1 : 0) | (needle_double ? 2 : 0), f.means3D, f.scales, f.rotations, f.cov3D_precomp,
-                           f.opacities, f.shs, f.colors_precomp, f.radii, c->G0, c->G1, c->G2, dkey, tcnt, bo);
-      // storage-order numbering of the pairs (where the backward puts its partial rows), the depth sort's digit width
-      // and first histogram, the device-side pair count -- published to the host slot by the kernel itself: one launch
-      // stream capture (hipGraph): the forward must not wait for anything, so the count has to be asynchronous, and it is
-      // not published to the host at all (a replayed graph would keep writing into a slot that has long been recycled)
-      hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-      const bool capturing = hipStreamIsCapturing(st, &cap_st) == hipSuccess && cap_st == hipStreamCaptureStatusActive;
-      if (capturing && !async_count)
-        return fail(set_err(GSR_ERR_STATE, "gsr_forward: a stream capture needs GSR_FLAG_ASYNC_COUNT and an earlier forward of "
-                            "the same (P, H, W) on this device (the pair count cannot be waited for while capturing)"));
-      if (!capturing && !slot_get(c->slot)) return fail(set_err(GSR_ERR_NOMEM, "gsr_forward: pinned host slot allocation failed"));
-      c->fwd_stream = st;
-      if (group_sums) hipLaunchKernelGGL(k_bout_group_sum, dim3(ngroups), dim3(K1_GROUP), 0, st, (const uint4*)bout, nk1, gsum);
-      hipLaunchKernelGGL(k_storage_scan_hist, dim3(nbP), blk, 0, st, (uint32_t)Pv, (const uint32_t*)tcnt, (const uint32_t*)dkey,
-                         (const uint4*)bout, (const uint4*)gsum, c->offg, table, nbP, c->dv, cap_pairs, c->slot.dev, c->slot.token,
-                         (uint32_t)depth_passes);
-      F_LAUNCH("preprocess");
-    }
-    {
-      StageTimer t(GSR_STAGE_DEPTH_SORT, st);
-      // Stable argsort of the live depth keys in three passes whose digit width the device chose from the keys' range:
-      // order[r] = Gaussian of depth rank r, r < V = dv[DV_V].  Pass 0 drops the Gaussians that emit nothing (its
-      // histogram came from k_storage_scan_hist), the last pass also gathers cnt[r] = tiles touched by rank r.
-      const uint32_t* nV = c->dv + DV_V;
-      DigitSpec d0{c->dv, 0, 0, 0u}, d1{c->dv, 1, 0, 0u}, d2{c->dv, 2, 0, 0u};
-      if (depth_passes == 4) {
-        // millions of keys (a batch of views, a large scene): four passes of <= 8 bits through the 256-bin kernels; passes
-        // 1-3 in the chunk size the tile sort would pick for that many keys
-        DigitSpec d3{c->dv, 3, 0, 0u};
-        const int rn = radix_rounds_for((uint32_t)Pv);
-        radix_pass<RS_BINS>(dkey, nullptr, k1, vtmp, (uint32_t)Pv, nullptr, d0, DROUNDS, table, tsums, false, 1, 1,
-                            c->dv + DV_V, nullptr, nullptr, st);
-        radix_pass<RS_BINS>(k1, vtmp, dkey, v2, (uint32_t)Pv, nV, d1, rn, table, tsums, true, 0, 0, nullptr, nullptr, nullptr, st);
-        radix_pass<RS_BINS>(dkey, v2, k1, vtmp, (uint32_t)Pv, nV, d2, rn, table, tsums, true, 0, 0, nullptr, nullptr, nullptr, st);
-        radix_pass<RS_BINS>(k1, vtmp, nullptr, c->order, (uint32_t)Pv, nV, d3, rn, table, tsums, true, 0, 0, nullptr, tcnt, v2, st,
-                            nullptr, 0, c->lanegroup ? tcnt8 : nullptr);
-      } else {
-      radix_pass<RS_BINS_DEV>(dkey, nullptr, k1, vtmp, (uint32_t)Pv, nullptr, d0, DROUNDS, table, tsums, false, 1, 1,
-                              c->dv + DV_V, nullptr, nullptr, st);
-      radix_pass<RS_BINS_DEV>(k1, vtmp, dkey, v2, (uint32_t)Pv, nV, d1, DROUNDS, table, tsums, true, 0, 0, nullptr, nullptr,
-                              nullptr, st);
-      radix_pass<RS_BINS_DEV>(dkey, v2, nullptr, c->order, (uint32_t)Pv, nV, d2, DROUNDS, table, tsums, true, 0, 0, nullptr,
-                              tcnt, vtmp, st, nullptr, 0, c->lanegroup ? tcnt8 : nullptr);
-      }
-      F_LAUNCH("depth sort");
-    }
-    if (want_color && fork_late) { const int rcol = launch_color(); if (rcol != GSR_OK) return rcol; }
-    if (!async_count) {
-      // (the rank-order scan is enqueued after this wait: it records the owners of the emission chunks' first slots, an
-      // array sized by N; the depth sort keeps the GPU busy well past the host's wake-up)
-      if (ctx_resolve_count(c) != GSR_OK) return fail(set_err(GSR_ERR_DEVICE, "gsr_forward: reading the pair count failed"));
-      if (c->n64 >= MAX_PAIRS)   // NSUB * N must stay below 2^32
-        return fail(set_err(GSR_ERR_NOMEM, "gsr_forward: %llu (tile, Gaussian) pairs exceed the supported %llu "
-                            "(splats cover too many tiles: check scales / scale_modifier)", c->n64, MAX_PAIRS));
-      nbound = (uint32_t)c->n64;
-    } else {
-      nbound = (uint32_t)cap_pairs;
-    }
+int FwdRun::allocate() {
+  c = new (std::nothrow) GsrCtx();
+  if (!c) return set_err(GSR_ERR_NOMEM, "gsr_forward: host allocation failed");
+  c->dev = dev; c->st = *f.s; c->P = p.P; c->K = p.K; c->gridx = p.gridx; c->gridy = p.gridy; c->ntiles = p.ntiles;
+  c->B = p.B; c->Ppad = p.Ppad; c->Pv = p.Pv; c->tpv = p.tpv;
+  if (p.B > 1) c->views.assign(f.s, f.s + p.B);
+  c->means3D = f.means3D; c->shs = f.shs; c->sh_objs = p.sh_objs; c->colors = f.colors_precomp; c->opac = f.opacities;
+  c->scales = f.scales; c->rots = f.rotations; c->cov3d = f.cov3D_precomp;
+  c->raw = f.raw; c->sh_dc = f.sh_dc;
+  c->fwd_only = f.fwd_only; c->objects_out = f.out_objects != nullptr && p.sh_objs != nullptr;
+  c->aux = f.out_depth != nullptr || f.out_alpha != nullptr; c->aux_depth_out = f.out_depth; c->aux_alpha_out = f.out_alpha;
+  if (f.segb) { c->has_b = true; c->b = *f.segb; }
+  c->lanegroup = p.lanegroup;
+  c->depth_passes = p.depth_passes; c->group_sums = p.group_sums; c->scan_items = scan_items_for((uint32_t)p.Pv);
+  Slab ksize, ssize;
+  keep_regions(ksize, p, c);
+  scratch_regions(ssize, p, w);
+  c->keep_bytes = ksize.block_bytes();
+  c->keep_blk = pool_alloc(dev, c->keep_bytes, st);
+  scratch_blk = pool_alloc(dev, ssize.block_bytes(), st);
+  if (!c->keep_blk || !scratch_blk)
+    return set_err(GSR_ERR_NOMEM, "gsr_forward: workspace allocation failed (P=%d, %dx%d)", p.P, p.W, p.H);
+  Slab ks(c->keep_blk, c->keep_bytes), ss(scratch_blk, ssize.block_bytes());
+  keep_regions(ks, p, c);
+  scratch_regions(ss, p, w);
+  if (!ks.ok || !ss.ok) return set_err(GSR_ERR_STATE, "gsr_forward: a workspace region ends beyond its block");
+  return GSR_OK;
+}
+
+// K1's colour half (SH -> RGB): on the side stream, beside the binning chain, unless the caller turned that off
+// (GSR_FLAG_NO_SIDE_STREAM / GSR_SIDE_STREAM=0).  render() joins it.
+int FwdRun::fork_color() {
+  static const int side_env = [] { const char* e = getenv("GSR_SIDE_STREAM"); return e ? atoi(e) : 1; }();
+  hipStream_t cs = st;
+  if (side_env != 0 && !(f.s->flags & GSR_FLAG_NO_SIDE_STREAM) && side_stream_for(dev, st, side)) {
+    HIP_TRY("side stream", hipEventRecord(side.fork, st));
+    HIP_TRY("side stream", hipStreamWaitEvent(side.side, side.fork, 0));
+    cs = side.side;
+    side_used = true;
+  }
+  // beside the chain: a thin grid (COLOR_BLOCKS workgroups looping over the chunks); alone: one per chunk
+  constexpr unsigned COLOR_BLOCKS = 512;
+  const dim3 gridC(side_used ? std::min<unsigned>(p.nkc, COLOR_BLOCKS) : p.nkc), blkCol(PREF_BLOCK);
+  // a batch of views: ONE launch reads every SH row once for all the views that see the Gaussian
+  if (p.B > 1) hipLaunchKernelGGL(k_pre_color_batch, gridC, blkCol, 0, cs, color_batch_args(c, w.tcnt));
+  else hipLaunchKernelGGL(f.raw ? k_pre_color<true> : k_pre_color<false>, gridC, blkCol, 0, cs, color_args(c, w.tcnt));
+  if (side_used) HIP_TRY("side stream", hipEventRecord(side.join, side.side));
+  return GSR_OK;
+}
+
+// K1 (geometry half, colour half forked off), then the storage scan: storage-order numbering of the pairs (where the
+// backward puts its partial rows), the depth sort's digit width and first histogram, the device-side pair count --
+// published to the host slot by the kernel itself: one launch
+int FwdRun::preprocess() {
+  const int ntiles = p.ntiles;
+  StageTimer t(GSR_STAGE_PREPROCESS, st);
+  PreBlockOut bo;
+  bo.bout = w.bout;
+  bo.ranges = p.P >= p.tpv ? c->ranges : nullptr;     // the tile ranges are cleared by K1's first threads
+  bo.ntiles = p.tpv;
+  if (!bo.ranges) {                                   // fewer Gaussians than tiles: spans (0xFFFFFFFF, 0) by two fills
+    HIP_TRY("ranges", hipMemset2DAsync(c->ranges, sizeof(uint2), 0xFF, sizeof(uint32_t), ntiles, st));
+    HIP_TRY("ranges", hipMemset2DAsync(reinterpret_cast<char*>(c->ranges) + sizeof(uint32_t), sizeof(uint2), 0, sizeof(uint32_t), ntiles, st));
+  }
+  if (p.B > 1) launch_pack_views(c, st);
+  if (c->lanegroup) {
+    // (a batch: ONE launch of the geometry kernel over the B views' padded ranges -- view = workgroup / workgroups per
+    // view; everything behind K1 then runs once over the B * Ppad virtual Gaussians.)
+    PreArgs pa = color_args(c, w.tcnt);      // what the colour half reads; the geometry half adds:
+    pa.Pfill = p.B > 1 ? p.Ppad : p.P; pa.vpack = p.B > 1 ? c->vpack : nullptr; pa.bpv = (int)p.nk1v;
+    pa.scales = f.scales; pa.rots = f.rotations; pa.cov3d = f.cov3D_precomp; pa.opac = f.opacities;
+    pa.colors = f.colors_precomp; pa.radii = f.radii; pa.dkey = w.dkey; pa.tcnt8 = w.tcnt8; pa.abc = c->abc;
+    pa.scales_b = f.segb ? f.segb->scaling : nullptr; pa.rots_b = f.segb ? f.segb->rotation : nullptr;
+    pa.opac_b = f.segb ? f.segb->opacity : nullptr;
+    pa.cull = p.cull; pa.bo = bo;
+    hipLaunchKernelGGL(pick_pre_geom(f.raw, p.needle_double), dim3(p.nk1), dim3(PREG_BLOCK), 0, st, pa);
+    if (!f.colors_precomp) { const int rcol = fork_color(); if (rcol != GSR_OK) return rcol; }
   } else {
-    F_TRY("init", hipMemsetAsync(c->off, 0, sizeof(uint32_t), st));
-    F_TRY("init", hipMemsetAsync(c->offg, 0, sizeof(uint32_t), st));
-    F_TRY("init", hipMemsetAsync(c->dv, 0, sizeof(uint32_t) * DV_WORDS, st));
-    F_TRY("ranges", hipMemsetAsync(c->ranges, 0, sizeof(uint2) * ntiles, st));
-    c->n_known = true;
+    hipLaunchKernelGGL(k_preprocess, dim3(p.nk1v), dim3(PREG_BLOCK), 0, st, p.P, p.K, view_args(*f.s),
+                       (p.cull ? 1 : 0) | (p.needle_double ? 2 : 0), f.means3D, f.scales, f.rotations, f.cov3D_precomp,
+                       f.opacities, f.shs, f.colors_precomp, f.radii, c->G0, c->G1, c->G2, w.dkey, w.tcnt, bo);
+  }
+  // stream capture (hipGraph): the forward must not wait for anything, so the count has to be asynchronous, and it is
+  // not published to the host at all (a replayed graph would keep writing into a slot that has long been recycled)
+  hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(st, &cap_st) == hipSuccess && cap_st == hipStreamCaptureStatusActive;
+  if (capturing && !p.async_count)
+    return set_err(GSR_ERR_STATE, "gsr_forward: a stream capture needs GSR_FLAG_ASYNC_COUNT and an earlier forward of "
+                   "the same (P, H, W) on this device (the pair count cannot be waited for while capturing)");
+  if (!capturing && !slot_get(c->slot)) return set_err(GSR_ERR_NOMEM, "gsr_forward: pinned host slot allocation failed");
+  c->fwd_stream = st;
+  if (p.group_sums) hipLaunchKernelGGL(k_bout_group_sum, dim3(p.ngroups), dim3(K1_GROUP), 0, st, (const uint4*)w.bout, p.nk1, w.gsum);
+  hipLaunchKernelGGL(k_storage_scan_hist, dim3(p.nbP), dim3(256), 0, st, (uint32_t)p.Pv, (const uint32_t*)w.tcnt, (const uint32_t*)w.dkey,
+                     (const uint4*)w.bout, (const uint4*)w.gsum, c->offg, w.table, p.nbP, c->dv, p.cap_pairs, c->slot.dev, c->slot.token,
+                     (uint32_t)p.depth_passes);
+  LAUNCH_CHECK("preprocess");
+  return GSR_OK;
+}
+
+// Stable argsort of the live depth keys in passes whose digit width the device chose from the keys' range:
+// order[r] = Gaussian of depth rank r, r < V = dv[DV_V].  Pass 0 drops the Gaussians that emit nothing (its
+// histogram came from k_storage_scan_hist), the last pass also gathers cnt[r] = tiles touched by rank r.
+int FwdRun::depth_sort() {
+  StageTimer t(GSR_STAGE_DEPTH_SORT, st);
+  const uint32_t Pv = (uint32_t)p.Pv;
+  const uint32_t* nV = c->dv + DV_V;
+  uint8_t* const cnt8 = c->lanegroup ? w.tcnt8 : nullptr;
+  DigitSpec d0{c->dv, 0, 0, 0u}, d1{c->dv, 1, 0, 0u}, d2{c->dv, 2, 0, 0u};
+  if (p.depth_passes == 4) {
+    // millions of keys (a batch of views, a large scene): four passes of <= 8 bits through the 256-bin kernels; passes
+    // 1-3 in the chunk size the tile sort would pick for that many keys
+    DigitSpec d3{c->dv, 3, 0, 0u};
+    const int rn = radix_rounds_for(Pv);
+    radix_pass<RS_BINS>(w.dkey, nullptr, w.k1, w.vtmp, Pv, nullptr, d0, DROUNDS, w.table, w.tsums, false, 1, 1,
+                        c->dv + DV_V, nullptr, nullptr, st);
+    radix_pass<RS_BINS>(w.k1, w.vtmp, w.dkey, w.v2, Pv, nV, d1, rn, w.table, w.tsums, true, 0, 0, nullptr, nullptr, nullptr, st);
+    radix_pass<RS_BINS>(w.dkey, w.v2, w.k1, w.vtmp, Pv, nV, d2, rn, w.table, w.tsums, true, 0, 0, nullptr, nullptr, nullptr, st);
+    radix_pass<RS_BINS>(w.k1, w.vtmp, nullptr, c->order, Pv, nV, d3, rn, w.table, w.tsums, true, 0, 0, nullptr, w.tcnt, w.v2, st,
+                        nullptr, 0, cnt8);
+  } else {
+    radix_pass<RS_BINS_DEV>(w.dkey, nullptr, w.k1, w.vtmp, Pv, nullptr, d0, DROUNDS, w.table, w.tsums, false, 1, 1,
+                            c->dv + DV_V, nullptr, nullptr, st);
+    radix_pass<RS_BINS_DEV>(w.k1, w.vtmp, w.dkey, w.v2, Pv, nV, d1, DROUNDS, w.table, w.tsums, true, 0, 0, nullptr, nullptr,
+                            nullptr, st);
+    radix_pass<RS_BINS_DEV>(w.dkey, w.v2, nullptr, c->order, Pv, nV, d2, DROUNDS, w.table, w.tsums, true, 0, 0, nullptr,
+                            w.tcnt, w.vtmp, st, nullptr, 0, cnt8);
+  }
+  LAUNCH_CHECK("depth sort");
+  return GSR_OK;
+}
+
+// nbound: what every pair-proportional buffer and grid is sized for -- the exact count, waited for, or the guess
+int FwdRun::pair_count() {
+  uint32_t nbound = 0;
+  if (!p.async_count) {
+    // (the rank-order scan is enqueued after this wait: it records the owners of the emission chunks' first slots, an
+    // array sized by N; the depth sort keeps the GPU busy well past the host's wake-up)
+    if (ctx_resolve_count(c) != GSR_OK) return set_err(GSR_ERR_DEVICE, "gsr_forward: reading the pair count failed");
+    if (c->n64 >= MAX_PAIRS)   // NSUB * N must stay below 2^32
+      return set_err(GSR_ERR_NOMEM, "gsr_forward: %llu (tile, Gaussian) pairs exceed the supported %llu "
+                     "(splats cover too many tiles: check scales / scale_modifier)", c->n64, MAX_PAIRS);
+    nbound = (uint32_t)c->n64;
+  } else {
+    nbound = (uint32_t)p.cap_pairs;
   }
   c->nbound = nbound;
-  c->async_count = async_count;
-  if (nbound == 0 && P > 0) F_TRY("init", hipMemsetAsync(c->off, 0, sizeof(uint32_t), st));
-  if (nbound > 0) {
-    const int rounds = radix_rounds_for(nbound);
-    c->tile_rounds = rounds;
-    const uint32_t chunkN = (uint32_t)rs_chunk(rounds);
-    const uint32_t nbN = (nbound + chunkN - 1) / chunkN;
-    const uint32_t tblN = RS_BINS * nbN;
-    for (int i = 0; i < 4; ++i) {
-      pairs_blk[i] = pool_alloc(dev, sizeof(uint32_t) * (size_t)nbound, st);
-      if (!pairs_blk[i]) return fail(set_err(GSR_ERR_NOMEM, "gsr_forward: pair buffers (N=%u) allocation failed", nbound));
-    }
-    const uint32_t ngrain = nbound / EMIT_GRAIN + 4;            // chunk_first entries
-    tbl_blk = pool_alloc(dev, sizeof(uint32_t) * ((size_t)tblN + RS_BINS + ngrain), st);
-    if (!tbl_blk) return fail(set_err(GSR_ERR_NOMEM, "gsr_forward: sort table allocation failed"));
-    uint32_t* tileA = static_cast<uint32_t*>(pairs_blk[0]); uint32_t* rankA = static_cast<uint32_t*>(pairs_blk[1]);
-    uint32_t* tileB = static_cast<uint32_t*>(pairs_blk[2]); uint32_t* rankB = static_cast<uint32_t*>(pairs_blk[3]);
-    uint32_t* tableN = static_cast<uint32_t*>(tbl_blk);
-    uint32_t* tsumsN = tableN + tblN;
-    uint32_t* chunk_first = tsumsN + RS_BINS;
-    const int tile_bits = ceil_log2((uint32_t)ntiles + 1);   // keys are 0..ntiles (ntiles = culled pair)
-    {
-      StageTimer t(GSR_STAGE_BIN, st);
-      // off[r] = pairs emitted by the ranks in front of r, off[V] = their total; chunk_first[c] = rank that owns slot
-      // c * EMIT_GRAIN
-      // (two launches: block sums, then carry + local scan.  Round 3's one-launch variant, in which a block waited for its
-      // predecessors' published sums, saved 2.4 us and could, in principle, give up waiting with nothing but a poisoned
-      // image to show for it: removed)
-      scan_exclusive_u32(depth_passes == 4 ? v2 : vtmp, c->off, (uint32_t)Pv, c->dv + DV_V, psums, st, chunk_first, (uint32_t)EMIT_GRAIN, ngrain);
-      F_LAUNCH("rank scan");
-      int sh0; uint32_t mask0;
-      radix_first_digit(tile_bits, sh0, mask0);
-      // a batch: the view of a virtual Gaussian is g / Ppad (one multiply by ceil(2^32 / Ppad) and one correction)
-      const uint32_t e_ppad = B > 1 ? (uint32_t)Ppad : 0u;
-      const uint32_t e_magic = B > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)Ppad - 1ull) / (uint64_t)Ppad) : 0u;
-      const bool rmin = rounds == RS_ROUNDS_MIN;
-      hipLaunchKernelGGL(rmin ? k_emit<RS_ROUNDS_MIN> : k_emit<RS_ROUNDS_MAX>, dim3(nbN),
-                         dim3(rs_chunk(rmin ? RS_ROUNDS_MIN : RS_ROUNDS_MAX) / EMIT_PER_THREAD), 0, st, (const uint32_t*)c->off, (const uint32_t*)c->order,
-                         (const uint32_t*)chunk_first, (const uint32_t*)c->dv, (const float4*)c->G0, (const float4*)c->G1, (const float4*)c->G2, gridx, W, H,
-                         (uint32_t)ntiles, cull, tileA, rankA, tableN, nbN, mask0, e_ppad, e_magic, (uint32_t)tpv);
-      F_LAUNCH("emit");
-    }
-    int res;
-    {
-      StageTimer t(GSR_STAGE_TILE_SORT, st);
-      res = radix_sort_pairs(tileA, rankA, tileB, rankB, nbound, c->dv + DV_N, 0, tile_bits, false, tableN, tsumsN, st, true,
-                             reinterpret_cast<uint32_t*>(c->ranges), (uint32_t)ntiles);
-      F_LAUNCH("tile sort");
-    }
-    c->pair_rank = res ? rankB : rankA;
-    c->rank_blk = res ? pairs_blk[3] : pairs_blk[1];
-    pool_free(dev, tbl_blk);
-    tbl_blk = nullptr;
-    for (void* b : pairs_blk) if (b != c->rank_blk) pool_free(dev, b);
-    for (void*& b : pairs_blk) b = nullptr;
+  c->async_count = p.async_count;
+  if (nbound == 0) HIP_TRY("init", hipMemsetAsync(c->off, 0, sizeof(uint32_t), st));
+  return GSR_OK;
+}
+
+// P = 0: no pairs, every tile's span empty; the compositor paints the background
+int FwdRun::empty_scene() {
+  const int ntiles = c->ntiles;
+  HIP_TRY("init", hipMemsetAsync(c->off, 0, sizeof(uint32_t), st));
+  HIP_TRY("init", hipMemsetAsync(c->offg, 0, sizeof(uint32_t), st));
+  HIP_TRY("init", hipMemsetAsync(c->dv, 0, sizeof(uint32_t) * DV_WORDS, st));
+  HIP_TRY("ranges", hipMemsetAsync(c->ranges, 0, sizeof(uint2) * ntiles, st));
+  c->n_known = true;
+  return GSR_OK;
+}
+
+int FwdRun::take_pair_buffers() {
+  const uint32_t nbound = c->nbound;
+  c->tile_rounds = rounds = radix_rounds_for(nbound);
+  const uint32_t chunkN = (uint32_t)rs_chunk(rounds);
+  nbN = (nbound + chunkN - 1) / chunkN;
+  for (uint32_t** b : {&tileA, &rankA, &tileB, &rankB}) {
+    *b = static_cast<uint32_t*>(pool_alloc(dev, sizeof(uint32_t) * (size_t)nbound, st));
+    if (!*b) return set_err(GSR_ERR_NOMEM, "gsr_forward: pair buffers (N=%u) allocation failed", nbound);
   }
-  if (side_used) F_TRY("side stream", hipStreamWaitEvent(st, side.join, 0));   // the colours are in place from here on
+  ngrain = nbound / EMIT_GRAIN + 4;
+  tableN = static_cast<uint32_t*>(pool_alloc(dev, sizeof(uint32_t) * ((size_t)(RS_BINS * nbN) + RS_BINS + ngrain), st));
+  if (!tableN) return set_err(GSR_ERR_NOMEM, "gsr_forward: sort table allocation failed");
+  tile_bits = ceil_log2((uint32_t)c->ntiles + 1);             // keys are 0..ntiles (ntiles = culled pair)
+  return GSR_OK;
+}
+
+// The rank-order scan -- off[r] = pairs emitted by the ranks in front of r, off[V] = their total; chunk_first[c] = rank
+// that owns slot c * EMIT_GRAIN -- and the emission of the (tile, rank) pairs.
+int FwdRun::emit() {
+  StageTimer t(GSR_STAGE_BIN, st);
+  // (two launches: block sums, then carry + local scan.  Round 3's one-launch variant, in which a block waited for its
+  // predecessors' published sums, saved 2.4 us and could, in principle, give up waiting with nothing but a poisoned
+  // image to show for it: removed)
+  scan_exclusive_u32(p.depth_passes == 4 ? w.v2 : w.vtmp, c->off, (uint32_t)p.Pv, c->dv + DV_V, w.psums, st, chunk_first(),
+                     (uint32_t)EMIT_GRAIN, ngrain);
+  LAUNCH_CHECK("rank scan");
+  int sh0; uint32_t mask0;
+  radix_first_digit(tile_bits, sh0, mask0);
+  // a batch: the view of a virtual Gaussian is g / Ppad (one multiply by ceil(2^32 / Ppad) and one correction)
+  const uint32_t e_ppad = p.B > 1 ? (uint32_t)p.Ppad : 0u;
+  const uint32_t e_magic = p.B > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)p.Ppad - 1ull) / (uint64_t)p.Ppad) : 0u;
+  const bool rmin = rounds == RS_ROUNDS_MIN;
+  hipLaunchKernelGGL(rmin ? k_emit<RS_ROUNDS_MIN> : k_emit<RS_ROUNDS_MAX>, dim3(nbN),
+                     dim3(rs_chunk(rmin ? RS_ROUNDS_MIN : RS_ROUNDS_MAX) / EMIT_PER_THREAD), 0, st, (const uint32_t*)c->off, (const uint32_t*)c->order,
+                     (const uint32_t*)chunk_first(), (const uint32_t*)c->dv, (const float4*)c->G0, (const float4*)c->G1, (const float4*)c->G2,
+                     p.gridx, p.W, p.H, (uint32_t)p.ntiles, p.cull, tileA, rankA, tableN, nbN, mask0, e_ppad, e_magic,
+                     (uint32_t)p.tpv);
+  LAUNCH_CHECK("emit");
+  return GSR_OK;
+}
+
+// The pairs sorted by tile (stable: depth order within a tile survives), the tiles' spans found on the way.  The rank
+// array the sort ended in stays with the context; the other pair buffers and the table go back to the pool.
+int FwdRun::tile_sort() {
+  int res;
   {
-    StageTimer t(GSR_STAGE_RENDER_FWD, st);
-    // Long tile lists are split into segments for the backward (gsr_kernels.hip.h, "Segments"): the forward stores the
-    // per-pixel (T, C) at the segment boundaries -- with object channels too (round 5): a backward without dL/dobjects then
-    // still walks segments; one WITH dL/dobjects ignores the records (the 16 running object sums are not stored).  Not
-    // for a forward-only call, not under GSR_FLAG_NO_SEGMENTS.
-    static const int seg_shift_env = [] { const char* e = getenv("GSR_SEG_SHIFT"); int v = e ? atoi(e) : 8; return (v >= 6 && v <= 16) ? v : 8; }();
-    if (nbound > 0 && f.ctx_out && !f.fwd_only && !(s->flags & GSR_FLAG_NO_SEGMENTS)) {
-      const uint32_t per = nbound >> seg_shift_env;
-      c->seg_shift = (uint32_t)seg_shift_env;
-      // sum over split tiles of ceil(len / seg) <= N / seg + min(T, N / seg): every split tile's records always fit
-      c->rec_cap = per + std::min<uint32_t>((uint32_t)ntiles, per) + 1u;
-      SlabPlan gp;
-      gp.add<float4>((size_t)c->rec_cap * PXL * 64); gp.add<uint2>(c->rec_cap); gp.add<uint32_t>(ntiles);
-      c->seg_blk = pool_alloc(dev, gp.bytes + 256, st);
-      if (!c->seg_blk) return fail(set_err(GSR_ERR_NOMEM, "gsr_forward: segment boundary buffer (N=%u) allocation failed", nbound));
-      Slab gs{static_cast<char*>(c->seg_blk), gp.bytes + 256, 0};
-      c->bnd = gs.take<float4>((size_t)c->rec_cap * PXL * 64); c->rec_item = gs.take<uint2>(c->rec_cap);
-      c->segoff = gs.take<uint32_t>(ntiles);
-    }
-    // always: it also turns the empty spans the tile sort left untouched into (0, 0)
-    // (more than 64 KB of dynamic LDS at 4K: a single workgroup may use all of the CU's 160 KB on gfx950)
-    // If the limit cannot be raised the lengths of the tiles beyond the default 64 KB's worth are read from HBM instead.
-    static const int sched_lds_cap = [] {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_schedule),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SCHED_LDS_TILES);
-      (void)hipGetLastError();
-      return e == hipSuccess ? SCHED_LDS_TILES : SCHED_LDS_TILES_DEFAULT;
-    }();
-    static const int batch_sched_env = [] { const char* e = getenv("GSR_BATCH_SCHED"); return e ? atoi(e) : 0; }();
-    hipLaunchKernelGGL(k_tile_schedule, dim3((c->segoff ? 2 : 1) * B), dim3(1024), sched_lds_bytes(tpv, sched_lds_cap), st, tpv,
-                       sched_lds_cap, c->ranges, c->sched, c->seg_shift, c->segoff, c->rec_item, c->rec_cap, c->dv + DV_NREC, B,
-                       batch_sched_env);
-    F_LAUNCH("tile schedule");
-    const int rk6 = launch_render_fwd(c, f.out_color, f.out_objects, st);
-    if (rk6 != GSR_OK) return fail(rk6);
-    c->aux_depth_out = nullptr; c->aux_alpha_out = nullptr;      // the caller's buffers: written once, by this launch
+    StageTimer t(GSR_STAGE_TILE_SORT, st);
+    res = radix_sort_pairs(tileA, rankA, tileB, rankB, c->nbound, c->dv + DV_N, 0, tile_bits, false, tableN, tsumsN(), st, true,
+                           reinterpret_cast<uint32_t*>(c->ranges), (uint32_t)c->ntiles);
+    LAUNCH_CHECK("tile sort");
   }
-  pool_free(dev, scratch_blk);
+  c->pair_rank = res ? rankB : rankA;
+  c->rank_blk = c->pair_rank;
+  pool_free(dev, tableN);
+  for (uint32_t* k : {tileA, rankA, tileB, rankB}) if (k != c->pair_rank) pool_free(dev, k);
+  tableN = tileA = rankA = tileB = rankB = nullptr;
+  return GSR_OK;
+}
+
+// The boundary-record plan of split tiles, the tile schedule, K6.
+int FwdRun::render() {
+  if (side_used) HIP_TRY("side stream", hipStreamWaitEvent(st, side.join, 0));   // the colours are in place from here on
+  StageTimer t(GSR_STAGE_RENDER_FWD, st);
+  // Long tile lists are split into segments for the backward (gsr_kernels.hip.h, "Segments"): the forward stores the
+  // per-pixel (T, C) at the segment boundaries -- with object channels too (round 5): a backward without dL/dobjects then
+  // still walks segments; one WITH dL/dobjects ignores the records (the 16 running object sums are not stored).  Not
+  // for a forward-only call, not under GSR_FLAG_NO_SEGMENTS.
+  static const int seg_shift_env = [] { const char* e = getenv("GSR_SEG_SHIFT"); int v = e ? atoi(e) : 8; return (v >= 6 && v <= 16) ? v : 8; }();
+  if (c->nbound > 0 && f.ctx_out && !f.fwd_only && !(f.s->flags & GSR_FLAG_NO_SEGMENTS)) {
+    const uint32_t per = c->nbound >> seg_shift_env;
+    c->seg_shift = (uint32_t)seg_shift_env;
+    // sum over split tiles of ceil(len / seg) <= N / seg + min(T, N / seg): every split tile's records always fit
+    c->rec_cap = per + std::min<uint32_t>((uint32_t)p.ntiles, per) + 1u;
+    Slab gsize;
+    seg_regions(gsize, c);
+    c->seg_blk = pool_alloc(dev, gsize.block_bytes(), st);
+    if (!c->seg_blk) return set_err(GSR_ERR_NOMEM, "gsr_forward: segment boundary buffer (N=%u) allocation failed", c->nbound);
+    Slab gs(c->seg_blk, gsize.block_bytes());
+    seg_regions(gs, c);
+    if (!gs.ok) return set_err(GSR_ERR_STATE, "gsr_forward: a segment region ends beyond its block");
+  }
+  // always: it also turns the empty spans the tile sort left untouched into (0, 0)
+  // (more than 64 KB of dynamic LDS at 4K: a single workgroup may use all of the CU's 160 KB on gfx950)
+  // If the limit cannot be raised the lengths of the tiles beyond the default 64 KB's worth are read from HBM instead.
+  static const int sched_lds_cap = [] {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_schedule),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SCHED_LDS_TILES);
+    (void)hipGetLastError();
+    return e == hipSuccess ? SCHED_LDS_TILES : SCHED_LDS_TILES_DEFAULT;
+  }();
+  static const int batch_sched_env = [] { const char* e = getenv("GSR_BATCH_SCHED"); return e ? atoi(e) : 0; }();
+  hipLaunchKernelGGL(k_tile_schedule, dim3((c->segoff ? 2 : 1) * p.B), dim3(1024), sched_lds_bytes(p.tpv, sched_lds_cap), st, p.tpv,
+                     sched_lds_cap, c->ranges, c->sched, c->seg_shift, c->segoff, c->rec_item, c->rec_cap, c->dv + DV_NREC, p.B,
+                     batch_sched_env);
+  LAUNCH_CHECK("tile schedule");
+  const int rk6 = launch_render_fwd(c, f.out_color, f.out_objects, st);
+  if (rk6 != GSR_OK) return rk6;
+  c->aux_depth_out = nullptr; c->aux_alpha_out = nullptr;      // the caller's buffers: written once, by this launch
+  return GSR_OK;
+}
+
+static int forward_impl(const FwdCall& f) {
+  if (f.ctx_out) *f.ctx_out = nullptr;
+  if (const int rc = check_forward(f)) return rc;
+  const int dev = cur_dev();
+  pending_harvest();
+  const FwdPlan p = plan_forward(f, dev);
+  FwdRun run{f, p, dev, static_cast<hipStream_t>(f.stream)};
+  int r;
+  if ((r = run.allocate()) != GSR_OK) return run.abandon(r);
+  if (p.P > 0) {
+    if ((r = run.preprocess()) != GSR_OK) return run.abandon(r);
+    if ((r = run.depth_sort()) != GSR_OK) return run.abandon(r);
+    if ((r = run.pair_count()) != GSR_OK) return run.abandon(r);
+  } else {
+    if ((r = run.empty_scene()) != GSR_OK) return run.abandon(r);
+  }
+  if (run.c->nbound > 0) {
+    if ((r = run.take_pair_buffers()) != GSR_OK) return run.abandon(r);
+    if ((r = run.emit()) != GSR_OK) return run.abandon(r);
+    if ((r = run.tile_sort()) != GSR_OK) return run.abandon(r);
+  }
+  if ((r = run.render()) != GSR_OK) return run.abandon(r);
+  GsrCtx* c = run.c;
+  pool_free(dev, run.scratch_blk);
   if (f.num_rendered) *f.num_rendered = c->n_known ? (int64_t)c->n64 : (int64_t)-1;   // -1: not known yet (asynchronous count)
   if (f.ctx_out) *f.ctx_out = c; else gsr_ctx_free(c);
   return GSR_OK;
-#undef F_TRY
-#undef F_LAUNCH
 }
 
 // The raw entry points name their inputs as the reference model does (RawSeg); this is where those names meet
@@ -1456,13 +1478,6 @@ static bool batch_k9_fused() {
 struct GradOut {
   float *means3D = nullptr, *means2D = nullptr, *shs = nullptr, *sh_dc = nullptr, *sh_objs = nullptr,
         *colors_precomp = nullptr, *opacities = nullptr, *scales = nullptr, *rotations = nullptr, *cov3D = nullptr;
-  // view v's own buffers of a per-view batch backward: the six raw attribute gradients lie v * stride floats further
-  GradOut of_view(int v, int64_t stride) const {
-    GradOut g = *this;
-    for (float** p : {&g.means3D, &g.shs, &g.sh_dc, &g.opacities, &g.scales, &g.rotations})
-      if (*p) *p += (size_t)v * (size_t)stride;
-    return g;
-  }
 };
 
 // One backward, as every backward entry point hands it to backward_impl.
@@ -1487,64 +1502,88 @@ static int check_ctx_kind(const char* fn, const GsrCtx* c, bool want_raw) {
   return set_err(GSR_ERR_STATE, "%s: context came from gsr_forward; use gsr_backward", fn);
 }
 
-static int backward_impl(GsrCtx* c, const BwdCall& b) {
-  if (!c) return set_err(GSR_ERR_STATE, "gsr_backward: null context");
-  const GradOut& d = b.d;
-  int nchunks = b.nchunks;
-  // gsr_ctx_request_sumsq is one-shot: the request is taken (and the context disarmed) here, whatever this call's fate --
-  // a backward that fails early must not leave the next one writing six doubles to a buffer that may be gone by then
-  double* ss_out = c->sumsq_out;
-  c->sumsq_out = nullptr;
-  // gsr_ctx_set_aux_grads is one-shot in the same way
-  const float* const aux_gd = c->aux_gd;
-  const float* const aux_ga = c->aux_ga;
-  c->aux_gd = nullptr; c->aux_ga = nullptr;
-  const bool aux = aux_gd != nullptr || aux_ga != nullptr;
-  if (!b.grad_color) return set_err(GSR_ERR_INVALID, "gsr_backward: grad_color is null");
-  hipStream_t st = static_cast<hipStream_t>(b.stream);
-  const int dev = c->dev;
-  const int P = c->P;
-  if (c->fwd_only)
-    return set_err(GSR_ERR_STATE, "gsr_backward: the context was kept by gsr_forward_raw2_keep (re-render only, no backward state)");
-  if (P == 0) return GSR_OK;
-  const bool obj = b.grad_objects != nullptr && c->sh_objs != nullptr;
-  // Only colour-side gradients wanted (SH / precomputed colours / object features): K7 and K8+K9 drop the geometry
-  // sums and the projection chain rule (the colour attack; BASELINE configs 2 and 3).
-  const bool geom = d.means3D || d.means2D || d.opacities || d.scales || d.rotations || d.cov3D;
-  if (aux) {
-    // (argument checks only: nothing has been launched)
-    if (b.view_stride != 0)
-      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: the per-view batch backward (gsr_backward_raw_batch_views / _obj_views) "
-                     "does not take depth / alpha gradients");
-    if (nchunks > 1)
-      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: gsr_backward_raw_chunked with more than one range does not take "
-                     "depth / alpha gradients");
-    if (b.grad_objects != nullptr)
-      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: depth / alpha gradients and grad_objects in one backward are not supported");
-    if (!geom)
-      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: depth / alpha gradients reach geometry and opacity only, and this "
-                     "backward asks for no such gradient");
-    if (!c->lanegroup)
-      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: a gsr_forward context with K != 16 SH coefficients does not take "
-                     "depth / alpha gradients");
-    if (c->st.flags & GSR_FLAG_NEEDLE_DOUBLE)
-      return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: not available under GSR_FLAG_NEEDLE_DOUBLE");
-  }
-  // an asynchronous-count forward: its pair count must have fitted the capacity guess (else the image it produced was
-  // poisoned with NaN and nothing downstream of it is meaningful).  (A forward recorded into a hipGraph publishes
-  // nothing to the host: c->slot is empty and this is a no-op.)
-  if (ctx_resolve_count(c) != GSR_OK) return set_err(GSR_ERR_DEVICE, "gsr_backward: reading the forward's pair count failed");
-  if (c->overflow)
-    return set_err(GSR_ERR_OVERFLOW, "gsr_backward: the forward emitted %llu (tile, Gaussian) pairs, more than the capacity "
-                   "%u guessed from earlier views (GSR_FLAG_ASYNC_COUNT); its image was filled with NaN -- render again",
-                   c->n64, c->nbound);
+// ---------------------------------------------------------------------------------------------
+// The backward.  backward_impl (at the end of this section) refuses what it has to before anything is allocated or
+// launched, then runs K7 (render_bwd) and the per-Gaussian stage K8+K9 (pre_bwd).
+// ---------------------------------------------------------------------------------------------
+// What one backward holds while it runs.
+struct BwdRun {
+  GsrCtx* c;
+  const BwdCall& b;
+  hipStream_t st;
+  // the context's one-shot requests, taken (and the context disarmed) when the call starts
+  double* ss_out = nullptr;                           // gsr_ctx_request_sumsq
+  const float *aux_gd = nullptr, *aux_ga = nullptr;   // gsr_ctx_set_aux_grads
+  bool aux = false;                                   // ... either of them
+  bool obj = false;                 // dL/d object channels comes in and the context has object features
+  bool geom = false;                // a geometry-side gradient is wanted
+  int nchunks = 1;                  // ranges of the per-Gaussian stage
+  bool batch_fused = false;         // a batch's per-Gaussian stage is ONE k_pre_bwd_batch launch per range
+  bool segs_on = false;             // K7 walks the long lists as segments
+  int bwd_npx = 4;                  // pixels per lane of K7
+  uint32_t nsub = 1;                // K7's partial rows per pair: PXL / bwd_npx
+  uint32_t tag_lo = 0, tag_hi = 0;  // 64-bit tag of this call: K7 stamps it into every partial row it writes, K8/K9 ignores rows without it
+  float4 *part = nullptr, *part_obj = nullptr;   // K7's partial rows (pool blocks)
+  int finish(int code) { pool_free(c->dev, part); pool_free(c->dev, part_obj); return code; }
+
+  int check_aux_grads() const;
+  int check_pre_bwd();
+  int take_partial_rows();
+  int render_bwd();                                   // K7
+  int pre_bwd();                                      // K8+K9, through one of the three launch forms per range:
+  PreBwdArgs shared_args() const;
+  void launch_batch(const PreBwdArgs& sh, int gb, int ge) const;
+  void launch_views(PreBwdArgs pa, int gb, int ge) const;
+  void launch_view(PreBwdArgs pa, int v, int gb, int ge) const;
+};
+
+// what a backward with depth / alpha gradients armed (gsr_ctx_set_aux_grads) cannot be
+int BwdRun::check_aux_grads() const {
+  if (b.view_stride != 0)
+    return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: the per-view batch backward (gsr_backward_raw_batch_views / _obj_views) "
+                   "does not take depth / alpha gradients");
+  if (b.nchunks > 1)
+    return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: gsr_backward_raw_chunked with more than one range does not take "
+                   "depth / alpha gradients");
+  if (b.grad_objects != nullptr)
+    return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: depth / alpha gradients and grad_objects in one backward are not supported");
+  if (!geom)
+    return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: depth / alpha gradients reach geometry and opacity only, and this "
+                   "backward asks for no such gradient");
+  if (!c->lanegroup)
+    return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: a gsr_forward context with K != 16 SH coefficients does not take "
+                   "depth / alpha gradients");
+  if (c->st.flags & GSR_FLAG_NEEDLE_DOUBLE)
+    return set_err(GSR_ERR_INVALID, "gsr_ctx_set_aux_grads: not available under GSR_FLAG_NEEDLE_DOUBLE");
+  return GSR_OK;
+}
+
+// What the per-Gaussian stage cannot serve: asked before K7 is launched, so that a refused backward launches nothing.
+// Also settles how that stage will run (nchunks, batch_fused).
+int BwdRun::check_pre_bwd() {
+  const float* const dsh = c->shs ? b.d.shs : nullptr;
+  if (c->raw && ((dsh == nullptr) != (b.d.sh_dc == nullptr)))
+    return set_err(GSR_ERR_INVALID, "gsr_backward_raw: dfeatures_dc and dfeatures_rest must both be given");
+  if (c->lanegroup && c->shs && geom && !c->D)
+    return set_err(GSR_ERR_STATE, "gsr_backward: the forward of this context was run without its backward state");
+  if (c->lanegroup && c->shs && geom && c->D_stale)
+    return set_err(GSR_ERR_STATE, "gsr_backward: geometry gradients asked of a context whose last gsr_ctx_rerender was "
+                   "told GSR_RERENDER_COLOR_GRADS_ONLY");
+  // The per-Gaussian stage covers the Gaussians in `nchunks` ranges (multiples of 64), one launch each; after a
+  // range's launch is enqueued the caller is told (chunk_done): its gradients are complete in stream order, so a
+  // collective over that range can be issued while the next range is still being computed.
+  nchunks = std::max(1, std::min(b.nchunks, (c->P + 63) / 64));
+  // a batch of views: ONE launch of k_pre_bwd_batch per range walks the B views and writes the gradients once
+  // (GSR_BATCH_K9=0: one k_pre_bwd launch per view instead, the others in accumulate mode -- the A/B and the bit-exact form)
+  batch_fused = c->B > 1 && c->raw && c->lanegroup && batch_k9_fused() && b.view_stride == 0;
+  if (ss_out && (!(c->lanegroup && c->raw) || b.accumulate || nchunks != 1 || (c->B > 1 && !batch_fused)))
+    return set_err(GSR_ERR_INVALID, "gsr_ctx_request_sumsq: served by an overwriting gsr_backward_raw* over one range only");
+  return GSR_OK;
+}
+
+// K7's partial rows (one per list entry and tile part), and the tag that tells this call's rows from stale ones
+int BwdRun::take_partial_rows() {
   const uint32_t N = c->nbound;
-  // the context's blocks are read here, on this stream: whoever takes them over after gsr_ctx_free orders behind it
-  pool_retag(dev, c->keep_blk, st); pool_retag(dev, c->rank_blk, st); pool_retag(dev, c->seg_blk, st);
-  void* part_blk = nullptr;
-  void* pobj_blk = nullptr;
-  float4* part = nullptr;
-  float4* part_obj = nullptr;
   // K7 runs one wave per 16x(4*npx) part of a tile; each writes its own partial row per list entry (4 pixels per lane:
   // one wave per tile; 2: two, and K8/K9 then sums twice the rows).  With long lists walked as segments every work item
   // is short whatever the tile count, so one wave per tile it is (S-hydrant-full, 2500 tiles: K7 0.169 -> 0.194 ms but
@@ -1553,170 +1592,200 @@ static int backward_impl(GsrCtx* c, const BwdCall& b) {
   // (The rule looks at the tiles of ONE view, also for a batch: the split decides how many partial rows K9 adds up per
   // pair -- the float32 association of the sums -- and a batch's per-view gradients are the single-view call's bit for bit.
   // Found by tests/diag_fuzz_batch.py with GSR_FLAG_NO_SEGMENTS on batches of >= 4096 tiles of views with fewer.)
-  const bool segs_on = c->bnd != nullptr && !obj && aux_gd == nullptr;   // (dL/ddepth walks whole lists: no running depth in the records)
-  const int bwd_npx = flag_bwd_npx(c->st.flags) ? flag_bwd_npx(c->st.flags) : ((c->tpv < 4096 && !segs_on) ? 2 : 4);
-  const uint32_t nsub = (uint32_t)(PXL / bwd_npx);
+  segs_on = c->bnd != nullptr && !obj && aux_gd == nullptr;   // (dL/ddepth walks whole lists: no running depth in the records)
+  bwd_npx = flag_bwd_npx(c->st.flags) ? flag_bwd_npx(c->st.flags) : ((c->tpv < 4096 && !segs_on) ? 2 : 4);
+  nsub = (uint32_t)(PXL / bwd_npx);
   if (N > 0) {
-    part_blk = pool_alloc(dev, sizeof(float4) * PART_F4 * (size_t)N * nsub, st);
-    if (obj) pobj_blk = pool_alloc(dev, sizeof(float4) * 4 * (size_t)N * nsub, st);
-    if (!part_blk || (obj && !pobj_blk)) {
-      pool_free(dev, part_blk); pool_free(dev, pobj_blk);
+    part = static_cast<float4*>(pool_alloc(c->dev, sizeof(float4) * PART_F4 * (size_t)N * nsub, st));
+    if (obj) part_obj = static_cast<float4*>(pool_alloc(c->dev, sizeof(float4) * 4 * (size_t)N * nsub, st));
+    if (!part || (obj && !part_obj))
       return set_err(GSR_ERR_NOMEM, "gsr_backward: partial-gradient buffer (N=%u) allocation failed", N);
-    }
-    part = static_cast<float4*>(part_blk);
-    part_obj = static_cast<float4*>(pobj_blk);
   }
-  auto done = [&](int code) { pool_free(dev, part_blk); pool_free(dev, pobj_blk); return code; };
-  // 64-bit tag of this call: K7 stamps it into every partial row it writes, K8/K9 ignores rows without it
   static std::atomic<uint64_t> tag_counter{0x243F6A8885A308D3ull};
   uint64_t z = tag_counter.fetch_add(0x9E3779B97F4A7C15ull) + 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
-  const uint32_t tag_lo = (uint32_t)z, tag_hi = (uint32_t)(z >> 32);
-  if (N > 0) {
-    StageTimer t(GSR_STAGE_RENDER_BWD, st, true);
-    RenderBwdArgs ra;
-    ra.tag_lo = tag_lo; ra.tag_hi = tag_hi;
-    ra.ranges = c->ranges; ra.pair_rank = c->pair_rank; ra.offg = c->offg; ra.R0 = c->G0; ra.R1 = c->G1; ra.R2 = c->G2;
-    ra.sh_objs = c->sh_objs; ra.bg = c->st.bg; ra.W = c->st.image_width; ra.H = c->st.image_height;
-    ra.map_mode = flag_tile_map(c->st.flags);
-    ra.sched = c->sched;
-    ra.wave_clock = g_wave_clock.load();
-    ra.gridx = c->gridx; ra.ntiles = c->ntiles; ra.final_T = c->final_T; ra.n_contrib = c->n_contrib;
-    ra.grad_color = b.grad_color; ra.grad_objects = obj ? b.grad_objects : nullptr; ra.part = part; ra.part_obj = part_obj;
-    // split tiles: one extra work item per boundary record, in front of the per-tile items
-    const bool segs = segs_on;
-    ra.grad_depth = aux_gd; ra.grad_alpha = aux_ga;
-    ra.bnd = segs ? c->bnd : nullptr; ra.segoff = c->segoff; ra.rec_item = c->rec_item; ra.nrec = c->dv + DV_NREC;
-    ra.seg_shift = c->seg_shift; ra.extra_blocks = segs ? c->rec_cap * nsub : 0u;
-    ra.tpv = c->tpv; ra.vpack = c->vpack; ra.Ppad = c->Ppad;
-    const dim3 gridT(ra.extra_blocks + (unsigned)render_grid(c->ntiles * (int)nsub)), blk(64);
-    CompStream comp_s{};
-    bool comp_used = false;
-    hipStream_t st7 = comp_enter(dev, st, comp_s, comp_used);
-    const Kern<RenderBwdArgs> k7 = pick_render_bwd(obj, bwd_npx, geom, aux);
-    if (t.on) hipExtLaunchKernelGGL(k7, gridT, blk, 0, st7, t.a, t.b, 0, ra);
-    else hipLaunchKernelGGL(k7, gridT, blk, 0, st7, ra);
-    hipError_t e = hipGetLastError();
-    const bool joined = comp_leave(st, comp_s, comp_used);
-    if (e != hipSuccess) return done(set_err(GSR_ERR_DEVICE, "render backward: launch failed: %s", hipGetErrorString(e)));
-    if (!joined) return done(set_err(GSR_ERR_DEVICE, "render backward: joining the compositor stream failed"));
+  tag_lo = (uint32_t)z; tag_hi = (uint32_t)(z >> 32);
+  return GSR_OK;
+}
+
+// K7: the backward compositor (a context with pairs only)
+int BwdRun::render_bwd() {
+  StageTimer t(GSR_STAGE_RENDER_BWD, st, true);
+  RenderBwdArgs ra;
+  ra.tag_lo = tag_lo; ra.tag_hi = tag_hi;
+  ra.ranges = c->ranges; ra.pair_rank = c->pair_rank; ra.offg = c->offg; ra.R0 = c->G0; ra.R1 = c->G1; ra.R2 = c->G2;
+  ra.sh_objs = c->sh_objs; ra.bg = c->st.bg; ra.W = c->st.image_width; ra.H = c->st.image_height;
+  ra.map_mode = flag_tile_map(c->st.flags);
+  ra.sched = c->sched;
+  ra.wave_clock = g_wave_clock.load();
+  ra.gridx = c->gridx; ra.ntiles = c->ntiles; ra.final_T = c->final_T; ra.n_contrib = c->n_contrib;
+  ra.grad_color = b.grad_color; ra.grad_objects = obj ? b.grad_objects : nullptr; ra.part = part; ra.part_obj = part_obj;
+  // split tiles: one extra work item per boundary record, in front of the per-tile items
+  ra.grad_depth = aux_gd; ra.grad_alpha = aux_ga;
+  ra.bnd = segs_on ? c->bnd : nullptr; ra.segoff = c->segoff; ra.rec_item = c->rec_item; ra.nrec = c->dv + DV_NREC;
+  ra.seg_shift = c->seg_shift; ra.extra_blocks = segs_on ? c->rec_cap * nsub : 0u;
+  ra.tpv = c->tpv; ra.vpack = c->vpack; ra.Ppad = c->Ppad;
+  const dim3 gridT(ra.extra_blocks + (unsigned)render_grid(c->ntiles * (int)nsub)), blk(64);
+  const Kern<RenderBwdArgs> k7 = pick_render_bwd(obj, bwd_npx, geom, aux);
+  if (t.on) hipExtLaunchKernelGGL(k7, gridT, blk, 0, st, t.a, t.b, 0, ra);
+  else hipLaunchKernelGGL(k7, gridT, blk, 0, st, ra);
+  LAUNCH_CHECK("render backward");
+  return GSR_OK;
+}
+
+// what every launch form of the per-Gaussian stage shares: one view (view 0 of a batch) over all its Gaussians
+PreBwdArgs BwdRun::shared_args() const {
+  const GradOut& g = b.d;
+  PreBwdArgs pa;
+  pa.P = c->P; pa.g0 = 0; pa.K = c->K; pa.va = view_args(c->st);
+  pa.offg = c->offg; pa.G0 = c->G0; pa.G1 = c->G1; pa.G2 = c->G2;
+  pa.part = part; pa.part_obj = obj ? part_obj : nullptr;
+  pa.tag_lo = tag_lo; pa.tag_hi = tag_hi; pa.nsub = nsub;
+  pa.means = c->means3D; pa.scales = c->scales; pa.rots = c->rots; pa.cov3d = c->cov3d; pa.sh = c->shs;
+  pa.sh_dc = c->sh_dc; pa.D = c->D; pa.abc = c->abc;
+  pa.needle_double = (c->st.flags & GSR_FLAG_NEEDLE_DOUBLE) != 0u ? 1 : 0;
+  // (a batch: the object-feature gradient is k_obj_grad_batch's, the per-Gaussian kernels leave it alone)
+  pa.dmeans3D = g.means3D; pa.dmeans2D = g.means2D; pa.dsh = c->shs ? g.shs : nullptr; pa.dsh_dc = g.sh_dc;
+  pa.dsh_objs = c->B > 1 ? nullptr : g.sh_objs; pa.dcolors = c->colors ? g.colors_precomp : nullptr; pa.dopac = g.opacities;
+  pa.dscales = c->cov3d ? nullptr : g.scales; pa.drots = c->cov3d ? nullptr : g.rotations;
+  pa.dcov3d = c->cov3d ? g.cov3D : nullptr;
+  pa.accumulate = b.accumulate ? 1 : 0;
+  pa.vpack = nullptr; pa.Ppad = 0; pa.Pscene = c->P; pa.vstride = 0;
+  pa.sumsq = nullptr;
+  return pa;
+}
+
+// Gaussians [gb, ge) of a batch, its views summed: ONE launch of k_pre_bwd_batch walks the B views and writes the gradients once
+void BwdRun::launch_batch(const PreBwdArgs& sh, int gb, int ge) const {
+  const GradOut& d = b.d;
+  PreBwdBatchArgs ba;
+  ba.P = ge; ba.g0 = gb; ba.B = c->B; ba.Ppad = c->Ppad; ba.Pscene = c->P; ba.vpack = c->vpack;
+  ba.H = c->st.image_height; ba.W = c->st.image_width; ba.deg = c->st.sh_degree; ba.mod = c->st.scale_modifier;
+  ba.offg = c->offg; ba.G0 = c->G0; ba.G1 = c->G1; ba.G2 = c->G2; ba.part = part;
+  ba.tag_lo = tag_lo; ba.tag_hi = tag_hi; ba.nsub = nsub;
+  ba.means = c->means3D; ba.scales = c->scales; ba.rots = c->rots; ba.D = c->D;
+  ba.dmeans3D = d.means3D; ba.dmeans2D = d.means2D; ba.dsh = d.shs; ba.dsh_dc = d.sh_dc; ba.dopac = d.opacities;
+  ba.dscales = d.scales; ba.drots = d.rotations; ba.sumsq = sh.sumsq;
+  const dim3 gridB((unsigned)((ge - gb + 63) / 64)), blkB(64 * BATCH_K9_WAVES);
+  const size_t lds = sizeof(float) * 3 * 64 * (size_t)c->B;
+  hipLaunchKernelGGL(pick_pre_bwd_batch(geom, b.accumulate, aux), gridB, blkB, lds, st, ba);
+}
+
+// Gaussians [gb, ge) of a batch, per-view gradients (gsr_backward_raw_batch_views): ONE launch whose grid.y is the view --
+// the B per-view launches' ramp-ups and tails happen once.  View v's buffers lie v * view_stride floats behind view 0's.
+void BwdRun::launch_views(PreBwdArgs pa, int gb, int ge) const {
+  pa.vpack = c->vpack; pa.Ppad = c->Ppad; pa.Pscene = c->P; pa.vstride = (long long)b.view_stride;
+  pa.accumulate = 0; pa.abc = nullptr;
+  pa.g0 = gb; pa.P = ge;
+  const dim3 gridV((unsigned)((ge - gb + PRE_BLOCK - 1) / PRE_BLOCK), (unsigned)c->B);
+  hipLaunchKernelGGL(pick_pre_bwd(true, geom, false, false, false), gridV, dim3(PRE_BLOCK), 0, st, pa);
+}
+
+// Gaussians [gb, ge) of one view: the only view, or view v of a batch under GSR_BATCH_K9=0 -- one launch per view over
+// the same range, the first overwriting (unless the caller asked for accumulation) and the others adding; the per-view
+// arrays of the virtual scene are offset by v * Ppad
+void BwdRun::launch_view(PreBwdArgs pa, int v, int gb, int ge) const {
+  const GradOut& d = b.d;
+  const bool acc_v = b.view_stride == 0 && (b.accumulate || v > 0);
+  if (c->B > 1) {
+    const size_t o = (size_t)v * (size_t)c->Ppad;
+    pa.va = view_args(c->views[v]);
+    pa.offg = c->offg + o; pa.G0 = c->G0 + REC * o; pa.G1 = c->G1 + REC * o; pa.G2 = c->G2 + REC * o;
+    pa.D = c->D ? c->D + 9 * o : nullptr; pa.abc = c->abc ? c->abc + o : nullptr;
+    pa.dmeans2D = d.means2D ? d.means2D + 3 * (size_t)v * (size_t)c->P : nullptr;
+    pa.accumulate = acc_v ? 1 : 0;
   }
-  {
-    StageTimer t(GSR_STAGE_PREPROCESS_BWD, st);
-    PreBwdArgs pa;
-    pa.P = P; pa.g0 = 0; pa.K = c->K; pa.va = view_args(c->st);
-    pa.offg = c->offg; pa.G0 = c->G0; pa.G1 = c->G1; pa.G2 = c->G2;
-    pa.part = part; pa.part_obj = obj ? part_obj : nullptr;
-    pa.tag_lo = tag_lo; pa.tag_hi = tag_hi; pa.nsub = nsub;
-    pa.means = c->means3D; pa.scales = c->scales; pa.rots = c->rots; pa.cov3d = c->cov3d; pa.sh = c->shs;
-    pa.sh_dc = c->sh_dc; pa.D = c->D; pa.abc = c->abc;
-    pa.needle_double = (c->st.flags & GSR_FLAG_NEEDLE_DOUBLE) != 0u ? 1 : 0;
-    // (a batch: the object-feature gradient is k_obj_grad_batch's below, the per-Gaussian kernels leave it alone)
-    auto set_grads = [&](const GradOut& g) {
-      pa.dmeans3D = g.means3D; pa.dmeans2D = g.means2D; pa.dsh = c->shs ? g.shs : nullptr; pa.dsh_dc = g.sh_dc;
-      pa.dsh_objs = c->B > 1 ? nullptr : g.sh_objs; pa.dcolors = c->colors ? g.colors_precomp : nullptr; pa.dopac = g.opacities;
-      pa.dscales = c->cov3d ? nullptr : g.scales; pa.drots = c->cov3d ? nullptr : g.rotations;
-      pa.dcov3d = c->cov3d ? g.cov3D : nullptr;
-    };
-    set_grads(d);
-    pa.accumulate = b.accumulate ? 1 : 0;
-    pa.vpack = nullptr; pa.Ppad = 0; pa.Pscene = P; pa.vstride = 0;
-    if (c->raw && ((pa.dsh == nullptr) != (pa.dsh_dc == nullptr)))
-      return done(set_err(GSR_ERR_INVALID, "gsr_backward_raw: dfeatures_dc and dfeatures_rest must both be given"));
-    if (c->lanegroup && c->shs && geom && !c->D)
-      return done(set_err(GSR_ERR_STATE, "gsr_backward: the forward of this context was run without its backward state"));
-    if (c->lanegroup && c->shs && geom && c->D_stale)
-      return done(set_err(GSR_ERR_STATE, "gsr_backward: geometry gradients asked of a context whose last gsr_ctx_rerender was "
-                          "told GSR_RERENDER_COLOR_GRADS_ONLY"));
-    // The per-Gaussian stage covers the Gaussians in `nchunks` ranges (multiples of 64), one launch each; after a
-    // range's launch is enqueued the caller is told (chunk_done): its gradients are complete in stream order, so a
-    // collective over that range can be issued while the next range is still being computed.
-    if (c->B > 1 && d.sh_objs) {
-      // dL/d object features of a batch: view by view as k_pre_bwd forms them, summed in view order (or per view)
-      ObjGradBatchArgs oa;
-      oa.P = P; oa.B = c->B; oa.Ppad = c->Ppad; oa.nsub = nsub; oa.tag_lo = tag_lo; oa.tag_hi = tag_hi;
-      oa.offg = c->offg; oa.part = part; oa.part_obj = (obj && N > 0) ? part_obj : nullptr; oa.dobj = d.sh_objs;
-      oa.vstride = b.view_stride != 0 ? (long long)P * NUM_OBJ : 0;
-      hipLaunchKernelGGL(k_obj_grad_batch, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, oa);
-    }
-    nchunks = std::max(1, std::min(nchunks, (P + 63) / 64));
-    const int per = (((P + nchunks - 1) / nchunks) + 63) / 64 * 64;
-    // gsr_ctx_request_sumsq (one-shot): the overwriting raw-parameter kernel also leaves per-workgroup sums of squares of
-    // what it writes; one small launch behind it adds them up per tensor (fixed order) into the caller's six doubles
-    // a batch of views: ONE launch of k_pre_bwd_batch per range walks the B views and writes the gradients once
-    // (GSR_BATCH_K9=0: one k_pre_bwd launch per view instead, the others in accumulate mode -- the A/B and the bit-exact form)
-    const bool batch_fused = c->B > 1 && c->raw && c->lanegroup && batch_k9_fused() && b.view_stride == 0;
-    void* ss_blk = nullptr;
-    const int ss_blocks = batch_fused ? ((P + 63) / 64) * BATCH_K9_WAVES : (P + PRE_BLOCK - 1) / PRE_BLOCK;
-    pa.sumsq = nullptr;
-    if (ss_out) {
-      if (!(c->lanegroup && c->raw) || b.accumulate || nchunks != 1 || (c->B > 1 && !batch_fused))
-        return done(set_err(GSR_ERR_INVALID, "gsr_ctx_request_sumsq: served by an overwriting gsr_backward_raw* over one range only"));
-      ss_blk = pool_alloc(dev, sizeof(float) * SUMSQ_W * (size_t)ss_blocks * PRE_WAVES, st);
-      if (!ss_blk) return done(set_err(GSR_ERR_NOMEM, "gsr_backward_raw: sum-of-squares partials allocation failed"));
-      pa.sumsq = static_cast<float*>(ss_blk);
-    }
-    for (int ck = 0; ck < nchunks; ++ck) {
-      const int gb = std::min(ck * per, P), ge = (ck == nchunks - 1) ? P : std::min((ck + 1) * per, P);
-      // (a batch of views: one launch per view over the same range of Gaussians, the first overwriting -- unless the caller
-      // asked for accumulation -- and the others adding; the per-view arrays of the virtual scene are offset by v * Ppad)
-      if (batch_fused && ge > gb) {
-        PreBwdBatchArgs ba;
-        ba.P = ge; ba.g0 = gb; ba.B = c->B; ba.Ppad = c->Ppad; ba.Pscene = P; ba.vpack = c->vpack;
-        ba.H = c->st.image_height; ba.W = c->st.image_width; ba.deg = c->st.sh_degree; ba.mod = c->st.scale_modifier;
-        ba.offg = c->offg; ba.G0 = c->G0; ba.G1 = c->G1; ba.G2 = c->G2; ba.part = part;
-        ba.tag_lo = tag_lo; ba.tag_hi = tag_hi; ba.nsub = nsub;
-        ba.means = c->means3D; ba.scales = c->scales; ba.rots = c->rots; ba.D = c->D;
-        ba.dmeans3D = d.means3D; ba.dmeans2D = d.means2D; ba.dsh = d.shs; ba.dsh_dc = d.sh_dc; ba.dopac = d.opacities;
-        ba.dscales = d.scales; ba.drots = d.rotations; ba.sumsq = pa.sumsq;
-        const dim3 gridB((unsigned)((ge - gb + 63) / 64)), blkB(64 * BATCH_K9_WAVES);
-        const size_t lds = sizeof(float) * 3 * 64 * (size_t)c->B;
-        hipLaunchKernelGGL(pick_pre_bwd_batch(geom, b.accumulate, aux), gridB, blkB, lds, st, ba);
-      }
-      // per-view gradients of a batch (gsr_backward_raw_batch_views): ONE launch whose grid.y is the view -- the B per-view
-      // launches' ramp-ups and tails happen once (GSR_BATCH_K9_VIEWS=0: one launch per view, the A/B form; same bits)
-      static const int views_one_launch = [] { const char* e = getenv("GSR_BATCH_K9_VIEWS"); return e ? atoi(e) : 1; }();
-      const bool views_fused = !batch_fused && b.view_stride != 0 && c->B > 1 && c->raw && c->lanegroup && views_one_launch != 0;
-      if (views_fused && ge > gb) {
-        pa.vpack = c->vpack; pa.Ppad = c->Ppad; pa.Pscene = P; pa.vstride = (long long)b.view_stride;
-        pa.accumulate = 0; pa.abc = nullptr;
-        pa.g0 = gb; pa.P = ge;
-        const dim3 gridV((unsigned)((ge - gb + PRE_BLOCK - 1) / PRE_BLOCK), (unsigned)c->B);
-        hipLaunchKernelGGL(pick_pre_bwd(true, geom, false, false, false), gridV, dim3(PRE_BLOCK), 0, st, pa);
-        pa.vpack = nullptr;
-      }
-      for (int v = 0; !batch_fused && !views_fused && ge > gb && v < c->B; ++v) {
-        const size_t o = (size_t)v * (size_t)c->Ppad;
-        const bool acc_v = b.view_stride == 0 && (b.accumulate || v > 0);
-        if (c->B > 1) {
-          if (b.view_stride != 0) set_grads(d.of_view(v, b.view_stride));   // this view's own gradient buffers
-          pa.va = view_args(c->views[v]);
-          pa.offg = c->offg + o; pa.G0 = c->G0 + REC * o; pa.G1 = c->G1 + REC * o; pa.G2 = c->G2 + REC * o;
-          pa.D = c->D ? c->D + 9 * o : nullptr; pa.abc = c->abc ? c->abc + o : nullptr;
-          pa.dmeans2D = d.means2D ? d.means2D + 3 * (size_t)v * (size_t)P : nullptr;
-          pa.accumulate = acc_v ? 1 : 0;
-        }
-        pa.g0 = gb; pa.P = ge;
-        const dim3 gridK9((unsigned)((ge - gb + PRE_BLOCK - 1) / PRE_BLOCK));
-        if (c->lanegroup) {
-          const bool ndl = pa.needle_double != 0 && pa.abc != nullptr;
-          hipLaunchKernelGGL(pick_pre_bwd(c->raw, geom, acc_v, ndl, aux), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-        } else {
-          if (geom && pa.needle_double) hipLaunchKernelGGL((k_preprocess_bwd<true, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-          else if (geom) hipLaunchKernelGGL((k_preprocess_bwd<true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-          else hipLaunchKernelGGL((k_preprocess_bwd<false>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
-        }
-      }
-      if (b.chunk_done) b.chunk_done(b.chunk_user, ck, (int64_t)gb, (int64_t)ge);
-    }
-    if (ss_out) {
-      hipLaunchKernelGGL(k_sumsq_reduce, dim3(6), dim3(256), 0, st, pa.sumsq, ss_blocks * PRE_WAVES, ss_out);
-      pool_free(dev, ss_blk);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return done(set_err(GSR_ERR_DEVICE, "preprocess backward: launch failed: %s", hipGetErrorString(e)));
+  pa.g0 = gb; pa.P = ge;
+  const dim3 gridK9((unsigned)((ge - gb + PRE_BLOCK - 1) / PRE_BLOCK));
+  if (c->lanegroup) {
+    const bool ndl = pa.needle_double != 0 && pa.abc != nullptr;
+    hipLaunchKernelGGL(pick_pre_bwd(c->raw, geom, acc_v, ndl, aux), gridK9, dim3(PRE_BLOCK), 0, st, pa);
+  } else {
+    if (geom && pa.needle_double) hipLaunchKernelGGL((k_preprocess_bwd<true, true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
+    else if (geom) hipLaunchKernelGGL((k_preprocess_bwd<true>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
+    else hipLaunchKernelGGL((k_preprocess_bwd<false>), gridK9, dim3(PRE_BLOCK), 0, st, pa);
   }
-  return done(GSR_OK);
+}
+
+// K8+K9: the partial rows summed per Gaussian, and the chain rule down to the caller's parameters
+int BwdRun::pre_bwd() {
+  const int P = c->P, dev = c->dev;
+  StageTimer t(GSR_STAGE_PREPROCESS_BWD, st);
+  PreBwdArgs pa = shared_args();
+  if (c->B > 1 && b.d.sh_objs) {
+    // dL/d object features of a batch: view by view as k_pre_bwd forms them, summed in view order (or per view)
+    ObjGradBatchArgs oa;
+    oa.P = P; oa.B = c->B; oa.Ppad = c->Ppad; oa.nsub = nsub; oa.tag_lo = tag_lo; oa.tag_hi = tag_hi;
+    oa.offg = c->offg; oa.part = part; oa.part_obj = (obj && c->nbound > 0) ? part_obj : nullptr; oa.dobj = b.d.sh_objs;
+    oa.vstride = b.view_stride != 0 ? (long long)P * NUM_OBJ : 0;
+    hipLaunchKernelGGL(k_obj_grad_batch, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, oa);
+  }
+  // gsr_ctx_request_sumsq (one-shot): the overwriting raw-parameter kernel also leaves per-workgroup sums of squares of
+  // what it writes; one small launch behind it adds them up per tensor (fixed order) into the caller's six doubles
+  void* ss_blk = nullptr;
+  const int ss_blocks = batch_fused ? ((P + 63) / 64) * BATCH_K9_WAVES : (P + PRE_BLOCK - 1) / PRE_BLOCK;
+  if (ss_out) {
+    ss_blk = pool_alloc(dev, sizeof(float) * SUMSQ_W * (size_t)ss_blocks * PRE_WAVES, st);
+    if (!ss_blk) return set_err(GSR_ERR_NOMEM, "gsr_backward_raw: sum-of-squares partials allocation failed");
+    pa.sumsq = static_cast<float*>(ss_blk);
+  }
+  const bool views_fused = !batch_fused && b.view_stride != 0 && c->B > 1;
+  const int per = (((P + nchunks - 1) / nchunks) + 63) / 64 * 64;
+  for (int ck = 0; ck < nchunks; ++ck) {
+    const int gb = std::min(ck * per, P), ge = (ck == nchunks - 1) ? P : std::min((ck + 1) * per, P);
+    if (ge > gb) {
+      if (batch_fused) launch_batch(pa, gb, ge);
+      else if (views_fused) launch_views(pa, gb, ge);
+      else for (int v = 0; v < c->B; ++v) launch_view(pa, v, gb, ge);
+    }
+    if (b.chunk_done) b.chunk_done(b.chunk_user, ck, (int64_t)gb, (int64_t)ge);
+  }
+  if (ss_out) {
+    hipLaunchKernelGGL(k_sumsq_reduce, dim3(6), dim3(256), 0, st, pa.sumsq, ss_blocks * PRE_WAVES, ss_out);
+    pool_free(dev, ss_blk);
+  }
+  LAUNCH_CHECK("preprocess backward");
+  return GSR_OK;
+}
+
+static int backward_impl(GsrCtx* c, const BwdCall& b) {
+  if (!c) return set_err(GSR_ERR_STATE, "gsr_backward: null context");
+  BwdRun r{c, b, static_cast<hipStream_t>(b.stream)};
+  // gsr_ctx_request_sumsq is one-shot: the request is taken (and the context disarmed) here, whatever this call's fate --
+  // a backward that fails early must not leave the next one writing six doubles to a buffer that may be gone by then
+  r.ss_out = c->sumsq_out;
+  c->sumsq_out = nullptr;
+  // gsr_ctx_set_aux_grads is one-shot in the same way
+  r.aux_gd = c->aux_gd; r.aux_ga = c->aux_ga;
+  c->aux_gd = nullptr; c->aux_ga = nullptr;
+  r.aux = r.aux_gd != nullptr || r.aux_ga != nullptr;
+  if (!b.grad_color) return set_err(GSR_ERR_INVALID, "gsr_backward: grad_color is null");
+  if (c->fwd_only)
+    return set_err(GSR_ERR_STATE, "gsr_backward: the context was kept by gsr_forward_raw2_keep (re-render only, no backward state)");
+  if (c->P == 0) return GSR_OK;
+  const GradOut& d = b.d;
+  r.obj = b.grad_objects != nullptr && c->sh_objs != nullptr;
+  // Only colour-side gradients wanted (SH / precomputed colours / object features): K7 and K8+K9 drop the geometry
+  // sums and the projection chain rule (the colour attack; BASELINE configs 2 and 3).
+  r.geom = d.means3D || d.means2D || d.opacities || d.scales || d.rotations || d.cov3D;
+  if (r.aux) { if (const int rc = r.check_aux_grads()) return rc; }
+  // an asynchronous-count forward: its pair count must have fitted the capacity guess (else the image it produced was
+  // poisoned with NaN and nothing downstream of it is meaningful).  (A forward recorded into a hipGraph publishes
+  // nothing to the host: c->slot is empty and this is a no-op.)
+  if (ctx_resolve_count(c) != GSR_OK) return set_err(GSR_ERR_DEVICE, "gsr_backward: reading the forward's pair count failed");
+  if (c->overflow)
+    return set_err(GSR_ERR_OVERFLOW, "gsr_backward: the forward emitted %llu (tile, Gaussian) pairs, more than the capacity "
+                   "%u guessed from earlier views (GSR_FLAG_ASYNC_COUNT); its image was filled with NaN -- render again",
+                   c->n64, c->nbound);
+  if (const int rc = r.check_pre_bwd()) return rc;
+  // every refusal has passed.  The context's blocks are read here, on this stream: whoever takes them over after
+  // gsr_ctx_free orders behind it
+  pool_retag(c->dev, c->keep_blk, r.st); pool_retag(c->dev, c->rank_blk, r.st); pool_retag(c->dev, c->seg_blk, r.st);
+  int rc;
+  if ((rc = r.take_partial_rows()) != GSR_OK) return r.finish(rc);
+  if (c->nbound > 0 && (rc = r.render_bwd()) != GSR_OK) return r.finish(rc);
+  if ((rc = r.pre_bwd()) != GSR_OK) return r.finish(rc);
+  return r.finish(GSR_OK);
 }
 
 // ---- what the five detector stages' entries (further down) share.  A stage states the regions of its workspace once, as a run of take()

@@ -32,9 +32,8 @@
  *     through a queue; nothing inside a context is locked;
  *   - gsr_last_error() is per thread: a thread reads the text of its own last refused call;
  *   - streams: a call's work is ordered by the stream it is given: whatever the caller enqueues on that stream afterwards
- *     runs behind it.  (A forward forks part of its work onto a side stream the library keeps per caller stream -- and,
- *     with GSR_COMP_CUMASK set, its compositors onto a companion stream -- and joins both back into the caller's stream
- *     before it returns.)  A context's backward or re-render (gsr_ctx_rerender) on ANOTHER stream than its previous use is
+ *     runs behind it.  (A forward forks part of its work onto a side stream the library keeps per caller stream and
+ *     joins it back into the caller's stream before it returns.)  A context's backward or re-render (gsr_ctx_rerender) on ANOTHER stream than its previous use is
  *     legal when the caller has ordered that stream behind the previous use (an event, or a host wait); the context's
  *     workspace then follows the new stream, and gsr_ctx_free returns it to the pool for that stream.
  *     gsr_ctx_export does NOT move the workspace: it only enqueues a copy out of it.  An export on another stream than
