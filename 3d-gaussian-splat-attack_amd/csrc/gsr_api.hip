@@ -33,6 +33,7 @@
 #include "gsr_setdet.hip.h"
 #include "gsr_rcnn.hip.h"
 #include "gsr_rpn.hip.h"
+#include "gsr_fpn.hip.h"
 
 using namespace gsr;
 
@@ -2965,6 +2966,95 @@ int gsr_rpn_nms(const GsrRpnSpec* d, const float* cand_boxes, const float* cand_
   LAUNCH_CHECK("gsr_rpn_nms (order)");
   hipLaunchKernelGGL(gsr_rpn::k_rpn_walk, dim3((unsigned)d->B), dim3(gsr_rpn::RPN_THREADS), 0, st, ar);
   LAUNCH_CHECK("gsr_rpn_nms (walk)");
+  return GSR_OK;
+}
+
+// ---- FPN RoI pooler (gsr_fpn.h / gsr_fpn.hip.h): no allocation, no copy, no host wait, no workspace (the level lists are
+// outputs the caller keeps for the backward); both entries check the whole spec on the host before the first launch.
+static int fpn_spec(const char* fn, const GsrFpnSpec* d, gsr_fpn::Spec& sp, unsigned long long& tiles) {
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->B > 65535) return set_err(GSR_ERR_INVALID, "%s: B=%d images (1..65535)", fn, d->B);
+  if (d->S < 1 || d->S > gsr_fpn::MAX_SAMPLE) return set_err(GSR_ERR_INVALID, "%s: S=%d RoIs per image (1..%d)", fn, d->S, gsr_fpn::MAX_SAMPLE);
+  if (d->Cf < 1 || d->Cf > 65535) return set_err(GSR_ERR_INVALID, "%s: Cf=%d channels (1..65535)", fn, d->Cf);
+  if (d->PH < 1 || d->PH > gsr_rcnn::MAX_POOL || d->PW < 1 || d->PW > gsr_rcnn::MAX_POOL)
+    return set_err(GSR_ERR_INVALID, "%s: the pooled size is %d x %d (1..%d each)", fn, d->PH, d->PW, gsr_rcnn::MAX_POOL);
+  if (d->sampling_ratio < 0) return set_err(GSR_ERR_INVALID, "%s: sampling_ratio=%d (>= 0)", fn, d->sampling_ratio);
+  if (d->nl < 1 || d->nl > gsr_fpn::MAX_LEVELS) return set_err(GSR_ERR_INVALID, "%s: nl=%d levels (1..%d)", fn, d->nl, gsr_fpn::MAX_LEVELS);
+  if (!finite_pos(d->canonical_size)) return set_err(GSR_ERR_INVALID, "%s: canonical_size must be finite and > 0", fn);
+  const unsigned long long pooled = (unsigned long long)d->B * (unsigned long long)d->S * (unsigned long long)d->Cf * (unsigned long long)(d->PH * d->PW);
+  if (pooled > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in pooled", fn);
+  sp = gsr_fpn::Spec{};
+  sp.B = d->B; sp.S = d->S; sp.Cf = d->Cf; sp.PH = d->PH; sp.PW = d->PW; sp.sampling_ratio = d->sampling_ratio; sp.nl = d->nl;
+  sp.canonical_size = d->canonical_size;
+  tiles = 0;
+  for (int l = 0; l < d->nl; ++l) {
+    if (d->Hf[l] < 1 || d->Wf[l] < 1) return set_err(GSR_ERR_INVALID, "%s: level %d is %d x %d cells (sizes >= 1)", fn, l, d->Hf[l], d->Wf[l]);
+    if (!finite_pos(d->scale[l])) return set_err(GSR_ERR_INVALID, "%s: scale[%d] must be finite and > 0", fn, l);
+    if (l >= 1 && (!finite_pos(d->thr[l]) || (l >= 2 && !(d->thr[l] > d->thr[l - 1]))))
+      return set_err(GSR_ERR_INVALID, "%s: thr[1..nl-1] must be finite, > 0 and strictly ascending (thr[%d])", fn, l);
+    const unsigned long long hw = (unsigned long long)d->Hf[l] * (unsigned long long)d->Wf[l];
+    if (hw > 0x7fffffffull || (unsigned long long)d->B * (unsigned long long)d->Cf * hw > 0x7fffffffull)
+      return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in the features of level %d", fn, l);
+    tiles += (unsigned long long)((d->Hf[l] + gsr_rcnn::RB_TILE - 1) / gsr_rcnn::RB_TILE) *
+             (unsigned long long)((d->Wf[l] + gsr_rcnn::RB_TILE - 1) / gsr_rcnn::RB_TILE);
+    sp.Hf[l] = d->Hf[l]; sp.Wf[l] = d->Wf[l]; sp.scale[l] = d->scale[l]; sp.thr[l] = l >= 1 ? d->thr[l] : 0.0f;
+  }
+  if (tiles > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 tiles in all levels", fn);
+  return GSR_OK;
+}
+
+int gsr_fpn_pool(const GsrFpnSpec* d, const float* const* features, const float* rois, const int32_t* n_roi, int32_t n_roi_stride,
+                 float* pooled, int32_t* roi_level, int32_t* level_list, int32_t* level_count, void* stream) {
+  gsr_fpn::PoolArgs ar{};
+  unsigned long long tiles = 0;
+  if (int rc = fpn_spec("gsr_fpn_pool", d, ar.sp, tiles)) return rc;
+  if (!features || !rois || !pooled || !roi_level || !level_list || !level_count)
+    return set_err(GSR_ERR_INVALID, "gsr_fpn_pool: null features / rois / pooled / roi_level / level_list / level_count");
+  if (n_roi && n_roi_stride < 1) return set_err(GSR_ERR_INVALID, "gsr_fpn_pool: n_roi_stride=%d (>= 1)", n_roi_stride);
+  for (int l = 0; l < d->nl; ++l) {
+    if (!features[l]) return set_err(GSR_ERR_INVALID, "gsr_fpn_pool: null features of level %d", l);
+    if (int rc = check_aligned4("gsr_fpn_pool", features[l])) return rc;
+    ar.features[l] = features[l];
+  }
+  if (int rc = check_aligned4("gsr_fpn_pool", rois, n_roi, pooled, roi_level, level_list, level_count)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ar.rois = rois; ar.n_roi = n_roi; ar.n_roi_stride = n_roi ? n_roi_stride : 0; ar.pooled = pooled;
+  ar.roi_level = roi_level; ar.level_list = level_list; ar.level_count = level_count;
+  hipLaunchKernelGGL(gsr_fpn::k_fpn_assign, dim3((unsigned)d->B), dim3((unsigned)((d->S + 63) / 64 * 64)), 0, st, ar);
+  LAUNCH_CHECK("gsr_fpn_pool (assign)");
+  const unsigned long long per_roi = (unsigned long long)d->Cf * (unsigned long long)(d->PH * d->PW);
+  hipLaunchKernelGGL(gsr_fpn::k_fpn_pool, dim3((unsigned)(d->B * d->S), (unsigned)((per_roi + gsr_rcnn::RA_THREADS - 1) / gsr_rcnn::RA_THREADS)),
+                     dim3(gsr_rcnn::RA_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_fpn_pool (pool)");
+  return GSR_OK;
+}
+
+int gsr_fpn_pool_backward(const GsrFpnSpec* d, const float* rois, const int32_t* level_list, const int32_t* level_count,
+                          const float* grad_pooled, float* const* grad_features, int32_t accumulate, void* stream) {
+  gsr_fpn::PoolArgs ar{};
+  unsigned long long tiles = 0;
+  if (int rc = fpn_spec("gsr_fpn_pool_backward", d, ar.sp, tiles)) return rc;
+  if (!rois || !level_list || !level_count || !grad_pooled || !grad_features)
+    return set_err(GSR_ERR_INVALID, "gsr_fpn_pool_backward: null rois / level_list / level_count / grad_pooled / grad_features");
+  unsigned long long first = 0;
+  for (int l = 0; l < gsr_fpn::MAX_LEVELS; ++l) {
+    ar.tile_start[l] = (uint32_t)first;
+    if (l >= d->nl) continue;
+    if (!grad_features[l]) return set_err(GSR_ERR_INVALID, "gsr_fpn_pool_backward: null grad_features of level %d", l);
+    if (int rc = check_aligned4("gsr_fpn_pool_backward", grad_features[l])) return rc;
+    ar.grad_features[l] = grad_features[l];
+    first += (unsigned long long)((d->Hf[l] + gsr_rcnn::RB_TILE - 1) / gsr_rcnn::RB_TILE) *
+             (unsigned long long)((d->Wf[l] + gsr_rcnn::RB_TILE - 1) / gsr_rcnn::RB_TILE);
+  }
+  ar.tile_start[gsr_fpn::MAX_LEVELS] = (uint32_t)tiles;
+  if (int rc = check_aligned4("gsr_fpn_pool_backward", rois, level_list, level_count, grad_pooled)) return rc;
+  ar.rois = rois; ar.grad_pooled = grad_pooled;
+  ar.level_list = const_cast<int32_t*>(level_list); ar.level_count = const_cast<int32_t*>(level_count);   // read only by this kernel
+  ar.accumulate = accumulate != 0 ? 1 : 0;
+  hipLaunchKernelGGL(gsr_fpn::k_fpn_pool_bwd,
+                     dim3((unsigned)tiles, (unsigned)((d->Cf + gsr_rcnn::RB_CHUNK - 1) / gsr_rcnn::RB_CHUNK), (unsigned)d->B),
+                     dim3(gsr_rcnn::RB_THREADS), 0, static_cast<hipStream_t>(stream), ar);
+  LAUNCH_CHECK("gsr_fpn_pool_backward");
   return GSR_OK;
 }
 

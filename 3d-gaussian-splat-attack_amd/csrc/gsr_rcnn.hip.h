@@ -15,6 +15,8 @@
 //                     wy[ph][row], wx[pw][col] of the others in LDS (samples added in index order) with the masks of their
 //                     non-zero bins, and every lane adds (wy * wx) * g over its bins in (ph, pw) order, divides by the
 //                     RoI's sample count and adds that to its pixel.  One store per element.
+//                     The per-element body of the forward (roi_pool_element) and the per-RoI step and store of the backward
+//                     (roi_bwd_step, roi_bwd_store) are device functions that gsr_fpn.hip.h's kernels call too.
 //   k_rcnn_count      one block: the rows with a label >= 0 (integers).
 //   k_rcnn_rows       one wave per sampled row: softmax statistics (lanes stride the row, wave butterflies), the
 //                     cross-entropy term and gradient, the box term and gradient; one partial pair per block.
@@ -179,6 +181,52 @@ __device__ __forceinline__ int roi_count(const RoiArgs& ar, int b) {
   return n < 0 ? 0 : (n > ar.sp.S ? ar.sp.S : n);
 }
 
+// What RoIAlign needs to know of one feature map (the single-level entries build it from their Spec, the FPN pooler --
+// gsr_fpn.hip.h -- from the level's members).
+struct RoiMap {
+  int Cf, Hf, Wf, PH, PW, sampling_ratio;
+  float scale;
+};
+
+__device__ __forceinline__ RoiMap roi_map(const Spec& sp) {
+  return RoiMap{sp.Cf, sp.Hf, sp.Wf, sp.PH, sp.PW, sp.sampling_ratio, sp.spatial_scale};
+}
+
+// One element of pooled: bin (ph, pw) of the finite RoI r on the channel plane f [Hf, Wf], the samples in (iy, ix) order.
+__device__ __forceinline__ float roi_pool_element(const RoiMap& mp, const float* f, const float* r, int ph, int pw) {
+  float sx, bx, sy, by;
+  int gx, gy;
+  roi_axis<float>(r[0], r[2], mp.scale, mp.PW, mp.sampling_ratio, sx, bx, gx);
+  roi_axis<float>(r[1], r[3], mp.scale, mp.PH, mp.sampling_ratio, sy, by, gy);
+  const int cnt = gx * gy > 1 ? gx * gy : 1;
+  float acc = 0.0f;
+  for (int iy = 0; iy < gy; ++iy) {
+    int yl, yh;
+    float hy, ly;
+    const bool oky = lerp_axis<float>(sample_pos<float>(sy, by, gy, ph, iy), mp.Hf, yl, yh, hy, ly);
+    for (int ix = 0; ix < gx; ++ix) {
+      int xl, xh;
+      float hx, lx;
+      const bool okx = lerp_axis<float>(sample_pos<float>(sx, bx, gx, pw, ix), mp.Wf, xl, xh, hx, lx);
+      float v = 0.0f;
+      if (oky && okx) {
+        GSR_FP_STRICT
+        const float v1 = f[(size_t)yl * (size_t)mp.Wf + (size_t)xl], v2 = f[(size_t)yl * (size_t)mp.Wf + (size_t)xh];
+        const float v3 = f[(size_t)yh * (size_t)mp.Wf + (size_t)xl], v4 = f[(size_t)yh * (size_t)mp.Wf + (size_t)xh];
+        v = ((hy * hx) * v1 + (hy * lx) * v2) + (ly * hx) * v3 + (ly * lx) * v4;
+      }
+      {
+        GSR_FP_STRICT
+        acc = acc + v;
+      }
+    }
+  }
+  {
+    GSR_FP_STRICT
+    return acc / (float)cnt;
+  }
+}
+
 __global__ void __launch_bounds__(RA_THREADS) k_roi_align(RoiArgs ar) {
   const Spec& sp = ar.sp;
   const unsigned bs = blockIdx.x;                                         // (image, RoI): the same in all lanes
@@ -193,40 +241,8 @@ __global__ void __launch_bounds__(RA_THREADS) k_roi_align(RoiArgs ar) {
   float out = 0.0f;
   float r[4];
   for (int k = 0; k < 4; ++k) r[k] = ar.rois[(size_t)bs * 4 + (size_t)k];
-  if (s < roi_count(ar, b) && roi_finite<float>(r)) {
-    float sx, bx, sy, by;
-    int gx, gy;
-    roi_axis<float>(r[0], r[2], sp.spatial_scale, sp.PW, sp.sampling_ratio, sx, bx, gx);
-    roi_axis<float>(r[1], r[3], sp.spatial_scale, sp.PH, sp.sampling_ratio, sy, by, gy);
-    const int cnt = gx * gy > 1 ? gx * gy : 1;
-    const float* f = ar.features + ((size_t)b * (size_t)sp.Cf + (size_t)c) * (size_t)sp.Hf * (size_t)sp.Wf;
-    float acc = 0.0f;
-    for (int iy = 0; iy < gy; ++iy) {
-      int yl, yh;
-      float hy, ly;
-      const bool oky = lerp_axis<float>(sample_pos<float>(sy, by, gy, ph, iy), sp.Hf, yl, yh, hy, ly);
-      for (int ix = 0; ix < gx; ++ix) {
-        int xl, xh;
-        float hx, lx;
-        const bool okx = lerp_axis<float>(sample_pos<float>(sx, bx, gx, pw, ix), sp.Wf, xl, xh, hx, lx);
-        float v = 0.0f;
-        if (oky && okx) {
-          GSR_FP_STRICT
-          const float v1 = f[(size_t)yl * (size_t)sp.Wf + (size_t)xl], v2 = f[(size_t)yl * (size_t)sp.Wf + (size_t)xh];
-          const float v3 = f[(size_t)yh * (size_t)sp.Wf + (size_t)xl], v4 = f[(size_t)yh * (size_t)sp.Wf + (size_t)xh];
-          v = ((hy * hx) * v1 + (hy * lx) * v2) + (ly * hx) * v3 + (ly * lx) * v4;
-        }
-        {
-          GSR_FP_STRICT
-          acc = acc + v;
-        }
-      }
-    }
-    {
-      GSR_FP_STRICT
-      out = acc / (float)cnt;
-    }
-  }
+  if (s < roi_count(ar, b) && roi_finite<float>(r))
+    out = roi_pool_element(roi_map(sp), ar.features + ((size_t)b * (size_t)sp.Cf + (size_t)c) * (size_t)sp.Hf * (size_t)sp.Wf, r, ph, pw);
   ar.pooled[e] = out;
 }
 
@@ -252,84 +268,105 @@ __device__ __forceinline__ bool span_misses(float start, float bin, int P, int c
   return hi < (float)(c0 - 2) || lo > (float)(c0 + RB_TILE + 1);
 }
 
-__global__ void __launch_bounds__(RB_THREADS) k_roi_align_bwd(RoiArgs ar) {
-  __shared__ float s_wy[RB_TILE][16], s_wx[RB_TILE][16];                  // [cell of the tile][bin]
-  __shared__ uint32_t s_my[RB_TILE], s_mx[RB_TILE];                       // the bins with a non-zero weight
-  const Spec& sp = ar.sp;
+// the backward's LDS: the separable weights of the RoI in hand, [cell of the tile][bin], and the bins with a non-zero weight
+struct RoiBwdLds {
+  float wy[RB_TILE][16], wx[RB_TILE][16];
+  uint32_t my[RB_TILE], mx[RB_TILE];
+};
+
+// One RoI's step of the gather for the tile at (x0, y0) of the map mp and the channels c0 .. c0 + RB_CHUNK - 1: r its row of
+// rois, g0 its [Cf, PH, PW] block of grad_pooled.  Every test up to the barriers is the same in all lanes, so the whole
+// workgroup takes the barriers or none of it does.  acc[k] gains this RoI's share of channel c0 + wave + k * RB_WAVES.
+__device__ __forceinline__ void roi_bwd_step(const RoiMap& mp, const float* r_in, const float* g0, int x0, int y0, int c0, RoiBwdLds& lds,
+                                             float (&acc)[RB_PER]) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int tiles_x = (sp.Wf + RB_TILE - 1) / RB_TILE;
-  const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * RB_TILE, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * RB_TILE;
-  const int c0 = (int)blockIdx.y * RB_CHUNK, b = (int)blockIdx.z;
   const int ty = lane >> 3, tx = lane & 7;
-  const int y = y0 + ty, x = x0 + tx;
-  const int n = roi_count(ar, b);
-  const size_t bins = (size_t)sp.PH * (size_t)sp.PW;
+  const size_t bins = (size_t)mp.PH * (size_t)mp.PW;
   // the build's layout: threads 0..127 make wy (cell = t / 16, bin = t % 16), threads 128..255 wx
   const int b_cell = (t & 127) >> 4, b_bin = t & 15;
   const bool b_isx = t >= 128;
+  float r[4];
+  for (int k = 0; k < 4; ++k) r[k] = r_in[k];
+  if (!roi_finite<float>(r)) return;
+  float sx, bx, sy, by;
+  int gx, gy;
+  roi_axis<float>(r[0], r[2], mp.scale, mp.PW, mp.sampling_ratio, sx, bx, gx);
+  roi_axis<float>(r[1], r[3], mp.scale, mp.PH, mp.sampling_ratio, sy, by, gy);
+  if (gx < 1 || gy < 1) return;
+  if (span_misses(sy, by, mp.PH, y0) || span_misses(sx, bx, mp.PW, x0)) return;
+  __syncthreads();                                                        // the previous RoI's weights have been read
+  {
+    const int P = b_isx ? mp.PW : mp.PH;
+    float w = 0.0f;
+    if (b_bin < P)
+      w = b_isx ? axis_weight(sx, bx, gx, b_bin, mp.Wf, x0 + b_cell) : axis_weight(sy, by, gy, b_bin, mp.Hf, y0 + b_cell);
+    (b_isx ? lds.wx : lds.wy)[b_cell][b_bin] = w;
+    const unsigned long long m = __ballot(w != 0.0f);                     // 4 cells of 16 bins per wave
+    if (b_bin == 0) (b_isx ? lds.mx : lds.my)[b_cell] = (uint32_t)((m >> ((lane >> 4) * 16)) & 0xffffull);
+  }
+  __syncthreads();
+  const uint32_t my = lds.my[ty], mx = lds.mx[tx];
+  if (my == 0u || mx == 0u) return;                                       // (the step's barriers are above: every lane passed them)
+  const float cnt = (float)(gx * gy);
+  float part[RB_PER];
+#pragma unroll
+  for (int k = 0; k < RB_PER; ++k) part[k] = 0.0f;
+  for (uint32_t my_ = my; my_; my_ &= my_ - 1u) {
+    const int ph = __ffs((int)my_) - 1;
+    const float wy = lds.wy[ty][ph];
+    for (uint32_t mx_ = mx; mx_; mx_ &= mx_ - 1u) {
+      GSR_FP_STRICT
+      const int pw = __ffs((int)mx_) - 1;
+      const float w = wy * lds.wx[tx][pw];
+      const size_t o = (size_t)ph * (size_t)mp.PW + (size_t)pw;
+#pragma unroll
+      for (int k = 0; k < RB_PER; ++k) {
+        const int c = c0 + wave + k * RB_WAVES;
+        if (c < mp.Cf) part[k] = part[k] + w * g0[(size_t)c * bins + o];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < RB_PER; ++k) {
+    GSR_FP_STRICT
+    acc[k] = acc[k] + part[k] / cnt;
+  }
+}
+
+// the tile's pixels of the channels c0 + wave + k * RB_WAVES of the plane stack g [Cf, Hf, Wf]: one store per element
+__device__ __forceinline__ void roi_bwd_store(const RoiMap& mp, float* g, int x0, int y0, int c0, int accumulate, const float (&acc)[RB_PER]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int y = y0 + (lane >> 3), x = x0 + (lane & 7);
+  if (y < mp.Hf && x < mp.Wf) {
+#pragma unroll
+    for (int k = 0; k < RB_PER; ++k) {
+      const int c = c0 + wave + k * RB_WAVES;
+      if (c >= mp.Cf) continue;
+      float* o = g + ((size_t)c * (size_t)mp.Hf + (size_t)y) * (size_t)mp.Wf + (size_t)x;
+      *o = accumulate ? *o + acc[k] : acc[k];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(RB_THREADS) k_roi_align_bwd(RoiArgs ar) {
+  __shared__ RoiBwdLds lds;
+  const Spec& sp = ar.sp;
+  const RoiMap mp = roi_map(sp);
+  const int tiles_x = (sp.Wf + RB_TILE - 1) / RB_TILE;
+  const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * RB_TILE, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * RB_TILE;
+  const int c0 = (int)blockIdx.y * RB_CHUNK, b = (int)blockIdx.z;
+  const int n = roi_count(ar, b);
+  const size_t per_roi = (size_t)sp.Cf * (size_t)sp.PH * (size_t)sp.PW;
 
   float acc[RB_PER];
 #pragma unroll
   for (int k = 0; k < RB_PER; ++k) acc[k] = 0.0f;
 
-  for (int s = 0; s < n; ++s) {                                           // n and every test up to the barriers: the same in all lanes
-    float r[4];
-    for (int k = 0; k < 4; ++k) r[k] = ar.rois[((size_t)b * (size_t)sp.S + (size_t)s) * 4 + (size_t)k];
-    if (!roi_finite<float>(r)) continue;
-    float sx, bx, sy, by;
-    int gx, gy;
-    roi_axis<float>(r[0], r[2], sp.spatial_scale, sp.PW, sp.sampling_ratio, sx, bx, gx);
-    roi_axis<float>(r[1], r[3], sp.spatial_scale, sp.PH, sp.sampling_ratio, sy, by, gy);
-    if (gx < 1 || gy < 1) continue;
-    if (span_misses(sy, by, sp.PH, y0) || span_misses(sx, bx, sp.PW, x0)) continue;
-    __syncthreads();                                                      // the previous RoI's weights have been read
-    {
-      const int P = b_isx ? sp.PW : sp.PH;
-      float w = 0.0f;
-      if (b_bin < P)
-        w = b_isx ? axis_weight(sx, bx, gx, b_bin, sp.Wf, x0 + b_cell) : axis_weight(sy, by, gy, b_bin, sp.Hf, y0 + b_cell);
-      (b_isx ? s_wx : s_wy)[b_cell][b_bin] = w;
-      const unsigned long long m = __ballot(w != 0.0f);                   // 4 cells of 16 bins per wave
-      if (b_bin == 0) (b_isx ? s_mx : s_my)[b_cell] = (uint32_t)((m >> ((lane >> 4) * 16)) & 0xffffull);
-    }
-    __syncthreads();
-    const uint32_t my = s_my[ty], mx = s_mx[tx];
-    if (my == 0u || mx == 0u) continue;                                   // (the loop's barriers are above: every lane passed them)
-    const float cnt = (float)(gx * gy);
-    const float* g0 = ar.grad_pooled + ((size_t)b * (size_t)sp.S + (size_t)s) * (size_t)sp.Cf * bins;
-    float part[RB_PER];
-#pragma unroll
-    for (int k = 0; k < RB_PER; ++k) part[k] = 0.0f;
-    for (uint32_t my_ = my; my_; my_ &= my_ - 1u) {
-      const int ph = __ffs((int)my_) - 1;
-      const float wy = s_wy[ty][ph];
-      for (uint32_t mx_ = mx; mx_; mx_ &= mx_ - 1u) {
-        GSR_FP_STRICT
-        const int pw = __ffs((int)mx_) - 1;
-        const float w = wy * s_wx[tx][pw];
-        const size_t o = (size_t)ph * (size_t)sp.PW + (size_t)pw;
-#pragma unroll
-        for (int k = 0; k < RB_PER; ++k) {
-          const int c = c0 + wave + k * RB_WAVES;
-          if (c < sp.Cf) part[k] = part[k] + w * g0[(size_t)c * bins + o];
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < RB_PER; ++k) {
-      GSR_FP_STRICT
-      acc[k] = acc[k] + part[k] / cnt;
-    }
+  for (int s = 0; s < n; ++s) {                                           // n: the same in all lanes
+    const size_t q = (size_t)b * (size_t)sp.S + (size_t)s;
+    roi_bwd_step(mp, ar.rois + q * 4, ar.grad_pooled + q * per_roi, x0, y0, c0, lds, acc);
   }
-  if (y < sp.Hf && x < sp.Wf) {
-#pragma unroll
-    for (int k = 0; k < RB_PER; ++k) {
-      const int c = c0 + wave + k * RB_WAVES;
-      if (c >= sp.Cf) continue;
-      float* o = ar.grad_features + (((size_t)b * (size_t)sp.Cf + (size_t)c) * (size_t)sp.Hf + (size_t)y) * (size_t)sp.Wf + (size_t)x;
-      *o = ar.accumulate ? *o + acc[k] : acc[k];
-    }
-  }
+  roi_bwd_store(mp, ar.grad_features + (size_t)b * (size_t)sp.Cf * (size_t)sp.Hf * (size_t)sp.Wf, x0, y0, c0, ar.accumulate, acc);
 }
 
 // ---- the box head's loss ----------------------------------------------------------------------------------------------------

@@ -88,6 +88,9 @@ SIGNATURES = {
     "gsr_rpn_workspace_bytes": (INT, _p(2)),
     "gsr_rpn_select": (INT, _p(8)),
     "gsr_rpn_nms": (INT, _p(5) + (I64,) + _p(5)),
+    # ---- FPN RoI pooler (features / grad_features: host arrays of device pointers)
+    "gsr_fpn_pool": (INT, _p(4) + (I32,) + _p(5)),
+    "gsr_fpn_pool_backward": (INT, _p(6) + (I32, PTR)),
     # ---- library state, profiling, test hooks
     "gsr_query": (INT, (I32, PTR)),
     "gsr_trim_pool": (None, ()),

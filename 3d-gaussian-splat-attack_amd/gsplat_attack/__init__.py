@@ -38,7 +38,7 @@ def __getattr__(name):
         from . import set_detector
         return getattr(set_detector, name)
     # both sides of a two-stage (R-CNN-style) detector
-    if name in ("ProposalSampler", "RoIHeadLoss", "RoIHeadOutput", "make_roi_loss_fn"):
+    if name in ("ProposalSampler", "RoIHeadLoss", "RoIHeadOutput", "FpnRoIPooler", "make_roi_loss_fn"):
         from . import roi_detector
         return getattr(roi_detector, name)
     # the region proposer in front of it

@@ -11,10 +11,12 @@ the formulas; INTEGRATION.md lists the stated deviations.
 
   ProposalSampler   .sample(proposals, gt_boxes, gt_cls, seed=...) -> rcnn_ops.Sample
   roi_align         (features, rois, counts, ...) -> pooled [B,S,Cf,PH,PW], differentiable with respect to the features
+  FpnRoIPooler      (features of a pyramid, rois, counts) -> pooled: every RoI from the level its size picks (Detectron2's
+                    ROIPooler), on diff_gaussian_rasterization.fpn_ops; .levels(rois, counts) -> the levels alone
   RoIHeadLoss       .loss(scores, deltas, sample, gt_boxes) -> (total, items[2] = cls, box)
   RoIHeadOutput     .detect(scores, deltas, proposals) -> (dets, counts); .verdicts(...) on gsr_det_verdict
   make_roi_loss_fn  renders -> detector_input -> backbone -> proposer (detached; gsplat_attack.proposals.RpnProposer is one)
-                    -> sample -> roi_align -> box_head -> loss
+                    -> sample -> roi_align (or, with pooler=..., an FpnRoIPooler on a pyramid) -> box_head -> loss
                     as pgd_attack's loss_fn; it takes the global view indices of the renders (loss_fn.takes_view_index)
 """
 from __future__ import annotations
@@ -23,7 +25,7 @@ from typing import Callable, Optional, Sequence, Tuple, Union
 
 import torch
 
-from diff_gaussian_rasterization import detect_ops, rcnn_ops
+from diff_gaussian_rasterization import detect_ops, fpn_ops, rcnn_ops
 from diff_gaussian_rasterization.rcnn_ops import RcnnSpec, Sample
 
 
@@ -70,6 +72,46 @@ def roi_align(features: torch.Tensor, rois: torch.Tensor, counts: Optional[torch
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
     spec = RcnnSpec(PH=int(ph), PW=int(pw), spatial_scale=float(spatial_scale), sampling_ratio=int(sampling_ratio))
     return rcnn_ops.roi_align(features, rois, counts, spec)
+
+
+class FpnRoIPooler:
+    """Detectron2's ROIPooler (ROIAlignV2) on a feature pyramid: strides, finest first, powers of two and each double the
+    last (p2..p5: 4, 8, 16, 32); a RoI of size sqrt(area) = canonical_size belongs to the level of stride
+    2^canonical_level, one of half that size to the level below, and so on, clamped to the levels there are.  The level
+    comes from thresholds on sqrt(area) / canonical_size, not from a logarithm: INTEGRATION.md section 8j."""
+
+    def __init__(self, strides: Sequence[int] = (4, 8, 16, 32), output_size=7, sampling_ratio: int = 0, canonical_size: float = 224.0,
+                 canonical_level: int = 4):
+        st = [int(v) for v in strides]
+        if not 1 <= len(st) <= fpn_ops.MAX_LEVELS:
+            raise ValueError(f"FpnRoIPooler: 1..{fpn_ops.MAX_LEVELS} strides")
+        if any(v < 1 or v & (v - 1) for v in st) or any(b != 2 * a for a, b in zip(st, st[1:])):
+            raise ValueError("FpnRoIPooler: the strides must be powers of two, each double the last")
+        ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
+        if not (1 <= int(ph) <= fpn_ops.MAX_POOL and 1 <= int(pw) <= fpn_ops.MAX_POOL) or int(sampling_ratio) < 0:
+            raise ValueError(f"FpnRoIPooler: output_size must be 1..{fpn_ops.MAX_POOL} each and sampling_ratio >= 0")
+        if not (0.0 < float(canonical_size) < float("inf")):
+            raise ValueError("FpnRoIPooler: canonical_size must be finite and > 0")
+        self.strides = tuple(st)
+        self.spec = fpn_ops.FpnSpec(scales=tuple(1.0 / v for v in st), thr=fpn_ops.level_thresholds(st, int(canonical_level)),
+                                    PH=int(ph), PW=int(pw), sampling_ratio=int(sampling_ratio), canonical_size=float(canonical_size))
+
+    def _maps(self, features) -> list:
+        maps = [features] if isinstance(features, torch.Tensor) else list(features)
+        if len(maps) != len(self.strides):
+            raise ValueError(f"FpnRoIPooler: {len(maps)} feature maps for {len(self.strides)} strides")
+        return maps
+
+    def __call__(self, features, rois: torch.Tensor, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """features: one [B,Cf,Hf_l,Wf_l] per stride; rois [B,S,4] in image pixels; counts: a Sample's counts (or int32 [B], or
+        None: every row) -> pooled [B,S,Cf,PH,PW], differentiable with respect to every map; rows without a level are zero."""
+        return fpn_ops.fpn_pool(self._maps(features), rois, counts, self.spec)
+
+    def levels(self, rois: torch.Tensor, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> int32 [B,S]: the index into strides of every RoI's level; -1 beyond the count and for a non-finite row."""
+        B = int(rois.shape[0])
+        maps = [torch.zeros((B, 1, 1, 1), dtype=torch.float32, device=rois.device) for _ in self.strides]
+        return fpn_ops.pool_forward(maps, rois, counts, self.spec._replace(PH=1, PW=1, sampling_ratio=1))[1]
 
 
 class RoIHeadLoss:
@@ -132,14 +174,17 @@ class RoIHeadOutput:
 
 def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable, detector_input: Optional[Callable],
                      sampler: ProposalSampler, head_loss: RoIHeadLoss, gt_bboxes, target: Union[int, Sequence[int]],
-                     output_size=(14, 14), spatial_scale: float = 1.0 / 16.0, sampling_ratio: int = 0) -> Callable:
+                     output_size=(14, 14), spatial_scale: float = 1.0 / 16.0, sampling_ratio: int = 0,
+                     pooler: Optional[Callable] = None) -> Callable:
     """-> loss_fn(renders [B,3,H,W], idx=None) -> total, for pgd_attack(loss_fn=...).  backbone(images) -> features
     [B,Cf,Hf,Wf]; proposer(features) -> proposals [B,R,4] in image pixels (taken detached, as Detectron2 does), or
     (proposals, n_prop int32 [B]) where only the first n_prop[b] rows of image b are proposals, as a
     gsplat_attack.proposals.RpnProposer returns them;
     box_head(pooled [B*S,Cf,PH,PW]) -> (scores [B*S,nc+1], deltas [B*S,4*nc or 4]); gt_bboxes [V,4]: every view's box in the
     frame of the detector's input; target: the class the loss pulls towards, one int or one per view; idx: the views the
-    renders show (default 0..B-1).  The sampler's seed is its own: every step draws the same RoIs for the same proposals."""
+    renders show (default 0..B-1).  The sampler's seed is its own: every step draws the same RoIs for the same proposals.
+    pooler: an FpnRoIPooler (or any (features, rois, counts) -> pooled); then backbone may return a sequence of maps, the
+    proposer receives each of them detached, and output_size, spatial_scale and sampling_ratio are the pooler's own."""
     gt_all = torch.as_tensor(gt_bboxes, dtype=torch.float32)
     tg_all = torch.as_tensor(target, dtype=torch.int32)
 
@@ -150,14 +195,20 @@ def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable,
             raise ValueError(f"loss_fn: {len(ids)} view indices for {int(x.shape[0])} renders")
         features = backbone(detector_input(x) if detector_input is not None else x)
         with torch.no_grad():
-            proposals = proposer(features.detach())
+            if pooler is not None and not isinstance(features, torch.Tensor):
+                proposals = proposer([f.detach() for f in features])
+            else:
+                proposals = proposer(features.detach())
         n_prop = None
         if not isinstance(proposals, torch.Tensor):                      # (proposals, n_prop): rows beyond the count are no candidates
             proposals, n_prop = proposals
         gt = gt_all[ids]
         cls = tg_all.expand(gt_all.shape[0])[ids] if tg_all.dim() == 0 else tg_all[ids]
         smp = sampler.sample(proposals, gt, cls, n_prop=n_prop)
-        pooled = roi_align(features, smp.rois, smp.counts, output_size, spatial_scale, sampling_ratio)
+        if pooler is not None:
+            pooled = pooler(features, smp.rois, smp.counts)
+        else:
+            pooled = roi_align(features, smp.rois, smp.counts, output_size, spatial_scale, sampling_ratio)
         B, S = int(pooled.shape[0]), int(pooled.shape[1])
         scores, deltas = box_head(pooled.reshape(B * S, *pooled.shape[2:]))
         return head_loss.loss(scores.reshape(B, S, -1), deltas.reshape(B, S, -1), smp, gt)[0]

@@ -844,7 +844,8 @@ int gsr_setdet_postprocess(const GsrSetDetSpec* spec, const float* logits, const
  * deviations); csrc/gsr_rcnn.h holds the arithmetic, compiled for the kernels and for a host harness alike.  All
  * arithmetic is float32, every operation rounded on its own; index-valued results are int32.  One GsrRcnnSpec serves all
  * entries; each checks the members it names below and ignores the others.  Proposals are an input: the RPN's own proposal
- * generation, the RPN losses, FPN level assignment and masks are not part of this stage.
+ * generation (the RPN proposal stage below), the RPN losses and masks are not part of this stage; pooling from a feature
+ * pyramid is the FPN RoI pooler's, further below.
  *
  * gsr_rcnn_sample (members B, R, M, S, C, max_pos, append_gt, seed, fg_iou).  proposals [B,R,4]: x1 y1 x2 y2 in pixels, in
  * the proposer's order; n_prop [B] int32 or NULL (= R; clamped to 0..R); gt_boxes [B,M,4]; gt_cls [B,M] int32, a row being
@@ -1021,6 +1022,62 @@ int gsr_rpn_select(const GsrRpnSpec* spec, const float* logits, const float* del
 int gsr_rpn_nms(const GsrRpnSpec* spec, const float* cand_boxes, const float* cand_scores, const int32_t* cand_level, void* ws,
                 int64_t ws_bytes, float* proposals, float* scores, int32_t* keep, int32_t* counts, void* stream);
 
+/* ---- FPN RoI pooler (present iff the library exports gsr_fpn_pool) ---------------------------------------------------------
+ * The step between gsr_rcnn_sample and the box head of a detector with a feature pyramid: Detectron2's ROIPooler with
+ * assign_boxes_to_levels.  Every RoI is pooled from ONE of nl feature maps, chosen by its size; the pooling is
+ * gsr_roi_align's, and the backward gsr_roi_align_backward's, operation by operation: a RoI of level l gives the bits
+ * gsr_roi_align gives on features[l] with spatial_scale = scale[l], and grad_features[l] the bits gsr_roi_align_backward gives
+ * over the RoIs of level l alone.  csrc/gsr_fpn.h holds the level arithmetic, compiled for the kernels and for a host
+ * harness alike (INTEGRATION.md section 8j lists the deviations).  All arithmetic is float32, every operation rounded on its
+ * own; index-valued results are int32.
+ *
+ * Level of row s of image b (rois [B,S,4] in image pixels; n_roi as gsr_roi_align reads it):
+ *       -1                                                          if s >= n_roi[b] or a coordinate is not finite
+ *       area = (x2 - x1) * (y2 - y1);   q = sqrt(area) / canonical_size + 1e-8f
+ *       level = the number of l in 1 .. nl - 1 with q >= thr[l]
+ *   thr[l] = 2^(log2(stride_0) + l - canonical_level) makes this Detectron2's floor(canonical_level + log2(q)) clamped to
+ *   the levels (canonical_size 224, canonical_level 4; strides 4, 8, 16, 32: thr = -, 0.5, 1, 2), without the logarithm: a
+ *   stated deviation, differing only where log2f's rounding crosses an integer.  A q that is NaN (a negative area) passes
+ *   no threshold: level 0, where Detectron2's result is undefined.  A row of level -1 belongs to no level.
+ *
+ * gsr_fpn_pool.  features: a HOST array of nl device pointers, level l being [B,Cf,Hf[l],Wf[l]].  Outputs: pooled
+ * [B,S,Cf,PH,PW] (zeros for a row of level -1; every element written), roi_level [B,S] and level_count [B,nl] (every
+ * element written), level_list [B,nl,S]: the rows of level l of image b in ASCENDING order in its first level_count[b,l]
+ * entries, the others untouched.  The three integer outputs are what gsr_fpn_pool_backward reads; the caller keeps them.
+ * Two launches: the assignment (one workgroup per image, one lane per RoI, ballots and a scan), then the pooling.
+ *
+ * gsr_fpn_pool_backward.  grad_features: a HOST array of nl device pointers, level l being [B,Cf,Hf[l],Wf[l]].  With the
+ * weights and the order of gsr_roi_align_backward,
+ *       grad_features[l][b,c,y,x] = sum over i ascending in 0 .. level_count[b,l] - 1, s = level_list[b,l,i], of
+ *                                   (sum over ph, then pw ascending of (wy[ph][y] * wx[pw][x]) * grad_pooled[b,s,c,ph,pw]) / count_s
+ *   Every element of every level is written exactly once (zeros where a level received no RoI); with accumulate != 0 the
+ *   sum is added to what is there.  level_count is clamped to 0..S and an entry of level_list outside 0..S-1 is skipped:
+ *   neither is trusted for an address.  A gather, no float atomics: two calls on the same input give the same bits, on any
+ *   stream.  One launch for all levels; a tile walks the RoIs of its own level alone.
+ *
+ * Both entries: 1 <= B, Cf <= 65535, 1 <= S <= 1024, 1 <= PH, PW <= 14, sampling_ratio >= 0, 1 <= nl <= 5, Hf[l], Wf[l] >= 1,
+ * scale[l] finite and > 0, thr[1 .. nl-1] finite, > 0 and strictly ascending (thr[0] is not read), canonical_size finite
+ * and > 0, at most 2^31 - 1 elements in a tensor and 8 x 8 tiles in all levels together.  Every tensor argument is a DEVICE
+ * pointer; the two pointer arrays live on the HOST and are read before the call returns.  A size out of range, a NULL
+ * required pointer (each of the nl level pointers is one), a tensor that is not 4-byte aligned return GSR_ERR_INVALID with
+ * a gsr_last_error text before any device call.  No allocation, no copy, no host synchronisation, no workspace: everything
+ * is enqueued on `stream`; capturable and re-entrant (each caller with its own outputs). */
+typedef struct GsrFpnSpec {
+  int32_t B, S, Cf;          /* images, RoIs per image (1..1024), channels of every level */
+  int32_t PH, PW;            /* 1..14; Detectron2's FPN box head: 7, 7 */
+  int32_t sampling_ratio;    /* 0 = adaptive */
+  int32_t nl;                /* levels, 1..5 */
+  int32_t Hf[5], Wf[5];      /* the level's feature map */
+  float   scale[5];          /* the level's spatial_scale: 1 / stride */
+  float   thr[5];            /* level thresholds on q, entry 0 unused; strides 4..32: -, 0.5, 1, 2 */
+  float   canonical_size;    /* Detectron2: 224 */
+} GsrFpnSpec;
+int gsr_fpn_pool(const GsrFpnSpec* spec, const float* const* features, const float* rois, const int32_t* n_roi,
+                 int32_t n_roi_stride, float* pooled, int32_t* roi_level, int32_t* level_list, int32_t* level_count,
+                 void* stream);
+int gsr_fpn_pool_backward(const GsrFpnSpec* spec, const float* rois, const int32_t* level_list, const int32_t* level_count,
+                          const float* grad_pooled, float* const* grad_features, int32_t accumulate, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
@@ -1034,7 +1091,9 @@ int gsr_rpn_nms(const GsrRpnSpec* spec, const float* cand_boxes, const float* ca
  * A library that predates item 4 answers it with GSR_ERR_INVALID: no later stage.  Item 4 is closed at these five bits
  * (31), for the same reason as item 3;
  * 5 every capability bit of this build: the five above and GSR_CAP_RPN = the RPN proposal stage
- * (gsr_rpn_workspace_bytes, gsr_rpn_select, gsr_rpn_nms).  A library that predates item 5 refuses it alike. */
+ * (gsr_rpn_workspace_bytes, gsr_rpn_select, gsr_rpn_nms).  A library that predates item 5 refuses it alike.
+ * The FPN RoI pooler (gsr_fpn_pool, gsr_fpn_pool_backward) has no bit and no item: items 3 to 5 are compared as whole
+ * values by their callers and stay as they are.  That stage is present iff the library exports gsr_fpn_pool. */
 #define GSR_CAP_IMAGE 1
 #define GSR_CAP_DETECT 2
 #define GSR_CAP_DETLOSS 4
