@@ -34,6 +34,7 @@
 #include "gsr_rcnn.hip.h"
 #include "gsr_rpn.hip.h"
 #include "gsr_fpn.hip.h"
+#include "gsr_imgloss.hip.h"
 
 using namespace gsr;
 
@@ -3055,6 +3056,68 @@ int gsr_fpn_pool_backward(const GsrFpnSpec* d, const float* rois, const int32_t*
                      dim3((unsigned)tiles, (unsigned)((d->Cf + gsr_rcnn::RB_CHUNK - 1) / gsr_rcnn::RB_CHUNK), (unsigned)d->B),
                      dim3(gsr_rcnn::RB_THREADS), 0, static_cast<hipStream_t>(stream), ar);
   LAUNCH_CHECK("gsr_fpn_pool_backward");
+  return GSR_OK;
+}
+
+// ---- fused image losses (gsr_imgloss.h / gsr_imgloss.hip.h): no allocation, no copy, no host wait; the workspace is the
+// caller's.  Every check is made on the host before a pointer is followed.
+static bool finite_any(float v) { return v >= -3.0e38f && v <= 3.0e38f; }       // false for a NaN
+
+static int imgloss_spec(const char* fn, const GsrImgLossSpec* d) {
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->C < 1 || d->H < 1 || d->W < 1)
+    return set_err(GSR_ERR_INVALID, "%s: the images are [%d,%d,%d,%d] (sizes >= 1)", fn, d->B, d->C, d->H, d->W);
+  if (d->C > gsr_il::MAX_CHANNELS) return set_err(GSR_ERR_INVALID, "%s: C=%d channels (1..%d)", fn, d->C, gsr_il::MAX_CHANNELS);
+  const unsigned long long hw = (unsigned long long)d->H * (unsigned long long)d->W;       // < 2^62
+  if (hw > 0x7fffffffull || (unsigned long long)d->C * hw > 0x7fffffffull || (unsigned long long)d->B * (unsigned long long)d->C * hw > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in an image tensor", fn);
+  if (!finite_any(d->w_l1) || !finite_any(d->w_l2) || !finite_any(d->w_ssim)) return set_err(GSR_ERR_INVALID, "%s: the weights must be finite", fn);
+  if ((d->flags & ~(GSR_IMGLOSS_CLAMP01 | GSR_IMGLOSS_NO_GRAD)) != 0u) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
+  return GSR_OK;
+}
+
+// the workspace's regions: the per-tile partials, then (with_grad) the three derivative maps
+static void imgloss_regions(Carve& c, const GsrImgLossSpec* d, bool with_grad, gsr_il::Args& ar) {
+  ar.tiles_x = (d->W + gsr_il::IMGLOSS_TW - 1) / gsr_il::IMGLOSS_TW;
+  ar.tpp = gsr_il::tiles_of(d->H, d->W);
+  const size_t tiles = (size_t)d->B * (size_t)d->C * (size_t)ar.tpp;                       // <= B C H W < 2^31
+  ar.part = c.take<float>(3 * tiles);
+  ar.dmaps = with_grad ? c.take<float>(3 * (size_t)d->B * (size_t)d->C * (size_t)d->H * (size_t)d->W) : nullptr;
+}
+
+int gsr_imgloss_workspace_bytes(const GsrImgLossSpec* d, int64_t* bytes) {
+  if (int rc = imgloss_spec("gsr_imgloss_workspace_bytes", d)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_imgloss_workspace_bytes: null bytes");
+  Carve c;
+  gsr_il::Args ar{};
+  imgloss_regions(c, d, (d->flags & GSR_IMGLOSS_NO_GRAD) == 0u, ar);
+  *bytes = (int64_t)c.off;
+  return GSR_OK;
+}
+
+int gsr_imgloss(const GsrImgLossSpec* d, const float* img, const float* ref, void* ws, int64_t ws_bytes, float* terms, float* grad_img,
+                float* ssim_map, void* stream) {
+  if (int rc = imgloss_spec("gsr_imgloss", d)) return rc;
+  if (!img || !ref || !terms || !ws) return set_err(GSR_ERR_INVALID, "gsr_imgloss: null img / ref / terms / ws");
+  if (grad_img && (d->flags & GSR_IMGLOSS_NO_GRAD) != 0u) return set_err(GSR_ERR_INVALID, "gsr_imgloss: grad_img given with GSR_IMGLOSS_NO_GRAD");
+  gsr_il::Args ar{};
+  Carve c(ws);
+  imgloss_regions(c, d, grad_img != nullptr, ar);
+  if (int rc = check_workspace("gsr_imgloss", ws, ws_bytes, c.off, 16, "gsr_imgloss_workspace_bytes")) return rc;
+  if (int rc = check_aligned4("gsr_imgloss", img, ref, terms, grad_img, ssim_map)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ar.B = d->B; ar.C = d->C; ar.H = d->H; ar.W = d->W; ar.w_l1 = d->w_l1; ar.w_l2 = d->w_l2; ar.w_ssim = d->w_ssim; ar.flags = d->flags;
+  ar.img = img; ar.ref = ref; ar.terms = terms; ar.grad = grad_img; ar.ssim_map = ssim_map;
+  ar.inv_n = 1.0f / (float)((long long)d->C * d->H * d->W);
+  const unsigned tiles = (unsigned)((size_t)d->B * (size_t)d->C * (size_t)ar.tpp);
+  hipLaunchKernelGGL(gsr_il::k_imgloss_tile, dim3(tiles), dim3(gsr_il::IL_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_imgloss (tiles)");
+  hipLaunchKernelGGL(gsr_il::k_imgloss_sum, dim3((unsigned)d->B), dim3(gsr_il::SUM_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_imgloss (sum)");
+  if (grad_img) {
+    hipLaunchKernelGGL(gsr_il::k_imgloss_grad, dim3(tiles), dim3(gsr_il::IL_THREADS), 0, st, ar);
+    LAUNCH_CHECK("gsr_imgloss (gradient)");
+  }
   return GSR_OK;
 }
 

@@ -91,6 +91,9 @@ SIGNATURES = {
     # ---- FPN RoI pooler (features / grad_features: host arrays of device pointers)
     "gsr_fpn_pool": (INT, _p(4) + (I32,) + _p(5)),
     "gsr_fpn_pool_backward": (INT, _p(6) + (I32, PTR)),
+    # ---- fused image losses
+    "gsr_imgloss_workspace_bytes": (INT, _p(2)),
+    "gsr_imgloss": (INT, _p(4) + (I64,) + _p(4)),
     # ---- library state, profiling, test hooks
     "gsr_query": (INT, (I32, PTR)),
     "gsr_trim_pool": (None, ()),

@@ -45,4 +45,8 @@ def __getattr__(name):
     if name in ("RpnProposer", "Proposals", "cell_anchors"):
         from . import proposals
         return getattr(proposals, name)
+    # losses that compare two images, and the stealth term built from them
+    if name in ("l1_loss", "l2_loss", "ssim", "psnr", "ImageLoss", "photometric_loss", "with_image_term"):
+        from . import image_loss
+        return getattr(image_loss, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

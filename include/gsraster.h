@@ -1078,6 +1078,56 @@ int gsr_fpn_pool(const GsrFpnSpec* spec, const float* const* features, const flo
 int gsr_fpn_pool_backward(const GsrFpnSpec* spec, const float* rois, const int32_t* level_list, const int32_t* level_count,
                           const float* grad_pooled, float* const* grad_features, int32_t accumulate, void* stream);
 
+/* ---- Fused image losses (present iff the library exports gsr_imgloss) -----------------------------------------------------
+ * L1, L2 and SSIM of an image x against a reference image y, and the gradient of their weighted sum with respect to x: the
+ * reference's utils/loss_utils.py (l1_loss, l2_loss, ssim) per image of a batch.  csrc/gsr_imgloss.h holds the per-pixel
+ * arithmetic, compiled for the kernels and for a host harness alike (INTEGRATION.md section 8k lists the deviations).  All
+ * per-pixel arithmetic is float32, every operation rounded on its own.
+ *
+ * x = img, y = ref, both [B,C,H,W] float32, 1 <= C <= 4; per image b, with n = C H W:
+ *       l1_b   = sum |x - y| / n          l2_b = sum (x - y)^2 / n          ssim_b = sum map / n
+ *       loss_b = w_l1 l1_b + w_l2 l2_b + w_ssim (1 - ssim_b)
+ *   map is the reference's _ssim per channel: win = an 11 x 11 Gaussian window with sigma 1.5 and zero padding of 5;
+ *       mu1 = win * x, mu2 = win * y, E11 = win * x^2, E22 = win * y^2, E12 = win * xy
+ *       s1 = E11 - mu1^2, s2 = E22 - mu2^2, s12 = E12 - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2
+ *       map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2))
+ *   The window is DEFINED as the eleven float32 taps the reference constructs, exp(-(k - 5)^2 / 4.5) as float32 divided by
+ *   their float32 sum, applied separably: rows first, then columns, each an 11-term sum in ascending k.  The reference's
+ *   2-D window is the rounded outer product of the same taps: one rounding per weight apart (a stated deviation).
+ *
+ * Gradient with respect to x (grad_img, when given): L1 gives sign(x - y) / n with sign(0) = 0, L2 gives 2 (x - y) / n, and
+ *       d ssim_b / d x(p) = [win * (dmap/dmu1) + 2 x(p) win * (dmap/dE11) + y(p) win * (dmap/dE12)](p) / n
+ *   where dmap/dmu1 is total (the paths through s1 and s12 included) and the three derivative maps are zero beyond the image:
+ *   a gather over the symmetric window, rows then columns, no float atomics.  Nothing flows to y.
+ *
+ * GSR_IMGLOSS_CLAMP01: both images are clamped to [0,1] on the way in, and the gradient gets gsr_image_resample's inclusive
+ * mask (0 <= x <= 1 passes; a NaN gives 0).  Without it nothing is clamped.  A NaN in image b makes image b's terms NaN
+ * and touches no other image.
+ * GSR_IMGLOSS_NO_GRAD: the caller will pass grad_img == NULL; gsr_imgloss_workspace_bytes then reports the bytes of the
+ * per-tile partial sums alone (without it: those plus three float maps of B C H W elements, needed only for a gradient).
+ * A non-null grad_img with this flag is refused.  The flag changes no output bit.
+ *
+ * Outputs: terms [B,4] = l1, l2, ssim, loss; grad_img [B,C,H,W] or NULL; ssim_map [B,C,H,W] or NULL.  Every element of
+ * every output given is written; what the workspace held before the call has no influence; terms are the same bits with
+ * and without grad_img and ssim_map.  Sums: a 16 x 32 tile's pixels by a fixed butterfly and wave order (float32), an
+ * image's tiles in a fixed order (double).  Three launches with a gradient, two without.
+ *
+ * B, C, H, W >= 1, C <= 4, B C H W < 2^31, finite weights, no unknown flag bits, ws_bytes >= what
+ * gsr_imgloss_workspace_bytes reports for what the call needs, ws 16-byte aligned, the tensors 4-byte aligned: otherwise
+ * GSR_ERR_INVALID with a gsr_last_error text before any pointer is followed.  No allocation, no copy, no host
+ * synchronisation: everything is enqueued on `stream`; capturable and re-entrant (each caller with its own workspace). */
+#define GSR_IMGLOSS_CLAMP01 1u
+#define GSR_IMGLOSS_NO_GRAD 2u
+typedef struct GsrImgLossSpec {
+  int32_t B, C, H, W;
+  float   w_l1, w_l2, w_ssim;
+  uint32_t flags;
+} GsrImgLossSpec;
+int gsr_imgloss_workspace_bytes(const GsrImgLossSpec* spec, int64_t* bytes);
+int gsr_imgloss(const GsrImgLossSpec* spec, const float* img, const float* ref, void* ws, int64_t ws_bytes,
+                float* terms /* [B,4]: l1, l2, ssim, loss */, float* grad_img /* [B,C,H,W] or null */,
+                float* ssim_map /* [B,C,H,W] or null */, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
@@ -1093,7 +1143,8 @@ int gsr_fpn_pool_backward(const GsrFpnSpec* spec, const float* rois, const int32
  * 5 every capability bit of this build: the five above and GSR_CAP_RPN = the RPN proposal stage
  * (gsr_rpn_workspace_bytes, gsr_rpn_select, gsr_rpn_nms).  A library that predates item 5 refuses it alike.
  * The FPN RoI pooler (gsr_fpn_pool, gsr_fpn_pool_backward) has no bit and no item: items 3 to 5 are compared as whole
- * values by their callers and stay as they are.  That stage is present iff the library exports gsr_fpn_pool. */
+ * values by their callers and stay as they are.  That stage is present iff the library exports gsr_fpn_pool, and the
+ * fused image losses (gsr_imgloss_workspace_bytes, gsr_imgloss) likewise iff it exports gsr_imgloss. */
 #define GSR_CAP_IMAGE 1
 #define GSR_CAP_DETECT 2
 #define GSR_CAP_DETLOSS 4
