@@ -35,6 +35,7 @@
 #include "gsr_rpn.hip.h"
 #include "gsr_fpn.hip.h"
 #include "gsr_imgloss.hip.h"
+#include "gsr_rpnloss.hip.h"
 
 using namespace gsr;
 
@@ -3118,6 +3119,164 @@ int gsr_imgloss(const GsrImgLossSpec* d, const float* img, const float* ref, voi
     hipLaunchKernelGGL(gsr_il::k_imgloss_grad, dim3(tiles), dim3(gsr_il::IL_THREADS), 0, st, ar);
     LAUNCH_CHECK("gsr_imgloss (gradient)");
   }
+  return GSR_OK;
+}
+
+// ---- RPN loss stage (gsr_rpnloss.h / gsr_rpnloss.hip.h): no allocation, no copy, no host wait, no float atomics; the
+// workspace is the caller's and one sizer serves both entries.  Every check is made on the host before a pointer is followed.
+// Workspace, each region rounded up to 256 bytes: [rowmax B*M u32][kind counts B*2 i32][thresholds B*2 u64][pre-labels B*R
+// i32][slab B*tiles*2 f32].
+struct RpnLossPlan {
+  gsr_rpnl::Spec sp;
+  int32_t off[gsr_rpnl::MAX_LEVELS + 1];
+  uint32_t tile_start[gsr_rpnl::MAX_LEVELS + 1];
+  long long R;
+  unsigned long long tiles;
+};
+
+static int rpnloss_spec(const char* fn, const GsrRpnLossSpec* d, RpnLossPlan& p) {
+  namespace RL = gsr_rpnl;
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->B > 65535) return set_err(GSR_ERR_INVALID, "%s: B=%d images (1..65535)", fn, d->B);
+  if (d->M < 1 || d->M > RL::MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: M=%d gt rows (1..%d)", fn, d->M, RL::MAX_ROWS);
+  if (d->nl < 1 || d->nl > RL::MAX_LEVELS) return set_err(GSR_ERR_INVALID, "%s: nl=%d levels (1..%d)", fn, d->nl, RL::MAX_LEVELS);
+  if (d->flags != 0u) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
+  if (d->batch_per_image < 1 || d->batch_per_image > RL::MAX_BATCH)
+    return set_err(GSR_ERR_INVALID, "%s: batch_per_image=%d (1..%d)", fn, d->batch_per_image, RL::MAX_BATCH);
+  if (d->pos_quota < 0 || d->pos_quota > d->batch_per_image)
+    return set_err(GSR_ERR_INVALID, "%s: pos_quota=%d (0..batch_per_image=%d)", fn, d->pos_quota, d->batch_per_image);
+  if (!finite_nonneg(d->iou_lo) || !finite_nonneg(d->iou_hi) || !(d->iou_lo <= d->iou_hi))
+    return set_err(GSR_ERR_INVALID, "%s: the thresholds are %g and %g (finite, 0 <= iou_lo <= iou_hi)", fn, (double)d->iou_lo, (double)d->iou_hi);
+  if (!all_finite_nonneg({d->beta, d->w_cls, d->w_loc})) return set_err(GSR_ERR_INVALID, "%s: beta and the weights must be finite and >= 0", fn);
+  p.sp = RL::Spec{};
+  p.sp.B = d->B; p.sp.M = d->M; p.sp.nl = d->nl; p.sp.batch_per_image = d->batch_per_image; p.sp.pos_quota = d->pos_quota;
+  p.sp.seed = d->seed; p.sp.iou_lo = d->iou_lo; p.sp.iou_hi = d->iou_hi; p.sp.beta = d->beta; p.sp.w_cls = d->w_cls; p.sp.w_loc = d->w_loc;
+  p.sp.flags = d->flags;
+  unsigned long long R = 0, tiles = 0;
+  for (int l = 0; l < RL::MAX_LEVELS; ++l) {
+    p.tile_start[l] = (uint32_t)tiles;
+    if (l >= d->nl) continue;
+    if (d->A[l] < 1 || d->Hf[l] < 1 || d->Wf[l] < 1)
+      return set_err(GSR_ERR_INVALID, "%s: level %d is %d anchors on %d x %d cells (sizes >= 1)", fn, l, d->A[l], d->Hf[l], d->Wf[l]);
+    const unsigned long long hw = (unsigned long long)d->Hf[l] * (unsigned long long)d->Wf[l];                                   // < 2^62
+    if (hw > (unsigned long long)RL::MAX_ANCHORS || (unsigned long long)d->A[l] * hw > (unsigned long long)RL::MAX_ANCHORS)       // < 2^55
+      return set_err(GSR_ERR_INVALID, "%s: more than 2^24 anchors in level %d", fn, l);
+    const unsigned long long n_l = (unsigned long long)d->A[l] * hw;
+    if ((unsigned long long)d->B * n_l * 4ull > 0x7fffffffull)
+      return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in the deltas of level %d", fn, l);
+    if (d->stride[l] < 1 || (long long)d->Hf[l] * d->stride[l] > (1ll << 24) || (long long)d->Wf[l] * d->stride[l] > (1ll << 24))
+      return set_err(GSR_ERR_INVALID, "%s: stride[%d]=%d (>= 1, Hf * stride and Wf * stride <= 2^24)", fn, l, d->stride[l]);
+    if (!finite_any(d->shift0[l])) return set_err(GSR_ERR_INVALID, "%s: shift0[%d] must be finite", fn, l);
+    p.sp.A[l] = d->A[l]; p.sp.Hf[l] = d->Hf[l]; p.sp.Wf[l] = d->Wf[l]; p.sp.stride[l] = d->stride[l]; p.sp.shift0[l] = d->shift0[l];
+    R += n_l;
+    tiles += (n_l + gsr_rpnl::RL_THREADS - 1) / gsr_rpnl::RL_THREADS;
+  }
+  p.tile_start[RL::MAX_LEVELS] = (uint32_t)tiles;
+  if (R > (unsigned long long)RL::MAX_ANCHORS) return set_err(GSR_ERR_INVALID, "%s: R=%llu anchors per image in all levels (1..2^24)", fn, R);
+  if ((unsigned long long)d->B * R > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in labels", fn);
+  p.R = RL::level_offsets(p.sp, p.off);
+  p.tiles = tiles;
+  return GSR_OK;
+}
+
+static void rpnloss_regions(Carve& c, const RpnLossPlan& p, gsr_rpnl::LabelArgs& la, gsr_rpnl::LossArgs& lo) {
+  const size_t B = (size_t)p.sp.B;
+  la.rowmax = c.take<uint32_t>(B * (size_t)p.sp.M);
+  la.kind_count = c.take<int32_t>(B * 2);
+  la.thr = c.take<unsigned long long>(B * 2);
+  la.pre = c.take<int32_t>(B * (size_t)p.R);
+  lo.slab = c.take<float>(B * (size_t)p.tiles * 2);
+}
+
+// nl level pointers of a host array: each non-null and 4-byte aligned
+static int rpnloss_levels(const char* fn, const char* what, const float* const* src, int nl, const float** dst) {
+  for (int l = 0; l < nl; ++l) {
+    if (!src[l]) return set_err(GSR_ERR_INVALID, "%s: null %s of level %d", fn, what, l);
+    if (int rc = check_aligned4(fn, src[l])) return rc;
+    dst[l] = src[l];
+  }
+  return GSR_OK;
+}
+
+int gsr_rpnloss_workspace_bytes(const GsrRpnLossSpec* d, int64_t* bytes) {
+  RpnLossPlan p;
+  if (int rc = rpnloss_spec("gsr_rpnloss_workspace_bytes", d, p)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_rpnloss_workspace_bytes: null bytes");
+  Carve c;
+  gsr_rpnl::LabelArgs la{};
+  gsr_rpnl::LossArgs lo{};
+  rpnloss_regions(c, p, la, lo);
+  *bytes = (int64_t)c.off;
+  return GSR_OK;
+}
+
+int gsr_rpnloss_label(const GsrRpnLossSpec* d, const float* const* cell_anchors, const float* gt_boxes, const int32_t* gt_cls, void* ws,
+                      int64_t ws_bytes, int32_t* labels, int32_t* matched, int32_t* counts, int32_t* prelabels, void* stream) {
+  namespace RL = gsr_rpnl;
+  const char* fn = "gsr_rpnloss_label";
+  RpnLossPlan p;
+  if (int rc = rpnloss_spec(fn, d, p)) return rc;
+  if (!cell_anchors || !gt_boxes || !gt_cls || !ws || !labels || !matched || !counts)
+    return set_err(GSR_ERR_INVALID, "%s: null cell_anchors / gt_boxes / gt_cls / ws / labels / matched / counts", fn);
+  RL::LabelArgs ar{};
+  RL::LossArgs unused{};
+  Carve c(ws);
+  rpnloss_regions(c, p, ar, unused);
+  if (int rc = check_workspace(fn, ws, ws_bytes, c.off, 16, "gsr_rpnloss_workspace_bytes")) return rc;
+  if (int rc = rpnloss_levels(fn, "cell_anchors", cell_anchors, d->nl, ar.cells)) return rc;
+  if (int rc = check_aligned4(fn, gt_boxes, gt_cls, labels, matched, counts, prelabels)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ar.sp = p.sp;
+  for (int l = 0; l <= RL::MAX_LEVELS; ++l) ar.off[l] = p.off[l];
+  ar.R = (int32_t)p.R;
+  ar.gt_boxes = gt_boxes; ar.gt_cls = gt_cls; ar.prelabels = prelabels; ar.labels = labels; ar.matched = matched; ar.counts = counts;
+  const unsigned n_init = (unsigned)d->B * (unsigned)std::max(d->M, 2);
+  const dim3 per_anchor((unsigned)((p.R + RL::RL_THREADS - 1) / RL::RL_THREADS), (unsigned)d->B);
+  hipLaunchKernelGGL(RL::k_rpnloss_init, dim3((n_init + RL::RL_THREADS - 1) / RL::RL_THREADS), dim3(RL::RL_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rpnloss_label (init)");
+  hipLaunchKernelGGL(RL::k_rpnloss_rowmax, per_anchor, dim3(RL::RL_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rpnloss_label (row maxima)");
+  hipLaunchKernelGGL(RL::k_rpnloss_prelabel, per_anchor, dim3(RL::RL_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rpnloss_label (pre-labels)");
+  hipLaunchKernelGGL(RL::k_rpnloss_select, dim3(2u, (unsigned)d->B), dim3(RL::RL_SEL_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rpnloss_label (select)");
+  hipLaunchKernelGGL(RL::k_rpnloss_labels, per_anchor, dim3(RL::RL_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rpnloss_label (labels)");
+  return GSR_OK;
+}
+
+int gsr_rpnloss(const GsrRpnLossSpec* d, const int32_t* labels, const int32_t* matched, const float* const* logits, const float* const* deltas,
+                const float* const* cell_anchors, const float* gt_boxes, void* ws, int64_t ws_bytes, float* loss, float* const* grad_logits,
+                float* const* grad_deltas, void* stream) {
+  namespace RL = gsr_rpnl;
+  const char* fn = "gsr_rpnloss";
+  RpnLossPlan p;
+  if (int rc = rpnloss_spec(fn, d, p)) return rc;
+  if (!labels || !matched || !logits || !deltas || !cell_anchors || !gt_boxes || !ws || !loss)
+    return set_err(GSR_ERR_INVALID, "%s: null labels / matched / logits / deltas / cell_anchors / gt_boxes / ws / loss", fn);
+  RL::LabelArgs unused{};
+  RL::LossArgs ar{};
+  Carve c(ws);
+  rpnloss_regions(c, p, unused, ar);
+  if (int rc = check_workspace(fn, ws, ws_bytes, c.off, 16, "gsr_rpnloss_workspace_bytes")) return rc;
+  if (int rc = rpnloss_levels(fn, "logits", logits, d->nl, ar.logits)) return rc;
+  if (int rc = rpnloss_levels(fn, "deltas", deltas, d->nl, ar.deltas)) return rc;
+  if (int rc = rpnloss_levels(fn, "cell_anchors", cell_anchors, d->nl, ar.cells)) return rc;
+  if (grad_logits)
+    if (int rc = rpnloss_levels(fn, "grad_logits", grad_logits, d->nl, const_cast<const float**>(ar.grad_logits))) return rc;
+  if (grad_deltas)
+    if (int rc = rpnloss_levels(fn, "grad_deltas", grad_deltas, d->nl, const_cast<const float**>(ar.grad_deltas))) return rc;
+  if (int rc = check_aligned4(fn, labels, matched, gt_boxes, loss)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ar.sp = p.sp;
+  for (int l = 0; l <= RL::MAX_LEVELS; ++l) { ar.off[l] = p.off[l]; ar.tile_start[l] = p.tile_start[l]; }
+  ar.R = (int32_t)p.R;
+  ar.gt_boxes = gt_boxes; ar.labels = labels; ar.matched = matched; ar.loss = loss;
+  ar.norm = (float)((long long)d->batch_per_image * (long long)d->B);
+  hipLaunchKernelGGL(RL::k_rpnloss_terms, dim3((unsigned)p.tiles, (unsigned)d->B), dim3(RL::RL_THREADS), 0, st, ar);
+  LAUNCH_CHECK("gsr_rpnloss (terms)");
+  hipLaunchKernelGGL(RL::k_rpnloss_final, dim3(1), dim3(RL::RL_THREADS), 0, st, ar, (unsigned)((unsigned long long)d->B * p.tiles));
+  LAUNCH_CHECK("gsr_rpnloss (final)");
   return GSR_OK;
 }
 

@@ -94,6 +94,10 @@ SIGNATURES = {
     # ---- fused image losses
     "gsr_imgloss_workspace_bytes": (INT, _p(2)),
     "gsr_imgloss": (INT, _p(4) + (I64,) + _p(4)),
+    # ---- RPN loss stage (cell_anchors / logits / deltas / grad_*: host arrays of device pointers)
+    "gsr_rpnloss_workspace_bytes": (INT, _p(2)),
+    "gsr_rpnloss_label": (INT, _p(5) + (I64,) + _p(5)),
+    "gsr_rpnloss": (INT, _p(8) + (I64,) + _p(4)),
     # ---- library state, profiling, test hooks
     "gsr_query": (INT, (I32, PTR)),
     "gsr_trim_pool": (None, ()),

@@ -42,7 +42,7 @@ def __getattr__(name):
         from . import roi_detector
         return getattr(roi_detector, name)
     # the region proposer in front of it
-    if name in ("RpnProposer", "Proposals", "cell_anchors"):
+    if name in ("RpnProposer", "RpnLoss", "Proposals", "cell_anchors"):
         from . import proposals
         return getattr(proposals, name)
     # losses that compare two images, and the stealth term built from them

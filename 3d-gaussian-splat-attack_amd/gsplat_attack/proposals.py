@@ -10,6 +10,9 @@ include/gsraster.h holds the formulas; INTEGRATION.md section 8i lists the state
   cell_anchors   (sizes, aspect_ratios) -> [A,4]: Detectron2's generate_cell_anchors
   RpnProposer    .propose(logits, deltas) -> Proposals(boxes, scores, counts); with a `head`, a callable for
                  make_roi_loss_fn: proposer(features) -> (boxes [B,R,4], counts [B])
+  RpnLoss        .loss(logits, deltas, gt_boxes, gt_cls=None) -> (total, terms[2] = cls, loc): the two RPN losses on
+                 diff_gaussian_rasterization.rpnloss_ops; .labels(sizes, gt_boxes, gt_cls=None) -> the anchors' labels alone;
+                 make_roi_loss_fn(..., rpn_loss=...) adds its total to the box head's loss
 """
 from __future__ import annotations
 
@@ -18,8 +21,9 @@ from typing import Callable, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
-from diff_gaussian_rasterization import rpn_ops
+from diff_gaussian_rasterization import rpn_ops, rpnloss_ops
 from diff_gaussian_rasterization.rpn_ops import RpnSpec
+from diff_gaussian_rasterization.rpnloss_ops import RpnLossSpec
 
 
 class Proposals(NamedTuple):
@@ -105,3 +109,84 @@ class RpnProposer:
         logits, deltas = self.head(features)
         p = self.propose(logits, deltas)
         return p.boxes, p.counts
+
+
+class RpnLoss:
+    """The two RPN losses (Detectron2's loss_rpn_cls and loss_rpn_loc) on the RPN loss stage's HIP kernels
+    (diff_gaussian_rasterization.rpnloss_ops): the only losses that act on the proposal stage itself.  levels: one
+    (cell_anchors [A,4], stride, offset) per feature level, in the head's order, as RpnProposer takes them;
+    batch_per_image anchors are sampled per image, at most int(batch_per_image * positive_fraction) of them positive
+    (Detectron2: 256, 0.5); iou = (lo, hi): an anchor whose best IoU is below lo is negative, from hi on positive, between
+    them ignored (0.3, 0.7); cls, loc: the weights of the two terms; beta: smooth L1's (0: plain L1); seed: the key of the
+    sample, which takes the place of Detectron2's randperm -- the same seed draws the same anchors on every run.
+    include/gsraster.h holds the formulas; INTEGRATION.md section 8l lists the stated deviations."""
+
+    def __init__(self, levels: Sequence[LevelDef], batch_per_image: int = 256, positive_fraction: float = 0.5,
+                 iou: Tuple[float, float] = (0.3, 0.7), cls: float = 1.0, loc: float = 1.0, beta: float = 0.0, seed: int = 0):
+        if len(levels) < 1 or len(levels) > rpnloss_ops.MAX_LEVELS:
+            raise ValueError(f"RpnLoss: 1..{rpnloss_ops.MAX_LEVELS} levels")
+        if not 1 <= int(batch_per_image) <= rpnloss_ops.MAX_BATCH:
+            raise ValueError(f"RpnLoss: batch_per_image must be 1..{rpnloss_ops.MAX_BATCH}")
+        if not 0.0 <= float(positive_fraction) <= 1.0:
+            raise ValueError("RpnLoss: positive_fraction must be in [0, 1]")
+        lo, hi = float(iou[0]), float(iou[1])
+        if not (0.0 <= lo <= hi < float("inf")):
+            raise ValueError("RpnLoss: iou must be (lo, hi) with 0 <= lo <= hi, both finite")
+        if not all(0.0 <= float(v) < float("inf") for v in (cls, loc, beta)):
+            raise ValueError("RpnLoss: the weights and beta must be finite and >= 0")
+        self.levels = []
+        for lv in levels:
+            ca, stride = torch.as_tensor(lv[0], dtype=torch.float32), int(lv[1])
+            offset = float(lv[2]) if len(lv) > 2 else 0.0
+            if ca.dim() != 2 or ca.shape[1] != 4 or ca.shape[0] < 1 or stride < 1:
+                raise ValueError("RpnLoss: a level is (cell_anchors [A,4], stride >= 1, offset)")
+            self.levels.append((ca, stride, offset))
+        self.spec = RpnLossSpec(batch_per_image=int(batch_per_image), pos_quota=int(int(batch_per_image) * float(positive_fraction)),
+                                seed=int(seed), iou_lo=lo, iou_hi=hi, beta=float(beta), w_cls=float(cls), w_loc=float(loc))
+
+    def _per_level(self, x, name: str):
+        xs = [x] if isinstance(x, torch.Tensor) else list(x)
+        if len(xs) != len(self.levels):
+            raise ValueError(f"RpnLoss: {len(xs)} {name} for {len(self.levels)} levels")
+        return xs
+
+    def _anchor_levels(self, sizes, device):
+        out = []
+        for i, hw in enumerate(sizes):
+            ca, stride, offset = self.levels[i]
+            if ca.device != device:                                        # moved once, kept
+                ca = ca.to(device)
+                self.levels[i] = (ca, stride, offset)
+            out.append(rpnloss_ops.AnchorLevel(ca, stride, (int(hw[0]), int(hw[1])), offset))
+        return out
+
+    @staticmethod
+    def _gt(gt_boxes, gt_cls, device):
+        """[B,M,4] / [B,M], or [B,4] / [B]: one row per image; gt_cls None: every row present; a row holding a NaN is absent."""
+        gb = torch.as_tensor(gt_boxes, dtype=torch.float32).to(device)
+        if gb.dim() == 2:
+            gb = gb[:, None, :]
+        if gt_cls is None:
+            gc = torch.zeros(gb.shape[:2], dtype=torch.int32, device=device)
+        else:
+            gc = torch.as_tensor(gt_cls).to(device=device, dtype=torch.int32).reshape(gb.shape[:2])
+        gc = torch.where(torch.isnan(gb).any(-1), torch.full_like(gc, -1), gc)
+        return torch.nan_to_num(gb, nan=0.0), gc
+
+    def labels(self, sizes, gt_boxes, gt_cls=None, seed: Optional[int] = None, want_pre: bool = False) -> "rpnloss_ops.Labels":
+        """sizes: one (Hf, Wf) per level (or the logits themselves); gt_boxes on the device the labels are wanted on ->
+        rpnloss_ops.Labels(labels, matched, counts, prelabels)."""
+        device = torch.as_tensor(gt_boxes).device
+        hw = [tuple(s.shape[-2:]) if isinstance(s, torch.Tensor) else tuple(s) for s in self._per_level(sizes, "sizes")]
+        gb, gc = self._gt(gt_boxes, gt_cls, device)
+        spec = self.spec if seed is None else self.spec._replace(seed=int(seed))
+        return rpnloss_ops.label(self._anchor_levels(hw, device), gb, gc, spec, want_pre=want_pre)
+
+    def loss(self, logits, deltas, gt_boxes, gt_cls=None, seed: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """logits [B,A,Hf,Wf] and deltas [B,4A,Hf,Wf], or one of each per level -> (total, terms[2] = cls, loc as they enter
+        the total); total is differentiable with respect to the logits and the deltas."""
+        lg, dl = self._per_level(logits, "logits"), self._per_level(deltas, "deltas")
+        device = lg[0].device
+        gb, gc = self._gt(gt_boxes, gt_cls, device)
+        spec = self.spec if seed is None else self.spec._replace(seed=int(seed))
+        return rpnloss_ops.rpn_loss(lg, dl, self._anchor_levels([tuple(x.shape[-2:]) for x in lg], device), gb, gc, spec)

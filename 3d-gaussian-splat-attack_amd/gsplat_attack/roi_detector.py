@@ -17,7 +17,9 @@ the formulas; INTEGRATION.md lists the stated deviations.
   RoIHeadOutput     .detect(scores, deltas, proposals) -> (dets, counts); .verdicts(...) on gsr_det_verdict
   make_roi_loss_fn  renders -> detector_input -> backbone -> proposer (detached; gsplat_attack.proposals.RpnProposer is one)
                     -> sample -> roi_align (or, with pooler=..., an FpnRoIPooler on a pyramid) -> box_head -> loss
-                    as pgd_attack's loss_fn; it takes the global view indices of the renders (loss_fn.takes_view_index)
+                    as pgd_attack's loss_fn; it takes the global view indices of the renders (loss_fn.takes_view_index);
+                    with rpn_loss=... (a gsplat_attack.proposals.RpnLoss) the RPN head runs with gradient and the two RPN
+                    losses are added
 """
 from __future__ import annotations
 
@@ -175,7 +177,7 @@ class RoIHeadOutput:
 def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable, detector_input: Optional[Callable],
                      sampler: ProposalSampler, head_loss: RoIHeadLoss, gt_bboxes, target: Union[int, Sequence[int]],
                      output_size=(14, 14), spatial_scale: float = 1.0 / 16.0, sampling_ratio: int = 0,
-                     pooler: Optional[Callable] = None) -> Callable:
+                     pooler: Optional[Callable] = None, rpn_loss=None) -> Callable:
     """-> loss_fn(renders [B,3,H,W], idx=None) -> total, for pgd_attack(loss_fn=...).  backbone(images) -> features
     [B,Cf,Hf,Wf]; proposer(features) -> proposals [B,R,4] in image pixels (taken detached, as Detectron2 does), or
     (proposals, n_prop int32 [B]) where only the first n_prop[b] rows of image b are proposals, as a
@@ -184,7 +186,12 @@ def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable,
     frame of the detector's input; target: the class the loss pulls towards, one int or one per view; idx: the views the
     renders show (default 0..B-1).  The sampler's seed is its own: every step draws the same RoIs for the same proposals.
     pooler: an FpnRoIPooler (or any (features, rois, counts) -> pooled); then backbone may return a sequence of maps, the
-    proposer receives each of them detached, and output_size, spatial_scale and sampling_ratio are the pooler's own."""
+    proposer receives each of them detached, and output_size, spatial_scale and sampling_ratio are the pooler's own.
+    rpn_loss: a gsplat_attack.proposals.RpnLoss; then the proposer must be an RpnProposer built with its head: the head runs
+    once WITH gradient, its detached outputs go to proposer.propose, and rpn_loss's total (every view's box as its one gt
+    row, a NaN row absent) is added to the box head's loss -- the only path from the RPN head back to the renders."""
+    if rpn_loss is not None and getattr(proposer, "head", None) is None:
+        raise ValueError("make_roi_loss_fn: rpn_loss needs a proposer with .head and .propose (an RpnProposer built with head=...)")
     gt_all = torch.as_tensor(gt_bboxes, dtype=torch.float32)
     tg_all = torch.as_tensor(target, dtype=torch.int32)
 
@@ -194,11 +201,19 @@ def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable,
         if len(ids) != int(x.shape[0]):
             raise ValueError(f"loss_fn: {len(ids)} view indices for {int(x.shape[0])} renders")
         features = backbone(detector_input(x) if detector_input is not None else x)
-        with torch.no_grad():
-            if pooler is not None and not isinstance(features, torch.Tensor):
-                proposals = proposer([f.detach() for f in features])
-            else:
-                proposals = proposer(features.detach())
+        rpn_logits = rpn_deltas = None
+        if rpn_loss is not None:                                         # the head once, with gradient; the proposals from its detached outputs
+            rpn_logits, rpn_deltas = proposer.head(features)
+            with torch.no_grad():
+                det = lambda v: v.detach() if isinstance(v, torch.Tensor) else [t.detach() for t in v]
+                p = proposer.propose(det(rpn_logits), det(rpn_deltas))
+                proposals = (p.boxes, p.counts)
+        else:
+            with torch.no_grad():
+                if pooler is not None and not isinstance(features, torch.Tensor):
+                    proposals = proposer([f.detach() for f in features])
+                else:
+                    proposals = proposer(features.detach())
         n_prop = None
         if not isinstance(proposals, torch.Tensor):                      # (proposals, n_prop): rows beyond the count are no candidates
             proposals, n_prop = proposals
@@ -211,7 +226,10 @@ def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable,
             pooled = roi_align(features, smp.rois, smp.counts, output_size, spatial_scale, sampling_ratio)
         B, S = int(pooled.shape[0]), int(pooled.shape[1])
         scores, deltas = box_head(pooled.reshape(B * S, *pooled.shape[2:]))
-        return head_loss.loss(scores.reshape(B, S, -1), deltas.reshape(B, S, -1), smp, gt)[0]
+        total = head_loss.loss(scores.reshape(B, S, -1), deltas.reshape(B, S, -1), smp, gt)[0]
+        if rpn_loss is None:
+            return total
+        return total + rpn_loss.loss(rpn_logits, rpn_deltas, gt.to(total.device))[0]
 
     loss_fn.takes_view_index = True
     return loss_fn

@@ -844,8 +844,8 @@ int gsr_setdet_postprocess(const GsrSetDetSpec* spec, const float* logits, const
  * deviations); csrc/gsr_rcnn.h holds the arithmetic, compiled for the kernels and for a host harness alike.  All
  * arithmetic is float32, every operation rounded on its own; index-valued results are int32.  One GsrRcnnSpec serves all
  * entries; each checks the members it names below and ignores the others.  Proposals are an input: the RPN's own proposal
- * generation (the RPN proposal stage below), the RPN losses and masks are not part of this stage; pooling from a feature
- * pyramid is the FPN RoI pooler's, further below.
+ * generation (the RPN proposal stage below) and masks are not part of this stage; pooling from a feature pyramid is the
+ * FPN RoI pooler's and the two RPN losses the RPN loss stage's, both further below.
  *
  * gsr_rcnn_sample (members B, R, M, S, C, max_pos, append_gt, seed, fg_iou).  proposals [B,R,4]: x1 y1 x2 y2 in pixels, in
  * the proposer's order; n_prop [B] int32 or NULL (= R; clamped to 0..R); gt_boxes [B,M,4]; gt_cls [B,M] int32, a row being
@@ -1128,6 +1128,87 @@ int gsr_imgloss(const GsrImgLossSpec* spec, const float* img, const float* ref, 
                 float* terms /* [B,4]: l1, l2, ssim, loss */, float* grad_img /* [B,C,H,W] or null */,
                 float* ssim_map /* [B,C,H,W] or null */, void* stream);
 
+/* ---- RPN loss stage (present iff the library exports gsr_rpnloss) ---------------------------------------------------------
+ * The two losses of the region proposal network, loss_rpn_cls and loss_rpn_loc, with their gradient: Detectron2's
+ * RPN.label_and_sample_anchors, Matcher (with low-quality matches), subsample_labels and RPN.losses.  Two entries:
+ * gsr_rpnloss_label labels and samples the anchors of every image from the anchors and the ground truth alone;
+ * gsr_rpnloss turns labels, the head's logits and deltas into loss[3] and both gradients.  These are the formulas of record
+ * (INTEGRATION.md section 8l lists the deviations); csrc/gsr_rpnloss.h holds the arithmetic, compiled for the kernels and
+ * for a host harness alike.  All arithmetic is float32, every operation rounded on its own; index-valued results are int32.
+ *
+ * Anchors.  Up to 5 levels in the head's order; level l has A[l] cell anchors (cell_anchors[l]: a device tensor [A,4], x1 y1
+ * x2 y2 relative to a cell's shift) on Hf[l] x Wf[l] cells, and anchor a of cell (x, y) is
+ *       cell_anchors[l][a] + ((float)(x * stride[l]) + shift0[l], (float)(y * stride[l]) + shift0[l])   added to both corners
+ * as in gsr_rpn_select.  Its flat index is r = level_offset[l] + (y * Wf + x) * A + a with level_offset[l] the anchors of
+ * the levels before l: Detectron2's concatenation order and gsr_rpn_select's candidate index.  R = sum A Hf Wf <= 2^24.
+ * gt_boxes [B,M,4]; gt_cls [B,M] int32, a row being PRESENT iff gt_cls >= 0 (the RPN is class-agnostic); 1 <= M <= 256.
+ *
+ * gsr_rpnloss_label, per image:
+ *   Match.  iou(m, r) is gsr_rcnn_sample's IoU (pairwise_iou).  best[r] = the first maximum of iou(m, r) over the present
+ *   rows in ascending m (the lowest m wins ties; a NaN is never the maximum), matched[r] that row; -1 without a present row.
+ *   Pre-label: 0 where best < iou_lo, -1 where iou_lo <= best < iou_hi, 1 where best >= iou_hi (Detectron2: 0.3, 0.7).  An
+ *   image without a present row has pre-label 0 everywhere.
+ *   Low-quality matches.  rowmax[m] = the maximum of iou(m, r) over all R anchors (NaN ignored).  Every anchor r with
+ *   iou(m, r) == rowmax[m] for some present row m with rowmax[m] > 0 gets pre-label 1; matched[r] stays its own best row, as
+ *   in Detectron2.  A row with rowmax[m] = 0 promotes nothing (a stated deviation: Detectron2 would promote every anchor).
+ *   Keyed sample.  key(b, r) as in gsr_rcnn_sample with r in the place of i.  #pos / #neg = the anchors of pre-label 1 / 0;
+ *       n_pos = min(pos_quota, #pos);   n_neg = min(batch_per_image - n_pos, #neg)
+ *   (pos_quota = int(batch_per_image * positive_fraction), computed by the caller; Detectron2: 256, 128).  The n_pos
+ *   smallest (key, r) among pre-label 1 keep label 1, the n_neg smallest among pre-label 0 keep label 0; every other anchor
+ *   gets -1.  This takes the place of Detectron2's randperm (a stated deviation): the same seed gives the same sample.
+ *   Outputs: labels [B,R], matched [B,R], counts [B,4] = #pos, #neg, n_pos, n_neg, and, when given, prelabels [B,R].  Every
+ *   element is written.  Five launches: a clear of the workspace's maxima and counts, the rows' maxima (an integer
+ *   atomicMax on the bit image of a non-negative float: a maximum does not depend on the order of arrival), the pre-labels,
+ *   a radix select of each kind's quota-th (key, r), labels.
+ *
+ * gsr_rpnloss.  logits[l] [B,A,Hf,Wf] and deltas[l] [B,4A,Hf,Wf] are the head's own layouts (delta k of anchor a is channel
+ * 4a + k); labels and matched as gsr_rpnloss_label wrote them (a label other than 0 or 1 counts as -1; a label 1 whose
+ * matched row is outside 0..M-1 takes part in cls alone).  With norm = (float)(batch_per_image * B) -- Detectron2's
+ * normaliser, not the sampled count -- and bce(x, t) = max(x, 0) - x t + log1p(exp(-|x|)):
+ *       S_cls = sum over label >= 0 of bce(logit, label)
+ *       S_loc = sum over label == 1, k < 4 of smooth_l1(delta_k - t_k, beta)
+ *               t = Box2BoxTransform(1, 1, 1, 1).get_deltas(anchor, gt[matched]) as in gsr_rcnn_loss; smooth_l1 as there
+ *               (Detectron2: beta = 0)
+ *       loss[3] = (total, cls, loc):  cls = (w_cls * S_cls) / norm,  loc = (w_loc * S_loc) / norm,  total = cls + loc
+ *       grad_logits = (w_cls / norm) * (sigmoid(logit) - label)  where label >= 0, else 0
+ *       grad_deltas = (w_loc / norm) * smooth_l1'(delta_k - t_k) in the four channels of an anchor of label 1, else 0
+ *   grad_logits[l] and grad_deltas[l] have the inputs' own layouts; either array may be NULL (the loss bits are the same
+ *   either way); when given, every element is written exactly once.  The logit and the deltas of an anchor that is not
+ *   sampled, and the deltas of one that is not positive, are never read: a NaN there reaches neither the loss nor a
+ *   gradient.  A non-finite value of a sampled anchor makes the loss non-finite and leaves every other anchor's gradient as
+ *   it is.  Sums: a block's 256 terms by an LDS tree, the blocks' partials by one block in index order.  Two launches.
+ *
+ * The four pointer arrays (cell_anchors, logits, deltas, grad_*) live on the HOST, hold nl device pointers each and are read
+ * before the call returns; every other tensor argument is a DEVICE pointer.  1 <= B <= 65535, 1 <= M <= 256, 1 <= nl <= 5,
+ * A, Hf, Wf >= 1, stride >= 1 with Hf * stride, Wf * stride <= 2^24, shift0 finite, R <= 2^24, B * R and the elements of a
+ * deltas tensor <= 2^31 - 1, 1 <= batch_per_image <= 65536, 0 <= pos_quota <= batch_per_image, 0 <= iou_lo <= iou_hi finite,
+ * beta and the weights finite and >= 0, flags 0.  ws: gsr_rpnloss_workspace_bytes(spec) bytes of device memory, 16-byte
+ * aligned, for either entry; what it held before has no influence.  A size out of range, a NULL required pointer (each of
+ * the nl level pointers is one), a tensor that is not 4-byte aligned, a workspace that is too small or misaligned return
+ * GSR_ERR_INVALID with a gsr_last_error text before any device call.  No allocation, no copy, no host synchronisation, no
+ * float atomics: everything is enqueued on `stream`; capturable and re-entrant (each caller with its own workspace). */
+typedef struct GsrRpnLossSpec {
+  int32_t B, M;              /* images, gt rows (1..256) */
+  int32_t nl;                /* levels, 1..5 */
+  int32_t A[5], Hf[5], Wf[5]; /* anchors per cell and the feature map of each level */
+  int32_t stride[5];         /* pixels per cell */
+  float   shift0[5];         /* Detectron2's offset * stride */
+  int32_t batch_per_image;   /* Detectron2: 256 */
+  int32_t pos_quota;         /* int(batch_per_image * positive_fraction); Detectron2: 128 */
+  uint32_t seed;             /* the sample's key */
+  float   iou_lo, iou_hi;    /* Detectron2: 0.3, 0.7 */
+  float   beta;              /* smooth-L1 beta; Detectron2: 0 */
+  float   w_cls, w_loc;      /* loss weights; Detectron2: 1, 1 */
+  uint32_t flags;            /* none defined: 0 */
+} GsrRpnLossSpec;
+int gsr_rpnloss_workspace_bytes(const GsrRpnLossSpec* spec, int64_t* bytes);
+int gsr_rpnloss_label(const GsrRpnLossSpec* spec, const float* const* cell_anchors, const float* gt_boxes, const int32_t* gt_cls,
+                      void* ws, int64_t ws_bytes, int32_t* labels, int32_t* matched, int32_t* counts,
+                      int32_t* prelabels /* [B,R] or null */, void* stream);
+int gsr_rpnloss(const GsrRpnLossSpec* spec, const int32_t* labels, const int32_t* matched, const float* const* logits,
+                const float* const* deltas, const float* const* cell_anchors, const float* gt_boxes, void* ws, int64_t ws_bytes,
+                float* loss /* [3]: total, cls, loc */, float* const* grad_logits, float* const* grad_deltas, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
@@ -1144,7 +1225,8 @@ int gsr_imgloss(const GsrImgLossSpec* spec, const float* img, const float* ref, 
  * (gsr_rpn_workspace_bytes, gsr_rpn_select, gsr_rpn_nms).  A library that predates item 5 refuses it alike.
  * The FPN RoI pooler (gsr_fpn_pool, gsr_fpn_pool_backward) has no bit and no item: items 3 to 5 are compared as whole
  * values by their callers and stay as they are.  That stage is present iff the library exports gsr_fpn_pool, and the
- * fused image losses (gsr_imgloss_workspace_bytes, gsr_imgloss) likewise iff it exports gsr_imgloss. */
+ * fused image losses (gsr_imgloss_workspace_bytes, gsr_imgloss) likewise iff it exports gsr_imgloss, the RPN loss stage
+ * (gsr_rpnloss_workspace_bytes, gsr_rpnloss_label, gsr_rpnloss) iff it exports gsr_rpnloss. */
 #define GSR_CAP_IMAGE 1
 #define GSR_CAP_DETECT 2
 #define GSR_CAP_DETLOSS 4
