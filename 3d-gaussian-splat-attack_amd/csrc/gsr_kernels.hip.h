@@ -463,12 +463,9 @@ k_emit(const uint32_t* __restrict__ off, const uint32_t* __restrict__ order, con
     }
     uint32_t mask = 0xFu;   // one bit per 16x4 strip of the tile that the Gaussian can reach
     if (cull) {
-      const float x0 = (float)(tx * TILE);
-      const float x1 = fminf(x0 + (float)(TILE - 1), (float)(W - 1));
-      // (the record's centre is relative to the rect's first tile: back to image coordinates for the footprint test)
-      mask = strip_masks4(ra[k].x + (float)((int)(minx - (rx >> 24)) * TILE), ra[k].y + (float)((int)(miny - (ry >> 24)) * TILE),
-                          ra[k].z, ra[k].w, rb[k].x, rb[k].y, x0,
-                          x1, (float)(ty * TILE), (float)(H - 1));
+      // (the record's centre is relative to the rect's first tile; the footprint test runs in this tile's coordinates)
+      mask = tile_strip_masks(ra[k].x, ra[k].y, ra[k].z, ra[k].w, rb[k].x, rb[k].y, (int)(minx - (rx >> 24)),
+                              (int)(miny - (ry >> 24)), (int)tx, (int)ty, W, H);
       if (mask == 0) key = ntiles;
     }
     pair_tile[e[k]] = key;

@@ -736,6 +736,18 @@ GSR_HD uint32_t strip_masks4(float cx, float cy, float A, float B, float C, floa
   return mask;
 }
 
+// strip_masks4 for tile (tx, ty) of a W x H image, in the TILE's own coordinates (what k_emit stores in a pair's top bits).
+// (rcx, rcy): the record's centre, relative to the first pixel of tile (bx, by); the centre handed on is relative to the
+// first pixel of (tx, ty), formed exactly as stage_splat forms it for the compositors, which skip strips on this mask
+// without re-checking: the mask sees the centre they see.  (In image coordinates the centre of a tile at 65504 px would
+// move in steps of 0.004 px, enough to drop a strip that a pixel still reaches: tests/test_host_math.py.)
+GSR_HD uint32_t tile_strip_masks(float rcx, float rcy, float A, float B, float C, float o, int bx, int by, int tx, int ty,
+                                 int W, int H) {
+  const int wlive = W - 1 - TILE * tx;
+  return strip_masks4(rcx + (float)((bx - tx) * TILE), rcy + (float)((by - ty) * TILE), A, B, C, o, 0.f,
+                      (float)(wlive < TILE - 1 ? wlive : TILE - 1), 0.f, (float)(H - 1 - TILE * ty));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Per-(pixel, Gaussian) blend weight (K6 inner step).  Returns false when the entry is skipped.
 // ---------------------------------------------------------------------------------------------

@@ -78,6 +78,15 @@ void hm_strip_masks4(int n, const float* geo, float x0, float x1, float y0, floa
   }
 }
 
+// geo [n,6] with the centre relative to the first pixel of tile (bx, by); out[n] = tile_strip_masks of tile (tx, ty) of a
+// W x H image (k_emit's call)
+void hm_tile_strip_masks(int n, const float* geo, int bx, int by, int tx, int ty, int W, int H, int* out) {
+  for (int i = 0; i < n; ++i) {
+    const float* g = geo + 6 * i;
+    out[i] = (int)tile_strip_masks(g[0], g[1], g[2], g[3], g[4], g[5], bx, by, tx, ty, W, H);
+  }
+}
+
 // geo [n,6] as above; rect_in [4] = rminx, rminy, rmaxx, rmaxy (tiles); out [n,4] = the tightened rect
 void hm_tighten_rect(int n, const float* geo, int gridx, int gridy, const int* rect_in, int* out) {
   for (int i = 0; i < n; ++i) {

@@ -52,18 +52,18 @@ BLOCK_S = 0.854            # isotropic: its alpha = 1/255 ring (d^2 = 11.4) lies
 # ---------------------------------------------------------------------------------------------------------------------
 # cameras
 # ---------------------------------------------------------------------------------------------------------------------
-def camera(H, W, yaw_px=0.0, pitch_px=0.0, forward=0.0):
+def camera(H, W, yaw_px=0.0, pitch_px=0.0, forward=0.0, focal=FOCAL):
     """World -> view in the row-vector convention ([p, 1] @ V).  yaw_px / pitch_px: rotation that moves the image by that
     many pixels at the optical axis (a rotation moves a stack by the same amount whatever its depth); forward: translation
-    along the view axis."""
-    ay, ax = math.atan(yaw_px / FOCAL), math.atan(pitch_px / FOCAL)
+    along the view axis; focal: focal length in pixels (the images of 65520 px need one that keeps tan(fov / 2) at 0.5)."""
+    ay, ax = math.atan(yaw_px / focal), math.atan(pitch_px / focal)
     Ry = np.array([[math.cos(ay), 0, math.sin(ay)], [0, 1, 0], [-math.sin(ay), 0, math.cos(ay)]])
     Rx = np.array([[1, 0, 0], [0, math.cos(ax), math.sin(ax)], [0, -math.sin(ax), math.cos(ax)]])
     R = Rx @ Ry                                            # column-vector rotation world -> view
     V = np.eye(4)
     V[:3, :3] = R.T
     V[3, :3] = (0.0, 0.0, -forward)
-    tanx, tany = W / (2.0 * FOCAL), H / (2.0 * FOCAL)
+    tanx, tany = W / (2.0 * focal), H / (2.0 * focal)
     Pm = np.zeros((4, 4))
     Pm[0, 0], Pm[1, 1] = 1.0 / tanx, 1.0 / tany
     Pm[2, 2], Pm[2, 3], Pm[3, 2] = ZFAR / (ZFAR - ZNEAR), -(ZFAR * ZNEAR) / (ZFAR - ZNEAR), 1.0
@@ -133,6 +133,8 @@ def model(means, scales, quats, opac, cam):
     ncon_cull = np.zeros((gy * TILE, gx * TILE), dtype=np.int64)
     fT = np.ones((gy * TILE, gx * TILE))
     blended = np.zeros(len(means), dtype=bool)
+    # per tile, along its list: kept by the default cull / blended by a pixel of the tile / [256, L] alpha >= 1/255 at a live pixel
+    keptd, blendd, hitd = {}, {}, {}
     yy, xx = np.meshgrid(np.arange(TILE), np.arange(TILE), indexing="ij")
     for (tx, ty), ids in lists.items():
         ids = np.array(ids)
@@ -161,16 +163,20 @@ def model(means, scales, quats, opac, cam):
         ncon[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE] = n.reshape(TILE, TILE)
         fT[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE] = Tf.reshape(TILE, TILE)
         blended[ids] |= (con & inside[:, None]).any(axis=0)
+        blendd[(tx, ty)] = (con & inside[:, None]).any(axis=0)
         # The default footprint cull (include/gsraster.h, GSR_FLAG_NO_CULL) drops a pair whose Gaussian cannot reach
         # alpha >= 1/255 anywhere on the tile's strips clipped to the image -- on the continuous rectangles, not only on the
         # pixel centres.  The kept entries, the list length under the cull, and n_contrib as a position in the kept list:
         kept = _reaches_tile(px[ids], py[ids], c[ids] / det[ids], -b[ids] / det[ids], a[ids] / det[ids], opac[ids], tx, ty, H, W)
         assert not np.any((valid & inside[:, None]).any(axis=0) & ~kept), f"tile {tx},{ty}: the cull would drop a pair a pixel blends"
         tile_len_cull[ty, tx] = int(kept.sum())
+        keptd[(tx, ty)] = kept
+        hitd[(tx, ty)] = valid & inside[:, None]
         rank = np.concatenate([[0], np.cumsum(kept)])
         ncon_cull[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE] = rank[n].reshape(TILE, TILE)
     return SimpleNamespace(cam=cam, tile_len=tile_len, n_contrib=ncon[:H, :W], final_T=fT[:H, :W], blended=blended,
-                           listed=listed, lists=lists, tile_len_cull=tile_len_cull, n_contrib_cull=ncon_cull[:H, :W])
+                           listed=listed, lists=lists, tile_len_cull=tile_len_cull, n_contrib_cull=ncon_cull[:H, :W],
+                           kept=keptd, blended_in=blendd, hits=hitd)
 
 
 def _reaches_tile(cx, cy, A, B, C, o, tx, ty, H, W):
@@ -234,8 +240,10 @@ def stack(L, blockers=None):
 
 
 class _Builder:
-    def __init__(self, H, W, seed):
-        self.H, self.W, self.rows = H, W, []
+    def __init__(self, H, W, seed, focal=FOCAL, depth_sigma=1.0):
+        """focal: of the cameras the scene is built for; depth_sigma: factor on the scale along the view axis (a wide
+        field of view stretches a footprint by (x / z)^2 of it)."""
+        self.H, self.W, self.rows, self.focal, self.depth_sigma = H, W, [], focal, depth_sigma
         self.rng = np.random.default_rng(seed)
 
     def add(self, tx, ty, entries, z0=2.0, dz=0.01):
@@ -250,11 +258,11 @@ class _Builder:
         r = r[self.rng.permutation(len(r))]                 # storage order is not depth order
         P = len(r)
         z = r[:, 2]
-        means = np.stack([(r[:, 0] - (self.W - 1) * 0.5) * z / FOCAL, (r[:, 1] - (self.H - 1) * 0.5) * z / FOCAL, z], axis=1)
+        means = np.stack([(r[:, 0] - (self.W - 1) * 0.5) * z / self.focal, (r[:, 1] - (self.H - 1) * 0.5) * z / self.focal, z], axis=1)
         an = np.where(np.arange(P) % 2 == 0, 1.06, 0.94)
         iso = (r[:, 3] == r[:, 4]) & (r[:, 3] != BLOCK_S) & (r[:, 3] != TINY_S)
         an = np.where(iso, an, 1.0)                          # (a bar keeps its two widths and stays along x)
-        scales = np.stack([r[:, 3] * an, r[:, 4] / an, 0.5 * (r[:, 3] + r[:, 4])], axis=1) * (z / FOCAL)[:, None]
+        scales = np.stack([r[:, 3] * an, r[:, 4] / an, self.depth_sigma * 0.5 * (r[:, 3] + r[:, 4])], axis=1) * (z / self.focal)[:, None]
         th = np.where(iso, self.rng.uniform(0, math.pi, P), 0.0)
         quats = np.stack([np.cos(th / 2), np.zeros(P), np.zeros(P), np.sin(th / 2)], axis=1)
         opac = r[:, 5]
@@ -270,7 +278,7 @@ class _Builder:
                    _rotation=t32(quats) * (0.5 + 1.5 * torch.rand(P, 1, generator=g)))
         act = activate(raw)
         m64 = lambda k: act[k].double().numpy()
-        cams = views if views is not None else [camera(self.H, self.W)]
+        cams = views if views is not None else [camera(self.H, self.W, focal=self.focal)]
         facts = [model(m64("means3D"), m64("scales"), m64("rotations"), m64("opacities")[:, 0], c) for c in cams]
         return SimpleNamespace(name=name, H=self.H, W=self.W, P=P, raw=raw, cams=cams, facts=facts,
                                tile=r[:, 6:8].astype(int), pos=r[:, 8].astype(int))
@@ -521,37 +529,52 @@ CLASSIC = ("means3D", "shs", "sh_objs", "opacities", "scales", "rotations")
 _ORACLE = {}
 
 
-def loss_weights(sc, view):
-    """Seeded dL/dC [3,H,W], dL/dobjects [16,H,W], dL/ddepth [H,W], dL/dalpha [H,W] of one view."""
+def loss_weights(sc, view, tile_windows=None):
+    """Seeded dL/dC [3,H,W], dL/dobjects [16,H,W], dL/ddepth [H,W], dL/dalpha [H,W] of one view; tile_windows (half-open tile
+    rectangles (tx0, ty0, tx1, ty1)): zero outside them."""
     g = torch.Generator().manual_seed(1000 + 17 * view + sc.P)
-    return dict(C=torch.randn(3, sc.H, sc.W, generator=g), O=torch.randn(16, sc.H, sc.W, generator=g),
-                D=torch.randn(sc.H, sc.W, generator=g), A=torch.randn(sc.H, sc.W, generator=g))
+    w = dict(C=torch.randn(3, sc.H, sc.W, generator=g), O=torch.randn(16, sc.H, sc.W, generator=g),
+             D=torch.randn(sc.H, sc.W, generator=g), A=torch.randn(sc.H, sc.W, generator=g))
+    if tile_windows is not None:
+        keep = window_px(sc, tile_windows).to(torch.float32)
+        w = {k: v * keep for k, v in w.items()}
+    return w
 
 
-def oracle_run(sc, view=0, dtype=torch.float64):
-    """oracle-R on one view, once per process: outputs (colour on BG, objects, depth = sum z alpha T and alpha on black,
+def window_px(sc, tile_windows):
+    """[H, W] bool: the pixels inside the tile windows."""
+    m = torch.zeros(sc.H, sc.W, dtype=torch.bool)
+    for (x0, y0, x1, y1) in tile_windows:
+        m[TILE * y0:TILE * y1, TILE * x0:TILE * x1] = True
+    return m
+
+
+def oracle_run(sc, view=0, dtype=torch.float64, tile_windows=None):
+    """oracle-R on one view (with tile_windows: on those tiles alone, the loss weights zero elsewhere), once per process: outputs
+    (colour on BG, objects, depth = sum z alpha T and alpha on black,
     final_T, n_contrib, fragile counts) and, for each of the four loss terms alone (gradients are linear in them), the
     gradient of every raw leaf, of every activated tensor (the classic surface's inputs) and of means2D."""
-    key = (getattr(sc, "oracle_key", sc.name), view, dtype)
+    key = (getattr(sc, "oracle_key", sc.name), view, dtype, None if tile_windows is None else tuple(tile_windows))
     if key in _ORACLE:
         return _ORACLE[key]
     from oracle import oracle_r as O
     cam = sc.cams[view]
     L = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in sc.raw.items()}
     a = activate(L)
+    tw = tile_windows
     m2d = torch.zeros(sc.P, 3, dtype=dtype, requires_grad=True)
     st = settings(cam, torch.tensor(BG), O.Settings)
     col = O.rasterize(a["means3D"], m2d, a["opacities"], st, shs=a["shs"], sh_objs=a["sh_objs"], scales=a["scales"],
-                      rotations=a["rotations"], dtype=dtype)
+                      rotations=a["rotations"], dtype=dtype, tile_windows=tw)
     z = (torch.cat([a["means3D"], torch.ones_like(a["means3D"][:, :1])], dim=1) @ cam.V.to(dtype))[:, 2]
     zc = torch.stack([z, torch.ones_like(z), torch.zeros_like(z)], dim=1)
     aux = O.rasterize(a["means3D"], m2d, a["opacities"], st._replace(bg=torch.zeros(3)), colors_precomp=zc,
-                      scales=a["scales"], rotations=a["rotations"], dtype=dtype)
+                      scales=a["scales"], rotations=a["rotations"], dtype=dtype, tile_windows=tw)
     outs = dict(C=col.color, O=col.objects, D=aux.color[0], A=aux.color[1])
     leaves = dict(L)
     leaves.update(a)
     leaves["means2D"] = m2d
-    w = loss_weights(sc, view)
+    w = loss_weights(sc, view, tile_windows)
     grads = {}
     for c, o in outs.items():
         loss = (o * w[c].to(dtype)).sum()

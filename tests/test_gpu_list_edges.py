@@ -72,12 +72,13 @@ def seg_shift():
     return v if 6 <= v <= 16 else 8
 
 
-def run_single(D, sc, flags, surface, obj, aux, terms, dev):
-    """One forward + backward on view 0.  -> (outputs dict on the CPU, gradients dict name -> tensor)."""
+def run_single(D, sc, flags, surface, obj, aux, terms, dev, tile_windows=None):
+    """One forward + backward on view 0 (tile_windows: loss weights zero outside them).  -> (outputs dict on the CPU,
+    gradients dict name -> tensor)."""
     cam = sc.cams[0]
     st = S.settings(cam, torch.tensor(S.BG), D.GaussianRasterizationSettings, device=dev)
     raw = {k: v.to(dev) for k, v in sc.raw.items()}
-    w = {k: v.to(dev) for k, v in S.loss_weights(sc, 0).items()}
+    w = {k: v.to(dev) for k, v in S.loss_weights(sc, 0, tile_windows).items()}
     with D.extra_flags(flags):
         if surface == "classic":
             act = {k: v.detach().clone().requires_grad_(True) for k, v in S.activate(raw).items()}
@@ -173,8 +174,8 @@ def check_grads(tag, grads, ref64, ref32, dead, first, worst):
             assert bool((g != 0).any(dim=1).all()), f"{tag}: a list's first entry has a zero {k} gradient"
 
 
-def refs_for(sc, view, terms, names):
-    r64, r32 = S.oracle_run(sc, view), S.oracle_run(sc, view, torch.float32)
+def refs_for(sc, view, terms, names, tile_windows=None):
+    r64, r32 = S.oracle_run(sc, view, tile_windows=tile_windows), S.oracle_run(sc, view, torch.float32, tile_windows=tile_windows)
     return ({k: S.grad_sum(r64, terms, k) for k in names}, {k: S.grad_sum(r32, terms, k) for k in names})
 
 
@@ -238,9 +239,14 @@ BATCH_CASES = [(f, "into") for f in BATCH_FORMS] + [(f, "views") for f in ("defa
 def test_batch_against_the_oracle_of_every_view(B, form, mode, worst):
     """Family D through the batch entry points: every view's forward state against that view's oracle; the `_into` backward
     against the float64 sum over the views, the `_views` backward view by view."""
+    batch_case(S.get(("D", B)), B, form, mode, worst)
+
+
+def batch_case(sc, B, form, mode, worst, oracle=S.oracle_run, first=first_entries):
+    """One batch form on a scene of B views.  oracle(sc, view): the float64 result check_forward compares with;
+    first(facts of a view): Gaussians whose opacity and colour gradients must not be zero.  -> (out, leaf, vsp, bset)."""
     D = _D()
     dev = torch.device("cuda:0")
-    sc = S.get(("D", B))
     aux, obj, colour = form.startswith("aux"), form == "objects", form == "colour-only"
     terms = {"aux-alpha": "CA", "aux-depth": "CDA", "objects": "CO"}.get(form, "C")
     flags = _batch_flags(D, form)
@@ -277,7 +283,7 @@ def test_batch_against_the_oracle_of_every_view(B, form, mode, worst):
         res = dict(color=out[0][v].detach().cpu(), objects=out[2][v].detach().cpu() if obj else None,
                    depth=out[2][v, 0].detach().cpu() if aux else None, alpha=out[3][v, 0].detach().cpu() if aux else None,
                    n_contrib=nc[v], final_T=fT[v], lens=lens[v * T:(v + 1) * T], records=None)
-        check_forward(f"{sc.name} / {form} / {mode} / view {v}", sc, v, res, S.oracle_run(sc, v),
+        check_forward(f"{sc.name} / {form} / {mode} / view {v}", sc, v, res, oracle(sc, v),
                       S.oracle_run(sc, v, torch.float32), True, worst)
     dead = S.dead_gaussians(sc)
     per_view = [refs_for(sc, v, terms, names + (() if colour else ("means2D",))) for v in range(B)]
@@ -291,7 +297,7 @@ def test_batch_against_the_oracle_of_every_view(B, form, mode, worst):
                          [t.detach().cpu() for t in bset.bucket(v).slices()]))
             g = {k: t.reshape(sc.raw[k].shape) for k, t in g.items()}
             check_grads(f"{sc.name} / {form} / views / view {v}", g, per_view[v][0], per_view[v][1], ~sc.facts[v].blended,
-                        first_entries(sc.facts[v]), worst)
+                        first(sc.facts[v]), worst)
         if obj:
             check_grads(f"{sc.name} / {form} / views / objects", {"_objects_dc": leaf["_objects_dc"].grad.cpu()},
                         {"_objects_dc": sum(p[0]["_objects_dc"] for p in per_view)},
@@ -300,7 +306,8 @@ def test_batch_against_the_oracle_of_every_view(B, form, mode, worst):
         g = {k: leaf[k].grad.detach().cpu() for k in names}
         ref64 = {k: sum(p[0][k] for p in per_view) for k in names}
         ref32 = {k: sum(p[1][k] for p in per_view) for k in names}
-        check_grads(f"{sc.name} / {form} / into", g, ref64, ref32, dead, first_entries(sc.facts[0]), worst)
+        check_grads(f"{sc.name} / {form} / into", g, ref64, ref32, dead, first(sc.facts[0]), worst)
+    return out, leaf, vsp, bset
 
 
 @pytest.mark.parametrize("shift", [6, 10])

@@ -240,6 +240,95 @@ def test_strip_masks_are_conservative_and_tight(lib):
         assert same >= 0.999 * n * (int(ymax) // 4 + 1)
 
 
+def _far_origin_conics(n, seed):
+    """[n, 6] float32 (tile-relative cx, cy, A, B, C, o): the random conics of the strip-mask test above."""
+    rng = np.random.default_rng(seed)
+    th = rng.uniform(0, math.pi, n)
+    s1, s2 = np.exp(rng.uniform(-1.5, 2.5, n)), np.exp(rng.uniform(-1.5, 2.5, n))
+    c, s = np.cos(th), np.sin(th)
+    a = (c * c) * s1 * s1 + (s * s) * s2 * s2 + 0.3
+    b = c * s * (s1 * s1 - s2 * s2)
+    cc = (s * s) * s1 * s1 + (c * c) * s2 * s2 + 0.3
+    det = a * cc - b * b
+    cx, cy = rng.uniform(-24, 40, n), rng.uniform(-24, 40, n)
+    o = np.concatenate([rng.uniform(0, 1, n // 2), rng.uniform(0, 0.02, n - n // 2)])
+    return np.ascontiguousarray(np.stack([cx, cy, cc / det, -b / det, a / det, o], 1).astype(np.float32))
+
+
+def _brute_strips(centre64, geo64, x1, ymax):
+    """[n, 4] bool: some live pixel centre of strip k passes the reference's alpha test (float64, tile-relative)."""
+    xs, ys = np.meshgrid(np.arange(x1 + 1.0), np.arange(ymax + 1.0))
+    dx = centre64[:, 0, None, None] - xs[None]
+    dy = centre64[:, 1, None, None] - ys[None]
+    power = -0.5 * (geo64[:, 2, None, None] * dx * dx + geo64[:, 4, None, None] * dy * dy) - geo64[:, 3, None, None] * dx * dy
+    ok = (power <= 0) & (np.minimum(0.99, geo64[:, 5, None, None] * np.exp(np.minimum(power, 0))) >= 1.0 / 255.0)
+    return np.stack([ok[:, 4 * k:4 * k + 4, :].any(axis=(1, 2)) if 4 * k <= ymax else np.zeros(len(geo64), bool)
+                     for k in range(4)], axis=1)
+
+
+def _image_coordinate_masks(lib, rel, x0, y0, x1, ymax):
+    """strip_masks4 in IMAGE coordinates, as k_emit called it before it moved to the tile's own: the centre is
+    float32(tile-relative centre + tile origin), the tile spans x0 .. x0 + x1, y0 .. y0 + ymax."""
+    geo = rel.copy()
+    geo[:, 0] = rel[:, 0] + np.float32(x0)
+    geo[:, 1] = rel[:, 1] + np.float32(y0)
+    out = np.zeros(len(rel), np.int32)
+    lib.hm_strip_masks4.argtypes = [ctypes.c_int, ctypes.c_void_p] + [ctypes.c_float] * 4 + [ctypes.c_void_p]
+    lib.hm_strip_masks4(len(rel), ptr(geo), cf(x0), cf(x0 + x1), cf(y0), cf(y0 + ymax), ptr(out))
+    return out
+
+
+# Two of the 300 000 conics of _far_origin_conics(300000, 3), tile-relative (cx, cy, A, B, C, o): with the tile at x0 = 65504
+# strip_masks4 in image coordinates drops strip 1 of the first (a pixel of it has alpha = 1.0020 / 255) and strip 2 of the
+# second (1.00007 / 255); at the origin it keeps both.  The only two of 130 204 contributing strips.
+DROPPED_AT_65504 = [[float.fromhex(h) for h in v] for v in (
+    ("-0x1.e91ff8p-1", "0x1.6baa24p+3", "0x1.ea37dp+0", "-0x1.13ca2cp-1", "0x1.47982cp-3", "0x1.a2001p-2"),
+    ("0x1.d6d1c8p+3", "0x1.806668p+0", "0x1.8e599ep-2", "-0x1.1432aap-3", "0x1.c513e6p-5", "0x1.467d6p-7"))]
+
+
+@pytest.mark.parametrize("origin", [(3824, 0), (65504, 0), (0, 3824), (0, 65504)], ids=lambda o: f"{o[0]}-{o[1]}")
+def test_strip_masks_are_conservative_at_tile_origins_away_from_zero(lib, origin):
+    """The compositors skip strips on k_emit's mask without re-checking, and they see a TILE-relative centre (stage_splat).
+    tile_strip_masks -- k_emit's call -- must therefore keep every strip in which a pixel passes the reference's alpha test
+    with that centre, and mark no strip beyond the image, at tile origins away from 0: the tiles at 3824 and at 65504 (the
+    last tile of the largest image) on one axis and 0 on the other, whole and clipped to the 1 .. 3 live rows or columns of
+    the far-edge scenes (tests/far_edge_scenes.py), with the record's centre relative to a first tile 0, 1 or 3 tiles away.
+    Truth: float64 brute force over the live pixel centres, centre = float32(record's centre + 16 (first tile - tile)).
+
+    k_emit used to hand strip_masks4 the centre rebuilt in image coordinates, float32(tile-relative centre + origin), which
+    at 65504 moves in steps of 0.004 px.  Measured with 300 000 conics of seed 3 on the whole tile, contributing strips
+    dropped: 0 of 130 204 at (0, 0) and (0, 65504), 2 at (65504, 0), 4 at (65504, 65504).  DROPPED_AT_65504 keeps the two, and
+    this test shows the image-coordinate call dropping the first.  (Another distribution of conics, drawn the same way
+    300 000 times, gave 0 of 197 078 at (65504, 0): the drops are rare and depend on the draw, which is why the two found
+    are kept as vectors.  Before tile_strip_masks existed this test could only fail for lack of the symbol; the defect itself
+    is what its last three lines show.)  The origin (65504, 65504) is excluded from the random
+    part: it needs an image of 65520 px on BOTH sides, 17 GB of colour alone, which no device holds."""
+    lib.hm_tile_strip_masks.argtypes = [ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p]
+    rel = np.concatenate([np.array(DROPPED_AT_65504, dtype=np.float32), _far_origin_conics(20000, 3)])
+    tx, ty = origin[0] // 16, origin[1] // 16
+    total = 0
+    for x1, ymax in ((15, 15), (15, 0), (15, 2), (0, 15), (1, 15), (0, 0), (1, 2), (14, 3)):
+        for away in (0, 1, 3):
+            bx, by = max(tx - away, 0), max(ty - away, 0)
+            rec = rel.copy()                               # the record: centre relative to tile (bx, by), in float32
+            rec[:, 0] = rel[:, 0] + np.float32(16 * (tx - bx))
+            rec[:, 1] = rel[:, 1] + np.float32(16 * (ty - by))
+            seen = rec[:, :2] + np.array([16 * (bx - tx), 16 * (by - ty)], dtype=np.float32)      # stage_splat's centre
+            out = np.zeros(len(rel), np.int32)
+            lib.hm_tile_strip_masks(len(rel), ptr(rec), bx, by, tx, ty, 16 * tx + x1 + 1, 16 * ty + ymax + 1, ptr(out))
+            touches = _brute_strips(seen.astype(np.float64), rel.astype(np.float64), x1, ymax)
+            bits = ((out[:, None] >> np.arange(4)[None]) & 1).astype(bool)
+            dropped = touches & ~bits
+            assert not dropped.any(), f"origin {origin}, x1 {x1}, ymax {ymax}, {away} tiles away: {int(dropped.sum())} of {int(touches.sum())} contributing strips dropped"
+            assert not bits[:, [k for k in range(4) if 4 * k > ymax]].any(), f"origin {origin}, x1 {x1}, ymax {ymax}: a strip outside the image was marked"
+            total += int(touches.sum())
+    assert total > 20000
+    if origin == (65504, 0):
+        old = _image_coordinate_masks(lib, rel[:2], 65504.0, 0.0, 15, 15)
+        truth = _brute_strips(rel[:2, :2].astype(np.float64), rel[:2].astype(np.float64), 15, 15)
+        assert truth[0, 1] and not (old[0] >> 1) & 1, "the image-coordinate call no longer drops the recorded strip"
+
+
 def test_tightened_rect_keeps_every_contributing_tile(lib):
     """tighten_rect (K1, default flags) shrinks a splat's 3-sigma tile rect to the bounding box of its alpha >= 1/255
     footprint.  No tile in which some pixel passes the reference's alpha test may fall outside the shrunk rect (brute
