@@ -36,6 +36,7 @@
 #include "gsr_fpn.hip.h"
 #include "gsr_imgloss.hip.h"
 #include "gsr_rpnloss.hip.h"
+#include "gsr_objmap.hip.h"
 
 using namespace gsr;
 
@@ -3277,6 +3278,78 @@ int gsr_rpnloss(const GsrRpnLossSpec* d, const int32_t* labels, const int32_t* m
   LAUNCH_CHECK("gsr_rpnloss (terms)");
   hipLaunchKernelGGL(RL::k_rpnloss_final, dim3(1), dim3(RL::RL_THREADS), 0, st, ar, (unsigned)((unsigned long long)d->B * p.tiles));
   LAUNCH_CHECK("gsr_rpnloss (final)");
+  return GSR_OK;
+}
+
+// ---- object-map classifier (gsr_objmap.h / gsr_objmap.hip.h): no allocation, no copy, no host wait, no float atomics; the
+// workspace is the caller's.  Every check is made on the host before a pointer is followed.
+static int objmap_spec(const char* fn, const GsrObjMapSpec* d) {
+  if (!d) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  if (d->B < 1 || d->H < 1 || d->W < 1) return set_err(GSR_ERR_INVALID, "%s: the map is [%d,16,%d,%d] (sizes >= 1)", fn, d->B, d->H, d->W);
+  if (d->K < 1 || d->K > gsr_om::MAX_CLASSES) return set_err(GSR_ERR_INVALID, "%s: K=%d classes (1..%d)", fn, d->K, gsr_om::MAX_CLASSES);
+  if (d->B > 65535) return set_err(GSR_ERR_INVALID, "%s: B=%d images (1..65535)", fn, d->B);
+  const unsigned long long hw = (unsigned long long)d->H * (unsigned long long)d->W;       // < 2^62
+  if (hw > 0x7fffffffull || (unsigned long long)d->B * gsr_om::CH * hw > 0x7fffffffull ||
+      (unsigned long long)d->B * (unsigned long long)d->K * 5ull > 0x7fffffffull)
+    return set_err(GSR_ERR_INVALID, "%s: more than 2^31 - 1 elements in a tensor", fn);
+  if ((d->flags & ~GSR_OBJMAP_LOSS) != 0u) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, d->flags);
+  return GSR_OK;
+}
+
+// the workspace's regions, with GSR_OBJMAP_LOSS alone: the classify workgroups' CE partials, the init workgroups' counts
+static void objmap_regions(Carve& c, const GsrObjMapSpec* d, gsr_om::Args& ar) {
+  ar.hw = d->H * d->W;
+  ar.nblk = gsr_om::blocks_of(d->H, d->W);
+  if ((d->flags & GSR_OBJMAP_LOSS) == 0u) return;
+  ar.slab = c.take<float>((size_t)d->B * (size_t)ar.nblk);
+  ar.vpart = c.take<int32_t>((size_t)d->B * gsr_om::INIT_BLOCKS);
+}
+
+int gsr_objmap_workspace_bytes(const GsrObjMapSpec* d, int64_t* bytes) {
+  if (int rc = objmap_spec("gsr_objmap_workspace_bytes", d)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_objmap_workspace_bytes: null bytes");
+  Carve c;
+  gsr_om::Args ar{};
+  objmap_regions(c, d, ar);
+  *bytes = (int64_t)c.off;
+  return GSR_OK;
+}
+
+int gsr_objmap(const GsrObjMapSpec* d, const float* objmap, const float* weight, const float* bias, const int32_t* target,
+               const uint8_t* palette, void* ws, int64_t ws_bytes, int32_t* ids, float* conf, int32_t* stats, uint8_t* paint,
+               float* terms, float* grad, void* stream) {
+  const char* fn = "gsr_objmap";
+  if (int rc = objmap_spec(fn, d)) return rc;
+  if (!objmap || !weight || !bias || !ids) return set_err(GSR_ERR_INVALID, "gsr_objmap: null objmap / weight / bias / ids");
+  if (paint && !palette) return set_err(GSR_ERR_INVALID, "gsr_objmap: paint given without a palette");
+  const bool loss_flag = (d->flags & GSR_OBJMAP_LOSS) != 0u;
+  if ((terms || grad) && !loss_flag) return set_err(GSR_ERR_INVALID, "gsr_objmap: terms / grad given without GSR_OBJMAP_LOSS");
+  if ((terms || grad) && !target) return set_err(GSR_ERR_INVALID, "gsr_objmap: terms / grad given without a target");
+  if (loss_flag && !ws) return set_err(GSR_ERR_INVALID, "gsr_objmap: null ws with GSR_OBJMAP_LOSS");
+  gsr_om::Args ar{};
+  Carve c(ws);
+  objmap_regions(c, d, ar);
+  if (int rc = check_workspace(fn, ws, ws_bytes, c.off, 16, "gsr_objmap_workspace_bytes")) return rc;
+  if (int rc = check_aligned4(fn, objmap, weight, bias, target, ids, conf, stats, terms, grad)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ar.B = d->B; ar.H = d->H; ar.W = d->W; ar.K = d->K;
+  ar.objmap = objmap; ar.target = target; ar.palette = palette;
+  ar.ids = ids; ar.conf = conf; ar.stats = stats; ar.paint = paint; ar.terms = terms; ar.grad = grad;
+  const bool loss = terms || grad;
+  const dim3 threads(gsr_om::OM_THREADS);
+  if (stats || loss) {
+    hipLaunchKernelGGL(gsr_om::k_objmap_init, dim3(gsr_om::INIT_BLOCKS, (unsigned)d->B), threads, 0, st, ar, weight, bias, loss ? 1 : 0);
+    LAUNCH_CHECK("gsr_objmap (init)");
+  }
+  const dim3 grid((unsigned)ar.nblk, (unsigned)d->B);
+  const size_t lds = stats ? 5 * (size_t)d->K * sizeof(int32_t) : 0;
+  if (loss) hipLaunchKernelGGL(gsr_om::k_objmap_classify<true>, grid, threads, lds, st, ar, weight, bias);
+  else hipLaunchKernelGGL(gsr_om::k_objmap_classify<false>, grid, threads, lds, st, ar, weight, bias);
+  LAUNCH_CHECK("gsr_objmap (classify)");
+  if (stats || terms) {
+    hipLaunchKernelGGL(gsr_om::k_objmap_final, dim3((unsigned)d->B), threads, 0, st, ar);
+    LAUNCH_CHECK("gsr_objmap (final)");
+  }
   return GSR_OK;
 }
 

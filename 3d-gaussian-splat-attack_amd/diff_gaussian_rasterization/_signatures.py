@@ -98,6 +98,9 @@ SIGNATURES = {
     "gsr_rpnloss_workspace_bytes": (INT, _p(2)),
     "gsr_rpnloss_label": (INT, _p(5) + (I64,) + _p(5)),
     "gsr_rpnloss": (INT, _p(8) + (I64,) + _p(4)),
+    # ---- object-map classifier
+    "gsr_objmap_workspace_bytes": (INT, _p(2)),
+    "gsr_objmap": (INT, _p(7) + (I64,) + _p(7)),
     # ---- library state, profiling, test hooks
     "gsr_query": (INT, (I32, PTR)),
     "gsr_trim_pool": (None, ()),

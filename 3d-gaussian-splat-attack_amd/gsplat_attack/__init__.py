@@ -49,4 +49,8 @@ def __getattr__(name):
     if name in ("l1_loss", "l2_loss", "ssim", "psnr", "ImageLoss", "photometric_loss", "with_image_term"):
         from . import image_loss
         return getattr(image_loss, name)
+    # the consumers of the object map: ids, boxes and a loss on the segmentation
+    if name in ("segment_objects", "object_boxes", "group_bboxes", "object_ce", "ObjectMaps"):
+        from . import objects
+        return getattr(objects, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

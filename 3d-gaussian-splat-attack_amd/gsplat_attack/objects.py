@@ -4,10 +4,16 @@ The attack itself never reads that output; the reference's evaluation viewer doe
 convolution classifies the 16 composited object features per pixel, the arg-max is the object id map, and ids are
 painted with a golden-ratio hue palette (``render.py:45-73``).  ``feature_to_rgb`` (``render.py:25-43``) shows the
 features themselves through their first three principal components.
+
+``segment_objects``, ``object_boxes``, ``group_bboxes`` and ``object_ce`` are the fused HIP counterparts
+(``diff_gaussian_rasterization.objmap_ops``, ``gsr_objmap``): the id map without the [K,H,W] logit tensor, per-class boxes
+and pixel counts taken inside the full scene, the painted image, and a cross-entropy loss on the segmentation whose
+gradient reaches ``_objects_dc`` through the rasteriser.  They need a HIP device; the torch functions above stay as they are.
 """
 from __future__ import annotations
 
 import colorsys
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -73,3 +79,93 @@ def feature_to_rgb(features: torch.Tensor) -> np.ndarray:
     if span == 0:
         return np.zeros((H, W, 3), dtype=np.uint8)
     return (255 * (proj - proj.min()) / span).astype("uint8")
+
+
+# ---- the fused stage (gsr_objmap) ---------------------------------------------------------------------------------------------
+class ObjectMaps(NamedTuple):
+    ids: torch.Tensor                  # [B,H,W] int32 ([H,W] for a [16,H,W] map); -1 where no logit compared greater than -inf
+    conf: Optional[torch.Tensor]       # the arg-max's softmax probability, shaped like ids
+    stats: torch.Tensor                # [B,K,5] int32 ([K,5]): count, left, upper, right, lower (right / lower exclusive)
+    paint: Optional[torch.Tensor]      # [B,H,W,3] uint8 ([H,W,3]): id2rgb of every id, -1 black
+
+
+def classifier_parameters(classifier):
+    """(weight [K,16], bias [K]) of an ObjectClassifier, an nn.Conv2d(16, K, 1) or a (weight, bias) pair, detached."""
+    if isinstance(classifier, ObjectClassifier):
+        classifier = classifier.conv
+    if isinstance(classifier, nn.Conv2d):
+        if tuple(classifier.kernel_size) != (1, 1) or classifier.in_channels != NUM_OBJECTS or classifier.groups != 1:
+            raise ValueError(f"the object classifier must be Conv2d({NUM_OBJECTS}, K, 1), got {classifier}")
+        weight, bias = classifier.weight, classifier.bias
+    elif isinstance(classifier, (tuple, list)) and len(classifier) == 2:
+        weight, bias = classifier
+    else:
+        raise TypeError("classifier must be an ObjectClassifier, an nn.Conv2d(16, K, 1) or a (weight, bias) pair")
+    weight = weight.detach().reshape(weight.shape[0], -1)
+    if bias is None:
+        bias = torch.zeros(weight.shape[0], dtype=weight.dtype, device=weight.device)
+    return weight, bias.detach()
+
+
+def object_palette(num_classes: int, device=None) -> torch.Tensor:
+    """uint8 [K,3]: id2rgb of every class id."""
+    rows = np.stack([id2rgb(i, max(256, num_classes)) for i in range(num_classes)])
+    return torch.from_numpy(rows).to(device)
+
+
+def segment_objects(render_object: torch.Tensor, classifier, *, conf: bool = False, paint: bool = False) -> ObjectMaps:
+    """[B,16,H,W] or [16,H,W] object map -> ObjectMaps: predict_objects' ids (the first maximum; a NaN logit never wins),
+    every class's pixel count and box, and on request the confidence and the painted image, in one fused call."""
+    from diff_gaussian_rasterization import objmap_ops
+    weight, bias = classifier_parameters(classifier)
+    dev = render_object.device
+    weight, bias = weight.to(dev), bias.to(dev)
+    pal = object_palette(int(weight.shape[0]), dev) if paint else None
+    out = objmap_ops.objmap_forward(render_object, weight, bias, palette=pal, want_conf=conf, want_stats=True, want_paint=paint)
+    if render_object.dim() == 3:
+        first = lambda t: None if t is None else t[0]
+        return ObjectMaps(out.ids[0], first(out.conf), out.stats[0], first(out.paint))
+    return ObjectMaps(out.ids, out.conf, out.stats, out.paint)
+
+
+def object_boxes(stats: torch.Tensor, ids: Sequence[int]):
+    """stats [B,K,5] (or [K,5]) of segment_objects, ids: the selected class ids -> per image (box, count): the union box
+    (left, upper, right, lower) of the pixels the selected ids own, right / lower exclusive as PIL's getbbox gives them, or
+    None when they own no pixel, and the number of those pixels.  A list for [B,K,5], one pair for [K,5].  One read-back."""
+    if stats.dim() not in (2, 3) or stats.shape[-1] != 5:
+        raise ValueError(f"object_boxes: stats must be [B,K,5] or [K,5], got {tuple(stats.shape)}")
+    K = int(stats.shape[-2])
+    sel = sorted({int(i) for i in ids})
+    if any(not 0 <= i < K for i in sel):
+        raise ValueError(f"object_boxes: ids must lie in 0..{K - 1}, got {sel}")
+    rows = (stats if stats.dim() == 3 else stats.unsqueeze(0))[:, sel].cpu().numpy().astype(np.int64)
+    out = []
+    for r in rows:
+        r = r[r[:, 0] > 0]
+        if len(r) == 0:
+            out.append((None, 0))
+        else:
+            out.append(((int(r[:, 1].min()), int(r[:, 2].min()), int(r[:, 3].max()), int(r[:, 4].max())), int(r[:, 0].sum())))
+    return out if stats.dim() == 3 else out[0]
+
+
+@torch.no_grad()
+def group_bboxes(model, cameras: Sequence, classifier, ids: Sequence[int], pipe=None) -> list:
+    """The object-map counterpart of attack.benign_bboxes: every view of the WHOLE scene rendered with its object channels, the
+    map classified per pixel, and the box of the pixels the selected ids own returned per view (None where they own none)
+    -- the visible extent of the selected object inside its scene, with no render of the object alone."""
+    from .renderer import PipelineParams, render_views
+    pipe = pipe or PipelineParams()
+    black = torch.zeros(3, device=model.get_xyz.device)
+    return [object_boxes(segment_objects(r["render_object"], classifier).stats, ids)[0]
+            for r in render_views(cameras, model, pipe, black)]
+
+
+def object_ce(render_object: torch.Tensor, target: torch.Tensor, classifier) -> torch.Tensor:
+    """[B,16,H,W] (or [16,H,W]) object map, target ids [B,H,W] (or [H,W]; an id outside 0..K-1 is ignored) -> loss [B]: the
+    mean cross entropy of the frozen classifier's per-pixel softmax against the target, differentiable with respect to the
+    map -- and through render() to the model's object features."""
+    from diff_gaussian_rasterization import objmap_ops
+    weight, bias = classifier_parameters(classifier)
+    dev = render_object.device
+    return objmap_ops.object_ce(render_object, weight.to(dev), bias.to(dev), target)

@@ -1209,6 +1209,55 @@ int gsr_rpnloss(const GsrRpnLossSpec* spec, const int32_t* labels, const int32_t
                 const float* const* deltas, const float* const* cell_anchors, const float* gt_boxes, void* ws, int64_t ws_bytes,
                 float* loss /* [3]: total, cls, loc */, float* const* grad_logits, float* const* grad_deltas, void* stream);
 
+/* ---- Object-map classifier (present iff the library exports gsr_objmap) ----------------------------------------------------
+ * What consumes render()'s 16-channel object map: the reference's torch.argmax(Conv2d(16, K, 1)(map), 0) (render.py:126-131)
+ * per pixel, fused with the arg-max's confidence, per-class boxes, a painted image, and the cross entropy against a target
+ * id map with its gradient with respect to the map.  No logit is stored: at K = 256 the torch expression writes and reads
+ * a [256,H,W] tensor, this call reads the map once.  csrc/gsr_objmap.h holds the per-pixel arithmetic, compiled for the
+ * kernels and for a host harness alike (INTEGRATION.md section 8m lists the deviations).  All arithmetic is float32; the
+ * softmax sum alone is carried in double and rounded to float32 once.
+ *
+ * objmap [B,16,H,W], weight [K,16] and bias [K] (the Conv2d's, row-major), 1 <= K <= 1024; per pixel with features f:
+ *       l_c  = fma chain: l = bias[c]; for k = 0..15: l = fmaf(weight[c,k], f[k], l)
+ *       id   = the first maximum of l_c over c = 0..K-1 under l > best, from -inf.  A NaN logit is never the maximum
+ *              (torch.argmax lets a NaN win: a stated deviation); a pixel none of whose logits compares greater than -inf
+ *              gets id -1
+ *       conf = 1 / sum_c exp(l_c - m), m the maximum, c ascending: the arg-max's softmax probability; 0 for id -1
+ *   stats [B,K,5] = (count, x0, y0, x1, y1) of each class's pixels in each image: PIL's getbbox convention, x1 and y1
+ *   exclusive; five zeros for a class without a pixel.  Accumulated per workgroup, then with integer atomicAdd / atomicMin /
+ *   atomicMax: commutative integer updates, the same bits whatever the order of arrival.
+ *   paint [B,H,W,3] uint8 = palette[id] (palette [K,3] uint8), black for id -1.
+ *
+ * GSR_OBJMAP_LOSS with a target [B,H,W] int32: a pixel is COUNTED iff its id >= 0 and its target lies in 0..K-1; valid_b is
+ * the number of counted pixels of image b.
+ *       ce(pixel) = (m - l_t) + log sum_c exp(l_c - m)
+ *       terms [B,2] = (sum of ce over the counted pixels / valid_b, valid_b as float); (0, 0) when valid_b = 0
+ *       grad [B,16,H,W]: d terms[b,0] / d objmap = (1 / valid_b) sum_c weight[c,k] (p_c - [c = t]), c ascending, one fmaf per
+ *       term, p_c = exp(l_c - m) conf; zeros at every pixel that is not counted.  The classifier is frozen: there is no
+ *       gradient to weight or bias.
+ *   A NaN logit beside a finite maximum makes that pixel's conf, ce and gradient NaN and image b's terms[b,0] NaN, and
+ *   touches no other image.  Sums: a workgroup's 256 terms by an LDS tree, an image's workgroups in index order (float32).
+ *
+ * ids is required; conf, stats, paint, terms and grad may each be NULL.  Every element of every output given is written;
+ * what the workspace held before the call has no influence; each output is the same bits whichever others are given.
+ * Two to three launches with stats or a loss, one without.
+ *
+ * B, H, W >= 1, B <= 65535, 1 <= K <= 1024, at most 2^31 - 1 elements in a tensor, no unknown flag bits; paint needs palette;
+ * terms and grad need target and GSR_OBJMAP_LOSS; ws_bytes >= what gsr_objmap_workspace_bytes reports (0 without
+ * GSR_OBJMAP_LOSS, and ws may then be NULL), ws 16-byte aligned, the float and int tensors 4-byte aligned: otherwise
+ * GSR_ERR_INVALID with a gsr_last_error text before any device call.  No allocation, no copy, no host synchronisation:
+ * everything is enqueued on `stream`; capturable and re-entrant (each caller with its own workspace). */
+#define GSR_OBJMAP_LOSS 1u
+typedef struct GsrObjMapSpec {
+  int32_t B, H, W, K;
+  uint32_t flags;
+} GsrObjMapSpec;
+int gsr_objmap_workspace_bytes(const GsrObjMapSpec* spec, int64_t* bytes);
+int gsr_objmap(const GsrObjMapSpec* spec, const float* objmap, const float* weight /* [K,16] */, const float* bias /* [K] */,
+               const int32_t* target /* [B,H,W] or null */, const uint8_t* palette /* [K,3] or null */, void* ws,
+               int64_t ws_bytes, int32_t* ids, float* conf, int32_t* stats /* [B,K,5] */, uint8_t* paint,
+               float* terms /* [B,2] */, float* grad, void* stream);
+
 /* Introspection. what: 0 version, 1 bytes held by the workspace pool on the current device,
  * 2 number of pairs of a context (ctx as int64 handle in *out on input is NOT used; see gsr_ctx_info),
  * 3 capability bits of this build (features added without a change of GSR_VERSION): GSR_CAP_IMAGE = the image front end
@@ -1226,7 +1275,8 @@ int gsr_rpnloss(const GsrRpnLossSpec* spec, const int32_t* labels, const int32_t
  * The FPN RoI pooler (gsr_fpn_pool, gsr_fpn_pool_backward) has no bit and no item: items 3 to 5 are compared as whole
  * values by their callers and stay as they are.  That stage is present iff the library exports gsr_fpn_pool, and the
  * fused image losses (gsr_imgloss_workspace_bytes, gsr_imgloss) likewise iff it exports gsr_imgloss, the RPN loss stage
- * (gsr_rpnloss_workspace_bytes, gsr_rpnloss_label, gsr_rpnloss) iff it exports gsr_rpnloss. */
+ * (gsr_rpnloss_workspace_bytes, gsr_rpnloss_label, gsr_rpnloss) iff it exports gsr_rpnloss, the object-map classifier
+ * (gsr_objmap_workspace_bytes, gsr_objmap) iff it exports gsr_objmap. */
 #define GSR_CAP_IMAGE 1
 #define GSR_CAP_DETECT 2
 #define GSR_CAP_DETLOSS 4
