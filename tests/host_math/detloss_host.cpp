@@ -1,6 +1,8 @@
 // The detector loss stage in plain loops over csrc/gsr_detloss.h, the same scalar source the HIP kernels compile:
-//   dlh_run_f32  float32, what gsr_detloss computes (sums taken pairwise, so that their rounding stays at the level of the
-//                kernels' trees instead of growing with the element count)
+//   dlh_run_f32  float32, what gsr_detloss computes; every sum is taken in the kernels' own order (gsr_detloss.hip.h: a
+//                strided run per thread, the fixed LDS tree, the slab of per-block partials added by one block), with
+//                four anchors per lane where A % 4 == 0, so that what is left between this build and the kernels is the
+//                two maths libraries
 //   dlh_run_f64  the same code in double: tests/test_detloss_host_cpu.py differentiates its `total` by central differences
 //                to check the hand-written backward against its own forward
 // Build: g++ -O1 -ffp-contract=off -shared -fPIC -I <csrc> detloss_host.cpp -o libdetlosshost.so
@@ -21,16 +23,24 @@ struct HostSpec {   // GsrDetLossSpec of include/gsraster.h
   uint32_t flags;
 };
 
+// gsr_block.hip.h's block_tree_sum over v[0 .. n-1], n a power of two: stride halving, t < s; the sum ends in v[0]
 template <class T>
-static T pairwise(const T* v, size_t n) {
-  if (n <= 8) {
-    T s = (T)0;
-    for (size_t i = 0; i < n; ++i) s = s + v[i];
-    return s;
-  }
-  const size_t h = n / 2;
-  return pairwise(v, h) + pairwise(v + h, n - h);
+static T tree_sum(std::vector<T>& v) {
+  for (size_t s = v.size() / 2; s > 0; s >>= 1)
+    for (size_t t = 0; t < s; ++t) v[t] = v[t] + v[t + s];
+  return v[0];
 }
+
+// n values as a workgroup of `threads` adds them: thread t runs over t, t + threads, ... in index order, then the tree
+template <class T>
+static T strided_tree_sum(const T* x, size_t n, size_t threads) {
+  std::vector<T> acc(threads, (T)0);
+  for (size_t t = 0; t < threads; ++t)
+    for (size_t i = t; i < n; i += threads) acc[t] = acc[t] + x[i];
+  return tree_sum(acc);
+}
+
+constexpr int ASG_THREADS = 1024, TERM_THREADS = 256, CLS_CHUNK = 16, FIN_THREADS = 256;   // gsr_detloss.hip.h's
 
 static bool to_spec(const HostSpec* d, Spec& sp) {
   if (!d || d->B < 1 || d->A < 1 || d->C < 1 || d->M < 1 || d->M > MAX_ROWS || d->nl < 1 || d->nl > MAX_LEVELS ||
@@ -132,11 +142,22 @@ static int run(const HostSpec* d, const T* pred, const T* gt_boxes, const int32_
     for (int a = 0; a < A; ++a)
       if (tg[a] >= 0) tsb[a] = target_score<T>(met[(size_t)tg[a] * sA + a], rov[tg[a]], rmet[tg[a]]);
   }
-  const T tss = clamp_tss<T>(pairwise<T>(ts, (size_t)B * sA));
+  T ts_all = (T)0;                                   // k_detloss_assign's per-image sums, added in image order
+  for (int b = 0; b < B; ++b) ts_all = ts_all + strided_tree_sum<T>(ts + (size_t)b * sA, sA, ASG_THREADS);
+  const T tss = clamp_tss<T>(ts_all);
 
-  std::vector<T> t_box((size_t)B * sA, (T)0), t_cls((size_t)B * sA, (T)0), t_dfl((size_t)B * sA, (T)0);
+  // k_detloss_terms' grid: (anchor tiles, 1 + class chunks, images), V anchors per lane; a lane's partial sums
+  const int V = A % 4 == 0 ? 4 : 1;
+  const size_t per = (size_t)TERM_THREADS * (size_t)V, tiles = (sA + per - 1) / per;
+  const size_t chunks = 1 + (size_t)((C + CLS_CHUNK - 1) / CLS_CHUNK), nblocks = tiles * chunks * (size_t)B;
+  std::vector<T> l_box(nblocks * TERM_THREADS, (T)0), l_cls(nblocks * TERM_THREADS, (T)0), l_dfl(nblocks * TERM_THREADS, (T)0);
+  auto lane_of = [&](int b, size_t chunk, int a) {
+    const size_t tile = (size_t)a / per, t = ((size_t)a % per) / (size_t)V;
+    return ((((size_t)b * chunks + chunk) * tiles + tile) * TERM_THREADS) + t;
+  };
   const T fB = (T)B;
-  for (int b = 0; b < B; ++b)
+  std::vector<T> t_bce((size_t)C * sA);
+  for (int b = 0; b < B; ++b) {
     for (int a = 0; a < A; ++a) {
       const size_t i = (size_t)b * sA + a;
       const T* pa = pred + (size_t)b * (size_t)K * sA + a;
@@ -150,23 +171,39 @@ static int run(const HostSpec* d, const T* pred, const T* gt_boxes, const int32_
         box_dfl_anchor<T>(pa, sA, (T)gx, (T)gy, (T)st, gt_boxes + ((size_t)b * (size_t)M + (size_t)m) * 4, fB * (T)sp.w_box * w,
                           fB * (T)sp.w_dfl * w, ga, sA, bt, dt, frozen && ciou_a ? ciou_a + i : nullptr,
                           !frozen && ciou_a ? ciou_a + i : nullptr);
-        t_box[i] = bt * ts[i];
-        t_dfl[i] = dt * ts[i];
+        const size_t ln = lane_of(b, 0, a);          // a lane takes its V anchors in index order, as this loop does
+        l_box[ln] = l_box[ln] + bt * ts[i];
+        l_dfl[ln] = l_dfl[ln] + dt * ts[i];
       } else if (ga) {
         for (int k = 0; k < BOX_CH; ++k) ga[(size_t)k * sA] = (T)0;
       }
       const int tc = m >= 0 ? gt_cls[(size_t)b * (size_t)M + (size_t)m] : -1;
       const T kc = fB * (T)sp.w_cls / tss;
-      T acc = (T)0;
       for (int c = 0; c < C; ++c) {
         T g;
-        acc = acc + bce<T>(pa[(size_t)(BOX_CH + c) * sA], tc == c ? ts[i] : (T)0, &g);
+        t_bce[(size_t)c * sA + a] = bce<T>(pa[(size_t)(BOX_CH + c) * sA], tc == c ? ts[i] : (T)0, &g);
         if (ga) ga[(size_t)(BOX_CH + c) * sA] = kc * g;
       }
-      t_cls[i] = acc;
     }
-  const T box = pairwise<T>(t_box.data(), t_box.size()) / tss, cls = pairwise<T>(t_cls.data(), t_cls.size()) / tss,
-          dfl = pairwise<T>(t_dfl.data(), t_dfl.size()) / tss;
+    // a lane of a class chunk adds class by class, and within a class its V anchors
+    for (int c = 0; c < C; ++c)
+      for (int a = 0; a < A; ++a) {
+        const size_t ln = lane_of(b, 1 + (size_t)(c / CLS_CHUNK), a);
+        l_cls[ln] = l_cls[ln] + t_bce[(size_t)c * sA + a];
+      }
+  }
+  // every block's tree -> the slab, which k_detloss_final's one block adds
+  std::vector<T> slab[3] = {std::vector<T>(nblocks), std::vector<T>(nblocks), std::vector<T>(nblocks)};
+  std::vector<T>* lanes[3] = {&l_box, &l_cls, &l_dfl};
+  T sums[3];
+  for (int j = 0; j < 3; ++j) {
+    for (size_t blk = 0; blk < nblocks; ++blk) {
+      std::vector<T> v(lanes[j]->begin() + (ptrdiff_t)(blk * TERM_THREADS), lanes[j]->begin() + (ptrdiff_t)((blk + 1) * TERM_THREADS));
+      slab[j][blk] = tree_sum(v);
+    }
+    sums[j] = strided_tree_sum<T>(slab[j].data(), nblocks, FIN_THREADS);
+  }
+  const T box = sums[0] / tss, cls = sums[1] / tss, dfl = sums[2] / tss;
   loss[0] = box;
   loss[1] = cls;
   loss[2] = dfl;
