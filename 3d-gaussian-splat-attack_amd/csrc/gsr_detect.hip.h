@@ -7,10 +7,9 @@
 //                        in A): one lane per anchor loops over the channels.  Layout 0 ([B,A,K], contiguous in K): 16
 //                        lanes per anchor stride over its row and combine with 4 shuffles; the preference is a total
 //                        order, so the combination tree gives the sequential answer.
-//   k_det_select_sort    one workgroup per image: counts the candidates; beyond max_candidates a radix select over the
-//                        64-bit composite (8 digits of 8 bits) finds the cut -- composites are unique, so exactly
-//                        max_candidates lie at or below it; gathers them into LDS (slot by an LDS atomic: the sort undoes
-//                        the arrival order) and sorts them there with a bitonic network (32 KiB).
+//   k_det_select_sort    one workgroup per image: counts the candidates; beyond max_candidates gsr_block's select over the
+//                        64-bit composite finds the cut; its gather and sort put the candidates at or below the cut into
+//                        LDS, best first (32 KiB).
 //   k_det_nms            one workgroup per image, greedy sweep: every thread holds 8 entries (box, area, class) in
 //                        registers, a 4096-bit alive mask sits in LDS; per kept box: all threads find the next alive
 //                        entry from the mask, its owner publishes the box, every thread tests its later entries and
@@ -20,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gsr_block.hip.h"
 #include "gsr_detect.h"
 
 namespace gsr_detect {
@@ -87,8 +87,6 @@ __global__ void __launch_bounds__(SEL_THREADS) k_det_select_sort(int A, int maxc
   __shared__ uint64_t keys[MAX_CAND];
   __shared__ uint32_t hist[256];
   __shared__ uint32_t s_count;
-  __shared__ uint64_t s_prefix;
-  __shared__ uint32_t s_k;
   const int b = blockIdx.x, t = threadIdx.x;
   const float* sc = score + (size_t)b * (size_t)A;
   int n_in = A;
@@ -109,62 +107,15 @@ __global__ void __launch_bounds__(SEL_THREADS) k_det_select_sort(int A, int maxc
     if (above) above[(size_t)b * (size_t)above_stride] = (int32_t)total;
     ncand[b] = n;
   }
-  uint64_t cut = ~0ull;                              // every candidate lies at or below it
-  if (total > (uint32_t)maxc) {
-    if (t == 0) { s_prefix = 0ull; s_k = (uint32_t)maxc; }
-    for (int shift = 56; shift >= 0; shift -= 8) {
-      if (t < 256) hist[t] = 0u;
-      __syncthreads();
-      const uint64_t prefix = s_prefix;
-      for (int a = t; a < n_in; a += SEL_THREADS) {
-        const float s = sc[a];
-        if (use_thr && !is_candidate(s, conf_thr)) continue;
-        const uint64_t c = composite(s, a);
-        if (shift == 56 || (c >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(uint32_t)(c >> shift) & 255u], 1u);
-      }
-      __syncthreads();
-      if (t == 0) {                                  // the digit at which the running count reaches k
-        uint32_t k = s_k, cum = 0u;
-        int d = 0;
-        for (; d < 255; ++d) {
-          if (cum + hist[d] >= k) break;
-          cum += hist[d];
-        }
-        s_k = k - cum;
-        s_prefix = prefix | ((uint64_t)d << shift);
-      }
-      __syncthreads();
-    }
-    cut = s_prefix;
-  }
-  if (t == 0) s_count = 0u;
-  __syncthreads();
-  for (int a = t; a < n_in; a += SEL_THREADS) {
+  const auto key_at = [&](int a, uint64_t& key) {
     const float s = sc[a];
-    if (use_thr && !is_candidate(s, conf_thr)) continue;
-    const uint64_t c = composite(s, a);
-    if (c <= cut) {
-      const uint32_t slot = atomicAdd(&s_count, 1u);
-      if (slot < (uint32_t)MAX_CAND) keys[slot] = c;
-    }
-  }
-  int P = 2;
-  while (P < n) P <<= 1;
-  __syncthreads();
-  for (int i = n + t; i < P; i += SEL_THREADS) keys[i] = ~0ull;
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = t; i < P; i += SEL_THREADS) {
-        const int x = i ^ j;
-        if (x > i) {
-          const uint64_t u = keys[i], v = keys[x];
-          const bool up = (i & k) == 0;
-          if ((u > v) == up) { keys[i] = v; keys[x] = u; }
-        }
-      }
-      __syncthreads();
-    }
+    key = composite(s, a);
+    return !use_thr || is_candidate(s, conf_thr);
+  };
+  uint64_t cut = ~0ull;                              // every candidate lies at or below it
+  int taken = n;
+  if (total > (uint32_t)maxc) cut = gsr_block::block_select_u64<SEL_THREADS>(hist, n_in, maxc, key_at, taken, (int)total);
+  gsr_block::block_gather_sort_u64<SEL_THREADS>(keys, &s_count, n_in, taken, cut, key_at);
   for (int i = t; i < n; i += SEL_THREADS) order[(size_t)b * (size_t)maxc + (size_t)i] = (int32_t)(uint32_t)keys[i];
 }
 

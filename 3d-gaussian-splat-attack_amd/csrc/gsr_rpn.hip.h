@@ -3,14 +3,11 @@
 // compares.  The integer LDS atomics below count (any order gives the same number) or hand out places in a list that is
 // sorted by unique keys afterwards, so the same input gives the same bits on every run.
 //
-//   k_rpn_select   one workgroup per image.  The k-th key of the image's A * Hf * Wf (logit, index) keys by a radix select,
-//                  eight bits a pass, read in memory order (coalesced); a pass whose digit group is exactly what is still
-//                  wanted ends the select early, which is every case without a tie across the k-th place.  The keys are
-//                  unique, so "key <= the k-th" names exactly k survivors, ties at the k-th place decided by index.  They
-//                  go into LDS in any order, are sorted there (bitonic, padded to a power of two with NO_KEY), and rank r
-//                  is decoded into slot cand_offset + r.
-//   k_rpn_order    one workgroup per image: the keys (score, slot) of the N slots with a level >= 0, sorted in LDS, as a
-//                  list of slots in walk order and its length.
+//   k_rpn_select   one workgroup per image.  The level's slots smallest of the image's A * Hf * Wf (logit, index) keys, read
+//                  in memory order (coalesced), by gsr_block's select, gather and sort (the early end is every case without
+//                  a tie across the k-th place); rank r is decoded into slot cand_offset + r.
+//   k_rpn_order    one workgroup per image: the keys (score, slot) of the N slots with a level >= 0, sorted in LDS
+//                  (block_sort_u64), as a list of slots in walk order and its length.
 //   k_rpn_walk     one workgroup per image, the kept boxes, areas and levels in LDS.  The ordered slots are taken 64 at a
 //                  time, lane l of every wave holding candidate l: wave w tests it against the kept boxes w, w + 16, ...
 //                  (an LDS broadcast each) and the waves' ballots are OR-ed; the 64 x 64 block inside the chunk is one
@@ -19,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gsr_block.hip.h"
 #include "gsr_rpn.h"
 
 namespace gsr_rpn {
@@ -51,28 +49,6 @@ struct NmsArgs {
   int32_t* counts;            // [B]
 };
 
-// ascending bitonic sort of s[0 .. n_pow2) by the whole workgroup; ends with a barrier
-__device__ __forceinline__ void lds_sort_u64(uint64_t* s, int n_pow2) {
-  const int t = threadIdx.x, half = n_pow2 >> 1;
-  __syncthreads();
-  for (int k = 2; k <= n_pow2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int q = t; q < half; q += RPN_THREADS) {
-        const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
-        const uint64_t a = s[i], b = s[l];
-        if ((a > b) == ((i & k) == 0)) { s[i] = b; s[l] = a; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-__device__ __forceinline__ int pow2_at_least(int n) {
-  int p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
 // the key of element m (memory order: anchor a = m / HW slowest) of an image's logits; false for a NaN
 __device__ __forceinline__ bool key_of(const float* lg, int m, int HW, int A, uint64_t& key) {
   const float v = lg[m];
@@ -84,72 +60,18 @@ __device__ __forceinline__ bool key_of(const float* lg, int m, int HW, int A, ui
 __global__ void __launch_bounds__(RPN_THREADS) k_rpn_select(SelectArgs ar) {
   __shared__ uint64_t s_key[MAX_SLOTS];
   __shared__ uint32_t s_hist[256];
-  __shared__ int s_cnt;
+  __shared__ uint32_t s_cnt;
   const Spec& sp = ar.sp;
   const int b = blockIdx.x, t = threadIdx.x;
   const int A = sp.A, HW = sp.Hf * sp.Wf, n_in = A * HW;
   const int slots = (int)level_slots(sp);                                  // <= N <= MAX_SLOTS
   const float* lg = ar.logits + (size_t)b * (size_t)n_in;
 
-  // ---- the k-th key: prefix / mask grow from the top digit down; every value below is the same in all threads
-  uint64_t prefix = 0ull, mask = 0ull, thr = 0ull;
-  int want = 0;                                                             // how many of the current group are still wanted
-  bool done = false;
-  for (int shift = 56; shift >= 0 && !done; shift -= 8) {
-    if (shift < 32 && ((uint64_t)(uint32_t)(n_in - 1) >> shift) == 0ull) {  // every index has a zero digit here
-      mask |= 0xffull << shift;
-      continue;
-    }
-    if (t < 256) s_hist[t] = 0u;
-    __syncthreads();
-    for (int m = t; m < n_in; m += RPN_THREADS) {
-      uint64_t key;
-      if (key_of(lg, m, HW, A, key) && (key & mask) == prefix) atomicAdd(&s_hist[(unsigned)(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (shift == 56) {
-      unsigned n_valid = 0u;
-      for (int d = 0; d < 256; ++d) n_valid += s_hist[d];
-      want = (unsigned)slots < n_valid ? slots : (int)n_valid;
-      if (want == 0) break;
-    }
-    unsigned below = 0u;
-    int d = 0;
-    for (; d < 255; ++d) {
-      const unsigned h = s_hist[d];
-      if (below + h >= (unsigned)want) break;
-      below += h;
-    }
-    want -= (int)below;
-    prefix |= (uint64_t)d << shift;
-    mask |= 0xffull << shift;
-    if (s_hist[d] == (unsigned)want) {                                      // the whole group is in
-      thr = prefix | ~mask;
-      done = true;
-    }
-    __syncthreads();                                                        // the histogram has been read
-  }
-  if (!done) thr = prefix;                                                  // all 64 bits fixed: the k-th key itself
-  const bool any = want > 0;
-
-  // ---- the survivors, in any order, then sorted
-  if (t == 0) s_cnt = 0;
-  __syncthreads();
-  if (any) {
-    for (int m = t; m < n_in; m += RPN_THREADS) {
-      uint64_t key;
-      if (key_of(lg, m, HW, A, key) && key <= thr) {
-        const int pos = atomicAdd(&s_cnt, 1);
-        if (pos < MAX_SLOTS) s_key[pos] = key;
-      }
-    }
-  }
-  __syncthreads();
-  int K = s_cnt;
-  K = K < slots ? K : slots;                                                // (= s_cnt: the select names exactly that many)
-  const int P = pow2_at_least(K > 1 ? K : 2);
-  for (int i = K + t; i < P; i += RPN_THREADS) s_key[i] = NO_KEY;
-  lds_sort_u64(s_key, P);
+  // ---- the slots smallest keys (fewer where fewer exist), sorted
+  const auto key_at = [&](int m, uint64_t& key) { return key_of(lg, m, HW, A, key); };
+  int taken;
+  const uint64_t thr = gsr_block::block_select_u64<RPN_THREADS>(s_hist, n_in, slots, key_at, taken);
+  const int K = gsr_block::block_gather_sort_u64<RPN_THREADS>(s_key, &s_cnt, n_in, taken, thr, key_at);
 
   // ---- rank r -> slot cand_offset + r
   for (int r = t; r < slots; r += RPN_THREADS) {
@@ -186,7 +108,7 @@ __global__ void __launch_bounds__(RPN_THREADS) k_rpn_order(NmsArgs ar) {
   const int b = blockIdx.x, t = threadIdx.x, N = sp.N;
   if (t == 0) s_cnt = 0;
   __syncthreads();
-  const int P = pow2_at_least(N > 1 ? N : 2);
+  const int P = gsr_block::pow2_at_least(N > 1 ? N : 2);
   int mine = 0;
   for (int i = t; i < P; i += RPN_THREADS) {
     uint64_t key = NO_KEY;
@@ -198,7 +120,7 @@ __global__ void __launch_bounds__(RPN_THREADS) k_rpn_order(NmsArgs ar) {
     s_key[i] = key;
   }
   if (mine) atomicAdd(&s_cnt, mine);                                        // integers: any order gives the same number
-  lds_sort_u64(s_key, P);
+  gsr_block::block_sort_u64<RPN_THREADS>(s_key, P);
   const int n = s_cnt;
   for (int i = t; i < N; i += RPN_THREADS) ar.order[(size_t)b * (size_t)N + (size_t)i] = i < n ? (int)(uint32_t)s_key[i] : -1;
   if (t == 0) ar.nvalid[b] = n;

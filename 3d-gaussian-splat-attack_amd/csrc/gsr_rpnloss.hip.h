@@ -12,10 +12,8 @@
 //                       the first-maximum row, the promotion, the pre-label; the kinds' counts by ballots, one integer
 //                       atomicAdd per block and kind
 //   k_rpnloss_select    (2, B), one workgroup per image and kind: the quota-th smallest composite key << 32 | r of the kind
-//                       by a radix select, eight bits a pass, a 256-bin LDS histogram, reads in index order; skipped when the
-//                       quota takes the whole kind, index digits that are zero for every anchor skipped, ended early by a
-//                       digit group that is exactly what is still wanted.  Every loop that holds a barrier has a trip count
-//                       computed by all threads from the same LDS words
+//                       by gsr_block's block_select_u64, reads in index order; returns before it when the quota takes
+//                       nothing or the whole kind, which every thread sees alike
 //   k_rpnloss_labels    (ceil(R/256), B): label = the pre-label where the composite is at or below its kind's threshold,
 //                       else -1; counts [B,4]
 //   k_rpnloss_terms     (tiles of all levels, B), lanes along the logits' memory order (anchor a slowest, then y, x): r is
@@ -157,46 +155,20 @@ __global__ void __launch_bounds__(RL_SEL_THREADS) k_rpnloss_select(LabelArgs ar)
   int n_pos, n_neg;
   quotas(all_pos, all_neg, sp.batch_per_image, sp.pos_quota, n_pos, n_neg);
   const int have = kind == 0 ? all_pos : all_neg;
-  int want = kind == 0 ? n_pos : n_neg;                                     // the same in all threads, like everything below
+  const int want = kind == 0 ? n_pos : n_neg;                               // the same in all threads
   const int wanted_pre = kind == 0 ? 1 : 0;
   unsigned long long* out = ar.thr + (size_t)b * 2 + (size_t)kind;
-  if (want <= 0 || want >= have) {                                          // nothing, or the whole kind: no select
-    if (t == 0) *out = TAKE_ALL;
+  if (want <= 0 || want >= have) {                                          // nothing, or the whole kind: no select, and
+    if (t == 0) *out = TAKE_ALL;                                            // no barrier has been met yet
     return;
   }
   const int32_t* pre = ar.pre + (size_t)b * (size_t)R;
-  uint64_t prefix = 0ull, mask = 0ull, thr = 0ull;
-  bool done = false;
-  for (int shift = 56; shift >= 0 && !done; shift -= 8) {
-    if (shift < 32 && ((uint64_t)(uint32_t)(R - 1) >> shift) == 0ull) {     // every index has a zero digit here
-      mask |= 0xffull << shift;
-      continue;
-    }
-    if (t < 256) s_hist[t] = 0u;
-    __syncthreads();
-    for (int r = t; r < R; r += RL_SEL_THREADS) {
-      if (pre[r] != wanted_pre) continue;
-      const uint64_t c = composite(sp.seed, b, r);
-      if ((c & mask) == prefix) atomicAdd(&s_hist[(unsigned)(c >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    unsigned below = 0u;
-    int d = 0;
-    for (; d < 255; ++d) {
-      const unsigned h = s_hist[d];
-      if (below + h >= (unsigned)want) break;
-      below += h;
-    }
-    want -= (int)below;
-    prefix |= (uint64_t)d << shift;
-    mask |= 0xffull << shift;
-    if (s_hist[d] == (unsigned)want) {                                      // the whole group is in
-      thr = prefix | ~mask;
-      done = true;
-    }
-    __syncthreads();                                                        // the histogram has been read
-  }
-  if (!done) thr = prefix;                                                  // all 64 bits fixed: the quota-th composite itself
+  const auto key_at = [&](int r, uint64_t& key) {
+    key = composite(sp.seed, b, r);                                         // needs no load: it runs while pre[r] is on its way
+    return pre[r] == wanted_pre;
+  };
+  int taken;
+  const uint64_t thr = gsr_block::block_select_u64<RL_SEL_THREADS>(s_hist, R, want, key_at, taken, have);
   if (t == 0) *out = thr;
 }
 

@@ -1,10 +1,11 @@
 """What the ctypes bindings of the image front end and the detector stages share (image_ops, detect_ops, detloss_ops,
-setdet_ops, rcnn_ops): the device check, the error of a non-zero return code, the capability test, the workspace and the one
-way a C entry point is called."""
+setdet_ops, rcnn_ops, rpn_ops, fpn_ops, imgloss_ops, rpnloss_ops, objmap_ops): the device check, the error of a non-zero
+return code, the capability test, the workspace, the cache of workspaces (one per sizer, device, stream and variant) and the
+one way a C entry point is called."""
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import Dict, Hashable, Optional, Tuple
 
 import torch
 
@@ -41,6 +42,24 @@ def workspace_bytes(symbol: str, cs) -> int:
 def workspace(nbytes: int, dev) -> torch.Tensor:
     """At least nbytes on dev as int64 words, a whole number of 16 bytes; its size in bytes is numel() * 8."""
     return torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+
+
+# The cached workspaces of the stages that keep one (imgloss_ops, rpnloss_ops, objmap_ops): per sizer symbol, device, stream
+# and variant, each of the last size asked for.  Calls on one stream run in order, so they may share a workspace; two
+# streams never do.
+_WS: Dict[Tuple[str, str, int, Hashable], Tuple[int, torch.Tensor]] = {}
+
+
+def cached_workspace(symbol: str, cs, dev, variant: Hashable = None) -> torch.Tensor:
+    """The workspace `symbol` sizes for the C spec `cs`, on dev's current stream: the one held for (symbol, dev, stream,
+    variant) when it has that byte count, else a new one in its place.  variant tells apart the kinds of call a loop
+    alternates between (with and without a gradient, say), so that they do not replace each other's workspace."""
+    n = workspace_bytes(symbol, cs)
+    key = (symbol, str(dev), int(torch.cuda.current_stream(dev).cuda_stream), variant)
+    held = _WS.get(key)
+    if held is None or held[0] != n:
+        held = _WS[key] = (n, workspace(n, dev))
+    return held[1]
 
 
 def _ptr(t: Optional[torch.Tensor]):

@@ -15,12 +15,12 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Dict, NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import _load
-from ._ops_common import _f32, _need_device, _ptr, call, workspace, workspace_bytes
+from ._ops_common import _f32, _need_device, _ptr, cached_workspace, call
 
 TILE = (16, 32)           # (TH, TW) of csrc/gsr_imgloss.h: one workgroup's tile of a plane
 MAX_CHANNELS = 4
@@ -57,21 +57,6 @@ def c_spec(spec: ImgLossSpec, shape=(1, 1, 1, 1), flags: int = 0) -> _CImgLossSp
     return _CImgLossSpec(B, C, H, W, float(spec.w_l1), float(spec.w_l2), float(spec.w_ssim), int(flags) | (CLAMP01 if spec.clamp else 0))
 
 
-# The cached workspaces: per device and stream, one for calls with a gradient and one for calls without, each of the last
-# size asked for (a loop alternates between at most those two).  Calls on one stream run in order, so they may share a
-# workspace; two streams never do.
-_WS: Dict[Tuple[str, int, bool], Tuple[int, torch.Tensor]] = {}
-
-
-def _workspace(cs: _CImgLossSpec, dev) -> torch.Tensor:
-    n = workspace_bytes("gsr_imgloss_workspace_bytes", cs)
-    key = (str(dev), int(torch.cuda.current_stream(dev).cuda_stream), bool(cs.flags & NO_GRAD))
-    held = _WS.get(key)
-    if held is None or held[0] != n:
-        held = _WS[key] = (n, workspace(n, dev))
-    return held[1]
-
-
 def _shapes(fn: str, img: torch.Tensor, ref: torch.Tensor):
     _need_device(img, fn, "img")
     _need_device(ref, fn, "ref")
@@ -92,7 +77,8 @@ def imgloss_forward(img: torch.Tensor, ref: torch.Tensor, spec: ImgLossSpec, wan
     x, y = _f32(img, dev), _f32(ref, dev)
     cs = c_spec(spec, x.shape, 0 if want_grad else NO_GRAD)
     if ws is None:
-        ws = _workspace(cs, dev)
+        # one cached workspace for calls with a gradient and one for calls without: a loop alternates between those two
+        ws = cached_workspace("gsr_imgloss_workspace_bytes", cs, dev, variant=not want_grad)
     terms = torch.empty((x.shape[0], 4), dtype=torch.float32, device=dev)
     grad = torch.empty_like(x) if want_grad else None
     smap = torch.empty_like(x) if want_map else None

@@ -16,12 +16,12 @@ loaded library exports gsr_objmap.
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import _load
-from ._ops_common import _f32, _i32, _need_device, _ptr, call, workspace, workspace_bytes
+from ._ops_common import _f32, _i32, _need_device, _ptr, cached_workspace, call
 
 CHANNELS = 16             # CH of csrc/gsr_objmap.h
 MAX_CLASSES = 1024        # MAX_CLASSES there (= GROUP_MAX_CLASSES)
@@ -52,20 +52,6 @@ def available() -> bool:
 def c_spec(shape=(1, 1, 1), K: int = 1, flags: int = 0) -> _CObjMapSpec:
     B, H, W = (int(v) for v in shape)
     return _CObjMapSpec(B, H, W, int(K), int(flags))
-
-
-# The cached workspaces: per device and stream, one for calls with a loss (calls without one need none), of the last size
-# asked for.  Calls on one stream run in order, so they may share a workspace; two streams never do.
-_WS: Dict[Tuple[str, int, bool], Tuple[int, torch.Tensor]] = {}
-
-
-def _workspace(cs: _CObjMapSpec, dev) -> torch.Tensor:
-    n = workspace_bytes("gsr_objmap_workspace_bytes", cs)
-    key = (str(dev), int(torch.cuda.current_stream(dev).cuda_stream), bool(cs.flags & LOSS))
-    held = _WS.get(key)
-    if held is None or held[0] != n:
-        held = _WS[key] = (n, workspace(n, dev))
-    return held[1]
 
 
 def _frozen(fn: str, **tensors) -> None:
@@ -126,7 +112,7 @@ def objmap_forward(objmap: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
     pal = palette.contiguous() if want_paint else None
     B, _, H, W = (int(v) for v in x.shape)
     cs = c_spec((B, H, W), K, LOSS if loss else 0)
-    ws = _workspace(cs, dev)
+    ws = cached_workspace("gsr_objmap_workspace_bytes", cs, dev, variant=loss)   # with a loss / without (which needs none)
     ids = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     conf = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_conf else None
     stats = torch.empty((B, K, 5), dtype=torch.int32, device=dev) if want_stats else None

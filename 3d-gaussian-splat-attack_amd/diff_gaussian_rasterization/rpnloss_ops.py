@@ -18,12 +18,12 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Dict, NamedTuple, Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _load
-from ._ops_common import _f32, _i32, _need_device, call, workspace, workspace_bytes
+from ._ops_common import _f32, _i32, _need_device, cached_workspace, call
 
 MAX_LEVELS = 5
 MAX_ROWS = 256
@@ -96,20 +96,6 @@ def c_spec(spec: RpnLossSpec, B: int = 1, M: int = 1, levels: Sequence[Tuple[int
     return cs
 
 
-# The cached workspaces: per device and stream, of the last size asked for.  Calls on one stream run in order, so they may
-# share a workspace; two streams never do.
-_WS: Dict[Tuple[str, int], Tuple[int, torch.Tensor]] = {}
-
-
-def _workspace(cs: _CRpnLossSpec, dev) -> torch.Tensor:
-    n = workspace_bytes("gsr_rpnloss_workspace_bytes", cs)
-    key = (str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
-    held = _WS.get(key)
-    if held is None or held[0] != n:
-        held = _WS[key] = (n, workspace(n, dev))
-    return held[1]
-
-
 def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
@@ -150,7 +136,7 @@ def label(levels: Sequence[AnchorLevel], gt_boxes: torch.Tensor, gt_cls: torch.T
     gb, gc = _f32(gt_boxes, dev), _i32(gt_cls, dev)
     cs = c_spec(spec, B=B, M=M, levels=geo)
     if ws is None:
-        ws = _workspace(cs, dev)
+        ws = cached_workspace("gsr_rpnloss_workspace_bytes", cs, dev)
     R = sum(a * h * w for a, h, w, _, _ in geo)
     out = Labels(torch.empty((B, R), dtype=torch.int32, device=dev), torch.empty((B, R), dtype=torch.int32, device=dev),
                  torch.empty((B, 4), dtype=torch.int32, device=dev), torch.empty((B, R), dtype=torch.int32, device=dev) if want_pre else None)
@@ -190,7 +176,7 @@ def loss_forward(logits: Sequence[torch.Tensor], deltas: Sequence[torch.Tensor],
     xs, ds, gb = [_f32(x, dev) for x in lg], [_f32(d, dev) for d in dl], _f32(gt_boxes, dev)
     cs = c_spec(spec, B=B, M=M, levels=geo)
     if ws is None:
-        ws = _workspace(cs, dev)
+        ws = cached_workspace("gsr_rpnloss_workspace_bytes", cs, dev)
     loss = torch.empty((3,), dtype=torch.float32, device=dev)
     gl = [torch.empty_like(x) for x in xs] if want_grad else None
     gd = [torch.empty_like(d) for d in ds] if want_grad else None

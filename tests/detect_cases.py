@@ -71,6 +71,11 @@ CASES = [
     Case(8400, C=3, layout=0, has_obj=True, box_format=1, frac=(0.02,), k=5, seed=0),
     # more survivors than max_det
     Case(1023, C=3, layout=1, frac=(0.9,), k=200, max_det=20, seed=0),
+    # (appended: tests pick earlier cases by position and by first match)
+    # 200 candidates on the 1/64 grid against a cap of 100: the select with a cap that is no power of two (28 pad slots),
+    # three of the four index digits zero for every anchor, ties at the cut
+    Case(200, C=3, layout=1, conf=0.05, frac=(0.0,), k=8, maxc=100, max_det=100, seed=0),
+    Case(64, C=1, layout=0, conf=0.48, frac=(1.0,), k=4, maxc=64, max_det=64, seed=0),      # exactly the cap, a power of two: no select, no padding
 ]
 
 

@@ -208,7 +208,18 @@ def _chain(with_rpn_loss):
     return fn, net, TR
 
 
-def test_pgd_attack_with_the_rpn_losses_repeats_and_reaches_the_head():
+@pytest.fixture
+def deterministic_conv():
+    """torch's own convolution backward picks, by the process's history, between solvers of which some sum a weight gradient
+    with atomics: two identical nets' conv.weight.grad then differ in the last bit, whatever this library does.  The test
+    below compares such gradients bit for bit, so it asks torch for its deterministic solvers; the flag is put back."""
+    was = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    yield
+    torch.backends.cudnn.deterministic = was
+
+
+def test_pgd_attack_with_the_rpn_losses_repeats_and_reaches_the_head(deterministic_conv):
     from gsplat_attack.attack import pgd_attack
     from gsplat_attack.renderer import PipelineParams, render_batch
     hists, params = [], []
