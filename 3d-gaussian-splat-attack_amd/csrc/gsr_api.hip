@@ -24,6 +24,7 @@
 #include "gsr_kernels.hip.h"
 #include "gsr_sort.hip.h"
 #include "gsr_knn.hip.h"
+#include "gsr_knnq.hip.h"
 #include "gsr_pgd.hip.h"
 #include "gsr_groups.hip.h"
 #include "gsr_hull.h"
@@ -2205,6 +2206,117 @@ int gsr_knn_dist2(const float* points, int32_t P, float* mean_dist2, void* strea
   hipLaunchKernelGGL(k_knn_search, dim3((n + 255) / 256), dim3(256), 0, st, points, P, g, sidx, cell_range, mean_dist2);
   pool_free(dev, blk);
   LAUNCH_CHECK("knn");
+  return GSR_OK;
+}
+
+int gsr_knn_query(const float* ref, int32_t R, const float* qry, int32_t Q, int32_t k, uint32_t flags, int32_t* out_idx,
+                  float* out_d2, void* stream) {
+  if (k < 1 || k > KNNQ_MAX_K) return set_err(GSR_ERR_INVALID, "gsr_knn_query: k=%d (1..%d)", k, KNNQ_MAX_K);
+  if (R < 0 || Q < 0) return set_err(GSR_ERR_INVALID, "gsr_knn_query: R=%d Q=%d", R, Q);
+  if (flags & ~KNNQ_EXCLUDE_SAME_INDEX) return set_err(GSR_ERR_INVALID, "gsr_knn_query: unknown flags 0x%x", flags);
+  if ((flags & KNNQ_EXCLUDE_SAME_INDEX) && Q != R)
+    return set_err(GSR_ERR_INVALID, "gsr_knn_query: EXCLUDE_SAME_INDEX is the self-query, Q=%d must equal R=%d", Q, R);
+  if ((R > 0 && !ref) || (Q > 0 && (!qry || !out_idx))) return set_err(GSR_ERR_INVALID, "gsr_knn_query: null argument");
+  if (Q == 0) return GSR_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t nq = (uint32_t)Q, nr = (uint32_t)R;
+  if (R == 0) {   // no reference: every slot is missing, no grid
+    const size_t n = (size_t)Q * (size_t)k;
+    hipLaunchKernelGGL(k_knnq_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, out_idx, out_d2);
+    LAUNCH_CHECK("gsr_knn_query");
+    return GSR_OK;
+  }
+  const int dev = cur_dev();
+  // ---- the references' bounding box, as gsr_knn_dist2 reads it (the one wait for the device) --------------------------
+  float host_bb[6] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
+  void* bb_blk = pool_alloc(dev, 256, st);
+  if (!bb_blk) return set_err(GSR_ERR_NOMEM, "gsr_knn_query: allocation failed");
+  float* bbox = static_cast<float*>(bb_blk);
+  hipError_t e = hipMemcpyAsync(bbox, host_bb, sizeof(host_bb), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_knn_bbox, dim3(std::min<uint32_t>((nr + 255) / 256, 1024u)), dim3(256), 0, st, ref, R, bbox);
+    e = hipMemcpyAsync(host_bb, bbox, sizeof(host_bb), hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  pool_free(dev, bb_blk);
+  if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "gsr_knn_query: bounding box: %s", hipGetErrorString(e));
+  const KnnGrid g = knn_make_grid(host_bb, R);   // gsr_knn.h
+  const uint32_t ncells = (uint32_t)g.dx * g.dy * g.dz;
+  const int bits = ceil_log2(ncells);
+  // ---- workspace: staged references | cell ranges | 4 sort arrays of R | 4 sort arrays of Q | table | sums -----------
+  const uint32_t tbl = radix_table_words(std::max(nr, nq));
+  const size_t words = (size_t)4 * nr + 2 * (size_t)ncells + (size_t)4 * nr + (size_t)4 * nq + tbl + RS_BINS;
+  void* blk = pool_alloc(dev, sizeof(uint32_t) * words, st);
+  if (!blk) return set_err(GSR_ERR_NOMEM, "gsr_knn_query: workspace allocation failed");
+  KnnqRef* staged = static_cast<KnnqRef*>(blk);                               // 16 bytes each, the block is 256-byte aligned
+  uint2* cell_range = reinterpret_cast<uint2*>(staged + nr);
+  uint32_t* k0 = reinterpret_cast<uint32_t*>(cell_range + ncells);
+  uint32_t* v0 = k0 + nr; uint32_t* k1 = v0 + nr; uint32_t* v1 = k1 + nr;
+  uint32_t* qk0 = v1 + nr; uint32_t* qv0 = qk0 + nq; uint32_t* qk1 = qv0 + nq; uint32_t* qv1 = qk1 + nq;
+  uint32_t* table = qv1 + nq; uint32_t* sums = table + tbl;
+  // ---- references: cell keys, sort, ranges, cell-sorted copy ----------------------------------------------------------
+  hipLaunchKernelGGL(k_knn_cells, dim3((nr + 255) / 256), dim3(256), 0, st, ref, R, g, k0);
+  const int res = radix_sort_pairs(k0, v0, k1, v1, nr, nullptr, 0, bits, true, table, sums, st);
+  const uint32_t* skeys = res ? k1 : k0;
+  const uint32_t* sidx = res ? v1 : v0;
+  if (bits == 0) hipLaunchKernelGGL(k_knnq_iota, dim3((nr + 255) / 256), dim3(256), 0, st, nr, v0);   // one cell: no pass ran
+  (void)hipMemsetAsync(cell_range, 0, sizeof(uint2) * ncells, st);
+  hipLaunchKernelGGL(k_knn_ranges, dim3((nr + 255) / 256), dim3(256), 0, st, nr, skeys, cell_range);
+  hipLaunchKernelGGL(k_knnq_stage, dim3((nr + 255) / 256), dim3(256), 0, st, ref, nr, sidx, staged);
+  // ---- queries: their cell keys in the REFERENCE grid, sorted, so that neighbouring lanes scan the same cells ---------
+  hipLaunchKernelGGL(k_knn_cells, dim3((nq + 255) / 256), dim3(256), 0, st, qry, Q, g, qk0);
+  const int qres = radix_sort_pairs(qk0, qv0, qk1, qv1, nq, nullptr, 0, bits, true, table, sums, st);
+  const uint32_t* qsidx = qres ? qv1 : qv0;
+  if (bits == 0) hipLaunchKernelGGL(k_knnq_iota, dim3((nq + 255) / 256), dim3(256), 0, st, nq, qv0);
+  const uint32_t qb = (nq + 255) / 256;
+  const int excl = (flags & KNNQ_EXCLUDE_SAME_INDEX) ? 1 : 0;
+  switch (k) {
+    case 1: launch_knnq_query<1>(qb, st, staged, R, g, cell_range, qry, Q, qsidx, excl, out_idx, out_d2); break;
+    case 2: launch_knnq_query<2>(qb, st, staged, R, g, cell_range, qry, Q, qsidx, excl, out_idx, out_d2); break;
+    case 3: launch_knnq_query<3>(qb, st, staged, R, g, cell_range, qry, Q, qsidx, excl, out_idx, out_d2); break;
+    case 4: launch_knnq_query<4>(qb, st, staged, R, g, cell_range, qry, Q, qsidx, excl, out_idx, out_d2); break;
+    case 5: launch_knnq_query<5>(qb, st, staged, R, g, cell_range, qry, Q, qsidx, excl, out_idx, out_d2); break;
+    case 6: launch_knnq_query<6>(qb, st, staged, R, g, cell_range, qry, Q, qsidx, excl, out_idx, out_d2); break;
+    case 7: launch_knnq_query<7>(qb, st, staged, R, g, cell_range, qry, Q, qsidx, excl, out_idx, out_d2); break;
+    default: launch_knnq_query<8>(qb, st, staged, R, g, cell_range, qry, Q, qsidx, excl, out_idx, out_d2); break;
+  }
+  pool_free(dev, blk);
+  LAUNCH_CHECK("gsr_knn_query");
+  return GSR_OK;
+}
+
+int gsr_knn_gather_mean(const int32_t* idx, int32_t Q, int32_t k, int32_t R, int32_t n_tensors, const float* const* src,
+                        const int32_t* cols, float* const* dst, void* stream) {
+  if (k < 1 || k > KNNQ_MAX_K) return set_err(GSR_ERR_INVALID, "gsr_knn_gather_mean: k=%d (1..%d)", k, KNNQ_MAX_K);
+  if (R < 0 || Q < 0) return set_err(GSR_ERR_INVALID, "gsr_knn_gather_mean: R=%d Q=%d", R, Q);
+  if (n_tensors < 1 || n_tensors > KNNQ_MAX_TENSORS)
+    return set_err(GSR_ERR_INVALID, "gsr_knn_gather_mean: %d tensors (1..%d)", n_tensors, KNNQ_MAX_TENSORS);
+  if (!src || !cols || !dst) return set_err(GSR_ERR_INVALID, "gsr_knn_gather_mean: null argument");
+  KnnqGather a;
+  memset(&a, 0, sizeof(a));
+  int total = 0;
+  for (int t = 0; t < n_tensors; ++t) {
+    if (cols[t] < 1 || cols[t] > KNNQ_MAX_COLS)
+      return set_err(GSR_ERR_INVALID, "gsr_knn_gather_mean: tensor %d: %d columns (1..%d)", t, cols[t], KNNQ_MAX_COLS);
+    a.first[t] = total;
+    total += cols[t];
+    if (total > KNNQ_MAX_COLS) return set_err(GSR_ERR_INVALID, "gsr_knn_gather_mean: more than %d columns in all", KNNQ_MAX_COLS);
+    a.cols[t] = cols[t];
+  }
+  for (int t = n_tensors; t <= KNNQ_MAX_TENSORS; ++t) a.first[t] = total;
+  a.total = total;
+  if (Q > 0) {
+    if (!idx) return set_err(GSR_ERR_INVALID, "gsr_knn_gather_mean: null idx");
+    for (int t = 0; t < n_tensors; ++t) {
+      if (!dst[t] || (R > 0 && !src[t])) return set_err(GSR_ERR_INVALID, "gsr_knn_gather_mean: tensor %d: null pointer", t);
+      a.src[t] = src[t]; a.dst[t] = dst[t];
+    }
+  }
+  if (Q == 0) return GSR_OK;
+  const size_t n = (size_t)Q * (size_t)total;
+  hipLaunchKernelGGL(k_knnq_gather_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), idx,
+                     (size_t)Q, k, R, a);
+  LAUNCH_CHECK("gsr_knn_gather_mean");
   return GSR_OK;
 }
 

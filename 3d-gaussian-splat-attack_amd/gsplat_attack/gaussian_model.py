@@ -98,6 +98,42 @@ class GaussianModel:
         for n in self._PARAM_ATTRS:
             setattr(self, n, nn.Parameter(getattr(self, n)[keep].detach().clone()))
 
+    def inpaint_setup(self, mask3d: torch.Tensor, k: int = 5) -> torch.Tensor:
+        """Fill the hole a removal leaves (reference scene/gaussian_model.py:264-348): the Gaussians NOT selected by mask3d
+        stay, first and in their order; behind them comes one new Gaussian per removed one, in the removed rows' order,
+        whose seven raw attributes (positions, logit opacities, log scales, raw quaternions, both SH blocks, object
+        features) are each the mean over the k remaining Gaussians nearest to the removed one's position.  All seven
+        tensors are re-wrapped in nn.Parameter.  -> the bool mask [P'] of the new rows.
+
+        On a HIP device the neighbours come from gsr_knn_query and the means from gsr_knn_gather_mean
+        (diff_gaussian_rasterization.knn_ops): nothing goes to the host, where the reference builds a scipy KDTree and takes
+        all seven tensors through numpy.  The mean is the float32 sum in rank order divided by the count.
+
+        Deviations from the reference: ties between equidistant neighbours go to the lower index (KDTree's choice is
+        arbitrary); with fewer than k remaining Gaussians the mean is over those there are, and with none a ValueError is
+        raised (the reference fails with an index error); the reference's distance_threshold / max_distance_threshold
+        arguments do not exist here, because the reference never reads them; no optimiser is set up."""
+        from diff_gaussian_rasterization import knn_ops
+        removed = mask3d.bool().reshape(-1).to(self._xyz.device)
+        if removed.numel() != self._xyz.shape[0]:
+            raise ValueError(f"inpaint_setup: mask of {removed.numel()} entries for {self._xyz.shape[0]} Gaussians")
+        keep = ~removed
+        n_new = int(removed.sum())
+        if n_new and n_new == removed.numel():
+            raise ValueError("inpaint_setup: no Gaussian remains to fill the hole from")
+        with torch.no_grad():
+            rest = [getattr(self, n)[keep].detach() for n in self._PARAM_ATTRS]
+            if n_new:
+                idx, _ = knn_ops.knn_query(rest[0], self._xyz.detach()[removed], k=k, exclude_self=False)
+                new = knn_ops.gather_mean(idx, rest)
+            else:
+                new = [r[:0] for r in rest]
+            for n, r, w in zip(self._PARAM_ATTRS, rest, new):
+                setattr(self, n, nn.Parameter(torch.cat([r, w.to(r.dtype)]).detach().clone()))
+        new_mask = torch.zeros(self._xyz.shape[0], dtype=torch.bool, device=self._xyz.device)
+        new_mask[self._xyz.shape[0] - n_new:] = n_new > 0
+        return new_mask
+
     def concat_setup(self, feature_name: str, tensor_to_concat: torch.Tensor, requires_grad: bool) -> None:
         """Append rows to one attribute and re-wrap it (reference :243-262)."""
         cur = getattr(self, f"_{feature_name}")

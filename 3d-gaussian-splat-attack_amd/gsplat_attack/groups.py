@@ -125,3 +125,16 @@ def split_group(model, mask3d: torch.Tensor):
     rest = model.clone()
     rest.removal_setup(sel)
     return group, rest
+
+
+def fill_group(model, mask3d: torch.Tensor, k: int = 5):
+    """-> (filled_model, new_mask): a clone of `model` with the selected Gaussians taken out and the hole filled as the
+    reference's inpaint_setup does it (GaussianModel.inpaint_setup: one new Gaussian per removed one, every raw attribute
+    the mean over the k nearest remaining Gaussians), and the bool mask of the new rows in the clone.  `model` itself is
+    untouched.  The deviations from the reference are inpaint_setup's (ties to the lower index, fewer than k remaining
+    Gaussians are averaged as they are, none remaining is a ValueError, no distance thresholds, no optimiser)."""
+    sel = mask3d.reshape(-1).bool()
+    if sel.numel() != model._xyz.shape[0]:
+        raise ValueError(f"fill_group: mask of {sel.numel()} entries for {model._xyz.shape[0]} Gaussians")
+    filled = model.clone()
+    return filled, filled.inpaint_setup(sel, k=k)

@@ -496,6 +496,41 @@ int gsr_pgd_step_multi(int32_t n, float* const* x, const float* const* grad, con
  * turns quadratic in the points that share a cell; exact still, run time not measured. */
 int gsr_knn_dist2(const float* points, int32_t P, float* mean_dist2, void* stream);
 
+/* Exact k-nearest-neighbour query WITH INDICES between two point sets, 1 <= k <= 8, and the gather-mean that the
+ * reference's inpaint_setup does on the host (scene/gaussian_model.py:264-307: scipy KDTree, k = 5, numpy mean).  No
+ * change of GSR_VERSION, no capability bit: the stage is present iff the library exports these two symbols.
+ *
+ * gsr_knn_query: ref [R,3], qry [Q,3] float32 device; out_idx [Q,k] int32 device; out_d2 [Q,k] float32 device or NULL.
+ *   Distance   d2 = (dx*dx + dy*dy) + dz*dz in double from the float32 coordinates, each difference formed in double,
+ *              in exactly that order without contraction (the bits of numpy float64); out_d2 is that value rounded once.
+ *              Double was chosen for exactness, not from a timing.
+ *   Order      a query's neighbours are the k smallest references under the total order (d2 ascending, reference index
+ *              ascending), written in that order: ties are decided, the result does not depend on any scan order.
+ *   Non-finite a d2 that is NaN or +inf is never a neighbour; a query with a non-finite coordinate has no neighbours; a
+ *              non-finite reference is invisible to every query.
+ *   Missing    with fewer than k neighbours (R < k, the excluded reference, non-finite references) the remaining slots
+ *              have index -1 and d2 = +inf.  R = 0 is valid: every slot is missing and no grid is built.  Q = 0 writes
+ *              nothing.
+ *   flags      GSR_KNNQ_EXCLUDE_SAME_INDEX (bit 0): query i never takes reference i -- the self-query, which requires
+ *              Q == R.  Any other bit is refused.
+ *   Synchronises the stream once, where gsr_knn_dist2 does (the references' bounding box); workspace from the pool.
+ *   Known limit, as for gsr_knn_dist2: the grid is uniform over the references' bounding box, so one far (or infinite)
+ *   reference puts the rest into a few cells and the search turns quadratic in the references that share a cell; a
+ *   query far outside the box scans more shells or all references.  Exact still; run time of such clouds not measured.
+ *
+ * gsr_knn_gather_mean: for each of n_tensors (1..8) source tensors src[t] [R, cols[t]] float32, dst[t] [Q, cols[t]]
+ *   receives per element (((v0 + v1) + v2) ...) / m in float32 over the m present neighbours of idx [Q,k] in rank order,
+ *   0 when m == 0.  An index outside 0 .. R-1 (-1 included) counts as missing and is never followed.  src, cols and dst
+ *   are HOST arrays (of device pointers / of ints): 1 <= cols[t] <= 128 and the sum of cols <= 128.  No atomics, no wait.
+ *
+ * Both refuse, before the first device call: k outside 1..8, negative R or Q, a null pointer where one is needed, unknown
+ * flags, EXCLUDE_SAME_INDEX with Q != R, n_tensors outside 1..8, cols outside 1..128 or summing to more than 128. */
+#define GSR_KNNQ_EXCLUDE_SAME_INDEX 1u
+int gsr_knn_query(const float* ref, int32_t R, const float* qry, int32_t Q, int32_t k, uint32_t flags, int32_t* out_idx,
+                  float* out_d2, void* stream);
+int gsr_knn_gather_mean(const int32_t* idx, int32_t Q, int32_t k, int32_t R, int32_t n_tensors, const float* const* src,
+                        const int32_t* cols, float* const* dst, void* stream);
+
 /* ---- groups set-up (C ABI 603) -----------------------------------------------------------------------------------
  * The reference's third way to set up an attack (attack.py:292-323): one Gaussian-Grouping scene, a 1x1-conv classifier
  * over the 16 object features, and the Gaussians of the selected object ids -- plus every Gaussian inside the convex
