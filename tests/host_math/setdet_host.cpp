@@ -1,6 +1,6 @@
 // The set-prediction detector stage in plain loops over csrc/gsr_setdet.h, the same scalar source the HIP kernels compile:
-//   sdh_run_f32   float32, what gsr_setdet_loss computes (sums taken pairwise, so that their rounding stays at the level of
-//                 the kernels' trees instead of growing with the element count)
+//   sdh_run_f32   float32, what gsr_setdet_loss computes (sums taken pairwise and a row's statistics in the wave's order, so
+//                 that their rounding stays at the level of the kernels' trees instead of growing with the element count)
 //   sdh_run_f64   the same code in double: tests/test_setdet_host_cpu.py differentiates its `total` by central differences
 //                 to check the hand-written backward against its own forward
 //   sdh_post_f32  what gsr_setdet_postprocess computes
@@ -34,6 +34,34 @@ static T pairwise(const T* v, size_t n) {
   return pairwise(v, h) + pairwise(v + h, n - h);
 }
 
+// The statistics of one row of n logits in the order k_setdet_cost takes them (gsr_block::wave_softmax_stats): 64 lanes
+// stride the row, then an xor butterfly over the lanes.  A serial sum of 1025 exponentials rounds an order of magnitude
+// more than that tree; softmax_stats stays what the output stage runs, on the device as here.
+template <class T>
+static void wave_stats(const T* x, int n, T& mx, T& sum) {
+  T a[64], o[64];
+  for (int l = 0; l < 64; ++l) {
+    T m = -m_inf<T>();
+    for (int k = l; k < n; k += 64) m = x[k] > m ? x[k] : m;
+    a[l] = m;
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    for (int l = 0; l < 64; ++l) o[l] = a[l ^ s] > a[l] ? a[l ^ s] : a[l];
+    for (int l = 0; l < 64; ++l) a[l] = o[l];
+  }
+  mx = a[0];
+  for (int l = 0; l < 64; ++l) {
+    T t = (T)0;
+    for (int k = l; k < n; k += 64) t = t + m_exp(x[k] - mx);
+    a[l] = t;
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    for (int l = 0; l < 64; ++l) o[l] = a[l] + a[l ^ s];
+    for (int l = 0; l < 64; ++l) a[l] = o[l];
+  }
+  sum = a[0];
+}
+
 static bool spec_ok(const HostSpec* d) {
   return d && d->B >= 1 && d->B <= 65535 && d->Q >= 1 && d->Q <= MAX_QUERIES && d->C >= 1 && d->C <= MAX_CLASSES && d->M >= 1 &&
          d->M <= MAX_ROWS && d->Q >= d->M && d->max_det >= 1 && d->max_det <= MAX_QUERIES && d->flags == 0u;
@@ -50,7 +78,7 @@ static int run(const HostSpec* d, const T* logits, const T* boxes, const T* gt_b
   const int B = d->B, Q = d->Q, C = d->C, M = d->M, n1 = C + 1;
   const size_t BQ = (size_t)B * (size_t)Q;
   std::vector<T> mx(BQ), sum(BQ);
-  for (size_t i = 0; i < BQ; ++i) softmax_stats<T>(logits + i * (size_t)n1, n1, mx[i], sum[i]);
+  for (size_t i = 0; i < BQ; ++i) wave_stats<T>(logits + i * (size_t)n1, n1, mx[i], sum[i]);
   if (!frozen) {
     std::vector<T> cost((size_t)M * (size_t)Q), u((size_t)M + 1), v((size_t)Q + 1), minv((size_t)Q + 1);
     std::vector<int32_t> p((size_t)Q + 1), way((size_t)Q + 1), used((size_t)Q + 1);

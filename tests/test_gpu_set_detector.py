@@ -3,7 +3,10 @@
 float32 oracle's own error, floor 2^-22, never above 1e-3), the same bits on every call, on a side stream and with or
 without the gradients and the optional outputs, every gradient element written, the autograd function, the output stage
 followed by gsr_det_verdict against the host restatement, and the stage behind a small torch head as pgd_attack's loss_fn:
-render -> head -> loss -> backward to the Gaussian parameters, bit for bit repeatable."""
+render -> head -> loss -> backward to the Gaussian parameters, bit for bit repeatable.  What the kernels add to the scalar
+source has cases of its own (setdet_cases: Q and C + 1 at the wave and workgroup widths, the stride loops' second trips,
+every maximum at once) and hand-made inputs: exact ties against the serial match, the backward at its kinks, the output
+stage at exact scores and at its limits, sentinel words around every output of the C entries, and non-finite inputs."""
 import ctypes
 
 import numpy as np
@@ -60,16 +63,16 @@ def _bits(t):
     return t.detach().cpu().numpy().tobytes()
 
 
-def _raw_call(SO, spec, x, bx, gb, gc, gl, gbx):
-    """The C entry on caller buffers (the binding allocates its own): gl / gbx arrive pre-filled."""
+def _raw_call(SO, spec, x, bx, gb, gc, gl, gbx, match=None, tgt=None):
+    """The C entry on caller buffers (the binding allocates its own): gl / gbx (and match / tgt) arrive pre-filled."""
     B, Q, n1 = x.shape
     cs = SO.c_spec(spec, B, Q, n1 - 1, gb.shape[1])
     ws = torch.empty(((SO.workspace_bytes(cs) + 15) // 16 * 2,), dtype=torch.int64, device=DEV)
     loss = torch.empty(4, dtype=torch.float32, device=DEV)
     lib = SO._lib()
     rc = lib.gsr_setdet_loss(ctypes.byref(cs), x.data_ptr(), bx.data_ptr(), gb.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                             loss.data_ptr(), gl.data_ptr(), gbx.data_ptr(), None, None,
-                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+                             loss.data_ptr(), gl.data_ptr(), gbx.data_ptr(), None if match is None else match.data_ptr(),
+                             None if tgt is None else tgt.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0, lib.gsr_last_error()
     return loss
 
@@ -112,6 +115,123 @@ def test_kernels_against_the_oracle_and_repeat(SO, host, c):
     torch.cuda.synchronize()
     assert _bits(s_loss) == _bits(loss) and _bits(s_gl) == _bits(gl) and _bits(s_gbx) == _bits(gbx)
     assert not (s_gl == SENTINEL).any() and not (s_gbx == SENTINEL).any()
+
+
+def _run_np(SO, inputs, **kw):
+    """SO.run on numpy inputs -> dict of numpy outputs (after a synchronise)."""
+    dev = tuple(torch.tensor(np.array(a)).to(DEV) for a in inputs)
+    loss, gl, gbx, match, tgt = SO.run(*dev, _spec(SO), **kw)
+    torch.cuda.synchronize()
+    return dict(loss=loss.cpu().numpy(), grad_logits=gl.cpu().numpy(), grad_boxes=gbx.cpu().numpy(), match=match.cpu().numpy(),
+                tgt=tgt.cpu().numpy())
+
+
+@pytest.mark.parametrize("kind", SC.TIE_KINDS)
+def test_exact_ties_equal_the_serial_match(SO, host, kind):
+    """setdet_cases.tie_inputs: equal candidates meet in the lanes' own scans, in the wave butterfly, in the merge of the four
+    waves and across the trips of the stride loop, and the lane-dealt match must return what the serial one does (the host
+    build; test_setdet_host_cpu.py holds that to the stated rule): integer-equal match and tgt, one-to-one, the oracle's
+    optimum in the oracle's own float64 cost matrix, loss and gradients within the bound with this match frozen."""
+    ref = SC.tie_reference(kind)
+    assert ref["gap"] > SC.GAP_MATCH
+    want = SC.host_run(host, *ref["inputs"], want_grad=False)
+    got = _run_np(SO, ref["inputs"])
+    SC.check_tie("device", kind, got, want["match"])
+    assert np.array_equal(got["tgt"], want["tgt"])
+    again = _run_np(SO, ref["inputs"])
+    assert all(got[k].tobytes() == again[k].tobytes() for k in got)
+
+
+def test_backward_at_its_kinks(SO, host):
+    """setdet_cases.kink_inputs, one image per kink: within the usual bound of the float64 oracle, whose autograd follows the
+    contract's conventions there; where every step of the box gradient is exact (KINK_EXACT) the same bits as the host
+    build of the same source."""
+    inputs = SC.kink_inputs()
+    o = SC.oracle(*inputs, want_gap=True)
+    assert o["gap_match"] > SC.GAP_MATCH
+    got = _run_np(SO, inputs)
+    assert np.array_equal(got["match"], o["match"].numpy()) and np.array_equal(got["tgt"], o["tgt"].numpy())
+    assert np.isfinite(got["grad_boxes"]).all() and np.isfinite(got["grad_logits"]).all() and np.isfinite(got["loss"]).all()
+    SC.check_with_match_frozen("device kinks", got, inputs)
+    h = SC.host_run(host, *inputs)
+    names = [k[0] for k in SC.KINKS]
+    for name in SC.KINK_EXACT:
+        b = names.index(name)
+        print(f"kink {name}: device {got['grad_boxes'][b, 0].tolist()} host {h['grad_boxes'][b, 0].tolist()}")
+        assert got["grad_boxes"][b].tobytes() == h["grad_boxes"][b].tobytes(), name
+    assert (got["grad_boxes"][names.index("equal")] == 0).all() and (got["grad_boxes"][:, 1] == 0).all()
+
+
+def test_postprocess_at_exact_scores_and_limits(SO):
+    """The output stage at exact scores (a class tie at 0.5, a score exactly at conf_thr, NaN and -inf logits), at max_det = 1
+    on 1024 queries and 1024 on 65, with all and none of 65 queries kept: setdet_cases.exact_score_expectations, what the
+    host build is held to as well."""
+    def post(x, bx, thr, max_det):
+        dets, counts = SO.postprocess(torch.tensor(np.array(x)).to(DEV), torch.tensor(np.array(bx)).to(DEV),
+                                      _spec(SO, conf_thr=thr, max_det=max_det))
+        torch.cuda.synchronize()
+        return dets.cpu().numpy(), counts.cpu().numpy()
+    SC.exact_score_expectations(post)
+
+
+PAD, F_FILL, I_FILL = 256, -12345.0, 0x5A5A5A5A
+
+
+def _padded(n, dtype):
+    """-> (buffer of PAD + n + PAD sentinel words, the address of word PAD)."""
+    buf = torch.full((PAD + n + PAD,), F_FILL if dtype == torch.float32 else I_FILL, dtype=dtype, device=DEV)
+    return buf, buf.data_ptr() + 4 * PAD
+
+
+def _pads_untouched(buf, n):
+    fill = F_FILL if buf.dtype == torch.float32 else I_FILL
+    return bool((buf[:PAD] == fill).all() and (buf[PAD + n:] == fill).all())
+
+
+def test_nothing_is_written_outside_the_outputs(SO):
+    """The C entries on caller buffers with 256 sentinel words on either side of every output, the optional match and tgt
+    among them, and behind the workspace: the binding's bits inside, every sentinel outside."""
+    B, Q, C, M = 2, 65, 4, 5
+    x, bx, gb, gc = (torch.tensor(a).to(DEV) for a in SC.make_inputs(SC.Case("pads", B, Q, C, M)))
+    spec = _spec(SO)
+    want = SO.run(x, bx, gb, gc, spec)
+    sizes = (4, B * Q * (C + 1), B * Q * 4, B * M, B * Q)
+    bufs = [_padded(n, torch.float32 if k < 3 else torch.int32) for k, n in enumerate(sizes)]
+    cs = SO.c_spec(spec, B, Q, C, M)
+    ws_bytes = SO.workspace_bytes(cs)
+    assert ws_bytes % 4 == 0
+    ws = torch.full((ws_bytes // 4 + PAD,), I_FILL, dtype=torch.int32, device=DEV)
+    lib = SO._lib()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rc = lib.gsr_setdet_loss(ctypes.byref(cs), x.data_ptr(), bx.data_ptr(), gb.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws_bytes,
+                             *[p for _, p in bufs], stream)
+    assert rc == 0, lib.gsr_last_error()
+    torch.cuda.synchronize()
+    for (buf, _), n, w in zip(bufs, sizes, want):
+        assert _bits(buf[PAD:PAD + n]) == _bits(w.reshape(-1)) and _pads_untouched(buf, n)
+    assert (ws[ws_bytes // 4:] == I_FILL).all()
+    # without the optional outputs and the gradients: the loss alone, nothing else touched
+    for buf, _ in bufs:
+        buf.fill_(F_FILL if buf.dtype == torch.float32 else I_FILL)
+    rc = lib.gsr_setdet_loss(ctypes.byref(cs), x.data_ptr(), bx.data_ptr(), gb.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws_bytes,
+                             bufs[0][1], None, None, None, None, stream)
+    assert rc == 0, lib.gsr_last_error()
+    torch.cuda.synchronize()
+    assert _bits(bufs[0][0][PAD:PAD + 4]) == _bits(want[0]) and _pads_untouched(bufs[0][0], 4)
+    assert all((buf == (F_FILL if buf.dtype == torch.float32 else I_FILL)).all() for buf, _ in bufs[1:])
+    assert (ws[ws_bytes // 4:] == I_FILL).all()
+    # the output stage: fewer rows than kept queries, and as many rows as queries
+    for max_det in (3, Q):
+        pspec = _spec(SO, conf_thr=SC.CONF_THR, max_det=max_det)
+        wd, wn = SO.postprocess(x, bx, pspec)
+        assert int(wn[:, 1].min()) > 3                                      # max_det = 3 cuts every image's rows
+        dets, counts = _padded(B * max_det * 6, torch.float32), _padded(B * 2, torch.int32)
+        pcs = SO.c_spec(pspec, B, Q, C, 1)
+        rc = lib.gsr_setdet_postprocess(ctypes.byref(pcs), x.data_ptr(), bx.data_ptr(), dets[1], counts[1], stream)
+        assert rc == 0, lib.gsr_last_error()
+        torch.cuda.synchronize()
+        assert _bits(dets[0][PAD:PAD + B * max_det * 6]) == _bits(wd.reshape(-1)) and _pads_untouched(dets[0], B * max_det * 6)
+        assert _bits(counts[0][PAD:PAD + B * 2]) == _bits(wn.reshape(-1)) and _pads_untouched(counts[0], B * 2)
 
 
 def test_other_weights_than_the_defaults(SO):
@@ -309,3 +429,39 @@ def test_pgd_attack_with_the_set_loss_repeats():
         assert all(torch.equal(a, b) for a, b in zip(params[i], params[j]))
     fresh = _scene()[0].named_parameters()
     assert not all(torch.equal(a, fresh[n].detach()) for a, n in zip(params[0], PARAMS))       # the attack moved the parameters
+
+
+# ---- non-finite inputs ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", SC.NONFINITE_CASES, ids=lambda c: c.id)
+def test_non_finite_inputs_stay_in_range_and_in_their_image(SO, c):
+    """NaN and +-inf in the logits and boxes of image 1 of three (setdet_cases.poisoned_inputs, shares 0.05, 0.5 and 1 of the
+    elements): the poisoned image's floats are unspecified, but every call returns, every index is in range, the match is
+    one-to-one over the present rows with tgt its inverse, every gradient element is written, the output stage's counts lie
+    in 0..Q, and images 0 and 2 keep the clean run's bits.
+
+    Why the kernels end and stay in range whatever the floats are (read from the source, not found by running):
+      * every loop of the five kernels is bounded by B, Q, C, M or a constant: the stride loops by Q, B, n or nblocks, the
+        match's row loop by M, its pass loop by `it <= M`, the path flip by `it <= M`;
+      * in k_setdet_match every value that steers a barrier or a break is the same in all lanes: i, present(s_cls[..]) and
+        s_p[j0] are read from LDS behind a barrier, j0 follows j1, and (delta, j1) are recomputed by every thread from
+        s_bv / s_bj behind a barrier (only lane 0 of a wave writes them, so lanes whose butterflies disagree over a NaN do
+        not matter); a delta that is not below +inf -- NaN included -- takes the lowest unmarked column with delta = 0;
+      * every index is an integer the algorithm made (s_p in 0..M, s_way in 0..Q, bj in {-1, 1..Q} and only ever an unmarked
+        column, so each pass marks a new one) or is clamped before use (tg < M, i <= M, present(tc), bc < C);
+      * the normalisers are integers (matched rows, B * Q) and every present row is matched either way, so nothing of image
+        1 reaches the other images' terms."""
+    logits, boxes, gtb, gtc = SC.make_inputs(c)
+    gb, gc = torch.tensor(gtb).to(DEV), torch.tensor(gtc).to(DEV)
+    spec = _spec(SO)
+    clean = _run_np(SO, (logits, boxes, gtb, gtc))
+    for frac in SC.NONFINITE_FRACS:
+        x, bx = (torch.tensor(a).to(DEV) for a in SC.poisoned_inputs(c, frac))
+        gl, gbx = torch.full_like(x, SENTINEL), torch.full_like(bx, SENTINEL)
+        match = torch.full((c.B, c.M), -9, dtype=torch.int32, device=DEV)
+        tgt = torch.full((c.B, c.Q), -9, dtype=torch.int32, device=DEV)
+        _raw_call(SO, spec, x, bx, gb, gc, gl, gbx, match, tgt)
+        _, counts = SO.postprocess(x, bx, _spec(SO, conf_thr=SC.CONF_THR))
+        torch.cuda.synchronize()                                           # raises on any HIP error
+        assert not (gl == SENTINEL).any() and not (gbx == SENTINEL).any()
+        got = dict(match=match.cpu().numpy(), tgt=tgt.cpu().numpy(), grad_logits=gl.cpu().numpy(), grad_boxes=gbx.cpu().numpy())
+        SC.check_poisoned(f"device {c.id} {frac}", c, got, clean, gtc, counts.cpu().numpy())

@@ -2,7 +2,9 @@
 compile) against the float64 PyTorch oracle of tests/setdet_cases.py, the oracle's own matcher against all permutations
 and scipy, hand-derived literals, the hand-written backward against central finite differences of its own forward in
 double, non-finite inputs in a child process, the output stage against a torch restatement of detr_detector.py:186-202,
-and the same source as a stand-alone program under the address and undefined-behaviour sanitizers.
+and the same source as a stand-alone program under the address and undefined-behaviour sanitizers.  The hand-made inputs
+of setdet_cases.py (exact ties, the backward's kinks, exact scores, one poisoned image of three) are held to the stated
+rules here first; the device tests then demand the same of the kernels.
 
 Bound on float errors (detloss_cases.bound): err = max|q - q64| / max|q64| of the host build may be at most 4 x the err of
 the float32 oracle (the yardstick) for the same case and tensor, floor 2^-22, never above 1e-3.  Measured ratios are
@@ -68,8 +70,25 @@ def test_the_cases_cover_what_they_claim(c):
         assert all(torch.isfinite(o[k]).all() for k in SC.COMPARED)
     if c.id == "wide":
         assert c.Q > 256 * 3 and c.Q % 256 != 0                            # several passes of the match's workgroup, a ragged last
-    if c.kind in ("plain", "ragged") and c.Q > 1:
+    claim = SC.EDGE_CLAIMS.get(c.id)
+    if claim is not None:                                                  # the edge cases: what the kernels add to the source
+        assert c.kind == "plain" and SC.covers(c, ref)
+        assert (c.B * c.Q) % 4 == claim["bq_mod4"]                         # the cost kernel's last workgroup: 4 queries each
+        assert present.all() and (match >= 0).all()                        # every row present and matched
+        if "images_above" in claim:
+            assert c.B > claim["images_above"] == 256                      # block_matched strides 256 threads over B
+        if "term_blocks_above" in claim:
+            assert SC.term_blocks(c) > claim["term_blocks_above"] == 256   # slab_sum strides 256 threads over the blocks
+        if c.id == "limits":
+            assert (c.Q, c.C, c.M) == (1024, 1024, 32) and SC.term_blocks(c) == 1025
+        assert (counts[:, 1] > 0).any() and (counts[:, 1] < c.Q).any()     # a query kept and a query dropped in the batch
+    elif c.kind in ("plain", "ragged") and c.Q > 1:
         assert (counts[:, 1] > 0).all() and (counts[:, 1] < c.Q).all()     # the output stage keeps some queries, not all
+
+
+def test_every_edge_case_is_a_case():
+    assert set(SC.EDGE_CLAIMS) <= set(SC.BY_ID) and len(SC.BY_ID) == len(SC.CASES)
+    assert [c.id for c in SC.CASES[:8]] == ["one", "tiny", "ragged", "contested", "full-rows", "no-gt", "saturated", "wide"]
 
 
 # ---- the oracle's matcher on its own ----------------------------------------------------------------------------------------
@@ -194,6 +213,69 @@ def test_equal_costs_go_to_the_lowest_query(lib):
     assert got["match"].tolist() == [[0, 1]] and got["tgt"].tolist() == [[0, 1, -1, -1]]
 
 
+@pytest.mark.parametrize("kind", SC.TIE_KINDS)
+def test_exact_ties_follow_the_stated_rule(lib, kind):
+    """setdet_cases.tie_inputs on the serial match: what the device test then demands of the lane-dealt one.  Identical
+    queries and rows: row m takes query m.  A cheaper block of equal candidates at queries 253..264: its first six.
+    Duplicated prototypes: the distinct costs of a row lie further apart than GAP_MATCH in the float64 oracle (so float32
+    keeps every order and every equality), the match is an optimum of the oracle's cost matrix and one-to-one."""
+    ref = SC.tie_reference(kind)
+    got = SC.host_run(lib, *ref["inputs"])
+    print(f"ties {kind}: distinct costs of a row at least {ref['gap']:.3e} apart; the oracle's own match {ref['match'].tolist()}")
+    assert ref["gap"] > SC.GAP_MATCH
+    if kind == "identical":
+        assert got["match"].tolist() == [[0, 1, 2, 3, 4, 5]]
+    if kind == "block":
+        assert got["match"].tolist() == [list(SC.TIE_BLOCK)[:SC.TIE_M]] == [[253, 254, 255, 256, 257, 258]]
+    if kind == "prototypes":
+        x, bx, gt, cls = ref["inputs"]
+        protos = {(x[0, q].tobytes(), bx[0, q].tobytes()) for q in range(SC.TIE_Q)}
+        assert len(protos) == 5 and len({(gt[0, m].tobytes(), int(cls[0, m])) for m in range(SC.TIE_M)}) == 4
+        for r in ref["cost"]:                                              # a row's cost has one value per prototype
+            assert len(np.unique(r)) == 5
+        # the rule on this input: every row takes the lowest free query of its cheapest prototype
+        want, taken = [], set()
+        for r in ref["cost"]:
+            q = min(q for q in range(SC.TIE_Q) if r[q] == r.min() and q not in taken)
+            want.append(q)
+            taken.add(q)
+        assert got["match"].tolist() == [want]
+    SC.check_tie("host", kind, got, got["match"])
+    d = SC.host_run(lib, *ref["inputs"], double=True, want_grad=False)
+    assert np.array_equal(d["match"], got["match"]) and np.array_equal(d["tgt"], got["tgt"])
+
+
+def test_backward_at_its_kinks(lib):
+    """setdet_cases.kink_inputs: the matched box equal to its gt, touching it, disjoint, containing it, inside with a shared
+    edge, of zero size.  torch's autograd follows the contract's conventions there (ties of max / min in halves, clamps
+    passing at 0, sign(0) = 0), so the usual bound against the float64 oracle holds; and where every step is exact the
+    values are literals: one image alone has n = 1, so k_l1 = 5 and k_giou = 2 exactly."""
+    inputs = SC.kink_inputs()
+    o = SC.oracle(*inputs, want_gap=True)
+    got = SC.host_run(lib, *inputs)
+    print(f"kinks: gap_match {o['gap_match']:.3e}")
+    assert o["gap_match"] > SC.GAP_MATCH and (o["match"] == 0).all()
+    assert np.array_equal(got["match"], o["match"].numpy()) and np.array_equal(got["tgt"], o["tgt"].numpy())
+    assert np.isfinite(got["grad_boxes"]).all() and np.isfinite(got["loss"]).all()
+    SC.check_with_match_frozen("host kinks", got, inputs)
+    names = [k[0] for k in SC.KINKS]
+    assert (got["grad_boxes"][names.index("equal"), 0] == 0).all() and (got["grad_boxes"][:, 1] == 0).all()
+    literals = {"equal": [0.0, 0.0, 0.0, 0.0], "inside-shared-edge": [-7.25, 0.0, -5.875, -7.0], "zero-size": [0.0, 0.0, -5.0, -5.0]}
+    assert set(literals) == set(SC.KINK_EXACT)
+    for name, want in literals.items():
+        one = SC.kink_inputs(name)
+        for double in (False, True):
+            g = SC.host_run(lib, *one, double=double)
+            assert g["match"].tolist() == [[0]] and g["grad_boxes"][0, 0].tolist() == want, (name, double)
+        assert SC.oracle(*one)["grad_boxes"][0, 0].tolist() == want, name
+
+
+def test_postprocess_at_exact_scores_and_limits(lib):
+    """The output stage at exact scores (a class tie at 0.5, a score exactly at conf_thr, NaN and -inf logits), at max_det = 1 and
+    1024 and with all and none of 65 queries kept: setdet_cases.exact_score_expectations, shared with the device test."""
+    SC.exact_score_expectations(lambda x, bx, thr, max_det: SC.host_post(lib, x, bx, thr=thr, max_det=max_det))
+
+
 # ---- the hand-written backward against its own forward ------------------------------------------------------------------------
 @pytest.mark.parametrize("cid", ["tiny", "contested"])
 def test_gradient_equals_the_finite_difference_of_the_forward(lib, cid):
@@ -258,13 +340,26 @@ for cid in ("ragged", "contested", "full-rows", "wide"):
             assert len(set(qs.tolist())) == len(qs), (cid, frac)
         dets, counts = SC.host_post(lib, x, bx)
         assert counts.min() >= 0 and counts.max() <= c.Q
+# one poisoned image of three: the other two keep the clean run's bits (the inputs of the device test)
+for c in SC.NONFINITE_CASES:
+    logits, boxes, gtb, gtc = SC.make_inputs(c)
+    assert c.B == 3 and ((gtc >= 0) & (gtc < c.C)).all()
+    clean = SC.host_run(lib, logits, boxes, gtb, gtc)
+    for frac in SC.NONFINITE_FRACS:
+        x, bx = SC.poisoned_inputs(c, frac)
+        assert np.array_equal(x[[0, 2]], logits[[0, 2]]) and np.array_equal(bx[[0, 2]], boxes[[0, 2]])
+        share = 1 - np.isfinite(x[1]).mean()
+        assert abs(share - frac) < 0.1 and np.isnan(x[1]).any() and np.isposinf(x[1]).any() and np.isneginf(x[1]).any()
+        got = SC.host_run(lib, x, bx, gtb, gtc)
+        SC.check_poisoned(f"host {c.id} {frac}", c, got, clean, gtc, SC.host_post(lib, x, bx)[1])
 print("poison ok")
 """
 
 
 def test_non_finite_inputs_return_with_every_index_in_range(lib):
     """NaN and +-inf in logits and boxes give unspecified floats, but the match stays one-to-one and in range and every
-    loop ends: run in a child process so that a loop that did not end would be cut off instead of hanging the suite."""
+    loop ends: run in a child process so that a loop that did not end would be cut off instead of hanging the suite.  With
+    one image of three poisoned, the other two keep the bits of the clean run (setdet_cases.check_poisoned)."""
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, "-c", _POISON, here], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "poison ok" in r.stdout, r.stdout + r.stderr
