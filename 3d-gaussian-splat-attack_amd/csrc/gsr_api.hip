@@ -26,6 +26,7 @@
 #include "gsr_knn.hip.h"
 #include "gsr_knnq.hip.h"
 #include "gsr_pgd.hip.h"
+#include "gsr_adam.hip.h"
 #include "gsr_groups.hip.h"
 #include "gsr_hull.h"
 #include "gsr_image.hip.h"
@@ -2157,6 +2158,57 @@ int gsr_pgd_step_multi(int32_t n, float* const* x, const float* const* grad, con
   if (blk) pool_free(dev, blk);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "gsr_pgd_step_multi: launch failed: %s", hipGetErrorString(e));
+  return GSR_OK;
+}
+
+int gsr_adam_step_multi(int32_t n, void* const* x, const void* const* g, void* const* m, void* const* v, const int64_t* rows,
+                        const int32_t* cols, const float* lr, const float* beta1, const float* beta2, const float* eps,
+                        int64_t step, const uint8_t* row_mask, int64_t row_begin, int64_t row_end, void* stream) {
+  if (n < 1 || n > ADAM_MAX_TENSORS) return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: n=%d (1..%d tensors)", n, ADAM_MAX_TENSORS);
+  if (step < 1) return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: step=%lld (the count of this step, >= 1)", (long long)step);
+  if (!x || !g || !m || !v || !rows || !cols || !lr || !beta1 || !beta2 || !eps)
+    return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: null argument");
+  const bool selected = row_mask != nullptr || row_begin != 0 || row_end != -1;
+  AdamMulti a;
+  memset(&a, 0, sizeof(a));
+  unsigned long long blocks = 0;
+  for (int t = 0; t < n; ++t) {
+    if (rows[t] < 0 || cols[t] < 1 || cols[t] > ADAM_MAX_COLS)
+      return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: tensor %d: rows=%lld cols=%d (1..%d columns)", t, (long long)rows[t], cols[t],
+                     ADAM_MAX_COLS);
+    if (rows[t] > 0 && (!x[t] || !g[t] || !m[t] || !v[t])) return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: tensor %d: null pointer", t);
+    if (selected && rows[t] != rows[0])
+      return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: tensor %d has %lld rows, tensor 0 has %lld: a row mask or a row range needs equal row counts",
+                     t, (long long)rows[t], (long long)rows[0]);
+    if (!std::isfinite(lr[t]) || !std::isfinite(beta1[t]) || !std::isfinite(beta2[t]) || !std::isfinite(eps[t]))
+      return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: tensor %d: lr, beta1, beta2 and eps must be finite", t);
+    if (!(beta1[t] >= 0.f && beta1[t] < 1.f) || !(beta2[t] >= 0.f && beta2[t] < 1.f) || eps[t] < 0.f)
+      return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: tensor %d: beta1=%g beta2=%g (both in [0, 1)) eps=%g (>= 0)", t, (double)beta1[t],
+                     (double)beta2[t], (double)eps[t]);
+    a.x[t] = static_cast<float*>(x[t]); a.g[t] = static_cast<const float*>(g[t]);
+    a.m[t] = static_cast<float*>(m[t]); a.v[t] = static_cast<float*>(v[t]);
+    a.rows[t] = (unsigned long long)rows[t]; a.cols[t] = cols[t];
+    adam_bias_corrections((double)lr[t], (double)beta1[t], (double)beta2[t], (long long)step, &a.step_size[t], &a.sqrt_bc2[t]);
+    a.b1[t] = beta1[t]; a.b2[t] = beta2[t]; a.eps[t] = eps[t];
+    a.first[t] = (unsigned)blocks;
+    blocks += adam_blocks((unsigned long long)rows[t] * (unsigned long long)cols[t]);
+    if (blocks > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: too many elements for one launch");
+  }
+  if (selected) {
+    if (row_end == -1) row_end = rows[0];
+    if (row_begin < 0 || row_begin > row_end || row_end > rows[0])
+      return set_err(GSR_ERR_INVALID, "gsr_adam_step_multi: row range [%lld, %lld) of %lld rows", (long long)row_begin, (long long)row_end,
+                     (long long)rows[0]);
+    a.row_mask = row_mask; a.row_begin = (unsigned long long)row_begin; a.row_end = (unsigned long long)row_end;
+  }
+  for (int t = n; t <= ADAM_MAX_TENSORS; ++t) a.first[t] = (unsigned)blocks;
+  a.n = n;
+  if (blocks == 0 || (selected && row_begin == row_end)) return GSR_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (selected) hipLaunchKernelGGL((k_adam_step_multi<true>), dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, st, a);
+  else hipLaunchKernelGGL((k_adam_step_multi<false>), dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "gsr_adam_step_multi: launch failed: %s", hipGetErrorString(e));
   return GSR_OK;
 }
 

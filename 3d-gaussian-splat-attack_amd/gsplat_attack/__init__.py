@@ -53,4 +53,8 @@ def __getattr__(name):
     if name in ("segment_objects", "object_boxes", "group_bboxes", "object_ce", "ObjectMaps"):
         from . import objects
         return getattr(objects, name)
+    # fitting a model: the optimiser of the reference's set-ups and the plain loop
+    if name in ("OptimizationParams", "GaussianAdam", "get_expon_lr_func", "refit"):
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -2,9 +2,9 @@
 the PGD step functions read.
 
 Counterpart of the getters of the reference's ``scene/gaussian_model.py:24-39,97-124``
-(seven parameter tensors + exp / sigmoid / normalize / cat activations).  Training-time
-machinery (densify / prune / optimiser state, :264-711) is out of scope: the attack never
-calls it.
+(seven parameter tensors + exp / sigmoid / normalize / cat activations).  The fitting set-ups
+(training_setup, finetune_setup, the tail of inpaint_setup, update_learning_rate: :160-214,350-375) put a
+gsplat_attack.optim.GaussianAdam on the model; densification (:652-711) is not here.
 """
 from __future__ import annotations
 
@@ -19,6 +19,10 @@ class GaussianModel:
         self.max_sh_degree = sh_degree
         self.active_sh_degree = sh_degree      # load_ply sets active = max (scene/gaussian_model.py:467)
         self.num_objects = NUM_OBJECTS
+        self.spatial_lr_scale = 1.0            # scales the position learning rates (scene/gaussian_model.py:56,131)
+        self.percent_dense = 0.0
+        self.optimizer = None
+        self.xyz_scheduler_args = None
         e = torch.empty(0)
         self._xyz = e
         self._features_dc = e
@@ -55,11 +59,13 @@ class GaussianModel:
         return m
 
     @classmethod
-    def create_from_pcd(cls, points, colors, sh_degree: int = 3, device="cpu", generator=None) -> "GaussianModel":
+    def create_from_pcd(cls, points, colors, sh_degree: int = 3, device="cpu", generator=None,
+                        spatial_lr_scale: float = 1.0) -> "GaussianModel":
         """Initial model from a sparse point cloud (reference scene/gaussian_model.py:130-158): DC colour = RGB2SH(rgb),
         higher bands 0, isotropic log-scale = log sqrt(mean squared distance to the 3 nearest neighbours)
         (``simple_knn._C.distCUDA2`` -- the HIP kernel on a device, clamped at 1e-7), identity rotations, opacity
-        logit(0.1), random object features RGB2SH(U[0,1)).  points [P,3], colors [P,3] in [0,1] (array-likes)."""
+        logit(0.1), random object features RGB2SH(U[0,1)).  points [P,3], colors [P,3] in [0,1] (array-likes).
+        spatial_lr_scale (the reference's second argument, the scene's camera extent) is kept for training_setup."""
         from simple_knn._C import distCUDA2
         from .sh import RGB2SH
         xyz = torch.as_tensor(points, dtype=torch.float32).to(device).contiguous()
@@ -73,8 +79,10 @@ class GaussianModel:
         opac = torch.full((P, 1), 0.1, device=xyz.device)
         opac = torch.log(opac / (1.0 - opac))                            # inverse_sigmoid, utils/general_utils.py:18-19
         objs = RGB2SH(torch.rand(P, NUM_OBJECTS, generator=generator).to(xyz.device))[:, None, :]
-        return cls.from_tensors(xyz, RGB2SH(rgb)[:, None, :], torch.zeros(P, K - 1, 3, device=xyz.device), scales, rots,
-                                opac, objs, sh_degree=sh_degree, device=xyz.device)
+        m = cls.from_tensors(xyz, RGB2SH(rgb)[:, None, :], torch.zeros(P, K - 1, 3, device=xyz.device), scales, rots,
+                             opac, objs, sh_degree=sh_degree, device=xyz.device)
+        m.spatial_lr_scale = float(spatial_lr_scale)
+        return m
 
     def parameters(self):
         return [self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
@@ -98,7 +106,42 @@ class GaussianModel:
         for n in self._PARAM_ATTRS:
             setattr(self, n, nn.Parameter(getattr(self, n)[keep].detach().clone()))
 
-    def inpaint_setup(self, mask3d: torch.Tensor, k: int = 5) -> torch.Tensor:
+    # ---- the fitting set-ups (scene/gaussian_model.py:160-214,350-375) ------------------------------------------------
+    def _setup_optimizer(self, opt, row_mask=None, rows=None) -> None:
+        from .optim import GaussianAdam, get_expon_lr_func, reference_groups
+        self.percent_dense = opt.percent_dense
+        self.optimizer = GaussianAdam(self, reference_groups(opt, self.spatial_lr_scale), eps=1e-15, row_mask=row_mask, rows=rows)
+        self.xyz_scheduler_args = get_expon_lr_func(lr_init=opt.position_lr_init * self.spatial_lr_scale,
+                                                    lr_final=opt.position_lr_final * self.spatial_lr_scale,
+                                                    lr_delay_mult=opt.position_lr_delay_mult,
+                                                    max_steps=opt.position_lr_max_steps)
+
+    def training_setup(self, opt) -> None:
+        """The optimiser of a full fit (reference :160-179): Adam(lr=0, eps=1e-15) over the seven groups xyz, f_dc, f_rest,
+        opacity, scaling, rotation, obj_dc with the rates of `opt` (gsplat_attack.optim.OptimizationParams), and the
+        position schedule.  Afterwards self.optimizer is a gsplat_attack.optim.GaussianAdam."""
+        self._setup_optimizer(opt)
+
+    def finetune_setup(self, opt, mask3d: torch.Tensor) -> None:
+        """Move only the Gaussians mask3d selects (reference :181-214); _objects_dc is frozen.  The reference registers
+        gradient hooks that multiply every gradient by mask3d and steps all rows; here the mask is the optimiser's row
+        mask and the other rows are neither read nor written.  The two agree: a row whose gradient is always zero and
+        whose moments start at zero never moves under Adam (m' = v' = 0, 0 / (0 + eps) = 0)."""
+        mask = mask3d.detach().reshape(-1)
+        if mask.numel() != self._xyz.shape[0]:
+            raise ValueError(f"finetune_setup: mask of {mask.numel()} entries for {self._xyz.shape[0]} Gaussians")
+        self._objects_dc.requires_grad = False
+        self._setup_optimizer(opt, row_mask=mask != 0)
+
+    def update_learning_rate(self, iteration: int) -> float:
+        """Set the xyz group's learning rate from the position schedule and return it (reference :369-375)."""
+        for group in self.optimizer.param_groups:
+            if group["name"] == "xyz":
+                lr = self.xyz_scheduler_args(iteration)
+                group["lr"] = lr
+                return lr
+
+    def inpaint_setup(self, mask3d: torch.Tensor, k: int = 5, opt=None) -> torch.Tensor:
         """Fill the hole a removal leaves (reference scene/gaussian_model.py:264-348): the Gaussians NOT selected by mask3d
         stay, first and in their order; behind them comes one new Gaussian per removed one, in the removed rows' order,
         whose seven raw attributes (positions, logit opacities, log scales, raw quaternions, both SH blocks, object
@@ -112,7 +155,13 @@ class GaussianModel:
         Deviations from the reference: ties between equidistant neighbours go to the lower index (KDTree's choice is
         arbitrary); with fewer than k remaining Gaussians the mean is over those there are, and with none a ValueError is
         raised (the reference fails with an index error); the reference's distance_threshold / max_distance_threshold
-        arguments do not exist here, because the reference never reads them; no optimiser is set up."""
+        arguments do not exist here, because the reference never reads them.
+
+        opt (gsplat_attack.optim.OptimizationParams, optional): also set up the optimiser of the reference's tail
+        (:350-367), with the new rows as its row range.  Deviation: in the reference every row ends up trainable, because
+        nn.Parameter re-enables the gradient of the concatenated tensors, although its comment says "Only the new points
+        will have gradients"; here the comment's intent is the behaviour, and setting `model.optimizer.rows = None`
+        restores the reference's.  Without opt no optimiser is set up."""
         from diff_gaussian_rasterization import knn_ops
         removed = mask3d.bool().reshape(-1).to(self._xyz.device)
         if removed.numel() != self._xyz.shape[0]:
@@ -132,6 +181,8 @@ class GaussianModel:
                 setattr(self, n, nn.Parameter(torch.cat([r, w.to(r.dtype)]).detach().clone()))
         new_mask = torch.zeros(self._xyz.shape[0], dtype=torch.bool, device=self._xyz.device)
         new_mask[self._xyz.shape[0] - n_new:] = n_new > 0
+        if opt is not None:
+            self._setup_optimizer(opt, rows=(self._xyz.shape[0] - n_new, self._xyz.shape[0]))
         return new_mask
 
     def concat_setup(self, feature_name: str, tensor_to_concat: torch.Tensor, requires_grad: bool) -> None:
@@ -143,6 +194,7 @@ class GaussianModel:
     def clone(self) -> "GaussianModel":
         m = GaussianModel(self.max_sh_degree)
         m.active_sh_degree = self.active_sh_degree
+        m.spatial_lr_scale = self.spatial_lr_scale
         for n in self._PARAM_ATTRS:
             p = getattr(self, n)
             setattr(m, n, nn.Parameter(p.detach().clone(), requires_grad=p.requires_grad))

@@ -486,6 +486,38 @@ int gsr_pgd_step_multi(int32_t n, float* const* x, const float* const* grad, con
                        const int32_t* cols, const float* alpha, const float* epsilon, int32_t l2, const double* const* sumsq,
                        void* stream);
 
+/*
+ * gsr_adam_step_multi: one Adam step (torch.optim.Adam without weight decay, amsgrad or maximize; reference
+ * scene/gaussian_model.py:160-214,350-367, the optimiser of training_setup / finetune_setup / inpaint_setup) on n <= 8
+ * tensors of one model in ONE launch, in place.  No change of GSR_VERSION, no capability bit: the stage is present iff
+ * the library exports this symbol.  Arrays of n HOST entries: x / g / m / v device pointers to float32 [rows, cols]
+ * (parameter, gradient, first and second moment; g is only read), rows, cols (1..48), lr, beta1, beta2, eps.  Per element,
+ * every operation rounded once in this order (csrc/gsr_adam.h):
+ *     m'  = m + (1 - beta1) * (g - m)
+ *     v'  = beta2 * v + (1 - beta2) * (g * g)
+ *     den = sqrtf(v') / sqrt_bc2 + eps
+ *     x'  = x - step_size * (m' / den)
+ * step_size = lr / (1 - beta1^step) and sqrt_bc2 = sqrt(1 - beta2^step) are formed on the host in double from the
+ * integer count `step` >= 1 of THIS step and rounded once to float32: no device scalar, no read-back.  Results are
+ * bitwise reproducible and bit for bit those of the host build of csrc/gsr_adam.h.
+ * Row selection, shared by all tensors of the call (which must then have equal row counts): row_mask = NULL or a device
+ * uint8 [rows] (non-zero = the row moves); [row_begin, row_end) with row_end = -1 meaning rows.  A row outside the range
+ * or with a zero byte is neither read nor written in x, m and v.  A workgroup (one wave, 1024 consecutive floats of a
+ * tensor) whose rows are all left out returns after reading their mask bytes.
+ * Non-finite and range (what torch.optim.Adam does on CPU float32 tensors, element by element; csrc/gsr_adam.h has the
+ * list): a NaN or infinite gradient element poisons m, v and x at that element only; g = 0 with zero moments moves
+ * nothing; a square that underflows leaves den = eps; |g| up to 1.84e19 keeps g * g and v finite (beyond it v = +inf and x stays); lr = 0 updates the moments
+ * and leaves x bit for bit.
+ * Refused before the launch: n outside 1..8, step < 1, a null array, cols outside 1..48, negative rows, a null pointer
+ * among the four of a tensor with rows > 0, unequal row counts with a mask or a range, a range outside
+ * 0 <= begin <= end <= rows, a beta outside [0, 1), eps < 0, a non-finite lr, beta or eps.  A tensor without rows is
+ * skipped; a call without any row to move launches nothing and returns 0.
+ */
+int gsr_adam_step_multi(int32_t n, void* const* x, const void* const* g, void* const* m, void* const* v, const int64_t* rows,
+                        const int32_t* cols, const float* lr, const float* beta1, const float* beta2, const float* eps,
+                        int64_t step, const uint8_t* row_mask /* or null */, int64_t row_begin, int64_t row_end /* -1: rows */,
+                        void* stream);
+
 /* Mean squared distance of every point to its 3 nearest other points (exact): replaces the reference's second native
  * import, simple_knn._C.distCUDA2 (reference scene/gaussian_model.py:17, called at :144 to seed the initial scales).
  * points [P,3] float32 device, mean_dist2 [P] float32 device.  Synchronises the stream once (scene set-up routine, not
