@@ -136,6 +136,50 @@ __device__ __forceinline__ void pre_block_epilogue(const PreBlockOut& o, int g, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Steps that every form of K1 and K8+K9 takes (generic-K, lane-group, batch): one copy each, here, in front of
+// k_preprocess_bwd and in front of k_pre_bwd.  A per-Gaussian step is changed in its helper, once.
+// ------------------------------------------------------------------------------------------------
+// Scale and rotation of Gaussian g; RAW: activated (exp, normalised quaternion; inv_qn = 1 / |q| for the backward).
+template <bool RAW>
+__device__ __forceinline__ void load_scale_rot(const float* scales, const float* rots, int g,
+                                               float sc[3], float q[4], float& inv_qn) {
+  sc[0] = scales[3 * g]; sc[1] = scales[3 * g + 1]; sc[2] = scales[3 * g + 2];
+  const float4 q4 = reinterpret_cast<const float4*>(rots)[g];
+  q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+  inv_qn = 1.f;
+  if (RAW) {
+    sc[0] = expf(sc[0]); sc[1] = expf(sc[1]); sc[2] = expf(sc[2]);
+    act_normalize4(q, q, inv_qn);
+  }
+}
+
+// The tile rect of a visible splat: shrunk to the alpha >= 1/255 footprint when `cull`, its first tile at most
+// RECT_OFF_MAX behind the reference rect's.  Returns the tiles it covers; when there are any, rx / ry are the record's
+// rect words and *G0rec = (px, py, A, B) is written.
+__device__ __forceinline__ uint32_t finish_rect(bool cull, const View& v, Splat& s, float op, float4* G0rec,
+                                                uint32_t& rx, uint32_t& ry) {
+  const int fminx = s.rminx, fminy = s.rminy;      // first tile of the reference's rect: the origin of the stored centre
+  if (cull) tighten_rect(s.px, s.py, s.A, s.B, s.C, op, v.gridx, v.gridy, s.rminx, s.rminy, s.rmaxx, s.rmaxy);
+  s.rminx = min(s.rminx, fminx + RECT_OFF_MAX); s.rminy = min(s.rminy, fminy + RECT_OFF_MAX);
+  const uint32_t cnt = (uint32_t)((s.rmaxx - s.rminx) * (s.rmaxy - s.rminy));
+  rx = 0u; ry = 0u;
+  if (cnt != 0u) {
+    rx = (uint32_t)s.rminx | ((uint32_t)s.rmaxx << 12) | ((uint32_t)(s.rminx - fminx) << 24);
+    ry = (uint32_t)s.rminy | ((uint32_t)s.rmaxy << 12) | ((uint32_t)(s.rminy - fminy) << 24);
+    *G0rec = make_float4((float)(s.pxd - (double)(fminx * TILE)), (float)(s.pyd - (double)(fminy * TILE)), s.A, s.B);
+  }
+  return cnt;
+}
+
+// A colour c >= 0 whose pre-clamp value was negative is stored as -0.0f: the compositors see 0 either way (x + -0 = x,
+// w * -0 adds nothing), and the backward reads the clamp flag off the sign bit instead of from a separate word -- so
+// the colour words of a record belong to the colour kernel alone and the geometry kernel never touches them.
+__device__ __forceinline__ float clamp_flagged(float c) { return c > 0.f ? c : (c < 0.f ? -0.0f : 0.0f); }
+__device__ __forceinline__ uint32_t clamp_bits_of(float r, float g, float b) {
+  return (__float_as_uint(r) >> 31) | ((__float_as_uint(g) >> 31) << 1) | ((__float_as_uint(b) >> 31) << 2);
+}
+
+// ------------------------------------------------------------------------------------------------
 // K1, generic form: one thread per Gaussian in storage order, any SH coefficient count K (the layouts the reference
 // uses -- K = 16, the raw dc | rest pair, precomputed colours -- take k_pre_geom / k_pre_color below).
 // cull bit 0: the tile rect is shrunk to the alpha >= 1/255 footprint's bounding box (tighten_rect); bit 1: needles get their
@@ -159,9 +203,8 @@ __global__ void __launch_bounds__(PREG_BLOCK) k_preprocess(int P, int K, ViewArg
 #pragma unroll
       for (int i = 0; i < 6; ++i) c6[i] = cov3d[6 * g + i];
     } else {
-      const float sc[3] = {scales[3 * g], scales[3 * g + 1], scales[3 * g + 2]};
-      const float4 q4 = reinterpret_cast<const float4*>(rots)[g];
-      const float q[4] = {q4.x, q4.y, q4.z, q4.w};
+      float sc[3], q[4], inv_qn;
+      load_scale_rot<false>(scales, rots, g, sc, q, inv_qn);
       cov3d_from_scale_rot(sc, va.mod, q, c6);
     }
     Splat s;
@@ -171,33 +214,25 @@ __global__ void __launch_bounds__(PREG_BLOCK) k_preprocess(int P, int K, ViewArg
     if (ok) {
       if ((cull & 2) && is_needle(s.ca, s.cb, s.cc)) {       // cull bit 1: GSR_FLAG_NEEDLE_DOUBLE
         // a needle's conic (compositors and footprint tests): the same chain in double (gsr_math.h cov2d_accurate)
-        float scd[3] = {0.f, 0.f, 0.f}, qd[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!cov3d) {
-          scd[0] = scales[3 * g]; scd[1] = scales[3 * g + 1]; scd[2] = scales[3 * g + 2];
-          const float4 q4d = reinterpret_cast<const float4*>(rots)[g];
-          qd[0] = q4d.x; qd[1] = q4d.y; qd[2] = q4d.z; qd[3] = q4d.w;
-        }
+        float scd[3] = {0.f, 0.f, 0.f}, qd[4] = {0.f, 0.f, 0.f, 0.f}, inv_qn;
+        if (!cov3d) load_scale_rot<false>(scales, rots, g, scd, qd, inv_qn);
         double ca, cb, cc;
         cov2d_accurate(v, p, scd, va.mod, qd, cov3d ? c6 : nullptr, ca, cb, cc);
         needle_conic_to_float(ca, cb, cc, s.A, s.B, s.C);
       }
-      const int fminx = s.rminx, fminy = s.rminy;      // first tile of the reference's rect: the origin of the stored centre
-      if (cull & 1) tighten_rect(s.px, s.py, s.A, s.B, s.C, o, v.gridx, v.gridy, s.rminx, s.rminy, s.rmaxx, s.rmaxy);
-      s.rminx = min(s.rminx, fminx + RECT_OFF_MAX); s.rminy = min(s.rminy, fminy + RECT_OFF_MAX);
-      cnt = (uint32_t)((s.rmaxx - s.rminx) * (s.rmaxy - s.rminy));
+      uint32_t rx, ry;
+      cnt = finish_rect((cull & 1) != 0, v, s, o, &G0[REC * g], rx, ry);
       if (cnt != 0u) {
         float rgb[3];
         uint32_t cl = 0;
         if (colors) { rgb[0] = colors[3 * g]; rgb[1] = colors[3 * g + 1]; rgb[2] = colors[3 * g + 2]; }
         else cl = sh_to_rgb(va.deg, sh + (size_t)g * K * 3, p, v.cam, rgb);
         key = __float_as_uint(s.depth);
-        const uint32_t rx = (uint32_t)s.rminx | ((uint32_t)s.rmaxx << 12) | ((uint32_t)(s.rminx - fminx) << 24);
-        const uint32_t ry = (uint32_t)s.rminy | ((uint32_t)s.rmaxy << 12) | ((uint32_t)(s.rminy - fminy) << 24);
-        // a clamped colour is stored as -0.0f: the backward reads the clamp flags off the sign bits
+        // a clamped colour is stored as -0.0f: the backward reads the clamp flags off the sign bits (sh_to_rgb hands back
+        // the clamped colours and the flags, not the signed sums clamp_flagged takes)
         if (cl & 1u) rgb[0] = -0.0f;
         if (cl & 2u) rgb[1] = -0.0f;
         if (cl & 4u) rgb[2] = -0.0f;
-        G0[REC * g] = make_float4((float)(s.pxd - (double)(fminx * TILE)), (float)(s.pyd - (double)(fminy * TILE)), s.A, s.B);
         G1[REC * g] = make_float4(s.C, o, rgb[0], rgb[1]);
         G2[REC * g] = make_float4(rgb[2], s.depth, __uint_as_float(rx), __uint_as_float(ry));
       }
@@ -882,9 +917,7 @@ __global__ void __launch_bounds__(64 * WPB, (OBJ && NPX == 2 && WPB == 1) ? GSR_
     if (WPB > 1) {
       __syncthreads();
     } else {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_handoff();
     }
 #pragma unroll
     for (int jb = 0; jb < BATCH; jb += 64) {              // the batch, 64 entries at a time
@@ -1355,9 +1388,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? (AUX ? 5 : 6) : 1) k_
         dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();
     // One list entry: its strips, the parking of its per-lane sums, and the transposed sum when the buffer is full.  The
     // walk below is unrolled by two over TWO register sets (a, b), each loaded while the other is processed: with one set
     // rotated every iteration the compiler ends every entry on five 64-bit register moves of the prefetched record.
@@ -1471,9 +1502,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? (AUX ? 5 : 6) : 1) k_
       }
       }
       if (red_n == RB || (j == 0 && red_n > 0)) {     // sslot[] is re-staged after j == 0: drain before that
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_handoff();
         const int jm = RB > 1 ? __builtin_amdgcn_ds_bpermute(red_e << 2, red_j) : j;
         if (red_e < red_n) {
           // chunk red_ch of register red_rr of parked entry red_e; the odd chunks' halves are stored swapped
@@ -1496,9 +1525,7 @@ __global__ void __launch_bounds__(64, (!OBJ && NPX == 4) ? (AUX ? 5 : 6) : 1) k_
           }
         }
         red_n = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_handoff();
       }
     };
     float4 a0 = s0[cnt - 1], a1 = s1[cnt - 1];
@@ -1583,6 +1610,44 @@ __global__ void __launch_bounds__(256) k_sumsq_reduce(const float* __restrict__ 
   if (threadIdx.x == 0) out[k] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
+// ---- steps of K8+K9 that its generic, lane-group and batch forms share ----------------------------------------------------
+// A partial row belongs to this backward call iff its words 9, 10 (p2 = the row's third float4) carry the call's tag;
+// any other row is stale: K7 wrote it in an earlier call, or nobody did.
+__device__ __forceinline__ bool row_tagged(const float4& p2, uint32_t tag_lo, uint32_t tag_hi) {
+  return __float_as_uint(p2.y) == tag_lo && __float_as_uint(p2.z) == tag_hi;
+}
+
+// acc = the sum over the tagged rows [o0, o1) of one (view, Gaussian) of their 16 object sums, in row order; zeros
+// without part_obj (no dL/dobjects).
+__device__ __forceinline__ void sum_object_rows(const float4* part, const float4* part_obj,
+                                                uint32_t o0, uint32_t o1, uint32_t tag_lo, uint32_t tag_hi,
+                                                float acc[NUM_OBJ]) {
+#pragma unroll
+  for (int c = 0; c < NUM_OBJ; ++c) acc[c] = 0.f;
+  if (part_obj) {
+    for (uint32_t e = o0; e < o1; ++e) {
+      if (!row_tagged(part[(size_t)e * PART_F4 + 2], tag_lo, tag_hi)) continue;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 v = part_obj[(size_t)e * 4 + q];
+        acc[4 * q] += v.x; acc[4 * q + 1] += v.y; acc[4 * q + 2] += v.z; acc[4 * q + 3] += v.w;
+      }
+    }
+  }
+}
+
+// A Gaussian without pairs: zeros to every gradient of an overwriting launch but dL/dSH, whose layout is the caller's.
+__device__ __forceinline__ void zero_unseen_grads(const PreBwdArgs& a, int g) {
+  if (a.dmeans3D) { a.dmeans3D[3 * g] = 0.f; a.dmeans3D[3 * g + 1] = 0.f; a.dmeans3D[3 * g + 2] = 0.f; }
+  if (a.dmeans2D) { a.dmeans2D[3 * g] = 0.f; a.dmeans2D[3 * g + 1] = 0.f; a.dmeans2D[3 * g + 2] = 0.f; }
+  if (a.dsh_objs) for (int i = 0; i < NUM_OBJ; ++i) a.dsh_objs[(size_t)g * NUM_OBJ + i] = 0.f;
+  if (a.dcolors) { a.dcolors[3 * g] = 0.f; a.dcolors[3 * g + 1] = 0.f; a.dcolors[3 * g + 2] = 0.f; }
+  if (a.dopac) a.dopac[g] = 0.f;
+  if (a.dscales) { a.dscales[3 * g] = 0.f; a.dscales[3 * g + 1] = 0.f; a.dscales[3 * g + 2] = 0.f; }
+  if (a.drots) { a.drots[4 * g] = 0.f; a.drots[4 * g + 1] = 0.f; a.drots[4 * g + 2] = 0.f; a.drots[4 * g + 3] = 0.f; }
+  if (a.dcov3d) for (int i = 0; i < 6; ++i) a.dcov3d[6 * g + i] = 0.f;
+}
+
 // Generic form (any K): one thread per Gaussian walks its own partial rows and its own SH row.
 // GEOM = false: the rows carry the three colour sums only (K7 without the geometry sums) and only the SH / colour /
 // object-feature gradients are produced.  NDL: GSR_FLAG_NEEDLE_DOUBLE was set in the forward (needles run needle_bwd_d).
@@ -1593,15 +1658,8 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess_bwd(PreBwdArgs a) {
   if (g >= a.P) return;
   const uint32_t o0 = a.offg[g] * a.nsub, o1 = a.offg[g + 1] * a.nsub;
   if (o1 == o0) {   // no pairs: zero gradients
-    if (a.dmeans3D) { a.dmeans3D[3 * g] = 0.f; a.dmeans3D[3 * g + 1] = 0.f; a.dmeans3D[3 * g + 2] = 0.f; }
-    if (a.dmeans2D) { a.dmeans2D[3 * g] = 0.f; a.dmeans2D[3 * g + 1] = 0.f; a.dmeans2D[3 * g + 2] = 0.f; }
+    zero_unseen_grads(a, g);
     if (a.dsh) for (int i = 0; i < 3 * K; ++i) a.dsh[(size_t)g * K * 3 + i] = 0.f;
-    if (a.dsh_objs) for (int i = 0; i < NUM_OBJ; ++i) a.dsh_objs[(size_t)g * NUM_OBJ + i] = 0.f;
-    if (a.dcolors) { a.dcolors[3 * g] = 0.f; a.dcolors[3 * g + 1] = 0.f; a.dcolors[3 * g + 2] = 0.f; }
-    if (a.dopac) a.dopac[g] = 0.f;
-    if (a.dscales) { a.dscales[3 * g] = 0.f; a.dscales[3 * g + 1] = 0.f; a.dscales[3 * g + 2] = 0.f; }
-    if (a.drots) { a.drots[4 * g] = 0.f; a.drots[4 * g + 1] = 0.f; a.drots[4 * g + 2] = 0.f; a.drots[4 * g + 3] = 0.f; }
-    if (a.dcov3d) for (int i = 0; i < 6; ++i) a.dcov3d[6 * g + i] = 0.f;
     return;
   }
   // (this kernel always overwrites its outputs: accumulation into a caller's bucket exists for the raw-parameter path
@@ -1610,25 +1668,13 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess_bwd(PreBwdArgs a) {
   float mx = 0.f, my = 0.f, mxx = 0.f, mxy = 0.f, myy = 0.f, dop = 0.f, dr = 0.f, dg = 0.f, db = 0.f;
   for (uint32_t e = o0; e < o1; ++e) {
     const float4 p0 = a.part[(size_t)e * PART_F4], p1 = a.part[(size_t)e * PART_F4 + 1], p2 = a.part[(size_t)e * PART_F4 + 2];
-    if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
+    if (!row_tagged(p2, a.tag_lo, a.tag_hi)) continue;
     if (GEOM) { mx += p0.x; my += p0.y; mxx += p0.z; mxy += p0.w; myy += p1.x; dop += p1.y; }
     dr += p1.z; dg += p1.w; db += p2.x;
   }
   if (a.dsh_objs) {
     float acc_o[NUM_OBJ];
-#pragma unroll
-    for (int c = 0; c < NUM_OBJ; ++c) acc_o[c] = 0.f;
-    if (a.part_obj) {
-      for (uint32_t e = o0; e < o1; ++e) {
-        const float4 tg = a.part[(size_t)e * PART_F4 + 2];
-        if (__float_as_uint(tg.y) != a.tag_lo || __float_as_uint(tg.z) != a.tag_hi) continue;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 v = a.part_obj[(size_t)e * 4 + q];
-          acc_o[4 * q] += v.x; acc_o[4 * q + 1] += v.y; acc_o[4 * q + 2] += v.z; acc_o[4 * q + 3] += v.w;
-        }
-      }
-    }
+    sum_object_rows(a.part, a.part_obj, o0, o1, a.tag_lo, a.tag_hi, acc_o);
 #pragma unroll
     for (int c = 0; c < NUM_OBJ; ++c) put(&a.dsh_objs[(size_t)g * NUM_OBJ + c], acc_o[c]);
   }
@@ -1637,6 +1683,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess_bwd(PreBwdArgs a) {
   const float4 e0 = a.G0[REC * g], e1 = a.G1[REC * g], e2 = a.G2[REC * g];
   const float A = e0.z, B = e0.w, C = e1.x;
   // dL/d(pixel centre) = -(A mx + B my, B mx + C my); screen-space means are reported in NDC units
+  // (from float32 sums in float32, where the lane-group kernels have double: another rounding, and this form's tested one)
   const float dndcx = -(A * mx + B * my) * 0.5f * (float)v.W;
   const float dndcy = -(B * mx + C * my) * 0.5f * (float)v.H;
   const float dA = -0.5f * mxx, dB = -mxy, dC = -0.5f * myy;
@@ -1646,7 +1693,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess_bwd(PreBwdArgs a) {
   float dp[3] = {0.f, 0.f, 0.f};
   if (a.dcolors) { put(&a.dcolors[3 * g], dr); put(&a.dcolors[3 * g + 1], dg); put(&a.dcolors[3 * g + 2], db); }
   if (a.sh) {
-    const uint32_t cl = (__float_as_uint(e1.z) >> 31) | ((__float_as_uint(e1.w) >> 31) << 1) | ((__float_as_uint(e2.x) >> 31) << 2);
+    const uint32_t cl = clamp_bits_of(e1.z, e1.w, e2.x);
     const float drgb[3] = {(cl & 1u) ? 0.f : dr, (cl & 2u) ? 0.f : dg, (cl & 4u) ? 0.f : db};
     if (a.dsh) {
       sh_to_rgb_bwd(v.sh_degree, K, a.sh + (size_t)g * K * 3, p, v.cam, drgb, a.dsh + (size_t)g * K * 3, dp);
@@ -1662,9 +1709,8 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess_bwd(PreBwdArgs a) {
 #pragma unroll
       for (int i = 0; i < 6; ++i) c6[i] = a.cov3d[6 * g + i];
     } else {
-      sc[0] = a.scales[3 * g]; sc[1] = a.scales[3 * g + 1]; sc[2] = a.scales[3 * g + 2];
-      const float4 q4 = reinterpret_cast<const float4*>(a.rots)[g];
-      q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+      float inv_qn;
+      load_scale_rot<false>(a.scales, a.rots, g, sc, q, inv_qn);
       cov3d_from_scale_rot(sc, a.va.mod, q, c6);
     }
     float dc6[6];
@@ -1805,14 +1851,6 @@ struct PreArgs {
   PreBlockOut bo;
 };
 
-// A colour c >= 0 whose pre-clamp value was negative is stored as -0.0f: the compositors see 0 either way (x + -0 = x,
-// w * -0 adds nothing), and the backward reads the clamp flag off the sign bit instead of from a separate word -- so
-// the colour words of a record belong to the colour kernel alone and the geometry kernel never touches them.
-__device__ __forceinline__ float clamp_flagged(float c) { return c > 0.f ? c : (c < 0.f ? -0.0f : 0.0f); }
-__device__ __forceinline__ uint32_t clamp_bits_of(float r, float g, float b) {
-  return (__float_as_uint(r) >> 31) | ((__float_as_uint(g) >> 31) << 1) | ((__float_as_uint(b) >> 31) << 2);
-}
-
 // K1, geometry half: one thread per Gaussian -- projection, culls, tile rect, depth key, tiles touched, the geometric
 // words of the 48-byte record ((px,py,A,B) (C,opacity,.,.) (.,depth,rect x,rect y)) -- and the workgroup sums the storage
 // scan starts from.  Reads 44 bytes per Gaussian.  With precomputed colours it writes those too (nothing else to do).
@@ -1842,15 +1880,8 @@ __global__ void __launch_bounds__(PREG_BLOCK) k_pre_geom(PreArgs a) {
 #pragma unroll
       for (int i = 0; i < 6; ++i) c6[i] = a.cov3d[6 * g + i];
     } else {
-      const float* scales = second ? a.scales_b : a.scales;
-      sc[0] = scales[3 * gl]; sc[1] = scales[3 * gl + 1]; sc[2] = scales[3 * gl + 2];
-      const float4 q4 = reinterpret_cast<const float4*>(second ? a.rots_b : a.rots)[gl];
-      q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-      if (RAW) {
-        sc[0] = expf(sc[0]); sc[1] = expf(sc[1]); sc[2] = expf(sc[2]);
-        float inv_n;
-        act_normalize4(q, q, inv_n);
-      }
+      float inv_qn;
+      load_scale_rot<RAW>(second ? a.scales_b : a.scales, second ? a.rots_b : a.rots, gl, sc, q, inv_qn);
       cov3d_from_scale_rot(sc, a.va.mod, q, c6);
     }
     Splat s;
@@ -1870,15 +1901,10 @@ __global__ void __launch_bounds__(PREG_BLOCK) k_pre_geom(PreArgs a) {
         needle_conic_to_float(ca, cb, cc, s.A, s.B, s.C);
       }
       if (NDL && a.abc) a.abc[vo + (size_t)g] = ndl ? ca : __longlong_as_double(0x7FF8000000000000ll);   // K9's needle mark
-      const int fminx = s.rminx, fminy = s.rminy;      // first tile of the reference's rect: the origin of the stored centre
-      if (a.cull) tighten_rect(s.px, s.py, s.A, s.B, s.C, op, v.gridx, v.gridy, s.rminx, s.rminy, s.rmaxx, s.rmaxy);
-      s.rminx = min(s.rminx, fminx + RECT_OFF_MAX); s.rminy = min(s.rminy, fminy + RECT_OFF_MAX);
-      cnt = (uint32_t)((s.rmaxx - s.rminx) * (s.rmaxy - s.rminy));
+      uint32_t rx, ry;
+      cnt = finish_rect(a.cull != 0, v, s, op, &a.G0[REC * (vo + g)], rx, ry);
       if (cnt != 0u) {
         key = __float_as_uint(s.depth);
-        const uint32_t rx = (uint32_t)s.rminx | ((uint32_t)s.rmaxx << 12) | ((uint32_t)(s.rminx - fminx) << 24);
-        const uint32_t ry = (uint32_t)s.rminy | ((uint32_t)s.rmaxy << 12) | ((uint32_t)(s.rminy - fminy) << 24);
-        a.G0[REC * (vo + g)] = make_float4((float)(s.pxd - (double)(fminx * TILE)), (float)(s.pyd - (double)(fminy * TILE)), s.A, s.B);
         float* g1 = reinterpret_cast<float*>(&a.G1[REC * (vo + g)]);
         float* g2 = reinterpret_cast<float*>(&a.G2[REC * (vo + g)]);
         if (a.colors) {
@@ -1931,9 +1957,7 @@ __global__ void __launch_bounds__(PREF_BLOCK) k_pre_color(PreArgs a) {
     float* sl = ws + 4 * __popcll(live & ((1ull << lane) - 1ull));
     sl[0] = dx * inv; sl[1] = dy * inv; sl[2] = dz * inv; sl[3] = __uint_as_float((uint32_t)g);
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_handoff();
   const int q = lane & 3, grp = lane >> 2;
   const int deg = a.va.deg;
   for (int r0 = 0; r0 < nlive; r0 += 16) {
@@ -1945,6 +1969,7 @@ __global__ void __launch_bounds__(PREF_BLOCK) k_pre_color(PreArgs a) {
       float sv[12];
       if (gg >= (uint32_t)a.Pa) load_sh12<RAW>(a.sh_b, a.sh_dc_b, gg - (uint32_t)a.Pa, q, sv);
       else load_sh12<RAW>(a.sh, a.sh_dc, gg, q, sv);
+      // colour evaluation -- contraction-sensitive: keep identical to the copy in k_pre_color_batch
       float b[16], gx[16], gy[16], gz[16];
 #pragma unroll
       for (int k = 0; k < 16; ++k) b[k] = 0.f;
@@ -1984,9 +2009,7 @@ __global__ void __launch_bounds__(PREF_BLOCK) k_pre_color(PreArgs a) {
       else if (q == 1) *reinterpret_cast<float*>(&a.G2[REC * gg]) = clamp_flagged(c2);
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the slots are rewritten by the next chunk
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_handoff();     // the slots are rewritten by the next chunk
   }
 }
 
@@ -2046,9 +2069,7 @@ __global__ void __launch_bounds__(PREF_BLOCK) k_pre_color_batch(PreColorBatchArg
       sl[0] = means[3 * gl]; sl[1] = means[3 * gl + 1]; sl[2] = means[3 * gl + 2]; sl[3] = __uint_as_float((uint32_t)g);
       wm[si] = seen;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();
     const int q = lane & 3, grp = lane >> 2;
     for (int r0 = 0; r0 < nlive; r0 += 16) {
       const int si = r0 + grp;
@@ -2066,6 +2087,7 @@ __global__ void __launch_bounds__(PREF_BLOCK) k_pre_color_batch(PreColorBatchArg
           const float dx = slv.x - cam[0], dy = slv.y - cam[1], dz = slv.z - cam[2];
           const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
           const float x = dx * inv, y = dy * inv, z = dz * inv;
+          // colour evaluation -- contraction-sensitive: keep identical to the copy in k_pre_color
           float b[16], gx[16], gy[16], gz[16];
 #pragma unroll
           for (int k = 0; k < 16; ++k) b[k] = 0.f;
@@ -2106,9 +2128,7 @@ __global__ void __launch_bounds__(PREF_BLOCK) k_pre_color_batch(PreColorBatchArg
         }
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the slots are rewritten by the next chunk
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();     // the slots are rewritten by the next chunk
   }
 }
 
@@ -2119,6 +2139,76 @@ __global__ void __launch_bounds__(PREF_BLOCK) k_pre_color_batch(PreColorBatchArg
 // view-direction term of dL/dmean from the nine d rgb / d dir values K1 left behind: the SH coefficients are not read.
 constexpr int ROW_CHUNK = 128;     // partial rows staged per round (6 KB per wave)
 constexpr int HAND_W = 7;          // hand-over: unit direction (3) + clamped dL/drgb (3), odd stride
+
+// What a Gaussian's partial rows of one view add up to: the first and second moments in double, dL/dopacity, dL/drgb and,
+// under AUX, dL/d(view depth) in float32.
+struct RowSums {
+  double mx = 0.0, my = 0.0, mxx = 0.0, mxy = 0.0, myy = 0.0;
+  float dop = 0.f, dr = 0.f, dg = 0.f, db = 0.f;
+  float dzv = 0.f;                                                 // AUX: dL/d(view depth)
+};
+
+// Sum the tagged partial rows [o0, o1) of this lane's Gaussian into s.  The rows of the wave's nw Gaussians gw0 .. are one
+// contiguous span, staged through the wave's LDS area wrow in rounds of ROW_CHUNK rows; the whole wave must call.
+// (the second moments are summed in double: what they feed -- dL/dconic -> dL/dcov2D -- cancels to first order for an
+// elongated splat, see project_splat_bwd, and amplifies the rounding of a float32 running sum over hundreds of rows;
+// conic . (mx, my) cancels the same way)
+template <bool GEOM, bool AUX>
+__device__ __forceinline__ void sum_partial_rows(const float4* part, float4* wrow, const uint32_t* offg,
+                                                 int gw0, int nw, uint32_t nsub, uint32_t o0, uint32_t o1, uint32_t tag_lo,
+                                                 uint32_t tag_hi, int lane, RowSums& s) {
+  const uint32_t S = offg[gw0] * nsub, E = offg[gw0 + nw] * nsub;
+  const bool big = (o1 - o0) > (uint32_t)ROW_CHUNK;
+  for (uint32_t c0 = S; c0 < E; c0 += (uint32_t)ROW_CHUNK) {
+    const uint32_t rows = min((uint32_t)ROW_CHUNK, E - c0);
+    const float4* src = part + (size_t)c0 * PART_F4;
+    for (uint32_t i = lane; i < rows * PART_F4; i += 64) wrow[i] = src[i];
+    wave_lds_handoff();
+    if (!big) {
+      const uint32_t lo = max(o0, c0), hi = min(o1, c0 + rows);
+      for (uint32_t e = lo; e < hi; ++e) {
+        const float4* r = &wrow[(e - c0) * PART_F4];
+        const float4 p0 = r[0], p1 = r[1], p2 = r[2];
+        if (!row_tagged(p2, tag_lo, tag_hi)) continue;
+        if (GEOM) { s.mx += (double)p0.x; s.my += (double)p0.y; s.mxx += (double)p0.z; s.mxy += (double)p0.w; s.myy += (double)p1.x; s.dop += p1.y; }
+        s.dr += p1.z; s.dg += p1.w; s.db += p2.x;
+        if constexpr (AUX) s.dzv += p2.w;
+      }
+    }
+    wave_lds_handoff();
+  }
+  uint64_t bm = __ballot(big);
+  while (bm) {                                         // a Gaussian with more rows than a chunk: the whole wave sums it
+    const int L = __ffsll((unsigned long long)bm) - 1;
+    bm &= bm - 1;
+    const uint32_t b0 = __shfl(o0, L, 64), b1 = __shfl(o1, L, 64);
+    float t[4] = {0.f, 0.f, 0.f, 0.f};                   // dop, dr, dg, db
+    float tz = 0.f;
+    double t2[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t e = b0 + lane; e < b1; e += 64) {
+      const float4 p0 = part[(size_t)e * PART_F4], p1 = part[(size_t)e * PART_F4 + 1], p2 = part[(size_t)e * PART_F4 + 2];
+      if (!row_tagged(p2, tag_lo, tag_hi)) continue;
+      if (GEOM) { t2[3] += (double)p0.x; t2[4] += (double)p0.y; t2[0] += (double)p0.z; t2[1] += (double)p0.w; t2[2] += (double)p1.x; t[0] += p1.y; }
+      t[1] += p1.z; t[2] += p1.w; t[3] += p2.x;
+      if constexpr (AUX) tz += p2.w;
+    }
+    if constexpr (AUX) { tz = __shfl(wave_sum_to_hi(tz), 63, 64); if (lane == L) s.dzv = tz; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = __shfl(wave_sum_to_hi(t[i]), 63, 64);
+    if (GEOM) {
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+#pragma unroll
+        for (int sft = 32; sft > 0; sft >>= 1) t2[i] += __shfl_xor(t2[i], sft, 64);
+      }
+    }
+    if (lane == L) { s.mx = t2[3]; s.my = t2[4]; s.mxx = t2[0]; s.mxy = t2[1]; s.myy = t2[2]; s.dop = t[0]; s.dr = t[1]; s.dg = t[2]; s.db = t[3]; }
+  }
+}
+
+// One gradient float: added to the caller's bucket or stored.
+template <bool ACC>
+__device__ __forceinline__ void put_grad(float* p, float v) { if (ACC) *p += v; else *p = v; }
 
 // ACC: the outputs are added to instead of overwritten (PreBwdArgs::accumulate) -- a template parameter so that the
 // overwriting kernel contains no loads of its outputs at all.
@@ -2157,7 +2247,6 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
   uint32_t o0 = 0, o1 = 0;
   if (g < a.P) { o0 = a.offg[g] * a.nsub; o1 = a.offg[g + 1] * a.nsub; }
   constexpr bool acc = ACC;
-  auto put = [](float* p, float v) { if (ACC) *p += v; else *p = v; };
   // the record and the position of a Gaussian with rows are requested now, ahead of the row summation that does not
   // depend on them (the kernel is a chain of dependent memory phases per wave: every phase started early is time won)
   float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = e0, e2 = e0;
@@ -2167,64 +2256,8 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
     p[0] = a.means[3 * g]; p[1] = a.means[3 * g + 1]; p[2] = a.means[3 * g + 2];
   }
   // ---- sum this Gaussian's partial rows (the wave's rows are one contiguous span) ------------------------------------
-  // (the second moments are summed in double: what they feed -- dL/dconic -> dL/dcov2D -- cancels to first order for an
-  // elongated splat, see project_splat_bwd, and amplifies the rounding of a float32 running sum over hundreds of rows)
-  float dop = 0.f, dr = 0.f, dg = 0.f, db = 0.f;
-  float dzv = 0.f;                                                 // AUX: dL/d(view depth)
-  double mx = 0.0, my = 0.0, mxx = 0.0, mxy = 0.0, myy = 0.0;      // (conic . (mx, my) cancels the same way)
-  {
-    const uint32_t S = a.offg[gw0] * a.nsub, E = a.offg[gw0 + nw] * a.nsub;
-    const bool big = (o1 - o0) > (uint32_t)ROW_CHUNK;
-    for (uint32_t c0 = S; c0 < E; c0 += (uint32_t)ROW_CHUNK) {
-      const uint32_t rows = min((uint32_t)ROW_CHUNK, E - c0);
-      const float4* src = a.part + (size_t)c0 * PART_F4;
-      for (uint32_t i = lane; i < rows * PART_F4; i += 64) wrow[i] = src[i];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (!big) {
-        const uint32_t lo = max(o0, c0), hi = min(o1, c0 + rows);
-        for (uint32_t e = lo; e < hi; ++e) {
-          const float4* r = &wrow[(e - c0) * PART_F4];
-          const float4 p0 = r[0], p1 = r[1], p2 = r[2];
-          if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
-          if (GEOM) { mx += (double)p0.x; my += (double)p0.y; mxx += (double)p0.z; mxy += (double)p0.w; myy += (double)p1.x; dop += p1.y; }
-          dr += p1.z; dg += p1.w; db += p2.x;
-          if constexpr (AUX) dzv += p2.w;
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    uint64_t bm = __ballot(big);
-    while (bm) {                                         // a Gaussian with more rows than a chunk: the whole wave sums it
-      const int L = __ffsll((unsigned long long)bm) - 1;
-      bm &= bm - 1;
-      const uint32_t b0 = __shfl(o0, L, 64), b1 = __shfl(o1, L, 64);
-      float t[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      float tz = 0.f;
-      double t2[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-      for (uint32_t e = b0 + lane; e < b1; e += 64) {
-        const float4 p0 = a.part[(size_t)e * PART_F4], p1 = a.part[(size_t)e * PART_F4 + 1], p2 = a.part[(size_t)e * PART_F4 + 2];
-        if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
-        if (GEOM) { t2[3] += (double)p0.x; t2[4] += (double)p0.y; t2[0] += (double)p0.z; t2[1] += (double)p0.w; t2[2] += (double)p1.x; t[5] += p1.y; }
-        t[6] += p1.z; t[7] += p1.w; t[8] += p2.x;
-        if constexpr (AUX) tz += p2.w;
-      }
-      if constexpr (AUX) { tz = __shfl(wave_sum_to_hi(tz), 63, 64); if (lane == L) dzv = tz; }
-#pragma unroll
-      for (int i = 0; i < 9; ++i) t[i] = __shfl(wave_sum_to_hi(t[i]), 63, 64);
-      if (GEOM) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-#pragma unroll
-          for (int sft = 32; sft > 0; sft >>= 1) t2[i] += __shfl_xor(t2[i], sft, 64);
-        }
-      }
-      if (lane == L) { mx = t2[3]; my = t2[4]; mxx = t2[0]; mxy = t2[1]; myy = t2[2]; dop = t[5]; dr = t[6]; dg = t[7]; db = t[8]; }
-    }
-  }
+  RowSums rs;
+  sum_partial_rows<GEOM, AUX>(a.part, wrow, a.offg, gw0, nw, a.nsub, o0, o1, a.tag_lo, a.tag_hi, lane, rs);
   // ---- phase A: chain rule per Gaussian ------------------------------------------------------------------------------
   float hdir[3] = {0.f, 0.f, 0.f}, hrgb[3] = {0.f, 0.f, 0.f};
   // squares of what this lane writes, per attribute tensor (PreBwdArgs::sumsq): the L2 step's global norms come out of
@@ -2234,6 +2267,8 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
   // (a wave without Gaussians returns above without writing its slot of the partial sums: with one wave per workgroup
   // there is no such wave inside the grid -- k_sumsq_reduce reads ss_blocks * PRE_WAVES slots)
   static_assert(PRE_WAVES == 1, "more waves per workgroup: empty waves must zero their sum-of-squares slot");
+  // the wave's sums of squares -> its slot of the partials; a copy of the one in k_pre_bwd_batch: as a shared function taking ssq it
+  // changed how the compiler packs and fuses the float32 chain of the whole kernel (dL/dmean lost bit-equality)
   auto flush_sumsq = [&]() {
     if (!want_ss) return;
 #pragma unroll
@@ -2251,30 +2286,11 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
       if (a.dmeans2D) { a.dmeans2D[3 * g] = 0.f; a.dmeans2D[3 * g + 1] = 0.f; a.dmeans2D[3 * g + 2] = 0.f; }
       if (a.dsh_objs) for (int i = 0; i < NUM_OBJ; ++i) a.dsh_objs[(size_t)g * NUM_OBJ + i] = 0.f;
     } else if (o1 == o0) {   // culled: zero gradients (dL/dSH: phase B writes the zeros)
-      if (a.dmeans3D) { a.dmeans3D[3 * g] = 0.f; a.dmeans3D[3 * g + 1] = 0.f; a.dmeans3D[3 * g + 2] = 0.f; }
-      if (a.dmeans2D) { a.dmeans2D[3 * g] = 0.f; a.dmeans2D[3 * g + 1] = 0.f; a.dmeans2D[3 * g + 2] = 0.f; }
-      if (a.dsh_objs) for (int i = 0; i < NUM_OBJ; ++i) a.dsh_objs[(size_t)g * NUM_OBJ + i] = 0.f;
-      if (a.dcolors) { a.dcolors[3 * g] = 0.f; a.dcolors[3 * g + 1] = 0.f; a.dcolors[3 * g + 2] = 0.f; }
-      if (a.dopac) a.dopac[g] = 0.f;
-      if (a.dscales) { a.dscales[3 * g] = 0.f; a.dscales[3 * g + 1] = 0.f; a.dscales[3 * g + 2] = 0.f; }
-      if (a.drots) { a.drots[4 * g] = 0.f; a.drots[4 * g + 1] = 0.f; a.drots[4 * g + 2] = 0.f; a.drots[4 * g + 3] = 0.f; }
-      if (a.dcov3d) for (int i = 0; i < 6; ++i) a.dcov3d[6 * g + i] = 0.f;
+      zero_unseen_grads(a, g);
     } else {
       if (a.dsh_objs) {
         float acc_o[NUM_OBJ];
-#pragma unroll
-        for (int c = 0; c < NUM_OBJ; ++c) acc_o[c] = 0.f;
-        if (a.part_obj) {
-          for (uint32_t e = o0; e < o1; ++e) {
-            const float4 tg = a.part[(size_t)e * PART_F4 + 2];
-            if (__float_as_uint(tg.y) != a.tag_lo || __float_as_uint(tg.z) != a.tag_hi) continue;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const float4 v4 = a.part_obj[(size_t)e * 4 + q];
-              acc_o[4 * q] += v4.x; acc_o[4 * q + 1] += v4.y; acc_o[4 * q + 2] += v4.z; acc_o[4 * q + 3] += v4.w;
-            }
-          }
-        }
+        sum_object_rows(a.part, a.part_obj, o0, o1, a.tag_lo, a.tag_hi, acc_o);
 #pragma unroll
         for (int c = 0; c < NUM_OBJ; ++c) a.dsh_objs[(size_t)g * NUM_OBJ + c] = acc_o[c];      // per view: never added to
       }
@@ -2285,27 +2301,30 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
       } else {
         load_view(v, a.va);
       }
+      // screen terms -- contraction-sensitive: keep identical to the copy in k_pre_bwd_batch
       const float A = e0.z, B = e0.w, C = e1.x;
       // dL/d(pixel centre) = -(A mx + B my, B mx + C my); screen-space means are reported in NDC units
-      const float dndcx = (float)(-((double)A * mx + (double)B * my) * (0.5 * (double)v.W));
-      const float dndcy = (float)(-((double)B * mx + (double)C * my) * (0.5 * (double)v.H));
-      const double dA = -0.5 * mxx, dB = -mxy, dC = -0.5 * myy;
+      const float dndcx = (float)(-((double)A * rs.mx + (double)B * rs.my) * (0.5 * (double)v.W));
+      const float dndcy = (float)(-((double)B * rs.mx + (double)C * rs.my) * (0.5 * (double)v.H));
+      const double dA = -0.5 * rs.mxx, dB = -rs.mxy, dC = -0.5 * rs.myy;
       if (GEOM && a.dmeans2D) { a.dmeans2D[3 * g] = dndcx; a.dmeans2D[3 * g + 1] = dndcy; a.dmeans2D[3 * g + 2] = 0.f; }   // per view
+      // gradient stores with their squares (here and below) -- contraction-sensitive: keep identical to the copy in k_pre_bwd_batch
       if (GEOM && a.dopac) {
-        const float dov = RAW ? dop * e1.y * (1.f - e1.y) : dop;                       // e1.y = sigmoid(raw opacity)
-        put(&a.dopac[g], dov);
+        const float dov = RAW ? rs.dop * e1.y * (1.f - e1.y) : rs.dop;                       // e1.y = sigmoid(raw opacity)
+        put_grad<ACC>(&a.dopac[g], dov);
         ssq[SUMSQ_OPACITY] = dov * dov;
       }
       float dp[3] = {0.f, 0.f, 0.f};
-      if (a.dcolors) { put(&a.dcolors[3 * g], dr); put(&a.dcolors[3 * g + 1], dg); put(&a.dcolors[3 * g + 2], db); }
+      if (a.dcolors) { put_grad<ACC>(&a.dcolors[3 * g], rs.dr); put_grad<ACC>(&a.dcolors[3 * g + 1], rs.dg); put_grad<ACC>(&a.dcolors[3 * g + 2], rs.db); }
       if (a.sh) {
         const uint32_t cl = clamp_bits_of(e1.z, e1.w, e2.x);
-        hrgb[0] = (cl & 1u) ? 0.f : dr; hrgb[1] = (cl & 2u) ? 0.f : dg; hrgb[2] = (cl & 4u) ? 0.f : db;
+        hrgb[0] = (cl & 1u) ? 0.f : rs.dr; hrgb[1] = (cl & 2u) ? 0.f : rs.dg; hrgb[2] = (cl & 4u) ? 0.f : rs.db;
         const float vx = p[0] - v.cam[0], vy = p[1] - v.cam[1], vz = p[2] - v.cam[2];
         const float inv = 1.0f / sqrtf(vx * vx + vy * vy + vz * vz);
         hdir[0] = vx * inv; hdir[1] = vy * inv; hdir[2] = vz * inv;
         if (GEOM) {
           // view-direction path of dL/dmean: dL/dd = D^T dL/drgb, then d = v/|v|: dL/dv = (dL/dd - d (d . dL/dd)) / |v|
+          // -- contraction-sensitive: keep identical to the copy in k_pre_bwd_batch
           const float* Dg = a.D + (size_t)g * 9;
           const float ddx = Dg[0] * hrgb[0] + Dg[3] * hrgb[1] + Dg[6] * hrgb[2];
           const float ddy = Dg[1] * hrgb[0] + Dg[4] * hrgb[1] + Dg[7] * hrgb[2];
@@ -2317,7 +2336,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
         }
       }
       if constexpr (AUX) {   // dL/dz through z = [p, 1] . V[:, 2]
-        dp[0] = fmaf(dzv, v.V[2], dp[0]); dp[1] = fmaf(dzv, v.V[6], dp[1]); dp[2] = fmaf(dzv, v.V[10], dp[2]);
+        dp[0] = fmaf(rs.dzv, v.V[2], dp[0]); dp[1] = fmaf(rs.dzv, v.V[6], dp[1]); dp[2] = fmaf(rs.dzv, v.V[10], dp[2]);
       }
       if (GEOM) {
         float c6[6];
@@ -2327,13 +2346,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
 #pragma unroll
           for (int i = 0; i < 6; ++i) c6[i] = a.cov3d[6 * g + i];
         } else {
-          sc[0] = a.scales[3 * g]; sc[1] = a.scales[3 * g + 1]; sc[2] = a.scales[3 * g + 2];
-          const float4 q4 = reinterpret_cast<const float4*>(a.rots)[g];
-          q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-          if (RAW) {
-            sc[0] = expf(sc[0]); sc[1] = expf(sc[1]); sc[2] = expf(sc[2]);
-            act_normalize4(q, q, inv_qn);
-          }
+          load_scale_rot<RAW>(a.scales, a.rots, g, sc, q, inv_qn);
           cov3d_from_scale_rot(sc, a.va.mod, q, c6);
         }
         float dc6[6];
@@ -2343,8 +2356,8 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
         if (NDL && needle) {
           // a needle: the whole chain rule in double on the float32 inputs (like its forward), activations included
           double dpd[3] = {(double)dp[0], (double)dp[1], (double)dp[2]}, dsd[3], dqd[4], dS6[6];
-          const double dnx = -((double)A * mx + (double)B * my) * (0.5 * (double)v.W);
-          const double dny = -((double)B * mx + (double)C * my) * (0.5 * (double)v.H);
+          const double dnx = -((double)A * rs.mx + (double)B * rs.my) * (0.5 * (double)v.W);
+          const double dny = -((double)B * rs.mx + (double)C * rs.my) * (0.5 * (double)v.H);
           needle_bwd_d(v, p, sc, a.va.mod, q, a.cov3d ? c6 : nullptr, dA, dB, dC, dnx, dny, dpd, dsd, dqd, dS6);
           dp[0] = (float)dpd[0]; dp[1] = (float)dpd[1]; dp[2] = (float)dpd[2];
 #pragma unroll
@@ -2361,11 +2374,11 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
           project_splat_bwd(v, p, c6, dA, dB, dC, dndcx, dndcy, dp, dc6);
         }
         if (a.dmeans3D) {
-          put(&a.dmeans3D[3 * g], dp[0]); put(&a.dmeans3D[3 * g + 1], dp[1]); put(&a.dmeans3D[3 * g + 2], dp[2]);
+          put_grad<ACC>(&a.dmeans3D[3 * g], dp[0]); put_grad<ACC>(&a.dmeans3D[3 * g + 1], dp[1]); put_grad<ACC>(&a.dmeans3D[3 * g + 2], dp[2]);
           ssq[SUMSQ_XYZ] = dp[0] * dp[0] + dp[1] * dp[1] + dp[2] * dp[2];
         }
         if (a.cov3d) {
-          if (a.dcov3d) for (int i = 0; i < 6; ++i) put(&a.dcov3d[6 * g + i], dc6[i]);
+          if (a.dcov3d) for (int i = 0; i < 6; ++i) put_grad<ACC>(&a.dcov3d[6 * g + i], dc6[i]);
         } else if (a.dscales || a.drots) {
           if (!(NDL && needle)) {
             cov3d_bwd(sc, a.va.mod, q, dc6, ds, dq);
@@ -2375,11 +2388,11 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
             }
           }
           if (a.dscales) {
-            put(&a.dscales[3 * g], ds[0]); put(&a.dscales[3 * g + 1], ds[1]); put(&a.dscales[3 * g + 2], ds[2]);
+            put_grad<ACC>(&a.dscales[3 * g], ds[0]); put_grad<ACC>(&a.dscales[3 * g + 1], ds[1]); put_grad<ACC>(&a.dscales[3 * g + 2], ds[2]);
             ssq[SUMSQ_SCALING] = ds[0] * ds[0] + ds[1] * ds[1] + ds[2] * ds[2];
           }
           if (a.drots) {
-            put(&a.drots[4 * g], dq[0]); put(&a.drots[4 * g + 1], dq[1]); put(&a.drots[4 * g + 2], dq[2]); put(&a.drots[4 * g + 3], dq[3]);
+            put_grad<ACC>(&a.drots[4 * g], dq[0]); put_grad<ACC>(&a.drots[4 * g + 1], dq[1]); put_grad<ACC>(&a.drots[4 * g + 2], dq[2]); put_grad<ACC>(&a.drots[4 * g + 3], dq[3]);
             ssq[SUMSQ_ROTATION] = dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3];
           }
         }
@@ -2393,9 +2406,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
     h[0] = hdir[0]; h[1] = hdir[1]; h[2] = hdir[2]; h[3] = hrgb[0]; h[4] = hrgb[1]; h[5] = hrgb[2];
     h[6] = (o1 != o0) ? 1.f : 0.f;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_handoff();
   const int q = lane & 3, grp = lane >> 2;
   const int deg = a.va.deg;
 #pragma unroll 1
@@ -2414,6 +2425,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
         const float bj = pick4(q, b[j], b[4 + j], b[8 + j], b[12 + j]);
         out[3 * j] = bj * g0; out[3 * j + 1] = bj * g1; out[3 * j + 2] = bj * g2;
       }
+      // dL/dSH tail -- contraction-sensitive: keep identical to the copy in k_pre_bwd_batch
       if (acc) {
         if (h[6] != 0.f) {
           float cur[12];
@@ -2441,8 +2453,8 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_pre_bwd(PreBwdArgs a) {
 
 // ------------------------------------------------------------------------------------------------
 // dL/d object features of a BATCH of views (gsr_backward_raw_batch_obj_*): one lane per Gaussian walks the views in order
-// and forms view v's sum over its tagged object rows exactly as k_pre_bwd does for one view (same rows, same order, same
-// tag test).  vstride == 0: dobj [P,16] = ((s_0 + s_1) + s_2) + ... -- the float32 adds autograd makes when B single-view
+// and forms view v's sum over its tagged object rows with the function k_pre_bwd uses for one view (sum_object_rows).
+// vstride == 0: dobj [P,16] = ((s_0 + s_1) + s_2) + ... -- the float32 adds autograd makes when B single-view
 // backwards accumulate into .grad; vstride != 0: view v's s_v at dobj + v * vstride.  A Gaussian no view sees gets zeros;
 // dobj is always overwritten.  Kept out of k_pre_bwd_batch: 16 more live sums there would cost that kernel its occupancy.
 // ------------------------------------------------------------------------------------------------
@@ -2465,20 +2477,9 @@ __global__ void __launch_bounds__(256) k_obj_grad_batch(ObjGradBatchArgs a) {
   for (int v = 0; v < a.B; ++v) {
     const size_t i = (size_t)v * (size_t)a.Ppad + (size_t)g;
     float s[NUM_OBJ];
-#pragma unroll
-    for (int c = 0; c < NUM_OBJ; ++c) s[c] = 0.f;
-    if (a.part_obj) {
-      const uint32_t o0 = a.offg[i] * a.nsub, o1 = a.offg[i + 1] * a.nsub;
-      for (uint32_t e = o0; e < o1; ++e) {
-        const float4 tg = a.part[(size_t)e * PART_F4 + 2];
-        if (__float_as_uint(tg.y) != a.tag_lo || __float_as_uint(tg.z) != a.tag_hi) continue;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 v4 = a.part_obj[(size_t)e * 4 + q];
-          s[4 * q] += v4.x; s[4 * q + 1] += v4.y; s[4 * q + 2] += v4.z; s[4 * q + 3] += v4.w;
-        }
-      }
-    }
+    uint32_t o0 = 0, o1 = 0;
+    if (a.part_obj) { o0 = a.offg[i] * a.nsub; o1 = a.offg[i + 1] * a.nsub; }
+    sum_object_rows(a.part, a.part_obj, o0, o1, a.tag_lo, a.tag_hi, s);
     if (a.vstride != 0) {
       float* d = a.dobj + (size_t)v * (size_t)a.vstride + (size_t)g * NUM_OBJ;
 #pragma unroll
@@ -2564,15 +2565,9 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
   // (the activated scale and rotation themselves are formed again behind the view loop, where dL/dSigma3D is pushed through
   // them: eight registers less across the loop)
   float c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  auto activated = [&](float sc[3], float q[4], float& inv_qn) {
-    sc[0] = expf(a.scales[3 * g]); sc[1] = expf(a.scales[3 * g + 1]); sc[2] = expf(a.scales[3 * g + 2]);
-    const float4 q4 = reinterpret_cast<const float4*>(a.rots)[g];
-    q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-    act_normalize4(q, q, inv_qn);
-  };
   if (GEOM && mine) {
     float sc[3], q[4], inv_qn;
-    activated(sc, q, inv_qn);
+    load_scale_rot<true>(a.scales, a.rots, g, sc, q, inv_qn);
     cov3d_from_scale_rot(sc, a.mod, q, c6);
   }
   float dp[3] = {0.f, 0.f, 0.f}, dc6s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dops = 0.f, opv = 0.f;
@@ -2587,82 +2582,31 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
     float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = e0, e2 = e0;
     if (has) { e0 = a.G0[REC * (o + g)]; e1 = a.G1[REC * (o + g)]; e2 = a.G2[REC * (o + g)]; }
     // ---- this view's partial rows of the wave's Gaussians (one contiguous span), as in k_pre_bwd -----------------------
-    float dop = 0.f, dr = 0.f, dg = 0.f, db = 0.f;
-    float dzv = 0.f;
-    double mx = 0.0, my = 0.0, mxx = 0.0, mxy = 0.0, myy = 0.0;
-    {
-      const uint32_t S = offg[gw0] * a.nsub, E = offg[gw0 + nw] * a.nsub;
-      const bool big = (o1 - o0) > (uint32_t)ROW_CHUNK;
-      for (uint32_t c0 = S; c0 < E; c0 += (uint32_t)ROW_CHUNK) {
-        const uint32_t rows = min((uint32_t)ROW_CHUNK, E - c0);
-        const float4* src = a.part + (size_t)c0 * PART_F4;
-        for (uint32_t i = lane; i < rows * PART_F4; i += 64) srow[i] = src[i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (!big) {
-          const uint32_t lo = max(o0, c0), hi = min(o1, c0 + rows);
-          for (uint32_t e = lo; e < hi; ++e) {
-            const float4* r = &srow[(e - c0) * PART_F4];
-            const float4 p0 = r[0], p1 = r[1], p2 = r[2];
-            if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
-            if (GEOM) { mx += (double)p0.x; my += (double)p0.y; mxx += (double)p0.z; mxy += (double)p0.w; myy += (double)p1.x; dop += p1.y; }
-            dr += p1.z; dg += p1.w; db += p2.x;
-            if constexpr (AUX) dzv += p2.w;
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-      uint64_t bm = __ballot(big);
-      while (bm) {                                         // a Gaussian with more rows than a chunk: the whole wave sums it
-        const int L = __ffsll((unsigned long long)bm) - 1;
-        bm &= bm - 1;
-        const uint32_t b0 = __shfl(o0, L, 64), b1 = __shfl(o1, L, 64);
-        float t[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        double t2[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        for (uint32_t e = b0 + lane; e < b1; e += 64) {
-          const float4 p0 = a.part[(size_t)e * PART_F4], p1 = a.part[(size_t)e * PART_F4 + 1], p2 = a.part[(size_t)e * PART_F4 + 2];
-          if (__float_as_uint(p2.y) != a.tag_lo || __float_as_uint(p2.z) != a.tag_hi) continue;
-          if (GEOM) { t2[3] += (double)p0.x; t2[4] += (double)p0.y; t2[0] += (double)p0.z; t2[1] += (double)p0.w; t2[2] += (double)p1.x; t[5] += p1.y; }
-          t[6] += p1.z; t[7] += p1.w; t[8] += p2.x;
-          if constexpr (AUX) t[0] += p2.w;                           // (t[0..4] are otherwise unused: the second moments are in t2)
-        }
-        if constexpr (AUX) { t[0] = __shfl(wave_sum_to_hi(t[0]), 63, 64); if (lane == L) dzv = t[0]; }
-#pragma unroll
-        for (int i = 5; i < 9; ++i) t[i] = __shfl(wave_sum_to_hi(t[i]), 63, 64);
-        if (GEOM) {
-#pragma unroll
-          for (int i = 0; i < 5; ++i) {
-#pragma unroll
-            for (int sft = 32; sft > 0; sft >>= 1) t2[i] += __shfl_xor(t2[i], sft, 64);
-          }
-        }
-        if (lane == L) { mx = t2[3]; my = t2[4]; mxx = t2[0]; mxy = t2[1]; myy = t2[2]; dop = t[5]; dr = t[6]; dg = t[7]; db = t[8]; }
-      }
-    }
+    RowSums rs;
+    sum_partial_rows<GEOM, AUX>(a.part, srow, offg, gw0, nw, a.nsub, o0, o1, a.tag_lo, a.tag_hi, lane, rs);
     // ---- chain rule of this view -------------------------------------------------------------------------------------
     float hr[3] = {0.f, 0.f, 0.f};
     if (has) {
       any = true;
       const ViewDev& vd = a.vpack[v];
       const uint32_t cl = clamp_bits_of(e1.z, e1.w, e2.x);
-      hr[0] = (cl & 1u) ? 0.f : dr; hr[1] = (cl & 2u) ? 0.f : dg; hr[2] = (cl & 4u) ? 0.f : db;
+      hr[0] = (cl & 1u) ? 0.f : rs.dr; hr[1] = (cl & 2u) ? 0.f : rs.dg; hr[2] = (cl & 4u) ? 0.f : rs.db;
       if (GEOM) {
         View vw;
         make_view(vw, vd.vm, vd.pm, vd.cam, a.H, a.W, vd.tanfovx, vd.tanfovy, a.mod, a.deg);
+        // screen terms -- contraction-sensitive: keep identical to the copy in k_pre_bwd
         const float A = e0.z, Bc = e0.w, C = e1.x;
-        const float dndcx = (float)(-((double)A * mx + (double)Bc * my) * (0.5 * (double)vw.W));
-        const float dndcy = (float)(-((double)Bc * mx + (double)C * my) * (0.5 * (double)vw.H));
-        const double dA = -0.5 * mxx, dB = -mxy, dC = -0.5 * myy;
+        const float dndcx = (float)(-((double)A * rs.mx + (double)Bc * rs.my) * (0.5 * (double)vw.W));
+        const float dndcy = (float)(-((double)Bc * rs.mx + (double)C * rs.my) * (0.5 * (double)vw.H));
+        const double dA = -0.5 * rs.mxx, dB = -rs.mxy, dC = -0.5 * rs.myy;
         if (a.dmeans2D) {
           float* m2 = a.dmeans2D + 3 * ((size_t)v * (size_t)a.Pscene + (size_t)g);
           m2[0] = dndcx; m2[1] = dndcy; m2[2] = 0.f;
         }
-        dops += dop;
+        dops += rs.dop;
         opv = e1.y;
         // view-direction path of dL/dmean (d colour / d direction left by the colour kernel)
+        // -- contraction-sensitive: keep identical to the copy in k_pre_bwd
         const float vx = p[0] - vw.cam[0], vy = p[1] - vw.cam[1], vz = p[2] - vw.cam[2];
         const float inv = 1.0f / sqrtf(vx * vx + vy * vy + vz * vz);
         const float hx = vx * inv, hy = vy * inv, hz = vz * inv;
@@ -2675,7 +2619,7 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
         dp[1] += (ddy - hy * dot) * inv;
         dp[2] += (ddz - hz * dot) * inv;
         if constexpr (AUX) {   // dL/dz through z = [p, 1] . V[:, 2]
-          dp[0] = fmaf(dzv, vw.V[2], dp[0]); dp[1] = fmaf(dzv, vw.V[6], dp[1]); dp[2] = fmaf(dzv, vw.V[10], dp[2]);
+          dp[0] = fmaf(rs.dzv, vw.V[2], dp[0]); dp[1] = fmaf(rs.dzv, vw.V[6], dp[1]); dp[2] = fmaf(rs.dzv, vw.V[10], dp[2]);
         }
         float dc6[6];
         project_splat_bwd(vw, p, c6, dA, dB, dC, dndcx, dndcy, dp, dc6);
@@ -2717,34 +2661,36 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
   // ---- the sums over the views: scale / rotation / opacity through the activations, then the stores (wave 0) --------------
   float ssq[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool want_ss = !ACC && a.sumsq != nullptr;
-  auto put = [](float* ptr, float val) { if (ACC) *ptr += val; else *ptr = val; };
   if (GEOM && wave == 0 && mine && (any || !ACC)) {
     float ds[3] = {0.f, 0.f, 0.f}, dq[4] = {0.f, 0.f, 0.f, 0.f};
     if (any && (a.dscales || a.drots)) {
       float sc[3], q[4], inv_qn;
-      activated(sc, q, inv_qn);
+      load_scale_rot<true>(a.scales, a.rots, g, sc, q, inv_qn);
       cov3d_bwd(sc, a.mod, q, dc6s, ds, dq);
       ds[0] *= sc[0]; ds[1] *= sc[1]; ds[2] *= sc[2];          // d exp(x) = exp(x)
       act_normalize4_bwd(q, inv_qn, dq, dq);
     }
+    // gradient stores with their squares -- contraction-sensitive: keep identical to the copy in k_pre_bwd
     if (a.dopac) {
       const float dov = dops * opv * (1.f - opv);              // opv = sigmoid(raw opacity)
-      put(&a.dopac[g], dov);
+      put_grad<ACC>(&a.dopac[g], dov);
       ssq[SUMSQ_OPACITY] = dov * dov;
     }
     if (a.dmeans3D) {
-      put(&a.dmeans3D[3 * g], dp[0]); put(&a.dmeans3D[3 * g + 1], dp[1]); put(&a.dmeans3D[3 * g + 2], dp[2]);
+      put_grad<ACC>(&a.dmeans3D[3 * g], dp[0]); put_grad<ACC>(&a.dmeans3D[3 * g + 1], dp[1]); put_grad<ACC>(&a.dmeans3D[3 * g + 2], dp[2]);
       ssq[SUMSQ_XYZ] = dp[0] * dp[0] + dp[1] * dp[1] + dp[2] * dp[2];
     }
     if (a.dscales) {
-      put(&a.dscales[3 * g], ds[0]); put(&a.dscales[3 * g + 1], ds[1]); put(&a.dscales[3 * g + 2], ds[2]);
+      put_grad<ACC>(&a.dscales[3 * g], ds[0]); put_grad<ACC>(&a.dscales[3 * g + 1], ds[1]); put_grad<ACC>(&a.dscales[3 * g + 2], ds[2]);
       ssq[SUMSQ_SCALING] = ds[0] * ds[0] + ds[1] * ds[1] + ds[2] * ds[2];
     }
     if (a.drots) {
-      put(&a.drots[4 * g], dq[0]); put(&a.drots[4 * g + 1], dq[1]); put(&a.drots[4 * g + 2], dq[2]); put(&a.drots[4 * g + 3], dq[3]);
+      put_grad<ACC>(&a.drots[4 * g], dq[0]); put_grad<ACC>(&a.drots[4 * g + 1], dq[1]); put_grad<ACC>(&a.drots[4 * g + 2], dq[2]); put_grad<ACC>(&a.drots[4 * g + 3], dq[3]);
       ssq[SUMSQ_ROTATION] = dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3];
     }
   }
+  // the wave's sums of squares -> its slot of the partials; a copy of the one in k_pre_bwd: as a shared function taking ssq it
+  // changed how the compiler packs and fuses the float32 chain of the whole kernel (dL/dmean lost bit-equality)
   auto flush_sumsq = [&]() {
     if (!want_ss) return;
 #pragma unroll
@@ -2759,9 +2705,7 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
   // ---- dL/dSH = sum over the views of basis(direction of the view) x dL/drgb of the view: four lanes per Gaussian, the
   // groups of 16 Gaussians dealt over the waves (the views' dL/drgb of all 64 are in LDS behind the barrier above) -----------
   if (BATCH_K9_WAVES == 1) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();
   }
   const int qd = lane & 3, grp = lane >> 2;
 #pragma unroll 1
@@ -2794,6 +2738,7 @@ __global__ void __launch_bounds__(64 * BATCH_K9_WAVES, GEOM ? GSR_BATCH_K9_OCC :
           }
         }
       }
+      // dL/dSH tail -- contraction-sensitive: keep identical to the copy in k_pre_bwd
       if (ACC) {
         if (seen) {
           float cur[12];

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gsr_sort.hip.h"   // wave_lds_handoff
 #include "gsr_pgd.h"   // the scalar source (shared with tests/host_math/pgd_host.cpp) and the non-finite / range contract
 
 namespace gsr {
@@ -93,9 +94,7 @@ __device__ __forceinline__ void pgd_step_wave(float* __restrict__ x, const float
     }
   }
   if (!L2) return;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_handoff();
   float f = 1.f;
   if (lane < nr) {
     float ss = 0.f;
@@ -106,9 +105,7 @@ __device__ __forceinline__ void pgd_step_wave(float* __restrict__ x, const float
   // below would return 0 for rows whose owner lane has already left the loop in the last, partial iteration:
   // ds_bpermute yields 0 for an inactive source lane.)
   sf[lane] = f;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_handoff();
   if (vec) {
     const int n4 = n >> 2;
     const float4* o4 = reinterpret_cast<const float4*>(x0 + base);

@@ -23,6 +23,14 @@ namespace gsr {
 
 constexpr int SCAN_THREADS = 256;
 
+// One wave hands LDS data from some of its lanes to others (or frees a staging area for its next round) without a
+// workgroup barrier: what the lanes wrote before is visible to every lane of the wave behind it.
+__device__ __forceinline__ void wave_lds_handoff() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
   const int lane = threadIdx.x & 63;
 #pragma unroll

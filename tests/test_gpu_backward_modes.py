@@ -142,13 +142,55 @@ class _Case:
 
 _CASES = {}
 
+# The (192, 3) case: the ordinary scene with four Gaussians made so large that each has more partial rows in a seeing
+# view than K8+K9 stages per round (ROW_CHUNK = 128), so that the whole wave sums them: a large one among small ones, one
+# in a wave's last lane, one in the next wave's first lane, and a wave with a single large one.
+WIDE_PB = (192, 3)
+WIDE = (5, 63, 64, 130)
+ROW_CHUNK = 128
+
+
+def _wide_scene(P, B):
+    params, cams = _scene(P, B, seed=1000 * B + P)
+    seeing = [v for v in range(B) if v != _blind_view(B)]
+    mid = 0.5 * 5.0 * (len(seeing) - 1)             # between the seeing cameras, in front of them all
+    for k, i in enumerate(WIDE):
+        params["xyz"][i] = torch.tensor([mid, 20.0 + k, 0.0])
+        params["sc"][i] = math.log(10.0 + k)        # sigma = half the distance: the footprint covers the 21 x 12 tiles
+        params["op"][i] = 0.0                       # alpha 0.5: what lies behind still gets a gradient
+    return params, cams
+
+
+def _check_wide(case):
+    """The premise of the case, from the batch context's storage-order scan of tiles touched (export item 9)."""
+    P, B = case.P, case.B
+    holder = case.batch(False)[0]
+    ppad = holder.info(5)
+    offg = torch.zeros(B * ppad + 1, dtype=torch.int32, device=case.dev)
+    assert case.lib.gsr_ctx_export(holder.handle, 9, ctypes.c_void_p(offg.data_ptr()), 4 * offg.numel(), case.stream()) == 0
+    torch.cuda.synchronize()
+    offg = offg.cpu().long() & 0xFFFFFFFF
+    tiles = (offg[1:] - offg[:-1]).view(B, ppad)[:, :P]
+    wide = torch.zeros(P, dtype=torch.bool)
+    wide[list(WIDE)] = True
+    for v in range(B):
+        if v == _blind_view(B):
+            assert not bool(tiles[v].any()), "the blind view sees something"
+        else:
+            assert bool((tiles[v][wide] > ROW_CHUNK).all()), (v, tiles[v][wide])
+            assert bool((tiles[v][~wide] <= ROW_CHUNK).all()), (v, int(tiles[v][~wide].max()))
+
 
 def _case(P, B):
     key = (P, B)
     if key not in _CASES:
         if len(_CASES) >= 2:                        # (the matrix is ordered by case: keep the last two only)
             _CASES.pop(next(iter(_CASES)))
-        _CASES[key] = _Case(P, B, _dev())
+        if key == WIDE_PB:
+            _CASES[key] = _Case(P, B, _dev(), *_wide_scene(P, B))
+            _check_wide(_CASES[key])
+        else:
+            _CASES[key] = _Case(P, B, _dev())
     return _CASES[key]
 
 
@@ -384,7 +426,7 @@ def _check_layout(case):
         assert pat.shape[0] >= 3, f"Gaussians [{a}, {a + third}) all have the same visibility"
 
 
-PB = [(63, 2), (64, 5), (65, 2), (65, 5), (1000, 2), (1000, 5), (1000, 16), (20_001, 2), (20_001, 5), (20_001, 16),
+PB = [(63, 2), (64, 5), (65, 2), (65, 5), WIDE_PB, (1000, 2), (1000, 5), (1000, 16), (20_001, 2), (20_001, 5), (20_001, 16),
       (60_000, 2), (60_000, 5)]
 BIG = 1 << 20                                       # more chunks than ceil(P / 64) for every P here
 MODES = [
