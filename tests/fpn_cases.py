@@ -67,9 +67,11 @@ def _box(w, h, x0=X0, y0=Y0):
     return [x0, y0, x0 + w, y0 + h]
 
 
-# straddling the map's edges (the frame is 500 x 388): near corner, far corner, far edge of one axis
-EDGES = ([-30.5, -20.25, 60.75, 70.5], [430.5, 300.25, 560.0, 420.75], [200.25, 350.5, 330.5, 430.0])
-EDGE_DECL = (FAR, FAR, FAR)
+# straddling the map's edges (the frame is 500 x 388): near corner, far corner, far edge of one axis; then an inverted RoI
+# (x2 < x1: a negative area, level 0 by definition; its samples run backwards at a fixed ratio, its adaptive grid is 0)
+EDGES = ([-30.5, -20.25, 60.75, 70.5], [430.5, 300.25, 560.0, 420.75], [200.25, 350.5, 330.5, 430.0], [200.4, 30.3, 120.2, 90.8])
+EDGE_DECL = (FAR, FAR, FAR, NEG)
+INVERTED = (0, len(TABLE) + 2 + 3)                      # (image, row) of the inverted RoI
 _IMG0 = [_box(w, h) for w, h, _, _ in TABLE] + [[NAN, 10.0, 50.0, 60.0], [10.0, 20.0, INF, 60.0]] + [list(e) for e in EDGES] + \
     [_box(50.0, 50.0), _box(300.0, 300.0), [NAN] * 4]                               # the last three: beyond the count
 _DECL0 = [d for _, _, _, d in TABLE] + [None, None] + list(EDGE_DECL)
@@ -286,6 +288,26 @@ def host_pool(lib, c: Case, n_roi=N_ROI):
     out = dict(pooled=pooled)
     out.update({f"grad{l}": g for l, g in enumerate(grads)})
     return out
+
+
+def edge_inputs():
+    """rcnn_cases.roi_edge_inputs as a one-level pyramid of stride 1: the samples exactly at -1 and at n, and the next
+    positions further out, through the pooler's own kernels -> (rcnn case, spec, (feat, grad_pooled, rois, n_roi), pooled
+    [S,Cf] and grad [Cf,Hf,Wf] written out by hand)."""
+    c, inputs, pooled, gf, _ = RC.roi_edge_inputs()
+    rois = inputs[2]
+    spec = c_spec(c.Cf, c.PH, c.PW, c.ratio, S_=rois.shape[1], Bn=1, sizes=((c.Hf, c.Wf),), strides=(1,), thr=(0.0,))
+    return c, spec, inputs, pooled, gf
+
+
+def host_pool_edges(lib):
+    c, spec, (feat, gp, rois, n_roi), _, _ = edge_inputs()
+    feat, gp, rois = (np.ascontiguousarray(a) for a in (feat, gp, rois))
+    lv = host_assign(lib, rois=rois, n_roi=n_roi, spec=spec)["roi_level"]
+    pooled, grad = np.empty(gp.shape, np.float32), np.zeros(feat.shape, np.float32)
+    assert lib.fh_pool(ctypes.byref(spec), _pp([feat]), _p(rois), _p(lv), _p(pooled)) == 0
+    assert lib.fh_pool_bwd(ctypes.byref(spec), _p(rois), _p(lv), _p(gp), _pp([grad])) == 0
+    return pooled, grad
 
 
 def lists_equal(level_list, level_count, lists) -> bool:

@@ -1,9 +1,9 @@
 // The two-stage detector stage in plain loops over csrc/gsr_rcnn.h, the same scalar source the HIP kernels compile:
 //   rh_sample         what gsr_rcnn_sample computes (integers and gathered boxes: equal to the kernel's)
 //   rh_roi_align      what gsr_roi_align computes, sample by sample
-//   rh_roi_align_bwd  its transpose as a plain scatter in RoI / bin / sample order (a different order of the same sum as
-//                     gsr_roi_align_backward's gather)
-//   rh_loss_f32       what gsr_rcnn_loss computes, sums taken in row order
+//   rh_roi_align_bwd  its transpose in gsr_roi_align_backward's order (a gather over separable weights)
+//   rh_roi_align_bwd_scatter  the same as a plain scatter in RoI / bin / sample order (a different order of the same sum)
+//   rh_loss_f32       what gsr_rcnn_loss computes, every sum in the kernels' order (wave_stats, kernel_order_sum)
 //   rh_loss_f64       the same code in double
 //   rh_post           what gsr_rcnn_postprocess computes: candidates, the NMS walk of csrc/gsr_detect.h, dets and counts
 // Build: g++ -O1 -ffp-contract=off -shared -fPIC -I <csrc> rcnn_host.cpp -o librcnnhost.so
@@ -139,9 +139,127 @@ extern "C" int rh_roi_align(const HostSpec* d, const float* features, const floa
   return roi_walk(d, features, rois, n_roi, stride, pooled, nullptr, nullptr);
 }
 
+extern "C" int rh_roi_align_bwd_scatter(const HostSpec* d, const float* rois, const int32_t* n_roi, int32_t stride, const float* grad_pooled,
+                                        float* grad_features) {
+  return roi_walk(d, nullptr, rois, n_roi, stride, nullptr, grad_pooled, grad_features);
+}
+
+// the weight of map cell `cell` in bin p of one axis, the samples' shares added in sample order (gsr_rcnn.hip.h's axis_weight)
+static float axis_weight(float start, float bin, int grid, int p, int n, int cell) {
+  float w = 0.0f;
+  for (int i = 0; i < grid; ++i) {
+    int lo, hi;
+    float wl, wh;
+    if (!lerp_axis<float>(sample_pos<float>(start, bin, grid, p, i), n, lo, hi, wl, wh)) continue;
+    if (lo == cell) w = w + wl;
+    if (hi == cell) w = w + wh;
+  }
+  return w;
+}
+
+// The backward in k_roi_align_bwd's order: per element the RoIs in ascending order; of a RoI the separable weights wy, wx,
+// the bins with a non-zero weight in (ph, pw) order, (wy * wx) * g added up, the sum divided by the sample count.  The
+// scatter above adds every sample's four shares one by one: with 16 x 16 samples in each of 49 bins its rounding grows to
+// 5 .. 7 x the float32 oracle's, where the kernel's few sums stay at it.  grad_features, zeroed by the caller, is added to.
 extern "C" int rh_roi_align_bwd(const HostSpec* d, const float* rois, const int32_t* n_roi, int32_t stride, const float* grad_pooled,
                                 float* grad_features) {
-  return roi_walk(d, nullptr, rois, n_roi, stride, nullptr, grad_pooled, grad_features);
+  if (!d || d->B < 1 || d->S < 1 || d->Cf < 1 || d->Hf < 1 || d->Wf < 1 || d->PH < 1 || d->PH > MAX_POOL || d->PW < 1 ||
+      d->PW > MAX_POOL || d->sampling_ratio < 0)
+    return 1;
+  const int Hf = d->Hf, Wf = d->Wf, PH = d->PH, PW = d->PW;
+  const size_t HW = (size_t)Hf * (size_t)Wf, bins = (size_t)PH * (size_t)PW;
+  std::vector<float> wy((size_t)Hf * (size_t)PH), wx((size_t)Wf * (size_t)PW);
+  std::vector<char> any_y((size_t)Hf), any_x((size_t)Wf);
+  for (int b = 0; b < d->B; ++b) {
+    const int n = n_roi ? clampi(n_roi[(size_t)b * (size_t)stride], 0, d->S) : d->S;
+    for (int s = 0; s < n; ++s) {
+      const float* r = rois + ((size_t)b * (size_t)d->S + (size_t)s) * 4;
+      if (!roi_finite<float>(r)) continue;
+      float sx, bx, sy, by;
+      int gx, gy;
+      roi_axis<float>(r[0], r[2], d->spatial_scale, PW, d->sampling_ratio, sx, bx, gx);
+      roi_axis<float>(r[1], r[3], d->spatial_scale, PH, d->sampling_ratio, sy, by, gy);
+      if (gx < 1 || gy < 1) continue;
+      for (int y = 0; y < Hf; ++y) {
+        any_y[(size_t)y] = 0;
+        for (int ph = 0; ph < PH; ++ph)
+          if ((wy[(size_t)y * (size_t)PH + (size_t)ph] = axis_weight(sy, by, gy, ph, Hf, y)) != 0.0f) any_y[(size_t)y] = 1;
+      }
+      for (int x = 0; x < Wf; ++x) {
+        any_x[(size_t)x] = 0;
+        for (int pw = 0; pw < PW; ++pw)
+          if ((wx[(size_t)x * (size_t)PW + (size_t)pw] = axis_weight(sx, bx, gx, pw, Wf, x)) != 0.0f) any_x[(size_t)x] = 1;
+      }
+      const float cnt = (float)(gx * gy);
+      for (int c = 0; c < d->Cf; ++c) {
+        const float* g0 = grad_pooled + (((size_t)b * (size_t)d->S + (size_t)s) * (size_t)d->Cf + (size_t)c) * bins;
+        float* gf = grad_features + ((size_t)b * (size_t)d->Cf + (size_t)c) * HW;
+        for (int y = 0; y < Hf; ++y)
+          for (int x = 0; x < Wf; ++x) {
+            if (!any_y[(size_t)y] || !any_x[(size_t)x]) continue;
+            float part = 0.0f;
+            for (int ph = 0; ph < PH; ++ph) {
+              const float vy = wy[(size_t)y * (size_t)PH + (size_t)ph];
+              if (vy == 0.0f) continue;
+              for (int pw = 0; pw < PW; ++pw) {
+                const float vx = wx[(size_t)x * (size_t)PW + (size_t)pw];
+                if (vx == 0.0f) continue;
+                const float w = vy * vx;
+                part = part + w * g0[(size_t)ph * (size_t)PW + (size_t)pw];
+              }
+            }
+            gf[(size_t)y * (size_t)Wf + (size_t)x] = gf[(size_t)y * (size_t)Wf + (size_t)x] + part / cnt;
+          }
+      }
+    }
+  }
+  return 0;
+}
+
+// The statistics of one row of n logits in the order k_rcnn_rows takes them (gsr_block::wave_softmax_stats): 64 lanes stride
+// the row, then an xor butterfly over the lanes.
+template <class T>
+static void wave_stats(const T* x, int n, T& mx, T& sum) {
+  T a[64], o[64];
+  for (int l = 0; l < 64; ++l) {
+    T m = (T)-INFINITY;
+    for (int k = l; k < n; k += 64) m = x[k] > m ? x[k] : m;
+    a[l] = m;
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    for (int l = 0; l < 64; ++l) o[l] = a[l ^ s] > a[l] ? a[l ^ s] : a[l];
+    for (int l = 0; l < 64; ++l) a[l] = o[l];
+  }
+  mx = a[0];
+  for (int l = 0; l < 64; ++l) {
+    T t = (T)0;
+    for (int k = l; k < n; k += 64) t = t + m_exp(x[k] - mx);
+    a[l] = t;
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    for (int l = 0; l < 64; ++l) o[l] = a[l] + a[l ^ s];
+    for (int l = 0; l < 64; ++l) a[l] = o[l];
+  }
+  sum = a[0];
+}
+
+// One column of the loss's sum in the kernels' order: the rows' terms four to a block, added in wave order (k_rcnn_rows);
+// the blocks' partials by 256 lanes, lane t taking the entries t, t + 256, ... in index order, then the stride-halving tree
+// (gsr_block::slab_sum in k_rcnn_final).  Summed serially, the 2048 rows of `s1024` put `loss` at 7.6 x the float32 oracle's
+// error; in this order it stays where the kernels are.
+template <class T>
+static T kernel_order_sum(const std::vector<T>& rows) {
+  const size_t blocks = (rows.size() + 3) / 4;
+  T lane[256];
+  for (int t = 0; t < 256; ++t) lane[t] = (T)0;
+  for (size_t j = 0; j < blocks; ++j) {
+    T s = rows[j * 4];
+    for (size_t w = 1; w < 4; ++w) s = s + (j * 4 + w < rows.size() ? rows[j * 4 + w] : (T)0);
+    lane[j % 256] = lane[j % 256] + s;
+  }
+  for (int s = 128; s > 0; s >>= 1)
+    for (int t = 0; t < s; ++t) lane[t] = lane[t] + lane[t + s];
+  return lane[0];
 }
 
 template <class T>
@@ -155,15 +273,15 @@ static int loss_run(const HostSpec* d, const T* scores, const T* deltas, const T
   const T nr = n > 1 ? (T)n : (T)1;
   const T kc = (T)d->w_cls / nr, kb = (T)d->w_box / nr;
   const T w[4] = {(T)d->bw_x, (T)d->bw_y, (T)d->bw_w, (T)d->bw_h};
-  T sum_ce = (T)0, sum_box = (T)0;
+  std::vector<T> row_ce(rows, (T)0), row_box(rows, (T)0);
   for (size_t i = 0; i < rows; ++i) {
     const int label = labels[i] > C ? -1 : labels[i], row = gt_row[i];
     const bool fg = label >= 0 && label < C && row >= 0 && row < d->M;
     const T* x = scores + i * (size_t)n1;
     if (label >= 0) {
       T mx, sm;
-      softmax_stats<T>(x, n1, mx, sm);
-      sum_ce = sum_ce + -log_softmax<T>(x[label], mx, sm);
+      wave_stats<T>(x, n1, mx, sm);
+      row_ce[i] = -log_softmax<T>(x[label], mx, sm);
       if (grad_scores)
         for (int k = 0; k < n1; ++k) grad_scores[i * (size_t)n1 + (size_t)k] = kc * (softmax_prob<T>(x[k], mx, sm) - (k == label ? (T)1 : (T)0));
     } else if (grad_scores) {
@@ -174,18 +292,18 @@ static int loss_run(const HostSpec* d, const T* scores, const T* deltas, const T
     if (fg) {
       const size_t b = i / (size_t)d->S;
       const int base = (d->flags & CLASS_AGNOSTIC) ? 0 : 4 * label;
-      T tg[4], row_box = (T)0;
+      T tg[4], box = (T)0;
       target_deltas<T>(rois + i * 4, gt_boxes + (b * (size_t)d->M + (size_t)row) * 4, w, tg);
       for (int k = 0; k < 4; ++k) {
         T g;
-        row_box = row_box + smooth_l1<T>(deltas[i * (size_t)D + (size_t)(base + k)] - tg[k], (T)d->beta, g);
+        box = box + smooth_l1<T>(deltas[i * (size_t)D + (size_t)(base + k)] - tg[k], (T)d->beta, g);
         if (grad_deltas) grad_deltas[i * (size_t)D + (size_t)(base + k)] = kb * g;
       }
-      sum_box = sum_box + row_box;
+      row_box[i] = box;
     }
   }
-  loss[0] = sum_ce / nr;
-  loss[1] = sum_box / nr;
+  loss[0] = kernel_order_sum<T>(row_ce) / nr;
+  loss[1] = kernel_order_sum<T>(row_box) / nr;
   loss[2] = (T)d->w_cls * loss[0] + (T)d->w_box * loss[1];
   return 0;
 }

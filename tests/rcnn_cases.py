@@ -14,6 +14,14 @@ Decisions that a rounding could flip are kept away from their thresholds, and th
             within 1e-4 of -1 or of the map's far edge (where the read jumps to 0)                     > 1e-4
   gap_conf  the smallest |score - conf_thr|, and the lead of the best class over the next              > 1e-4
   gap_nms   the smallest |IoU - iou_thr| over pairs of candidates of one class                           > 1e-4
+
+What the margins exclude is tested on inputs made by hand, whose expected outputs are literals here and equal in float32 and
+float64: sample_exact_inputs (an IoU exactly at fg_iou, identical and absent gt rows), roi_edge_inputs (a sample exactly at -1
+and at n, and the next positions further out), post_exact_inputs (a score exactly at conf_thr, a class tie),
+post_poison_inputs (non-finite logits) and loss_guard_inputs (labels above C, gt_row outside 0 .. M - 1).  The cases past the
+ones each stage was merged with sit where the kernels take another path than the scalar source (several items per thread,
+a partial last block, a second turn of a strided loop, tiles that skip RoIs, maps with a side of 1); the CPU tests'
+*_cases_cover_what_they_claim assert each premise from the oracle's outputs.
 """
 import ctypes
 import math
@@ -66,6 +74,7 @@ class SampleCase(NamedTuple):
     far: bool = False             # no proposal reaches fg_iou
     seed: int = 7
     data_seed: int = 0
+    B: int = 2
 
 
 NC = 5
@@ -83,6 +92,10 @@ SAMPLE_CASES = (
     SampleCase("no-append", 70, 3, 32, 8, append_gt=False),
     SampleCase("gt-only-fg", 40, 1, 16, 4, far=True),
     SampleCase("gt-only-fg-no-append", 40, 1, 16, 4, append_gt=False, far=True),
+    SampleCase("n1024", 1022, 2, 512, 128),                              # N = 1024 exactly: per = 1, every lane holds a candidate
+    SampleCase("n3073", 3070, 3, 512, 128),                              # N = 3073: the first N with per = 4; both quotas bite
+    SampleCase("n3072", 3069, 3, 512, 128),                              # N = 3072: per = 3 with every lane's three slots full
+    SampleCase("n2049", 2047, 2, 512, 128),                              # N = 2049: the first N with per = 3; lanes from 683 on empty
 )
 
 
@@ -104,10 +117,10 @@ def grid_boxes(rs, M):
 def sample_inputs(c: SampleCase):
     """-> proposals [B,R,4], gt_boxes [B,M,4], gt_cls [B,M], n_prop [B] or None: read-only numpy arrays."""
     rs = np.random.RandomState(1000 + c.data_seed + c.R * 7 + c.M)
-    gt = np.stack([grid_boxes(rs, c.M) for _ in range(B)])
-    cls = np.array(c.cls, np.int32) if c.cls is not None else rs.randint(0, NC, size=(B, c.M)).astype(np.int32)
-    prop = np.zeros((B, c.R, 4), np.float32)
-    for b in range(B):
+    gt = np.stack([grid_boxes(rs, c.M) for _ in range(c.B)])
+    cls = np.array(c.cls, np.int32) if c.cls is not None else rs.randint(0, NC, size=(c.B, c.M)).astype(np.int32)
+    prop = np.zeros((c.B, c.R, 4), np.float32)
+    for b in range(c.B):
         g64 = torch.tensor(gt[b]).double()
         for i in range(c.R):
             while True:                                                # drawn again while its best IoU is within 1e-3 of fg_iou
@@ -197,20 +210,74 @@ def sample_reference(c: SampleCase, seed: Optional[int] = None):
     return oracle_sample(prop, gt, cls, n_prop, NC, c.S, c.max_pos, c.append_gt, c.seed if seed is None else seed)
 
 
+def sample_exact_inputs():
+    """The two exact decisions of match_candidate, which the margins keep the seeded cases away from -> (a SampleCase, its
+    inputs, the expected idx / labels / gt_row / counts written out by hand).
+
+    Every image has three copies of one gt box G = (10, 10, 20, 20), area 100.  Image 0: row 0 is absent (class -1), rows 1 and
+    2 present (classes 2 and 3); image 1: classes (4, -1, 0).  The proposals:
+      0  (10, 10, 20, 15), area 50 inside G: inter 50, union (50 + 100) - 50 = 100, IoU 50 / 100 = 0.5 in every precision;
+         with fg_iou = 0.5 it is foreground (>=)
+      1  G itself: IoU 1 with all three rows -- the first present one wins (row 1 in image 0, skipping the absent row 0 in
+         front of it; row 0 in image 1)
+      2  (10, 10, 20, 14): IoU 0.4, background
+      3  (100, 100, 110, 110): IoU 0, background
+    and the appended gt rows (candidates 4..6): the absent one is no candidate, the present ones match the first present row.
+    S = 8 and max_pos = 8: everything is taken, in candidate order."""
+    c = SampleCase("exact", 4, 3, 8, 8)
+    G = (10.0, 10.0, 20.0, 20.0)
+    prop = np.array([[(10.0, 10.0, 20.0, 15.0), G, (10.0, 10.0, 20.0, 14.0), (100.0, 100.0, 110.0, 110.0)]] * 2, np.float32)
+    gt = np.array([[G, G, G]] * 2, np.float32)
+    cls = np.array([[-1, 2, 3], [4, -1, 0]], np.int32)
+    want = dict(idx=np.array([[0, 1, 2, 3, 5, 6, -1, -1], [0, 1, 2, 3, 4, 6, -1, -1]], np.int32),
+                labels=np.array([[2, 2, NC, NC, 2, 2, -1, -1], [4, 4, NC, NC, 4, 4, -1, -1]], np.int32),
+                gt_row=np.array([[1, 1, -1, -1, 1, 1, -1, -1], [0, 0, -1, -1, 0, 0, -1, -1]], np.int32),
+                counts=np.array([[6, 4], [6, 4]], np.int32))
+    return c, (prop, gt, cls, None), want
+
+
 # ---- RoIAlign -----------------------------------------------------------------------------------------------------------------
+HF, WF, SCALE = 9, 11, 1.0 / 16.0
+
+
 class RoiCase(NamedTuple):
     Cf: int
     PH: int
     PW: int
     ratio: int
+    Hf: int = HF
+    Wf: int = WF
+    scale: float = SCALE
+    table: str = "base"           # base: ROIS / N_ROI below; wide, wide-zero, gen, prop: roi_table()
+    name: Optional[str] = None
+    S: int = 8                    # rows per image of a generated table
+    seed: int = 0                 # of a generated table
 
     @property
     def id(self):
-        return f"c{self.Cf}-{self.PH}x{self.PW}-r{self.ratio}"
+        return self.name or f"c{self.Cf}-{self.PH}x{self.PW}-r{self.ratio}"
 
 
-HF, WF, SCALE = 9, 11, 1.0 / 16.0
-ROI_CASES = tuple(RoiCase(cf, ph, pw, r) for cf in (3, 70) for ph, pw in ((2, 2), (7, 7), (14, 14), (3, 5)) for r in (0, 2))
+WIDE = dict(Hf=9, Wf=27)          # 2 x 4 tiles of the backward: tiles_x != tiles_y
+ROI_CASES = tuple(RoiCase(cf, ph, pw, r) for cf in (3, 70) for ph, pw in ((2, 2), (7, 7), (14, 14), (3, 5)) for r in (0, 2)) + \
+    tuple(RoiCase(cf, 7, 7, r, table="wide", name=f"wide-c{cf}-r{r}", **WIDE) for cf in (1, 32, 33) for r in (0, 1, 16)) + (
+    RoiCase(3, 7, 7, 2, table="wide", name="wide-c3-r2", **WIDE),            # the inverted rows' samples run backwards
+    RoiCase(33, 7, 7, 0, table="wide-zero", name="wide-zero-c33-r0", **WIDE),  # image 1 has count 0
+    RoiCase(3, 7, 7, 2, table="wide-zero", name="wide-zero-c3-r2", **WIDE),
+    RoiCase(3, 3, 5, 0, Hf=1, Wf=11, table="gen", name="h1-r0"),
+    RoiCase(3, 3, 5, 2, Hf=1, Wf=11, table="gen", name="h1-r2"),
+    RoiCase(3, 3, 5, 0, Hf=9, Wf=1, table="gen", name="w1-r0"),
+    RoiCase(3, 3, 5, 2, Hf=9, Wf=1, table="gen", name="w1-r2"),
+    RoiCase(3, 2, 2, 0, Hf=1, Wf=1, table="gen", name="one-r0"),
+    RoiCase(3, 2, 2, 2, Hf=1, Wf=1, table="gen", name="one-r2"),
+    RoiCase(3, 7, 7, 0, Hf=8, Wf=16, table="gen", name="mult8-r0"),          # both sides exact multiples of the tile
+    RoiCase(3, 7, 7, 2, Hf=8, Wf=16, table="gen", name="mult8-r2"),
+    RoiCase(3, 7, 7, 0, Hf=16, Wf=24, scale=1.0, table="gen", name="scale-1"),
+    RoiCase(3, 7, 7, 0, Hf=16, Wf=24, scale=0.25, table="gen", name="scale-quarter"),
+    RoiCase(3, 14, 1, 0, table="gen", name="14x1-r0"),
+    RoiCase(3, 1, 14, 2, table="gen", name="1x14-r2"),
+    RoiCase(3, 2, 2, 0, table="prop", name="s1024", S=1024),                 # counts (1000, 0)
+)
 NAN = float("nan")
 ROIS = np.array([
     [[20.3, 31.7, 101.9, 110.2],        # inside the map
@@ -246,6 +313,122 @@ def roi_inputs(Cf: int, PH: int, PW: int):
     feat.setflags(write=False)
     gp.setflags(write=False)
     return feat, gp
+
+
+# The wide map's table (9 x 27 cells at scale 1/16; a sample at feature position f comes from pixel (f + 0.5) * 16).  The
+# backward's tiles start at x0 = 0, 8, 16, 24 and y0 = 0, 8; span_misses skips a RoI on an axis when its span [lo, hi]
+# has hi < c0 - 2 or lo > c0 + 9.
+ROIS_WIDE = np.array([
+    [[28.3, 25.7, 91.9, 86.2],          # 0  x in cells 1..5:   the x0 = 0 tile alone
+     [155.3, 30.2, 230.1, 90.7],        # 1  x in cells 9..14:  the x0 = 8 tile alone
+     [283.1, 40.4, 355.6, 100.3],       # 2  x in cells 17..22: the x0 = 16 tile alone
+     [401.3, 20.2, 425.7, 70.9],        # 3  the last column tile (x0 = 24, three columns wide)
+     [60.2, 138.3, 100.4, 145.1],       # 4  y in (8.1, 8.6): the second row tile (y0 = 8, one row high) alone
+     [120.0, 24.0, 232.0, 88.0],        # 5  x span [7, 14] exactly (bin 1): hi = 16 - 2, so `hi < c0 - 2` is false for x0 = 16 -- walked
+     [152.0, 24.0, 264.0, 88.0],        # 6  x span [9, 16] exactly: lo = 0 + 9, so `lo > c0 + 9` is false for x0 = 0 -- walked
+     [120.0, 24.0, 231.0, 88.0],        # 7  x span [7, 13.9375]: hi < 14, skipped by x0 = 16
+     [153.0, 24.0, 264.0, 88.0],        # 8  x span [9.0625, 16]: lo > 9, skipped by x0 = 0
+     [200.4, 30.3, 120.2, 90.8],        # 9  x inverted
+     [300.2, 100.6, 380.9, 20.3],       # 10 y inverted
+     [90.7, 120.2, 20.3, 40.9],         # 11 both inverted
+     [400.2, 136.4, 420.3, 143.8]],     # 12 the far corner tile (x0 = 24, y0 = 8)
+    [[390.3, 10.4, 430.2, 60.7],
+     [10.2, 130.9, 50.6, 150.3],
+     [140.7, 50.2, 250.3, 110.5],
+     [260.3, 10.1, 270.9, 30.4],
+     [330.3, 40.2, 280.1, 100.4],       # x inverted
+     [20.0, 20.0, 100.0, 100.0],        # beyond n_roi from here on
+     [NAN, NAN, NAN, NAN],
+     [1.0e30, 0.0, 3.0e38, 50.0],
+     [20.0, 20.0, 100.0, 100.0],
+     [20.0, 20.0, 100.0, 100.0],
+     [20.0, 20.0, 100.0, 100.0],
+     [20.0, 20.0, 100.0, 100.0],
+     [20.0, 20.0, 100.0, 100.0]]], np.float32)
+N_ROI_WIDE = np.array([[13, 1], [5, 0]], np.int32)
+N_ROI_WIDE_ZERO = np.array([[13, 3], [0, 9]], np.int32)       # image 1: count 0
+WIDE_INVERTED = ((0, 9), (0, 10), (0, 11), (1, 4))
+for _a in (ROIS_WIDE, N_ROI_WIDE, N_ROI_WIDE_ZERO):
+    _a.setflags(write=False)
+RB_TILE = 8
+
+
+def span_misses(start, bin_, P, c0, dtype=np.float32):
+    """csrc/gsr_rcnn.hip.h's span test restated, in `dtype`."""
+    start, bin_ = dtype(start), dtype(bin_)
+    end = dtype(start + dtype(dtype(P) * bin_))
+    lo, hi = (start, end) if start < end else (end, start)
+    return bool(hi < dtype(c0 - 2) or lo > dtype(c0 + RB_TILE + 1))
+
+
+def roi_span(r, scale, PH, PW, dtype=np.float32):
+    """-> (sy, by, sx, bx) of roi_axis, in `dtype`."""
+    r, sc, half = np.asarray(r, np.float32).astype(dtype), dtype(np.float32(scale)), dtype(0.5)
+    out = []
+    for lo, hi, P in ((r[1], r[3], PH), (r[0], r[2], PW)):
+        start = dtype(dtype(lo * sc) - half)
+        end = dtype(dtype(hi * sc) - half)
+        out += [start, dtype(dtype(end - start) / dtype(P))]
+    return tuple(out)
+
+
+def tiles_walked(c: "RoiCase", r, dtype=np.float32):
+    """The tiles (y0, x0) of the backward that do not skip the finite RoI r."""
+    sy, by, sx, bx = roi_span(r, c.scale, c.PH, c.PW, dtype)
+    return [(y0, x0) for y0 in range(0, c.Hf, RB_TILE) for x0 in range(0, c.Wf, RB_TILE)
+            if not span_misses(sy, by, c.PH, y0, dtype) and not span_misses(sx, bx, c.PW, x0, dtype)]
+
+
+@lru_cache(maxsize=None)
+def roi_table(c: RoiCase):
+    """-> (rois float32 [B,S,4], n_roi int32 [B,2], read with stride 2), read-only."""
+    if c.table == "base":
+        return ROIS, N_ROI
+    if c.table == "wide":
+        return ROIS_WIDE, N_ROI_WIDE
+    if c.table == "wide-zero":
+        return ROIS_WIDE, N_ROI_WIDE_ZERO
+    if c.table == "prop":                                             # drawn like the sampler's proposals, in the sampler's frame
+        prop = sample_inputs(SampleCase("roi-prop", c.S, 3, 16, 4, data_seed=c.seed))[0]
+        n_roi = np.array([[1000, 2], [0, 7]], np.int32)
+        n_roi.setflags(write=False)
+        return prop, n_roi
+    assert c.table == "gen"
+    # in feature cells: a near corner anywhere from two cells in front of the map to its far edge, a side from a fifth of a
+    # cell to two cells more than the map's -- inside, across either edge, within one cell, over the whole map
+    rs = np.random.RandomState(4000 + c.seed + 131 * c.Hf + 7 * c.Wf + c.PH)
+    x1, y1 = rs.uniform(-2.0, c.Wf, (B, c.S)), rs.uniform(-2.0, c.Hf, (B, c.S))
+    w, h = rs.uniform(0.2, c.Wf + 2.0, (B, c.S)), rs.uniform(0.2, c.Hf + 2.0, (B, c.S))
+    sc = float(np.float32(c.scale))
+    rois = (np.stack([x1 + 0.5, y1 + 0.5, x1 + w + 0.5, y1 + h + 0.5], -1) / sc).astype(np.float32)
+    rois[0, 1] = [(-1.3 + 0.5) / sc, (-1.2 + 0.5) / sc, (c.Wf + 0.4 + 0.5) / sc, (c.Hf + 0.3 + 0.5) / sc]    # the whole map and beyond
+    rois[1, c.S - 2] = NAN                                            # beyond n_roi
+    rois[1, c.S - 1] = [1.0e30, 0.0, 3.0e38, 50.0]
+    n_roi = np.array([[c.S, 1], [c.S - 2, 0]], np.int32)
+    for a in (rois, n_roi):
+        a.setflags(write=False)
+    return rois, n_roi
+
+
+@lru_cache(maxsize=None)
+def roi_case_inputs(c: RoiCase):
+    """-> (feat [B,Cf,Hf,Wf], grad_pooled [B,S,Cf,PH,PW], rois, n_roi); the base table on the base map: roi_inputs()."""
+    rois, n_roi = roi_table(c)
+    if c.table == "base" and (c.Hf, c.Wf) == (HF, WF):
+        return roi_inputs(c.Cf, c.PH, c.PW) + (rois, n_roi)
+    rs = np.random.RandomState(177 + c.Cf + 31 * c.Hf + c.Wf)
+    feat = rs.standard_normal((B, c.Cf, c.Hf, c.Wf)).astype(np.float32)
+    gp = rs.standard_normal((B, rois.shape[1], c.Cf, c.PH, c.PW)).astype(np.float32)
+    feat.setflags(write=False)
+    gp.setflags(write=False)
+    return feat, gp, rois, n_roi
+
+
+def roi_dead_rows(c: RoiCase):
+    """The (b, s) whose pooled row must be zero whatever the features: beyond the count, or not finite."""
+    rois, n_roi = roi_table(c)
+    return [(b, s) for b in range(rois.shape[0]) for s in range(rois.shape[1])
+            if s >= min(max(int(n_roi[b, 0]), 0), rois.shape[1]) or not np.isfinite(rois[b, s]).all()]
 
 
 def _axis(lo, hi, scale, P, ratio, n, dtype):
@@ -310,9 +493,9 @@ def oracle_roi_align(feat, rois, n_roi, stride, PH, PW, scale, ratio, dtype=torc
 
 
 def roi_run(c: RoiCase, dtype):
-    feat, gp = roi_inputs(c.Cf, c.PH, c.PW)
+    feat, gp, rois, n_roi = roi_case_inputs(c)
     f = torch.tensor(feat).to(dtype).requires_grad_(True)
-    pooled, grids, gap = oracle_roi_align(f, ROIS, N_ROI, 2, c.PH, c.PW, SCALE, c.ratio, dtype)
+    pooled, grids, gap = oracle_roi_align(f, rois, n_roi, 2, c.PH, c.PW, c.scale, c.ratio, dtype)
     (pooled * torch.tensor(gp).to(dtype)).sum().backward()
     return dict(pooled=pooled.detach(), grad_features=f.grad.detach(), grids=grids, gap=gap)
 
@@ -329,6 +512,49 @@ def roi_margins_ok(ref) -> bool:
     return ref["gap_grid"] > GAP
 
 
+def edge_pos(lo, hi, dtype):
+    """The one sample of a 1-bin, ratio-1 axis at scale 1 (roi_axis and sample_pos of csrc/gsr_rcnn.h), rounded in `dtype`."""
+    t = dtype
+    lo, hi = t(np.float32(lo)), t(np.float32(hi))
+    start, end = t(t(lo * t(1)) - t(0.5)), t(t(hi * t(1)) - t(0.5))
+    bin_ = t(t(end - start) / t(1))
+    return t(t(start + t(t(0) * bin_)) + t(t(t(0.5) * bin_) / t(1)))
+
+
+def roi_edge_inputs():
+    """The two exact edges of lerp_axis, which gap_grid keeps the seeded cases away from: one image, a 4 x 6 map of two
+    channels holding distinct integers, scale 1, one bin, one sample per bin -> (case, (feat, grad_pooled, rois, n_roi),
+    pooled [S,Cf] and grad_features [Cf,Hf,Wf] written out by hand, the per-row (y, x) cell or None).
+
+    A RoI (lo, hi) puts its sample at (lo + hi) / 2 - 0.5.  (-3, 2) gives exactly -1: valid, clamped to cell 0 with weight 1.
+    (2, 7) gives exactly 4 = Hf and (4, 9) exactly 6 = Wf: valid, the far border cell with weight 1.  Further out the read is 0:
+    lo one float32 step below -3 (-1 - 2^-22 in float32, -1 - 2^-23 in float64) and 2^-21 below it, x's hi one float32 step
+    above 9 (6 + 2^-21 in both) and y's hi two steps above 7 (4 + 2^-21 in both; one step gives 4 + 2^-22, which float32
+    rounds back onto the edge, so that row would be decided by the rounding and is left out)."""
+    Hf, Wf, Cf = 4, 6, 2
+    c = RoiCase(Cf, 1, 1, 1, Hf=Hf, Wf=Wf, scale=1.0, name="edges")
+    f32 = np.float32
+    dn = lambda v: float(np.nextafter(f32(v), f32(-1e9)))
+    up = lambda v: float(np.nextafter(f32(v), f32(1e9)))
+    rows = [((-3.0, -3.0, 2.0, 2.0), (0, 0)),                              # the sample at (-1, -1)
+            ((4.0, 2.0, 9.0, 7.0), (Hf - 1, Wf - 1)),                      # at (Hf, Wf)
+            ((-3.0, 2.0, 2.0, 7.0), (Hf - 1, 0)),                          # at (Hf, -1)
+            ((4.0, -3.0, 9.0, 2.0), (0, Wf - 1)),                          # at (-1, Wf)
+            ((dn(-3.0), -3.0, 2.0, 2.0), None), ((-3.0, dn(-3.0), 2.0, 2.0), None),
+            ((-3.0 - 2.0 ** -21, -3.0, 2.0, 2.0), None), ((-3.0, -3.0 - 2.0 ** -21, 2.0, 2.0), None),
+            ((4.0, 2.0, up(9.0), 7.0), None), ((4.0, 2.0, 9.0, 7.0 + 2.0 ** -20), None)]
+    rois = np.array([[r for r, _ in rows]], np.float32)
+    S = len(rows)
+    feat = (1.0 + np.arange(Cf * Hf * Wf, dtype=np.float32)).reshape(1, Cf, Hf, Wf)
+    gp = (1.0 + np.arange(S * Cf, dtype=np.float32)).reshape(1, S, Cf, 1, 1)
+    pooled, gf = np.zeros((S, Cf), np.float32), np.zeros((Cf, Hf, Wf), np.float32)
+    for s, (_, cell) in enumerate(rows):
+        if cell is not None:
+            pooled[s] = feat[0, :, cell[0], cell[1]]
+            gf[:, cell[0], cell[1]] += gp[0, s, :, 0, 0]                  # no cell is hit twice: each sum has one term
+    return c, (feat, gp, rois, np.array([[S, 0]], np.int32)), pooled, gf, [cell for _, cell in rows]
+
+
 # ---- the loss -------------------------------------------------------------------------------------------------------------------
 class LossCase(NamedTuple):
     id: str
@@ -338,6 +564,12 @@ class LossCase(NamedTuple):
     w: Tuple[float, float] = (1.0, 1.0)
     all_bg: bool = False          # no present row: every sampled row is background
     pad_image: bool = False       # image 1 holds padding rows only
+    S: int = 16
+    B: int = 2
+    M: int = 2
+    R: int = 30
+    max_pos: int = 6
+    spread: bool = False          # the gt rows' classes span 0 .. C - 1 (otherwise: the sampler cases' 0 .. 4, mod C)
 
 
 LOSS_S, LOSS_R, LOSS_M = 16, 30, 2
@@ -351,6 +583,13 @@ LOSS_CASES = (
     LossCase("all-background", 5, all_bg=True),
     LossCase("padding-image", 5, pad_image=True, beta=0.5),
     LossCase("weights", 5, w=(0.7, 2.5)),
+    LossCase("rows-33", 5, beta=0.5, B=3, S=11),                         # 33 rows: the last block holds one wave of four
+    LossCase("s1024", 5, S=1024, R=1400, max_pos=1024),                  # 512 slab rows: two turns of slab_sum, eight of k_rcnn_count
+    LossCase("c63", 63, M=6, max_pos=12, spread=True),
+    LossCase("c64", 64, M=6, max_pos=12, spread=True, beta=0.5),
+    LossCase("c65", 65, M=6, max_pos=12, spread=True),
+    LossCase("c1024", 1024, M=6, max_pos=12, spread=True, beta=0.5),
+    LossCase("c1024-agnostic", 1024, M=6, max_pos=12, spread=True, agnostic=True),
 )
 LOSS_COMPARED = ("loss", "grad_scores", "grad_deltas")
 
@@ -359,24 +598,26 @@ LOSS_COMPARED = ("loss", "grad_scores", "grad_deltas")
 def loss_inputs(c: LossCase):
     """-> dict of read-only numpy arrays: scores, deltas, rois, labels, gt_row, gt_boxes; zero_row: a (b, s) whose residual is
     exactly 0 (a ground-truth candidate: its target deltas are 0 in every precision, and so are its deltas), or None."""
-    sc = SampleCase("loss", LOSS_R, LOSS_M, LOSS_S, 6, data_seed=c.C)
+    sc = SampleCase("loss", c.R, c.M, c.S, c.max_pos, data_seed=c.C, B=c.B)
     prop, gt, cls, _ = sample_inputs(sc)
     cls = np.array(cls) % c.C
+    if c.spread:                                                       # 0 and C - 1 in every image, the rest evenly between
+        cls = np.stack([np.roll(np.round(np.linspace(0, c.C - 1, c.M)).astype(np.int32), b) for b in range(c.B)])
     if c.all_bg:
         cls[:] = -1
-    n_prop = np.array([LOSS_R, 0], np.int32) if c.pad_image else None
+    n_prop = np.array([c.R, 0], np.int32) if c.pad_image else None
     if c.pad_image:
         cls[1] = -1                                                    # no candidate at all in image 1
-    smp = oracle_sample(prop, gt, cls, n_prop, c.C, LOSS_S, 6, True, 11)
+    smp = oracle_sample(prop, gt, cls, n_prop, c.C, c.S, c.max_pos, True, 11)
     assert sample_margins_ok(smp)
     rs = np.random.RandomState(500 + c.C)
     D = 4 if c.agnostic else 4 * c.C
-    scores = (rs.standard_normal((B, LOSS_S, c.C + 1)) * 2.0).astype(np.float32)
-    deltas = (rs.standard_normal((B, LOSS_S, D)) * 1.5).astype(np.float32)
+    scores = (rs.standard_normal((c.B, c.S, c.C + 1)) * 2.0).astype(np.float32)
+    deltas = (rs.standard_normal((c.B, c.S, D)) * 1.5).astype(np.float32)
     zero_row = None
-    for b in range(B):
-        for s in range(LOSS_S):
-            if smp["idx"][b, s] >= LOSS_R and zero_row is None:        # a ground-truth candidate
+    for b in range(c.B):
+        for s in range(c.S):
+            if smp["idx"][b, s] >= c.R and zero_row is None:           # a ground-truth candidate
                 base = 0 if c.agnostic else 4 * int(smp["labels"][b, s])
                 deltas[b, s, base:base + 4] = 0.0
                 zero_row = (b, s)
@@ -403,7 +644,7 @@ def oracle_loss(scores, deltas, rois, labels, gt_row, gt_boxes, agnostic=False, 
     logp = x - x.max(-1, keepdim=True).values
     logp = logp - logp.exp().sum(-1, keepdim=True).log()
     cls_term = -(logp.gather(-1, lb.clamp(min=0)[..., None])[..., 0] * live.to(dtype)).sum() / n
-    fg = live & (lb < C) & (gr >= 0)
+    fg = live & (lb < C) & (gr >= 0) & (gr < gb.shape[1])
     box_term = torch.zeros((), dtype=dtype)
     if bool(fg.any()):
         bi, si = fg.nonzero(as_tuple=True)
@@ -434,11 +675,39 @@ def oracle_loss(scores, deltas, rois, labels, gt_row, gt_boxes, agnostic=False, 
 
 @lru_cache(maxsize=None)
 def loss_reference(c: LossCase):
-    i = loss_inputs(c)
+    return loss_reference_of(c, loss_inputs(c))
+
+
+def loss_reference_of(c: LossCase, i):
     args = (i["scores"], i["deltas"], i["rois"], i["labels"], i["gt_row"], i["gt_boxes"])
     o64 = oracle_loss(*args, agnostic=c.agnostic, beta=c.beta, w=c.w)
     o32 = oracle_loss(*args, agnostic=c.agnostic, beta=c.beta, w=c.w, dtype=torch.float32)
     return dict(o64=o64, yard={k: err(o32[k], o64[k]) for k in LOSS_COMPARED})
+
+
+GUARD_CASE = "c5-beta"
+
+
+@lru_cache(maxsize=None)
+def loss_guard_inputs():
+    """The guards of k_rcnn_rows and k_rcnn_count on the inputs of `c5-beta` -> (case, base, bad_labels, clean_labels,
+    bad_rows, rows): bad_labels has C + 1, 2^31 - 1 and -7 on three live rows (one of them foreground) and clean_labels -1
+    there -- the two must give the same bits; bad_rows has gt_row = M, M + 100 and -3 on three foreground rows (`rows`),
+    which keep their cross-entropy term and gradient, add nothing to the box term and get a zero grad_deltas row."""
+    c = next(k for k in LOSS_CASES if k.id == GUARD_CASE)
+    base = loss_inputs(c)
+    lb, gr = np.array(base["labels"]), np.array(base["gt_row"])
+    fg = [(b, s) for b in range(c.B) for s in range(c.S) if 0 <= lb[b, s] < c.C and gr[b, s] >= 0 and (b, s) != base["zero_row"]]
+    bg = [(b, s) for b in range(c.B) for s in range(c.S) if lb[b, s] == c.C]
+    assert len(fg) >= 4 and len(bg) >= 2
+    bad, clean = lb.copy(), lb.copy()
+    for (b, s), v in zip((fg[0], bg[0], bg[1]), (c.C + 1, 2 ** 31 - 1, -7)):
+        bad[b, s], clean[b, s] = v, -1
+    rows = fg[1:4]
+    bad_gr = gr.copy()
+    for (b, s), v in zip(rows, (c.M, c.M + 100, -3)):
+        bad_gr[b, s] = v
+    return c, base, dict(base, labels=bad), dict(base, labels=clean), dict(base, gt_row=bad_gr), rows
 
 
 # ---- the output stage ---------------------------------------------------------------------------------------------------------
@@ -448,6 +717,11 @@ class PostCase(NamedTuple):
     max_det: int
     many: bool = False
     agnostic: bool = False
+    R: int = 0                    # 0: the hand-made tables' 12 or 40; otherwise post_gen_inputs() places `ncand` candidates
+    C: int = 3
+    B: int = 2
+    ncand: int = 0
+    empty: Tuple[int, ...] = ()   # images with n_prop = 0
 
 
 POST_C = 3
@@ -456,6 +730,15 @@ POST_CASES = (
     PostCase("conf-0.7", 0.7, 8),
     PostCase("agnostic-deltas", 0.5, 8, agnostic=True),
     PostCase("over-max-det", 0.5, 5, many=True),
+    PostCase("r1024", 0.5, 250, R=1024, ncand=200),                      # per = 1, every thread holds a proposal
+    PostCase("r1025", 0.5, 250, R=1025, ncand=200),                      # per = 2: the threads from 513 on hold none
+    PostCase("r2049", 0.5, 300, R=2049, ncand=250),                      # per = 3
+    PostCase("r4096", 0.5, 320, R=4096, ncand=400),                      # per = 4; k_rcnn_gather's loop beyond 256 rows
+    PostCase("c64", 0.5, 20, R=70, C=64, ncand=30),
+    PostCase("c1024", 0.5, 20, R=70, C=1024, ncand=30),
+    PostCase("maxdet-1", 0.5, 1),
+    PostCase("maxdet-R", 0.5, 40, many=True),
+    PostCase("b3-empty-middle", 0.5, 20, R=70, B=3, ncand=30, empty=(1,)),
 )
 IOU_THR = 0.5
 
@@ -469,9 +752,71 @@ def _logits(C, cls, p, rs):
     return np.log(rest).astype(np.float32)
 
 
+def post_gen_inputs(c: PostCase):
+    """R proposals per image of which `ncand` are candidates (score 0.55 .. 0.95), at chosen indices: 0, 1023, 1024 and R - 1
+    where the image has them, a run of eight in a row (every slot of two threads at four proposals per thread), the rest drawn
+    over the whole range.  The candidates sit on disjoint sites of the frame; a quarter of the sites hold a second candidate
+    shifted by a tenth of the box (IoU about 0.7), alternately of the same class (suppressed) and of another (kept).  Every
+    other row has its best class at 0.3 .. 0.4 and the rest spread evenly.  The last image's n_prop is 37 short of R, with five
+    rows behind it that would be candidates; an image of `empty` has n_prop = 0."""
+    rs = np.random.RandomState(1700 + c.R + 3 * c.C + c.B)
+    R, C, K, Bn = c.R, c.C, c.ncand, c.B
+    D = 4 if c.agnostic else 4 * C
+    deltas = (rs.standard_normal((Bn, R, D)) * 0.3).astype(np.float32)
+    scores = np.zeros((Bn, R, C + 1), np.float32)
+    prop = np.zeros((Bn, R, 4), np.float32)
+    n_prop = np.full(Bn, R, np.int32)
+    n_prop[Bn - 1] = R - 37
+    for b in c.empty:
+        n_prop[b] = 0
+    for b in range(Bn):
+        npb = int(n_prop[b]) if n_prop[b] > 0 else R                    # an empty image gets the same rows: they must not count
+        w, h = rs.uniform(4, 40, R), rs.uniform(4, 40, R)
+        x1, y1 = rs.uniform(0, FRAME[0] - w), rs.uniform(0, FRAME[1] - h)
+        prop[b] = np.stack([x1, y1, x1 + w, y1 + h], -1)
+        k0, p0 = rs.randint(C, size=R), rs.uniform(0.3, 0.4, R)
+        scores[b] = np.log((1.0 - p0) / C)[:, None]
+        scores[b, np.arange(R), k0] = np.log(p0)
+        run0 = (npb // 2) // 8 * 8
+        must = sorted({i for i in (0, 1023, 1024, R - 1) if i < npb} | set(range(run0, run0 + 8)))
+        others = np.setdiff1d(np.arange(npb), must)
+        cand = np.array(sorted(must + rs.choice(others, K - len(must), replace=False).tolist()))
+        order = rs.permutation(K)                                        # candidate order[j] goes to site j (or is its twin)
+        n_site = K - K // 4
+        sites = grid_boxes(rs, n_site)
+        site_cls = rs.randint(C, size=n_site)
+        site_cls[:2] = (C - 1, 0)
+        for j in range(K):
+            i = int(cand[order[j]])
+            site = j if j < n_site else j - n_site                       # the twins of the first K // 4 sites
+            bx, k = sites[site].copy(), int(site_cls[site])
+            if j >= n_site:
+                bx[[0, 2]] += 0.1 * (bx[2] - bx[0])
+                if site % 2 and C > 1:
+                    k = (k + 1) % C
+            prop[b, i] = bx
+            scores[b, i] = _logits(C, k, float(rs.uniform(0.55, 0.95)), rs)
+            o = 0 if c.agnostic else 4 * k
+            deltas[b, i, o:o + 4] = (rs.uniform(-0.3, 0.3), rs.uniform(-0.3, 0.3), rs.uniform(-0.2, 0.2), rs.uniform(-0.2, 0.2))
+        for i in range(npb, min(npb + 5, R)):                            # behind n_prop
+            scores[b, i] = _logits(C, int(rs.randint(C)), 0.9, rs)
+    for a in (scores, deltas, prop, n_prop):
+        a.setflags(write=False)
+    return scores, deltas, prop, n_prop
+
+
+def post_candidates(c: PostCase):
+    """The generator's premise, from the oracle's own candidate test: per image the ascending proposal indices above conf_thr."""
+    scores, _, _, n_prop = post_inputs(c)
+    p = torch.softmax(torch.tensor(np.array(scores)).double(), -1)[..., :c.C].max(-1).values.numpy()
+    return [[i for i in range(int(n_prop[b])) if p[b, i] > float(np.float32(c.conf))] for b in range(c.B)]
+
+
 @lru_cache(maxsize=None)
 def post_inputs(c: PostCase):
     """-> scores [B,R,C+1], deltas [B,R,4C or 4], proposals [B,R,4], n_prop [B]."""
+    if c.R:
+        return post_gen_inputs(c)
     rs = np.random.RandomState(900 + int(c.conf * 10) + c.max_det)
     C = POST_C
     D = 4 if c.agnostic else 4 * C
@@ -533,21 +878,19 @@ def oracle_post(scores, deltas, prop, n_prop, conf, iou_thr, max_det, frame=FRAM
     C = n1 - 1
     f32 = lambda v: torch.tensor(v, dtype=torch.float32).to(dtype)
     p = torch.softmax(x, -1)[..., :C]
-    top = torch.sort(p, -1, descending=True).values
+    top = torch.topk(p, min(2, C), -1).values                         # (every row at once: the large cases have thousands)
+    best, best_k = p.max(-1)
+    lead = (top[..., 0] - top[..., 1]) if C > 1 else torch.full_like(best, math.inf)
     gap_conf, gap_nms = math.inf, math.inf
     dets, counts, classes, order = np.zeros((Bn, max_det, 6)), np.zeros((Bn, 2), np.int32), [], []
     for b in range(Bn):
         npb = R if n_prop is None else int(n_prop[b])
         cand = []
-        for i in range(npb):
-            sc, k = float(p[b, i].max()), int(p[b, i].argmax())
-            if sc != sc:
-                continue
-            gap_conf = min(gap_conf, abs(sc - float(f32(conf))))
-            if C > 1:
-                gap_conf = min(gap_conf, float(top[b, i, 0] - top[b, i, 1]))
-            if not sc > float(f32(conf)):
-                continue
+        ok = ~torch.isnan(best[b, :npb])
+        if bool(ok.any()):
+            gap_conf = min(gap_conf, float((best[b, :npb][ok] - f32(conf)).abs().min()), float(lead[b, :npb][ok].min()))
+        for i in (ok & (best[b, :npb] > f32(conf))).nonzero()[:, 0].tolist():
+            sc, k = float(best[b, i]), int(best_k[b, i])
             r = pr[b, i]
             dl = d[b, i, (0 if agnostic else 4 * k):(0 if agnostic else 4 * k) + 4]
             w_, h_ = r[2] - r[0], r[3] - r[1]
@@ -591,6 +934,51 @@ def post_margins_ok(o) -> bool:
 def post_reference(c: PostCase):
     scores, deltas, prop, n_prop = post_inputs(c)
     return oracle_post(scores, deltas, prop, n_prop, c.conf, IOU_THR, c.max_det, agnostic=c.agnostic)
+
+
+BELOW_HALF = float(np.nextafter(np.float32(0.5), np.float32(0.0)))
+
+
+def post_exact_inputs():
+    """The output stage's exact decisions, which gap_conf keeps the seeded cases away from -> a list of (name, PostCase,
+    inputs, dets [B,max_det,6] and counts [B,2] written out by hand).  One proposal (10, 20, 50, 60) with zero deltas decodes
+    to itself in every precision: width 40, centre 30, exp(0) * 40 = 40, 30 -+ 20.
+      at-conf     C = 1, logits (0, 0): p = exp(0) / (1 + 1) = 0.5 exactly; conf_thr = 0.5 drops it (>)
+      below-conf  the same with conf_thr one float32 step below 0.5: kept, score 0.5
+      class-tie   C = 4, logits (-200, 0, 0, 0, 0): exp(-200) is 0 in float32 and 2^-288 in float64, where 4 + 2^-288 rounds
+                  to 4; classes 1, 2, 3 have p = 1 / 4 exactly and class 1, the lowest, wins: its deltas are zero, those of
+                  classes 2 and 3 are not, so the box tells which class the deltas were taken from
+    Row 1 of every image is far below the threshold."""
+    box = (10.0, 20.0, 50.0, 60.0)
+    prop = np.array([[box, (100.0, 100.0, 140.0, 150.0)]] * 2, np.float32)
+    n_prop = np.array([2, 2], np.int32)
+    out = []
+    s1 = np.array([[(0.0, 0.0), (-3.0, 0.0)]] * 2, np.float32)
+    d1 = np.zeros((2, 2, 4), np.float32)
+    out.append(("at-conf", PostCase("at-conf", 0.5, 2, C=1), (s1, d1, prop, n_prop), np.zeros((2, 2, 6), np.float32),
+                np.zeros((2, 2), np.int32)))
+    dets = np.zeros((2, 2, 6), np.float32)
+    dets[:, 0] = box + (0.5, 0.0)
+    out.append(("below-conf", PostCase("below-conf", BELOW_HALF, 2, C=1), (s1, d1, prop, n_prop), dets, np.array([[1, 1]] * 2, np.int32)))
+    s4 = np.array([[(-200.0, 0.0, 0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 0.0, 5.0)]] * 2, np.float32)
+    d4 = np.zeros((2, 2, 16), np.float32)
+    d4[:, 0, 0:4] = (3.0, -2.0, 1.0, 1.0)
+    d4[:, 0, 8:12] = (5.0, 5.0, 1.0, 1.0)
+    d4[:, 0, 12:16] = (-5.0, 2.0, -1.0, 0.5)
+    dets = np.zeros((2, 2, 6), np.float32)
+    dets[:, 0] = box + (0.25, 1.0)
+    out.append(("class-tie", PostCase("class-tie", 0.125, 2, C=4), (s4, d4, prop, n_prop), dets, np.array([[1, 1]] * 2, np.int32)))
+    return out
+
+
+def post_poison_inputs():
+    """`conf-0.5` with a row of NaN logits (row 8) and a +inf logit (row 9) in image 0 -> (case, clean inputs, poisoned inputs)."""
+    c = POST_CASES[0]
+    scores, deltas, prop, n_prop = post_inputs(c)
+    bad = np.array(scores)
+    bad[0, 8] = NAN
+    bad[0, 9, 1] = float("inf")
+    return c, (scores, deltas, prop, n_prop), (bad, deltas, prop, n_prop)
 
 
 def verdict_ref(dets, counts, gt, target, untarget, targeted, iou_match=0.5):
@@ -645,6 +1033,8 @@ def host_lib():
     lib.rh_sample.argtypes = [sp] + [vp] * 9
     lib.rh_roi_align.argtypes = [sp, vp, vp, vp, ctypes.c_int32, vp]
     lib.rh_roi_align_bwd.argtypes = [sp, vp, vp, ctypes.c_int32, vp, vp]
+    lib.rh_roi_align_bwd_scatter.argtypes = [sp, vp, vp, ctypes.c_int32, vp, vp]
+    lib.rh_roi_align_bwd_scatter.restype = ctypes.c_int
     lib.rh_loss_f32.argtypes = [sp] + [vp] * 9
     lib.rh_loss_f64.argtypes = [sp] + [vp] * 9
     lib.rh_post.argtypes = [sp] + [vp] * 6
@@ -657,32 +1047,33 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-def host_sample(lib, c: SampleCase, seed=None):
-    prop, gt, cls, n_prop = (None if a is None else np.ascontiguousarray(a) for a in sample_inputs(c))
-    s = c_spec(R=c.R, M=c.M, S=c.S, C=NC, max_pos=c.max_pos, append_gt=int(c.append_gt), seed=c.seed if seed is None else seed)
-    out = dict(idx=np.empty((B, c.S), np.int32), rois=np.empty((B, c.S, 4), np.float32), labels=np.empty((B, c.S), np.int32),
-               gt_row=np.empty((B, c.S), np.int32), counts=np.empty((B, 2), np.int32))
+def host_sample(lib, c: SampleCase, seed=None, inputs=None):
+    prop, gt, cls, n_prop = (None if a is None else np.ascontiguousarray(a) for a in (sample_inputs(c) if inputs is None else inputs))
+    s = c_spec(B=c.B, R=c.R, M=c.M, S=c.S, C=NC, max_pos=c.max_pos, append_gt=int(c.append_gt), seed=c.seed if seed is None else seed)
+    out = dict(idx=np.empty((c.B, c.S), np.int32), rois=np.empty((c.B, c.S, 4), np.float32), labels=np.empty((c.B, c.S), np.int32),
+               gt_row=np.empty((c.B, c.S), np.int32), counts=np.empty((c.B, 2), np.int32))
     assert lib.rh_sample(ctypes.byref(s), _p(prop), _p(n_prop), _p(gt), _p(cls), _p(out["idx"]), _p(out["rois"]), _p(out["labels"]),
                          _p(out["gt_row"]), _p(out["counts"])) == 0
     return out
 
 
-def host_roi(lib, c: RoiCase):
-    feat, gp = (np.ascontiguousarray(a) for a in roi_inputs(c.Cf, c.PH, c.PW))
-    rois, n_roi = np.ascontiguousarray(ROIS), np.ascontiguousarray(N_ROI)
-    s = c_spec(S=ROIS.shape[1], Cf=c.Cf, Hf=HF, Wf=WF, PH=c.PH, PW=c.PW, sampling_ratio=c.ratio)
+def host_roi(lib, c: RoiCase, inputs=None):
+    feat, gp, rois, n_roi = (np.ascontiguousarray(a) for a in (roi_case_inputs(c) if inputs is None else inputs))
+    s = c_spec(B=feat.shape[0], S=rois.shape[1], Cf=c.Cf, Hf=c.Hf, Wf=c.Wf, PH=c.PH, PW=c.PW, spatial_scale=c.scale, sampling_ratio=c.ratio)
     pooled, gf = np.empty(gp.shape, np.float32), np.zeros(feat.shape, np.float32)
     assert lib.rh_roi_align(ctypes.byref(s), _p(feat), _p(rois), _p(n_roi), 2, _p(pooled)) == 0
     assert lib.rh_roi_align_bwd(ctypes.byref(s), _p(rois), _p(n_roi), 2, _p(gp), _p(gf)) == 0
-    return dict(pooled=pooled, grad_features=gf)
+    scatter = np.zeros(feat.shape, np.float32)                          # the same sum, every sample's shares added one by one
+    assert lib.rh_roi_align_bwd_scatter(ctypes.byref(s), _p(rois), _p(n_roi), 2, _p(gp), _p(scatter)) == 0
+    return dict(pooled=pooled, grad_features=gf, scatter=scatter)
 
 
-def host_loss(lib, c: LossCase, double=False, want_grad=True):
-    i = loss_inputs(c)
+def host_loss(lib, c: LossCase, double=False, want_grad=True, inputs=None):
+    i = loss_inputs(c) if inputs is None else inputs
     ft = np.float64 if double else np.float32
     x, d, r, gb = (np.ascontiguousarray(i[k], dtype=ft) for k in ("scores", "deltas", "rois", "gt_boxes"))
     lb, gr = np.ascontiguousarray(i["labels"]), np.ascontiguousarray(i["gt_row"])
-    s = c_spec(S=LOSS_S, M=LOSS_M, C=c.C, beta=c.beta, w_cls=c.w[0], w_box=c.w[1], flags=1 if c.agnostic else 0)
+    s = c_spec(B=c.B, S=c.S, M=c.M, C=c.C, beta=c.beta, w_cls=c.w[0], w_box=c.w[1], flags=1 if c.agnostic else 0)
     loss = np.empty(3, ft)
     gs, gd = (np.empty_like(x), np.empty_like(d)) if want_grad else (None, None)
     fn = lib.rh_loss_f64 if double else lib.rh_loss_f32
@@ -690,9 +1081,10 @@ def host_loss(lib, c: LossCase, double=False, want_grad=True):
     return dict(loss=loss, grad_scores=gs, grad_deltas=gd)
 
 
-def host_post(lib, c: PostCase):
-    scores, deltas, prop, n_prop = (np.ascontiguousarray(a) for a in post_inputs(c))
-    s = c_spec(R=scores.shape[1], C=POST_C, conf_thr=c.conf, max_det=c.max_det, flags=1 if c.agnostic else 0)
-    dets, counts = np.empty((B, c.max_det, 6), np.float32), np.empty((B, 2), np.int32)
+def host_post(lib, c: PostCase, inputs=None):
+    scores, deltas, prop, n_prop = (np.ascontiguousarray(a) for a in (post_inputs(c) if inputs is None else inputs))
+    Bn = scores.shape[0]
+    s = c_spec(B=Bn, R=scores.shape[1], C=scores.shape[2] - 1, conf_thr=c.conf, max_det=c.max_det, flags=1 if c.agnostic else 0)
+    dets, counts = np.empty((Bn, c.max_det, 6), np.float32), np.empty((Bn, 2), np.int32)
     assert lib.rh_post(ctypes.byref(s), _p(scores), _p(deltas), _p(prop), _p(n_prop), _p(dets), _p(counts)) == 0
     return dict(dets=dets, counts=counts)

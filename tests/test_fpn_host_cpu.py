@@ -70,3 +70,16 @@ def test_host_pooled_and_gradients_match_the_oracle(host, c):
     lv, _, _ = FC.oracle_levels(FC.ROIS, FC.N_ROI, 2)
     assert (got["pooled"][lv == -1] == 0).all()
     assert (got[f"grad{FC.NL - 1}"][1] == 0).all()                                    # image 1 has no RoI of the last level
+    b, s = FC.INVERTED                                                                # the inverted RoI: level 0, backwards or grid 0
+    assert FC.ROIS[b, s, 2] < FC.ROIS[b, s, 0] and lv[b, s] == 0
+    for p in (ref["o64"]["pooled"][b, s].numpy(), got["pooled"][b, s]):
+        assert (float(np.abs(p).max()) > 0) == (c.ratio > 0)
+    assert (ref["o64"]["grids"][0, b, s].min() == 0) == (c.ratio == 0)
+
+
+def test_host_exact_edges_by_hand(host):
+    """The samples exactly at -1 and at n (valid: the border cell with weight 1) and the next positions further out (0), through
+    the pooler's host build on a one-level pyramid of stride 1: the values rcnn_cases.roi_edge_inputs writes out by hand."""
+    _, _, _, pooled, gf = FC.edge_inputs()
+    got_p, got_g = FC.host_pool_edges(host)
+    assert np.array_equal(got_p[0, :, :, 0, 0], pooled) and np.array_equal(got_g[0], gf)

@@ -50,14 +50,14 @@ def _spec(FO, c, nl=FC.NL):
                       canonical_size=FC.CANON_SIZE)
 
 
-def _raw(FO, c, n_roi=FC.N_ROI, fill=SENTINEL, accumulate=False, grads=None, nl=FC.NL, rois=FC.ROIS, feats=None, gp=None):
+def _raw(FO, c, n_roi=FC.N_ROI, fill=SENTINEL, accumulate=False, grads=None, nl=FC.NL, rois=FC.ROIS, feats=None, gp=None, spec=None):
     """Both C entries on sentinel-filled caller buffers -> dict(pooled, roi_level, level_list, level_count, grad0..)."""
     if feats is None:
         feats, gp = FC.inputs(c.Cf, c.PH, c.PW)
     feats = [_t(f) for f in feats[:nl]]
     gp, r, n = _t(gp), _t(rois), _t(n_roi)
     Bn, S = int(r.shape[0]), int(r.shape[1])
-    cs = FO.c_spec(_spec(FO, c, nl), B=Bn, S=S, Cf=c.Cf, sizes=[tuple(f.shape[2:]) for f in feats])
+    cs = FO.c_spec(_spec(FO, c, nl) if spec is None else spec, B=Bn, S=S, Cf=c.Cf, sizes=[tuple(f.shape[2:]) for f in feats])
     out = dict(pooled=torch.full((Bn, S, c.Cf, c.PH, c.PW), fill, dtype=torch.float32, device=DEV),
                roi_level=torch.full((Bn, S), ISENT, dtype=torch.int32, device=DEV),
                level_list=torch.full((Bn, nl, S), ISENT, dtype=torch.int32, device=DEV),
@@ -123,6 +123,21 @@ def test_pooled_and_gradients_match_the_oracle(FO, c):
     lv, _, counts = FC.oracle_levels(FC.ROIS, FC.N_ROI, 2)
     assert (got["pooled"][_t(lv == -1)] == 0).all()
     assert counts[1, FC.NL - 1] == 0 and (got[f"grad{FC.NL - 1}"][1] == 0).all()       # a level that received no RoI
+    b, s = FC.INVERTED                                                                  # backwards at a fixed ratio, grid 0 when adaptive
+    assert lv[b, s] == 0 and (float(got["pooled"][b, s].abs().max()) > 0) == (c.ratio > 0)
+
+
+def test_exact_edges_by_hand(FO, host):
+    """The samples exactly at -1 and at n (valid: the border cell with weight 1) and the next positions further out (0) through
+    the pooler's kernels, on a one-level pyramid of stride 1: the values rcnn_cases.roi_edge_inputs writes out by hand, and the
+    host build's bits."""
+    c, _, (feat, gp, rois, n_roi), pooled, gf = FC.edge_inputs()
+    spec = FO.FpnSpec(scales=(1.0,), thr=(0.0,), PH=c.PH, PW=c.PW, sampling_ratio=c.ratio, canonical_size=FC.CANON_SIZE)
+    got = _raw(FO, c, n_roi=n_roi, nl=1, rois=rois, feats=(feat,), gp=gp, spec=spec)
+    h_p, h_g = FC.host_pool_edges(host)
+    assert (got["roi_level"] == 0).all()
+    assert np.array_equal(got["pooled"].cpu().numpy()[0, :, :, 0, 0], pooled) and _bits(got["pooled"]) == h_p.tobytes()
+    assert np.array_equal(got["grad0"].cpu().numpy()[0], gf) and _bits(got["grad0"]) == h_g.tobytes()
 
 
 # ---- 3. bit for bit the single-level entries ----------------------------------------------------------------------------------
