@@ -26,6 +26,7 @@ import contextlib
 import copy
 import json
 import time
+import types
 from typing import Callable, Iterable, List, Optional, Sequence
 
 import torch
@@ -62,45 +63,44 @@ class SurrogateDetector(nn.Module):
 MULTI_STEP = True       # the stepped tensors of an iteration in one launch (gsr_pgd_step_multi); False: tensor by tensor (A/B, tests)
 
 
+# the raw tensors of every group, in the order they are stepped (colour: _features_rest first, reference attack.py:138-173)
+_GROUP_ATTRS = {"color": ("_features_rest", "_features_dc"), "position": ("_xyz",), "scaling": ("_scaling",),
+                "rotation": ("_rotation",), "opacity": ("_opacity",)}
+
+
 def _step(model, originals, groups: Sequence[str], norm: str, alpha: float, epsilon: float, norms=None) -> None:
     """norms: a diff_gaussian_rasterization.GradNorms whose sums of squares -- when still valid for this iteration's
     gradients -- spare the L2 rules their own pass over the gradient (same rule, attack.py:53-119, 138-173)."""
-    attrs = {"color": ("_features_rest", "_features_dc"), "position": ("_xyz",), "scaling": ("_scaling",),
-             "rotation": ("_rotation",), "opacity": ("_opacity",)}
-    todo = [a for g in groups for a in attrs[g]]
-    have = all(getattr(model, a).grad is not None for a in todo)
-    if norm == "l2" and norms is not None and have and all(norms.sumsq_of(a) is not None for a in todo):
+    l2 = norm == "l2"
+    names = [a for g in groups for a in _GROUP_ATTRS[g]]
+    tensors = [getattr(model, a) for a in names]
+    have = all(t.grad is not None for t in tensors)
+    sumsq = [norms.sumsq_of(a) for a in names] if l2 and norms is not None and have else [None]
+    normed = all(s is not None for s in sumsq)
+    if not normed:
+        sumsq = [None] * len(names)
+    items = [(t, t.grad, originals[a], s) for t, a, s in zip(tensors, names, sumsq)]
+    if normed:
         # the raster backward left ||grad||^2 of every tensor on the device: one launch for all of them
-        if MULTI_STEP and pgd.multi_step_([(getattr(model, a), getattr(model, a).grad, originals[a], norms.sumsq_of(a))
-                                           for a in todo], alpha, epsilon, True):
+        if MULTI_STEP and pgd.multi_step_(items, alpha, epsilon, True):
             return
-        for a in todo:
-            t = getattr(model, a)
-            pgd.l2_step_(t, t.grad, alpha, epsilon, originals[a], sumsq=norms.sumsq_of(a))
+        for x, grad, x0, s in items:
+            pgd.l2_step_(x, grad, alpha, epsilon, x0, sumsq=s)
         return
-    if have and len(todo) > 1 and MULTI_STEP:
+    if have and len(items) > 1 and MULTI_STEP:
         # every stepped tensor has a gradient (the reference's own condition for stepping a group, attack.py:496): the
         # same rules on all of them in one launch (an L2 norm that is not on the device yet is summed in front)
-        if pgd.multi_step_([(getattr(model, a), getattr(model, a).grad, originals[a], None) for a in todo], alpha, epsilon,
-                           norm == "l2"):
+        if pgd.multi_step_(items, alpha, epsilon, l2):
             return
-    fn = {("color", "l2"): lambda: pgd.gaussian_color_l2_attack(model, alpha, epsilon, originals["_features_rest"],
-                                                                  originals["_features_dc"]),
-          ("color", "linf"): lambda: pgd.gaussian_color_linf_attack(model, alpha, epsilon, originals["_features_rest"],
-                                                                      originals["_features_dc"])}
-    single = {"position": ("_xyz", "position"), "scaling": ("_scaling", "scaling"),
-              "rotation": ("_rotation", "rotation"), "opacity": ("_opacity", "opacity")}
+    rule = pgd.l2_step_ if l2 else pgd.linf_step_
     for g in groups:
-        if g == "color":
-            # the reference steps only when both colour gradients exist (attack.py:496)
-            if model._features_rest.grad is None or model._features_dc.grad is None:
-                continue
-            fn[(g, norm)]()
-        else:
-            attr, name = single[g]
-            if getattr(model, attr).grad is None:      # no gradient reached this group (e.g. a rank without views)
-                continue
-            getattr(pgd, f"gaussian_{name}_{norm}_attack")(model, alpha, epsilon, originals[attr])
+        part, items = items[:len(_GROUP_ATTRS[g])], items[len(_GROUP_ATTRS[g]):]
+        # a group without a gradient is not stepped (e.g. a rank without views); the reference steps colour only when
+        # both colour gradients exist (attack.py:496)
+        if any(grad is None for _, grad, _, _ in part):
+            continue
+        for x, grad, x0, _ in part:
+            rule(x, grad, alpha, epsilon, x0)
 
 
 class PhaseTimer:
@@ -158,9 +158,7 @@ def gather_success(flags: Sequence[bool], n_views: int, rank: int, world: int, d
     if idx:
         full[torch.tensor(idx, device=device)] = torch.tensor([int(bool(f)) for f in flags], dtype=torch.int32, device=device)
     if world > 1:
-        if device.type == "cuda" and torch.distributed.get_backend() == "gloo":
-            full = full.cpu()
-        torch.distributed.all_reduce(full)
+        gdist.all_reduce_sum_(full)
     return [bool(v) for v in full.tolist()]
 
 
@@ -170,6 +168,315 @@ def batch_done(flags: Sequence[bool], n_views: int) -> bool:
     attack.py:590-598) has to succeed itself -- the literal B - 1 = 0 would retire it after one iteration whatever the
     detector says."""
     return sum(bool(f) for f in flags) >= max(n_views - 1, 1)
+
+
+class _NoTimer:
+    """Stands in for the PhaseTimer nobody asked for: every lap of the loop is one unguarded line."""
+
+    def start(self):
+        pass
+
+    def lap(self, phase: str):
+        pass
+
+
+class _AttackPlan(types.SimpleNamespace):
+    """What one pgd_attack call decided before its first iteration (_plan_attack); nothing in it changes afterwards.
+      as given      model, cameras, groups, norm, alpha, epsilon, accumulate_grads, batch_loss, loss_reduction, background,
+                    success_fn, save_path, log
+      derived       dev, on_device, bg, originals, rank, world, my_idx / mine (the rank's view indices / cameras),
+                    loss_of(imgs, ids), timer (a _NoTimer when none was given)
+      decided       pipe (this call's own copy), frozen (parameters without gradient during the attack), reduce_names,
+                    use_batch, ring, buckets, norms, overlap, check_stream"""
+
+
+def _plan_attack(model, cameras, *, groups, norm, loss_fn, pipe, bg, streams, accumulate_grads, batch_loss, success_fn,
+                 originals, use_buckets, timer, overlap_success, cache_binning, fused_norms, batched, loss_reduction,
+                 **as_given) -> _AttackPlan:
+    """Takes every decision of a pgd_attack call, once.  Each predicate stands here and nowhere else; `pipe` is copied
+    up front and modified only here."""
+    groups = tuple(groups)
+    assert all(g in GROUPS for g in groups) and norm in ("l2", "linf") and loss_reduction in ("sum", "mean")
+    dev = model.get_xyz.device
+    on_device = dev.type == "cuda"
+    pipe = copy.copy(pipe or PipelineParams(skip_objects=True))
+    fused = takes_fused_path(model, pipe)                  # render() hands the raw parameters to the rasteriser
+    loss_fn = loss_fn or SurrogateDetector().to(dev)
+    if getattr(loss_fn, "takes_view_index", False):
+        # a loss that needs to know which views it is shown (detector_loss.make_loss_fn: every view has its own gt box)
+        # gets the global view indices of the renders; every other loss is called as before
+        loss_of = lambda imgs, ids: loss_fn(imgs, idx=list(ids))
+    else:
+        loss_of = lambda imgs, ids: loss_fn(imgs)
+    rank, world = _world()
+    my_idx = gdist.views_of_rank(len(cameras), rank, world)
+    mine = [cameras[i] for i in my_idx]
+    if originals is None:
+        originals = {n: getattr(model, n).detach().clone() for n in gdist.ATTACK_PARAMS}
+    # A colour-only attack needs no geometry gradients: those parameters are frozen for the duration of the attack and the
+    # rasteriser's backward drops the geometry sums and the projection chain rule (the reference computes and discards
+    # them: all seven tensors are re-wrapped with requires_grad=True, SURVEY.md section 3.1 quirk 2).
+    frozen = []
+    if groups == ("color",):
+        pipe.viewspace_grad = False
+        frozen = [p for p in (getattr(model, n) for n in ("_xyz", "_scaling", "_rotation", "_opacity")) if p.requires_grad]
+        if cache_binning and on_device and getattr(pipe, "render_cache", None) is None and fused:
+            from diff_gaussian_rasterization import RenderCache
+            pipe.render_cache = RenderCache(max_entries=4 * max(len(mine), 1) + 8)
+    # the rank's views through one launch chain (see `batched`)
+    # (a colour-only attack with kept binning keeps the BATCH's context: colour kernel + one compositor launch for all views)
+    use_batch = bool(batched and on_device and len(mine) >= 2 and can_batch(mine, model, pipe))
+    ring = StreamRing(min(streams, max(len(mine), 1)), dev) if on_device and not batch_loss and not use_batch else None
+    # Gradient buckets (fused path, all five groups differentiated): the rasteriser's backward writes a view's 59
+    # attribute gradients per Gaussian straight into a caller-owned flat buffer -- the first view of the iteration
+    # overwrites it, the others add -- instead of allocating 236 bytes per Gaussian per view and leaving the
+    # accumulation into .grad to autograd's read-modify-write.  One bucket per stream, folded once per iteration;
+    # the folded bucket IS the all-reduce buffer and becomes .grad without a copy.
+    # (only render()'s fused path fills a bucket: the same predicate decides here -- with convert_SHs_python /
+    # compute_cov3D_python the classic surface runs and autograd accumulates into .grad as before)
+    buckets = None
+    if (use_buckets and on_device and not frozen and fused
+            and all(getattr(model, n).requires_grad for n in gdist.ATTACK_PARAMS)):
+        from diff_gaussian_rasterization import GradBucket
+        buckets = [GradBucket(int(model.get_xyz.shape[0]), dev) for _ in range(ring.n if ring is not None else 1)]
+        pipe.grad_bucket = (lambda: buckets[ring.current]) if ring is not None else buckets[0]
+    # L2 steps: the global norms come out of the raster backward (GradNorms) while one backward per iteration writes the
+    # gradients the step uses -- one view, or one BATCH, per iteration on one GPU without the running-sum quirk
+    # (BASELINE config 3)
+    norms = None
+    if (fused_norms and norm == "l2" and on_device and world == 1 and not accumulate_grads and fused
+            and getattr(pipe, "grad_norms", None) is None):
+        from diff_gaussian_rasterization import GradNorms
+        norms = pipe.grad_norms = GradNorms(dev)
+    # overlap is off with batch_loss, with a timer, without success_fn, and off the device
+    overlap = bool(overlap_success and success_fn is not None and on_device and not batch_loss and timer is None)
+    return _AttackPlan(model=model, cameras=cameras, groups=groups, norm=norm, accumulate_grads=accumulate_grads,
+                       batch_loss=batch_loss, loss_reduction=loss_reduction, success_fn=success_fn, **as_given,
+                       dev=dev, on_device=on_device, bg=torch.zeros(3, device=dev) if bg is None else bg.to(dev),
+                       originals=originals, rank=rank, world=world, my_idx=my_idx, mine=mine, loss_of=loss_of,
+                       timer=_NoTimer() if timer is None else timer, pipe=pipe, frozen=frozen,
+                       reduce_names=("_features_dc", "_features_rest") if frozen else gdist.ATTACK_PARAMS,
+                       use_batch=use_batch, ring=ring, buckets=buckets, norms=norms, overlap=overlap,
+                       check_stream=_check_stream(dev) if overlap else None)
+
+
+class _AttackRun:
+    """What lives across the iterations of one pgd_attack call, and the stages of an iteration as methods.  What must
+    not move is stated where it is kept."""
+
+    def __init__(self, plan: _AttackPlan):
+        self.plan = plan
+        self.history = []
+        self.pending = None          # overlap: (rec, (success renders, event)) of the iteration whose flags are not read yet
+        self.cleared = True          # this iteration's gradients are cleared (not while `pending` holds the previous ones)
+        self.stopped = False         # the batch turned out to be done
+        self.run_flat = None         # accumulate_grads with buckets: the running sum
+        self.running = {}            # accumulate_grads without buckets, world > 1: the running sums of the reduced gradients
+        self.t_mark = time.perf_counter()
+
+    def clear_gradients(self) -> None:
+        p = self.plan
+        if p.norms is not None:
+            p.norms.begin()
+        if p.buckets is not None:
+            for b in p.buckets:
+                b.reset()
+        elif not p.accumulate_grads or p.world > 1:
+            p.model.zero_grad()                            # multi-GPU: .grad holds THIS step's gradient until reduced
+        self.cleared = True
+
+    def read_pending_flags(self) -> bool:
+        """Reads the flags of the iteration whose success check is still pending, if any; False: the batch is done."""
+        if self.pending is not None:
+            pending, self.pending = self.pending, None
+            self.stopped = self.finish_iteration(*pending)
+        return not self.stopped
+
+    def begin_iteration(self) -> bool:
+        """With a success check pending, iteration i's gradients stay in place until its flags are read: a batch that
+        turns out to be done returns with them and with iteration i's parameters, like the serial loop.  The flags are
+        read behind the first forward (after_first_forward); a rank without views has no forward to hide the wait
+        behind and reads them here, at the top of the iteration."""
+        if not self.plan.mine and not self.read_pending_flags():
+            return False
+        self.cleared = False
+        if self.pending is None:
+            self.clear_gradients()
+        return True
+
+    def after_first_forward(self) -> bool:
+        """The ONE copy of what follows the iteration's first forward, called with that forward enqueued and before
+        anything of it is used (in the per-view form after the first view only; later views pass through to the lap):
+        the previous iteration's success renders ran beside it, so now read their flags; if the batch is done return
+        False -- the forward was speculative, the caller drops it, nothing of it is differentiated, accumulated or
+        stepped --; else clear the gradients that were kept for that case; then the "render" lap."""
+        if not self.read_pending_flags():
+            return False
+        if not self.cleared:
+            self.clear_gradients()
+        self.plan.timer.lap("render")
+        return True
+
+    def _scaled(self, loss: torch.Tensor, stacked: bool) -> torch.Tensor:
+        """loss_reduction="mean" declares that loss_fn averages over the renders it is shown: a stacked loss of the rank's
+        views is weighted by (its views / B), a single view's by 1 / B."""
+        p = self.plan
+        if p.loss_reduction != "mean":
+            return loss
+        return loss * (len(p.mine) / len(p.cameras)) if stacked else loss / len(p.cameras)
+
+    def _backward(self, loss: torch.Tensor) -> None:
+        self.plan.timer.lap("loss")
+        loss.backward()
+        self.plan.timer.lap("backward")
+
+    def forward_backward(self) -> list:
+        """The iteration's forward and backward in the form the plan chose -> the detached losses of the rank's views."""
+        if self.plan.use_batch:
+            return self._batched()
+        return self._stacked() if self.plan.batch_loss else self._per_view()
+
+    def _batched(self) -> list:
+        """The rank's views through one launch chain; ONE raster backward for all of them."""
+        p = self.plan
+        imgs = render_batch(p.mine, p.model, p.pipe, p.bg)["render"]
+        if not self.after_first_forward():
+            return []
+        if p.batch_loss:
+            loss = self._scaled(p.loss_of(imgs, p.my_idx), True)
+            per_view = [loss]
+        else:
+            # (unbind, not slices: a slice's backward materialises a zero [B,3,H,W] tensor per view and adds it in)
+            per_view = [self._scaled(p.loss_of(im[None], [i]), False) for im, i in zip(imgs.unbind(0), p.my_idx)]
+            loss = torch.stack(per_view).sum()
+        self._backward(loss)
+        return [l_.detach() for l_ in per_view]
+
+    def _stacked(self) -> list:
+        """batch_loss without the batched launch chain: one render per view, stacked, one loss, one backward."""
+        p = self.plan
+        if not p.mine:
+            return []
+        renders = torch.stack([render(cam, p.model, p.pipe, p.bg)["render"] for cam in p.mine])
+        if not self.after_first_forward():                 # (overlap is off with batch_loss: nothing is ever pending here)
+            return []
+        loss = self._scaled(p.loss_of(renders, p.my_idx), True)
+        self._backward(loss)
+        return [loss.detach()]
+
+    def _per_view(self) -> list:
+        """One forward + backward per view over the stream ring: peak memory = one view per stream."""
+        p = self.plan
+        losses = []
+        for cam, i in zip(p.mine, p.my_idx):
+            with (p.ring.next() if p.ring is not None else contextlib.nullcontext()):
+                img = render(cam, p.model, p.pipe, p.bg)["render"]
+                if not self.after_first_forward():
+                    break
+                loss = self._scaled(p.loss_of(img[None], [i]), False)
+                self._backward(loss)
+                losses.append(loss.detach())
+        if p.ring is not None:
+            p.ring.join()
+        return losses
+
+    def reduce(self, losses: list) -> torch.Tensor:
+        """Bucket fold, all-reduce, running sums, .grad; -> the global loss of the iteration (still on the device)."""
+        p = self.plan
+        total = torch.stack(losses).sum() if losses else torch.zeros((), device=p.dev)
+        if p.buckets is not None:
+            tot = p.buckets[0]
+            for b in p.buckets[1:]:
+                tot.add_(b)
+            if not tot.used:
+                # a bucket that none of the rank's views wrote: with views, the renders did not take the path the buckets
+                # were made for; a rank without views contributes zeros
+                if p.mine:
+                    raise RuntimeError(
+                        "pgd_attack: the gradient bucket was not written by any of this rank's views (render() did "
+                        "not take the fused raw-parameter path); pass use_buckets=False")
+                tot.flat.zero_()
+                tot.used, tot.fresh = True, False
+            if p.world > 1:
+                gdist.all_reduce_sum_(tot.flat)            # ONE collective over 59 floats per Gaussian
+                torch.distributed.all_reduce(total)
+            if p.accumulate_grads:
+                # .grad aliases the running sum while the bucket keeps its own buffer
+                self.run_flat = tot.flat.clone() if self.run_flat is None else self.run_flat.add_(tot.flat)
+                keep = tot.flat
+                tot.flat = self.run_flat
+                tot.assign_to(p.model)
+                tot.flat = keep
+            else:
+                tot.assign_to(p.model)
+        elif p.world > 1:
+            gdist.allreduce_attribute_grads(p.model, names=p.reduce_names)     # one bucket: 236 MB, or 192 MB colour-only
+            torch.distributed.all_reduce(total)
+            if p.accumulate_grads:
+                # .grad is the running sum of the reduced gradients, identical on every rank
+                for n in p.reduce_names:
+                    q = getattr(p.model, n)
+                    self.running[n] = q.grad.clone() if n not in self.running else self.running[n].add_(q.grad)
+                    q.grad = self.running[n]
+        p.timer.lap("reduce")
+        return total
+
+    def step(self) -> None:
+        p = self.plan
+        _step(p.model, p.originals, p.groups, p.norm, p.alpha, p.epsilon, p.norms)
+        p.timer.lap("step")
+
+    def record(self, it: int, total: torch.Tensor) -> dict:
+        self.history.append(float(total))
+        return {"iter": it, "loss": self.history[-1], "views": len(self.plan.cameras)}
+
+    def check(self, rec: dict) -> bool:
+        """The success check behind the step; True: the batch is done.  With overlap the renders go to the side stream,
+        which waits for an event recorded behind the step, and the flags stay pending: the next iteration's first
+        forward is enqueued beside them."""
+        p = self.plan
+        if p.success_fn is None:
+            return self.finish_iteration(rec, None)
+        if p.overlap:
+            stepped = torch.cuda.Event()
+            stepped.record(torch.cuda.current_stream(p.dev))
+            p.check_stream.wait_event(stepped)
+            with torch.cuda.stream(p.check_stream):
+                imgs = render_combined(p.model, p.background, p.mine, p.bg, p.pipe)
+                rendered = torch.cuda.Event()
+                rendered.record(p.check_stream)
+            self.pending = (rec, (imgs, rendered))
+            return False
+        imgs = render_combined(p.model, p.background, p.mine, p.bg, p.pipe)
+        p.timer.lap("rerender")
+        return self.finish_iteration(rec, (imgs, None))
+
+    def finish_iteration(self, rec: dict, imgs_and_event) -> bool:
+        """Reads the success flags of an iteration (its renders are in `imgs_and_event`), logs it; True: batch done."""
+        p = self.plan
+        done = False
+        if imgs_and_event is not None:
+            imgs, ev = imgs_and_event
+            # overlap: success_fn runs on the side stream, and the main stream waits for the render event before the
+            # parameters are stepped again
+            with (torch.cuda.stream(p.check_stream) if ev is not None else contextlib.nullcontext()):
+                mine_flags = [p.success_fn(im, i) for im, i in zip(imgs, p.my_idx)]
+            if ev is not None:
+                torch.cuda.current_stream(p.dev).wait_event(ev)
+            flags = gather_success(mine_flags, len(p.cameras), p.rank, p.world, p.dev)
+            pgd_attack.last_successes = flags
+            rec["successes"] = flags
+            done = batch_done(flags, len(p.cameras))
+        if p.log is not None:
+            if p.on_device:
+                torch.cuda.synchronize()                  # log synchronises the device before it takes the time
+            now = time.perf_counter()
+            rec["seconds"] = now - self.t_mark
+            self.t_mark = now
+            p.log(rec)
+        if done and p.save_path is not None and p.rank == 0:
+            p.model.save_ply(p.save_path)
+        return done
 
 
 def pgd_attack(model, cameras: Sequence, *, iters: int = 20, alpha: float = 0.5, epsilon: float = 5.0,
@@ -230,265 +537,32 @@ def pgd_attack(model, cameras: Sequence, *, iters: int = 20, alpha: float = 0.5,
                         gsr_ctx_request_sumsq): one launch per tensor and one read of the gradient instead of two.  With
                         more than one view per iteration, several ranks or accumulate_grads the sums do not describe the
                         gradient the step uses and the step sums it itself, as before."""
-    groups = tuple(groups)
-    assert all(g in GROUPS for g in groups) and norm in ("l2", "linf") and loss_reduction in ("sum", "mean")
-    dev = model.get_xyz.device
-    pipe = pipe or PipelineParams(skip_objects=True)
-    bg = torch.zeros(3, device=dev) if bg is None else bg.to(dev)
-    loss_fn = loss_fn or SurrogateDetector().to(dev)
-    if getattr(loss_fn, "takes_view_index", False):
-        # a loss that needs to know which views it is shown (detector_loss.make_loss_fn: every view has its own gt box)
-        # gets the global view indices of the renders; every other loss is called as before
-        loss_of = lambda imgs, ids: loss_fn(imgs, idx=list(ids))
-    else:
-        loss_of = lambda imgs, ids: loss_fn(imgs)
-    rank, world = _world()
-    my_idx = gdist.views_of_rank(len(cameras), rank, world)
-    mine = [cameras[i] for i in my_idx]
-    if originals is None:
-        originals = {n: getattr(model, n).detach().clone() for n in gdist.ATTACK_PARAMS}
+    plan = _plan_attack(model, cameras, groups=groups, norm=norm, loss_fn=loss_fn, pipe=pipe, bg=bg, streams=streams,
+                        accumulate_grads=accumulate_grads, batch_loss=batch_loss, success_fn=success_fn, originals=originals,
+                        use_buckets=use_buckets, timer=timer, overlap_success=overlap_success, cache_binning=cache_binning,
+                        fused_norms=fused_norms, batched=batched, alpha=alpha, epsilon=epsilon, loss_reduction=loss_reduction,
+                        background=background, save_path=save_path, log=log)
+    run = _AttackRun(plan)
     pgd_attack.last_successes = None
-    # A colour-only attack needs no geometry gradients: freeze those parameters for the duration of the attack and the
-    # rasteriser's backward drops the geometry sums and the projection chain rule (the reference computes and discards
-    # them: all seven tensors are re-wrapped with requires_grad=True, SURVEY.md section 3.1 quirk 2).
-    frozen = []
-    if groups == ("color",):
-        pipe = copy.copy(pipe)
-        pipe.viewspace_grad = False
-        for n in ("_xyz", "_scaling", "_rotation", "_opacity"):
-            p = getattr(model, n)
-            if p.requires_grad:
-                p.requires_grad_(False)
-                frozen.append(p)
-    if (cache_binning and groups == ("color",) and dev.type == "cuda" and getattr(pipe, "render_cache", None) is None
-            and takes_fused_path(model, pipe)):
-        from diff_gaussian_rasterization import RenderCache
-        pipe.render_cache = RenderCache(max_entries=4 * max(len(mine), 1) + 8)      # pipe is this call's own copy here
-    # the rank's views through one launch chain (see `batched`)
-    # (a colour-only attack with kept binning keeps the BATCH's context: colour kernel + one compositor launch for all views)
-    use_batch = bool(batched and dev.type == "cuda" and len(mine) >= 2 and can_batch(mine, model, pipe))
-    reduce_names = ("_features_dc", "_features_rest") if frozen else gdist.ATTACK_PARAMS
-    running = {}                                           # accumulate_grads with world > 1: the running sums
     try:
-        history = []
-        ring = StreamRing(min(streams, max(len(mine), 1)), dev) if dev.type == "cuda" and not batch_loss and not use_batch else None
-        # Gradient buckets (fused path, all five groups differentiated): the rasteriser's backward writes a view's 59
-        # attribute gradients per Gaussian straight into a caller-owned flat buffer -- the first view of the iteration
-        # overwrites it, the others add -- instead of allocating 236 bytes per Gaussian per view and leaving the
-        # accumulation into .grad to autograd's read-modify-write.  One bucket per stream, folded once per iteration;
-        # the folded bucket IS the all-reduce buffer and becomes .grad without a copy.
-        buckets = None
-        # (only render()'s fused path fills a bucket: the same predicate decides here -- with convert_SHs_python /
-        # compute_cov3D_python the classic surface runs and autograd accumulates into .grad as before)
-        if (use_buckets and dev.type == "cuda" and not frozen and takes_fused_path(model, pipe)
-                and all(getattr(model, n).requires_grad for n in gdist.ATTACK_PARAMS)):
-            from diff_gaussian_rasterization import GradBucket
-            P = int(model.get_xyz.shape[0])
-            buckets = [GradBucket(P, dev) for _ in range(ring.n if ring is not None else 1)]
-            pipe = copy.copy(pipe)
-            pipe.grad_bucket = (lambda: buckets[ring.current]) if ring is not None else buckets[0]
-        # L2 steps: the global norms come out of the raster backward (GradNorms) while one backward per iteration writes the
-        # gradients the step uses -- one view per iteration on one GPU without the running-sum quirk (BASELINE config 3)
-        norms = None
-        # (or one BATCH per iteration: its one backward writes the summed gradient)
-        if (fused_norms and norm == "l2" and dev.type == "cuda" and world == 1 and not accumulate_grads and takes_fused_path(model, pipe)
-                and getattr(pipe, "grad_norms", None) is None):
-            from diff_gaussian_rasterization import GradNorms
-            norms = GradNorms(dev)
-            pipe = copy.copy(pipe)
-            pipe.grad_norms = norms
-        run_flat = None                                    # accumulate_grads with buckets: the running sum
-        overlap = (overlap_success and success_fn is not None and dev.type == "cuda" and not batch_loss and timer is None)
-        check_stream = _check_stream(dev) if overlap else None
-        pending = None                                     # overlap: the success renders whose flags have not been read yet
-        t_mark = [time.perf_counter()]
-
-        def finish_iteration(rec, imgs_and_event):
-            """Reads the success flags of an iteration (its renders are in `imgs_and_event`), logs it; True: batch done."""
-            done = False
-            if imgs_and_event is not None:
-                imgs, ev = imgs_and_event
-                if ev is not None:
-                    with torch.cuda.stream(check_stream):
-                        mine_flags = [success_fn(im, i) for im, i in zip(imgs, my_idx)]
-                    torch.cuda.current_stream(dev).wait_event(ev)      # the parameters are not stepped under the renders
-                else:
-                    mine_flags = [success_fn(im, i) for im, i in zip(imgs, my_idx)]
-                flags = gather_success(mine_flags, len(cameras), rank, world, dev)
-                pgd_attack.last_successes = flags
-                rec["successes"] = flags
-                done = batch_done(flags, len(cameras))
-            if log is not None:
-                if dev.type == "cuda":
-                    torch.cuda.synchronize()
-                now = time.perf_counter()
-                rec["seconds"] = now - t_mark[0]
-                t_mark[0] = now
-                log(rec)
-            if done and save_path is not None and rank == 0:
-                model.save_ply(save_path)
-            return done
-
-        stopped = False
+        for p in plan.frozen:
+            p.requires_grad_(False)
         for it in range(iters):
-            if timer is not None:
-                timer.start()
-            if pending is not None and not mine:           # a rank without views has no forward to hide the wait behind
-                stopped = finish_iteration(*pending)
-                pending = None
-                if stopped:
-                    break
-            def clear_gradients():
-                if norms is not None:
-                    norms.begin()
-                if buckets is not None:
-                    for b in buckets:
-                        b.reset()
-                elif not accumulate_grads or world > 1:
-                    model.zero_grad()                      # multi-GPU: .grad holds THIS step's gradient until reduced
-            # (with a success check pending, the gradients of the previous iteration stay in place until its flags are
-            # read: a batch that turns out to be done returns with them, like the serial loop)
-            cleared = pending is None
-            if cleared:
-                clear_gradients()
-            losses = []
-            if use_batch:
-                imgs_b = render_batch(mine, model, pipe, bg)["render"]
-                if pending is not None:
-                    # the previous iteration's success renders ran beside this forward: now read their flags
-                    stopped = finish_iteration(*pending)
-                    pending = None
-                    if stopped:
-                        del imgs_b                         # speculative: never differentiated, nothing accumulated
-                        break
-                if not cleared:
-                    clear_gradients()
-                    cleared = True
-                if timer is not None:
-                    timer.lap("render")
-                if batch_loss:
-                    loss = loss_of(imgs_b, my_idx)
-                    if loss_reduction == "mean":
-                        loss = loss * (len(mine) / len(cameras))
-                    losses.append(loss.detach())
-                else:
-                    # (unbind, not slices: a slice's backward materialises a zero [B,3,H,W] tensor per view and adds it in)
-                    per_view = [loss_of(im[None], [i]) for im, i in zip(imgs_b.unbind(0), my_idx)]
-                    if loss_reduction == "mean":
-                        per_view = [l_ / len(cameras) for l_ in per_view]
-                    losses.extend(l_.detach() for l_ in per_view)
-                    loss = torch.stack(per_view).sum()
-                if timer is not None:
-                    timer.lap("loss")
-                loss.backward()                            # ONE raster backward for the rank's views
-                if timer is not None:
-                    timer.lap("backward")
-            elif batch_loss:
-                if mine:
-                    renders = torch.stack([render(cam, model, pipe, bg)["render"] for cam in mine])
-                    loss = loss_of(renders, my_idx)
-                    if loss_reduction == "mean":
-                        loss = loss * (len(mine) / len(cameras))
-                    loss.backward()
-                    losses.append(loss.detach())
-            else:
-                for vi, cam in enumerate(mine):            # one forward+backward per view: peak memory = one view per stream
-                    with (ring.next() if ring is not None else contextlib.nullcontext()):
-                        img = render(cam, model, pipe, bg)["render"]
-                        if pending is not None:
-                            # the previous iteration's success renders ran beside this forward: now read their flags
-                            stopped = finish_iteration(*pending)
-                            pending = None
-                            if stopped:
-                                del img                    # speculative: never differentiated, nothing accumulated
-                                break
-                        if not cleared:
-                            clear_gradients()
-                            cleared = True
-                        if timer is not None:
-                            timer.lap("render")
-                        loss = loss_of(img[None], [my_idx[vi]])
-                        if loss_reduction == "mean":
-                            loss = loss / len(cameras)
-                        if timer is not None:
-                            timer.lap("loss")
-                        loss.backward()
-                        if timer is not None:
-                            timer.lap("backward")
-                        losses.append(loss.detach())
-                if ring is not None:
-                    ring.join()
-                if stopped:
-                    break
-            total = torch.stack(losses).sum() if losses else torch.zeros((), device=dev)
-            if buckets is not None:
-                tot = buckets[0]
-                for b in buckets[1:]:
-                    tot.add_(b)
-                if not tot.used:
-                    if mine:                               # a bucket that no backward of this rank's views wrote: the
-                        raise RuntimeError(                # renders did not take the path the buckets were made for
-                            "pgd_attack: the gradient bucket was not written by any of this rank's views (render() did "
-                            "not take the fused raw-parameter path); pass use_buckets=False")
-                    tot.flat.zero_()                       # a rank without views contributes zeros
-                    tot.used, tot.fresh = True, False
-                if world > 1:
-                    flat = tot.flat
-                    if flat.is_cuda and torch.distributed.get_backend() == "gloo":
-                        host = flat.cpu()                  # rehearsal on one GPU: gloo reduces host tensors
-                        torch.distributed.all_reduce(host)
-                        flat.copy_(host)
-                    else:
-                        torch.distributed.all_reduce(flat)     # ONE collective over 59 floats per Gaussian
-                    torch.distributed.all_reduce(total)
-                if accumulate_grads:
-                    run_flat = tot.flat.clone() if run_flat is None else run_flat.add_(tot.flat)
-                    keep = tot.flat
-                    tot.flat = run_flat
-                    tot.assign_to(model)
-                    tot.flat = keep
-                else:
-                    tot.assign_to(model)
-            elif world > 1:
-                gdist.allreduce_attribute_grads(model, names=reduce_names)     # one bucket: 236 MB, or 192 MB colour-only
-                torch.distributed.all_reduce(total)
-                if accumulate_grads:
-                    for n in reduce_names:
-                        p = getattr(model, n)
-                        running[n] = p.grad.clone() if n not in running else running[n].add_(p.grad)
-                        p.grad = running[n]
-            if timer is not None:
-                timer.lap("reduce")
-            _step(model, originals, groups, norm, alpha, epsilon, norms)
-            if timer is not None:
-                timer.lap("step")
-            history.append(float(total))
-            rec = {"iter": it, "loss": history[-1], "views": len(cameras)}
-            if success_fn is None:
-                finish_iteration(rec, None)
-                continue
-            if overlap:
-                # success renders on the side stream, behind the step; the next iteration's first forward goes beside them
-                stepped = torch.cuda.Event()
-                stepped.record(torch.cuda.current_stream(dev))
-                check_stream.wait_event(stepped)
-                with torch.cuda.stream(check_stream):
-                    imgs = render_combined(model, background, mine, bg, pipe)
-                    rendered = torch.cuda.Event()
-                    rendered.record(check_stream)
-                pending = (rec, (imgs, rendered))
-                continue
-            imgs = render_combined(model, background, mine, bg, pipe)
-            if timer is not None:
-                timer.lap("rerender")
-            if finish_iteration(rec, (imgs, None)):
+            plan.timer.start()
+            if not run.begin_iteration():                  # a rank without views reads the pending flags here
                 break
-        if pending is not None:                            # the last iteration's flags
-            finish_iteration(*pending)
+            losses = run.forward_backward()
+            if run.stopped:                                # the flags read behind the first forward: the batch was done
+                break
+            total = run.reduce(losses)
+            run.step()
+            if run.check(run.record(it, total)):
+                break
+        run.read_pending_flags()                           # the last iteration's flags are read before returning
     finally:
-        for p in frozen:
+        for p in plan.frozen:                              # on every exit, an exception included
             p.requires_grad_(True)
-    return history
+    return run.history
 
 
 pgd_attack.last_successes = None

@@ -22,6 +22,8 @@ import torch
 from diff_gaussian_rasterization import detloss_ops
 from diff_gaussian_rasterization.detloss_ops import DetLossSpec
 
+from ._views import ViewRows, gt_rows
+
 Levels = List[Tuple[int, int, float]]
 
 
@@ -67,16 +69,7 @@ class DetectorLoss:
         return flat, levels
 
     def _gt(self, gt_boxes, gt_cls, device) -> Tuple[torch.Tensor, torch.Tensor]:
-        gb = torch.as_tensor(gt_boxes, dtype=torch.float32).to(device)
-        gc = torch.as_tensor(gt_cls).to(device=device, dtype=torch.int32)
-        if gb.dim() == 2:
-            gb, gc = gb[:, None, :], gc.reshape(-1, 1)
-        s, ox, oy = self.affine
-        if (s, ox, oy) != (1.0, 0.0, 0.0):
-            gb = gb * s + torch.tensor([ox, oy, ox, oy], dtype=torch.float32, device=device)
-        # a row holding a NaN is absent
-        gc = torch.where(torch.isnan(gb).any(-1), torch.full_like(gc, -1), gc)
-        return torch.nan_to_num(gb, nan=0.0), gc
+        return gt_rows(gt_boxes, gt_cls, device, self.affine)
 
     def loss(self, pred: Union[torch.Tensor, Sequence[torch.Tensor]], gt_boxes, gt_cls) -> Tuple[torch.Tensor, torch.Tensor]:
         """pred [B,64+nc,A] or the head's feature maps; gt_boxes [B,M,4] (or [B,4]: one row per image) x1 y1 x2 y2; gt_cls
@@ -99,17 +92,11 @@ def make_loss_fn(detector_head: Callable, detector_input: Optional[Callable], de
     the frame detector_loss expects (use detector_loss.to_letterbox for boxes in the render's frame); target: the class
     the loss pulls towards, one int or one per view; idx: the views the renders show (default 0..B-1).  The loss of a
     batch is normalised over the batch, as the library does; pgd_attack(batch_loss=True) calls it once per step."""
-    gt_all = torch.as_tensor(gt_bboxes, dtype=torch.float32)
-    tg_all = torch.as_tensor(target, dtype=torch.int32)
+    views = ViewRows(gt_bboxes, target)
 
     def loss_fn(renders: torch.Tensor, idx: Optional[Sequence[int]] = None) -> torch.Tensor:
-        x = renders[None] if renders.dim() == 3 else renders
-        ids = list(range(int(x.shape[0]))) if idx is None else [int(i) for i in idx]
-        if len(ids) != int(x.shape[0]):
-            raise ValueError(f"loss_fn: {len(ids)} view indices for {int(x.shape[0])} renders")
+        x, gt, cls = views(renders, idx)
         feats = detector_head(detector_input(x) if detector_input is not None else x)
-        gt = gt_all[ids]
-        cls = tg_all.expand(gt_all.shape[0])[ids] if tg_all.dim() == 0 else tg_all[ids]
         return detector_loss.loss(feats, gt, cls)[0]
 
     loss_fn.takes_view_index = True

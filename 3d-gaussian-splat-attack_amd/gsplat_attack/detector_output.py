@@ -22,6 +22,8 @@ import torch
 from diff_gaussian_rasterization import detect_ops
 from diff_gaussian_rasterization.detect_ops import DetSpec
 
+from ._views import ViewRows, verdict_of
+
 
 class DetectorOutput:
     """layout 0: raw [B,A,4+has_obj+C] (YOLOv3/v5), 1: raw [B,4+has_obj+C,A] (YOLOv8/v11); box_format 0: (xc, yc, w, h),
@@ -60,16 +62,7 @@ class DetectorOutput:
         """gt_bboxes [B,4] (x1 y1 x2 y2 in the frame the affine maps to; None or a NaN row: no box for that view)
         -> (flags int32 [B] on the device: bit 0 success, bit 1 target_exists, bit 2 untarget_absent;
             best [B,4]: iou, score, class, row of the detection closest to the gt box, -1 where there is none)."""
-        dets, counts = self.detections(raw)
-        gt = None if gt_bboxes is None else torch.as_tensor(gt_bboxes, dtype=torch.float32).to(dets.device)
-        return detect_ops.verdict(dets, counts, gt, target, untarget, is_targeted, iou_match)
-
-
-def _gt_rows(gt_bboxes, idx: Sequence[int], device) -> Optional[torch.Tensor]:
-    if gt_bboxes is None:
-        return None
-    gt = torch.as_tensor(gt_bboxes, dtype=torch.float32)
-    return gt[list(idx)].to(device)
+        return verdict_of(*self.detections(raw), gt_bboxes, target, untarget, is_targeted, iou_match)
 
 
 def batch_success(images: torch.Tensor, detector_head: Callable[[torch.Tensor], torch.Tensor], detector_input: Callable,
@@ -78,10 +71,9 @@ def batch_success(images: torch.Tensor, detector_head: Callable[[torch.Tensor], 
     """images [B,3,H,W] -> detector_input -> detector_head (raw output) -> detector_output.verdict; the B success bits
     come back in one device-to-host copy.  gt_bboxes: [V,4] or None; idx: the views the images show (default 0..B-1)."""
     with torch.no_grad():
-        x = images[None] if images.dim() == 3 else images
-        idx = list(range(int(x.shape[0]))) if idx is None else list(idx)
+        x, gt, _ = ViewRows(gt_bboxes)(images, idx)
         raw = detector_head(detector_input(x) if detector_input is not None else x)
-        flags, _ = detector_output.verdict(raw, _gt_rows(gt_bboxes, idx, raw.device), target, untarget, is_targeted, iou_match)
+        flags, _ = detector_output.verdict(raw, gt, target, untarget, is_targeted, iou_match)
         return [bool(v & 1) for v in flags.cpu().tolist()]
 
 

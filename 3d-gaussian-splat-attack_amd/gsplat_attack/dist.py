@@ -42,6 +42,17 @@ def views_of_rank(n_views: int, rank: int, world: int) -> List[int]:
     return list(range(rank, n_views, world))
 
 
+def all_reduce_sum_(tensor: torch.Tensor, group=None) -> None:
+    """Sum all-reduce in place.  gloo reduces host tensors only: a device tensor under it (tests, rehearsals on one GPU)
+    travels through the host."""
+    if tensor.is_cuda and dist.get_backend(group) == "gloo":
+        host = tensor.cpu()
+        dist.all_reduce(host, group=group)
+        tensor.copy_(host)
+    else:
+        dist.all_reduce(tensor, group=group)
+
+
 def _flat_view_of(grads):
     """If the gradients are back-to-back slices of one buffer (the fused backward allocates them that way), return a
     1-D tensor aliasing exactly that span, else None."""
@@ -116,9 +127,7 @@ class BucketAllReduce:
         self.bytes += sum(p.numel() for p in pieces) * 4
         if dist.get_backend(self.group) == "gloo" and pieces[0].is_cuda:
             for p in pieces:
-                h = p.cpu()
-                dist.all_reduce(h, group=self.group)
-                p.copy_(h)
+                all_reduce_sum_(p, self.group)
         else:
             for p in pieces:
                 self.works.append(dist.all_reduce(p, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
@@ -129,14 +138,8 @@ class BucketAllReduce:
         if not self.active:
             return 0
         if self.bytes == 0:                              # unchunked: one collective over the flat buffer
-            flat = self.bucket.flat
-            if dist.get_backend(self.group) == "gloo" and flat.is_cuda:
-                h = flat.cpu()
-                dist.all_reduce(h, group=self.group)
-                flat.copy_(h)
-            else:
-                dist.all_reduce(flat, group=self.group)
-            self.bytes = flat.numel() * 4
+            all_reduce_sum_(self.bucket.flat, self.group)
+            self.bytes = self.bucket.flat.numel() * 4
         for w in self.works:
             if w is not None:
                 w.wait()

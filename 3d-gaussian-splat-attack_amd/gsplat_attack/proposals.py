@@ -25,6 +25,8 @@ from diff_gaussian_rasterization import rpn_ops, rpnloss_ops
 from diff_gaussian_rasterization.rpn_ops import RpnSpec
 from diff_gaussian_rasterization.rpnloss_ops import RpnLossSpec
 
+from ._views import gt_rows
+
 
 class Proposals(NamedTuple):
     """boxes [B,R,4] x1 y1 x2 y2 in image pixels, best first, zero rows beyond the count; scores [B,R]: their objectness
@@ -160,25 +162,12 @@ class RpnLoss:
             out.append(rpnloss_ops.AnchorLevel(ca, stride, (int(hw[0]), int(hw[1])), offset))
         return out
 
-    @staticmethod
-    def _gt(gt_boxes, gt_cls, device):
-        """[B,M,4] / [B,M], or [B,4] / [B]: one row per image; gt_cls None: every row present; a row holding a NaN is absent."""
-        gb = torch.as_tensor(gt_boxes, dtype=torch.float32).to(device)
-        if gb.dim() == 2:
-            gb = gb[:, None, :]
-        if gt_cls is None:
-            gc = torch.zeros(gb.shape[:2], dtype=torch.int32, device=device)
-        else:
-            gc = torch.as_tensor(gt_cls).to(device=device, dtype=torch.int32).reshape(gb.shape[:2])
-        gc = torch.where(torch.isnan(gb).any(-1), torch.full_like(gc, -1), gc)
-        return torch.nan_to_num(gb, nan=0.0), gc
-
     def labels(self, sizes, gt_boxes, gt_cls=None, seed: Optional[int] = None, want_pre: bool = False) -> "rpnloss_ops.Labels":
         """sizes: one (Hf, Wf) per level (or the logits themselves); gt_boxes on the device the labels are wanted on ->
         rpnloss_ops.Labels(labels, matched, counts, prelabels)."""
         device = torch.as_tensor(gt_boxes).device
         hw = [tuple(s.shape[-2:]) if isinstance(s, torch.Tensor) else tuple(s) for s in self._per_level(sizes, "sizes")]
-        gb, gc = self._gt(gt_boxes, gt_cls, device)
+        gb, gc = gt_rows(gt_boxes, gt_cls, device)
         spec = self.spec if seed is None else self.spec._replace(seed=int(seed))
         return rpnloss_ops.label(self._anchor_levels(hw, device), gb, gc, spec, want_pre=want_pre)
 
@@ -187,6 +176,6 @@ class RpnLoss:
         the total); total is differentiable with respect to the logits and the deltas."""
         lg, dl = self._per_level(logits, "logits"), self._per_level(deltas, "deltas")
         device = lg[0].device
-        gb, gc = self._gt(gt_boxes, gt_cls, device)
+        gb, gc = gt_rows(gt_boxes, gt_cls, device)
         spec = self.spec if seed is None else self.spec._replace(seed=int(seed))
         return rpnloss_ops.rpn_loss(lg, dl, self._anchor_levels([tuple(x.shape[-2:]) for x in lg], device), gb, gc, spec)

@@ -27,18 +27,10 @@ from typing import Callable, Optional, Sequence, Tuple, Union
 
 import torch
 
-from diff_gaussian_rasterization import detect_ops, fpn_ops, rcnn_ops
+from diff_gaussian_rasterization import fpn_ops, rcnn_ops
 from diff_gaussian_rasterization.rcnn_ops import RcnnSpec, Sample
 
-
-def _gt(gt_boxes, gt_cls, device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """[B,M,4] / [B,M], or [B,4] / [B]: one row per image; a row holding a NaN is absent."""
-    gb = torch.as_tensor(gt_boxes, dtype=torch.float32).to(device)
-    gc = torch.as_tensor(gt_cls).to(device=device, dtype=torch.int32)
-    if gb.dim() == 2:
-        gb, gc = gb[:, None, :], gc.reshape(-1, 1)
-    gc = torch.where(torch.isnan(gb).any(-1), torch.full_like(gc, -1), gc)
-    return torch.nan_to_num(gb, nan=0.0), gc
+from ._views import ViewRows, gt_rows, verdict_of
 
 
 class ProposalSampler:
@@ -62,7 +54,7 @@ class ProposalSampler:
                n_prop: Optional[torch.Tensor] = None) -> Sample:
         """proposals [B,R,4] x1 y1 x2 y2 in pixels, in the proposer's order; gt_boxes [B,M,4] (or [B,4]); gt_cls [B,M] (or [B]),
         negative: absent.  The same seed gives the same sample; pass a new one for a fresh draw."""
-        gb, gc = _gt(gt_boxes, gt_cls, proposals.device)
+        gb, gc = gt_rows(gt_boxes, gt_cls, proposals.device)
         spec = self.spec._replace(seed=self.seed if seed is None else int(seed))
         return rcnn_ops.sample(proposals, gb, gc, self.nc, spec, n_prop=n_prop)
 
@@ -170,8 +162,7 @@ class RoIHeadOutput:
         -> (flags int32 [B] on the device: bit 0 success, bit 1 target_exists, bit 2 untarget_absent;
             best [B,4]: iou, score, class, row of the detection closest to the gt box, -1 where there is none)."""
         dets, counts = self.detect(scores, deltas, proposals, n_prop=n_prop)
-        gt = None if gt_bboxes is None else torch.as_tensor(gt_bboxes, dtype=torch.float32).to(dets.device)
-        return detect_ops.verdict(dets, counts, gt, target, untarget, is_targeted, iou_match)
+        return verdict_of(dets, counts, gt_bboxes, target, untarget, is_targeted, iou_match)
 
 
 def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable, detector_input: Optional[Callable],
@@ -192,14 +183,10 @@ def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable,
     row, a NaN row absent) is added to the box head's loss -- the only path from the RPN head back to the renders."""
     if rpn_loss is not None and getattr(proposer, "head", None) is None:
         raise ValueError("make_roi_loss_fn: rpn_loss needs a proposer with .head and .propose (an RpnProposer built with head=...)")
-    gt_all = torch.as_tensor(gt_bboxes, dtype=torch.float32)
-    tg_all = torch.as_tensor(target, dtype=torch.int32)
+    views = ViewRows(gt_bboxes, target)
 
     def loss_fn(renders: torch.Tensor, idx: Optional[Sequence[int]] = None) -> torch.Tensor:
-        x = renders[None] if renders.dim() == 3 else renders
-        ids = list(range(int(x.shape[0]))) if idx is None else [int(i) for i in idx]
-        if len(ids) != int(x.shape[0]):
-            raise ValueError(f"loss_fn: {len(ids)} view indices for {int(x.shape[0])} renders")
+        x, gt, cls = views(renders, idx)
         features = backbone(detector_input(x) if detector_input is not None else x)
         rpn_logits = rpn_deltas = None
         if rpn_loss is not None:                                         # the head once, with gradient; the proposals from its detached outputs
@@ -217,8 +204,6 @@ def make_roi_loss_fn(backbone: Callable, proposer: Callable, box_head: Callable,
         n_prop = None
         if not isinstance(proposals, torch.Tensor):                      # (proposals, n_prop): rows beyond the count are no candidates
             proposals, n_prop = proposals
-        gt = gt_all[ids]
-        cls = tg_all.expand(gt_all.shape[0])[ids] if tg_all.dim() == 0 else tg_all[ids]
         smp = sampler.sample(proposals, gt, cls, n_prop=n_prop)
         if pooler is not None:
             pooled = pooler(features, smp.rois, smp.counts)

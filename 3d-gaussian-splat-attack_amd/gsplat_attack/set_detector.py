@@ -20,8 +20,10 @@ from typing import Callable, Optional, Sequence, Tuple, Union
 
 import torch
 
-from diff_gaussian_rasterization import detect_ops, setdet_ops
+from diff_gaussian_rasterization import setdet_ops
 from diff_gaussian_rasterization.setdet_ops import SetDetSpec
+
+from ._views import ViewRows, gt_rows, verdict_of
 
 
 def _frame(frame) -> Tuple[float, float]:
@@ -55,13 +57,7 @@ class SetDetectorLoss:
         self.spec = SetDetSpec(w, h, *(float(v) for v in vals))
 
     def _gt(self, gt_boxes, gt_cls, device) -> Tuple[torch.Tensor, torch.Tensor]:
-        gb = torch.as_tensor(gt_boxes, dtype=torch.float32).to(device)
-        gc = torch.as_tensor(gt_cls).to(device=device, dtype=torch.int32)
-        if gb.dim() == 2:
-            gb, gc = gb[:, None, :], gc.reshape(-1, 1)
-        # a row holding a NaN is absent
-        gc = torch.where(torch.isnan(gb).any(-1), torch.full_like(gc, -1), gc)
-        return torch.nan_to_num(gb, nan=0.0), gc
+        return gt_rows(gt_boxes, gt_cls, device)
 
     def _check(self, logits: torch.Tensor) -> None:
         if logits.dim() != 3 or logits.shape[2] != self.nc + 1:
@@ -103,9 +99,7 @@ class SetDetectorOutput:
         """gt_bboxes [B,4] (x1 y1 x2 y2 in the frame; None or a NaN row: no box for that view)
         -> (flags int32 [B] on the device: bit 0 success, bit 1 target_exists, bit 2 untarget_absent;
             best [B,4]: iou, score, class, row of the detection closest to the gt box, -1 where there is none)."""
-        dets, counts = self.detect(logits, boxes)
-        gt = None if gt_bboxes is None else torch.as_tensor(gt_bboxes, dtype=torch.float32).to(dets.device)
-        return detect_ops.verdict(dets, counts, gt, target, untarget, is_targeted, iou_match)
+        return verdict_of(*self.detect(logits, boxes), gt_bboxes, target, untarget, is_targeted, iou_match)
 
 
 def make_set_loss_fn(detector_head: Callable, detector_input: Optional[Callable], detector_loss: SetDetectorLoss, gt_bboxes,
@@ -114,17 +108,11 @@ def make_set_loss_fn(detector_head: Callable, detector_input: Optional[Callable]
     {"pred_logits", "pred_boxes"} or (logits, boxes); gt_bboxes [V,4]: every view's box in detector_loss's frame; target: the
     class the loss pulls towards, one int or one per view; idx: the views the renders show (default 0..B-1).  The loss of a
     batch is normalised over the batch, as the criterion does; pgd_attack(batch_loss=True) calls it once per step."""
-    gt_all = torch.as_tensor(gt_bboxes, dtype=torch.float32)
-    tg_all = torch.as_tensor(target, dtype=torch.int32)
+    views = ViewRows(gt_bboxes, target)
 
     def loss_fn(renders: torch.Tensor, idx: Optional[Sequence[int]] = None) -> torch.Tensor:
-        x = renders[None] if renders.dim() == 3 else renders
-        ids = list(range(int(x.shape[0]))) if idx is None else [int(i) for i in idx]
-        if len(ids) != int(x.shape[0]):
-            raise ValueError(f"loss_fn: {len(ids)} view indices for {int(x.shape[0])} renders")
+        x, gt, cls = views(renders, idx)
         logits, boxes = _head_output(detector_head(detector_input(x) if detector_input is not None else x))
-        gt = gt_all[ids]
-        cls = tg_all.expand(gt_all.shape[0])[ids] if tg_all.dim() == 0 else tg_all[ids]
         return detector_loss.loss(logits, boxes, gt, cls)[0]
 
     loss_fn.takes_view_index = True

@@ -41,7 +41,7 @@ def _worker(rank, world, port, n_views, out_dir, accumulate):
     torch.cuda.set_device(dev)
     model, cams, _ = make_scene("nyc-1M", device=dev, n_views=n_views, **KW)
     # the fused backward hands out ONE flat bucket: the collective is a single all-reduce of 59 floats per Gaussian
-    render(cams[rank], model, PipelineParams(skip_objects=True), torch.zeros(3, device=dev))["render"].sum().backward()
+    render(cams[rank % n_views], model, PipelineParams(skip_objects=True), torch.zeros(3, device=dev))["render"].sum().backward()
     flat = gdist._flat_view_of([getattr(model, n).grad for n in gdist.ATTACK_PARAMS])
     assert flat is not None and flat.numel() == 59 * model.get_xyz.shape[0]
     assert gdist.allreduce_attribute_grads(model) == flat.numel() * 4
@@ -53,7 +53,7 @@ def _worker(rank, world, port, n_views, out_dir, accumulate):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("n_views,accumulate", [(4, False), (3, True)])
+@pytest.mark.parametrize("n_views,accumulate", [(4, False), (3, True), (1, False)])    # one view: rank 1 folds a bucket nothing wrote
 def test_two_rank_attack_equals_the_single_process_batch(tmp_path, n_views, accumulate):
     from gsplat_attack import dist as gdist
     from gsplat_attack.scenes import make_scene
