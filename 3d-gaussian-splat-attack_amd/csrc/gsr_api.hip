@@ -27,6 +27,7 @@
 #include "gsr_knnq.hip.h"
 #include "gsr_pgd.hip.h"
 #include "gsr_adam.hip.h"
+#include "gsr_densify.hip.h"
 #include "gsr_groups.hip.h"
 #include "gsr_hull.h"
 #include "gsr_image.hip.h"
@@ -2209,6 +2210,223 @@ int gsr_adam_step_multi(int32_t n, void* const* x, const void* const* g, void* c
   else hipLaunchKernelGGL((k_adam_step_multi<false>), dim3((unsigned)blocks), dim3(ADAM_BLOCK), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "gsr_adam_step_multi: launch failed: %s", hipGetErrorString(e));
+  return GSR_OK;
+}
+
+// ---- adaptive density control (gsr_densify.h / gsr_densify.hip.h): the plan's workspace is the caller's; one read-back (the
+// three totals) in gsr_densify_plan, none elsewhere.  Every check is made on the host before the first launch.
+struct DensWs {
+  uint8_t* code;
+  uint32_t *off_keep, *off_clone, *off_split, *sums, *totals;
+};
+
+// the workspace's regions: the class codes, the three 0/1 counts (scanned in place, P + 1 words each), the scan's block sums,
+// the three totals
+static DensWs dens_regions(Carve& c, long long P) {
+  DensWs w;
+  w.code = c.take<uint8_t>((size_t)P + 1);
+  w.off_keep = c.take<uint32_t>((size_t)P + 1);
+  w.off_clone = c.take<uint32_t>((size_t)P + 1);
+  w.off_split = c.take<uint32_t>((size_t)P + 1);
+  w.sums = c.take<uint32_t>((size_t)P / 2048 + 2);
+  w.totals = c.take<uint32_t>(4);
+  return w;
+}
+
+int gsr_densify_plan_bytes(int64_t P, int64_t* bytes) {
+  if (P < 0 || P > DENS_MAX_ROWS) return set_err(GSR_ERR_INVALID, "gsr_densify_plan_bytes: P=%lld (0..2^28 rows)", (long long)P);
+  if (!bytes) return set_err(GSR_ERR_INVALID, "gsr_densify_plan_bytes: null bytes");
+  Carve c;
+  dens_regions(c, P);
+  *bytes = (int64_t)c.off;
+  return GSR_OK;
+}
+
+int gsr_densify_stats(const float* grad, const int32_t* radii, const uint8_t* filter, int32_t B, int64_t P, float* accum,
+                      float* denom, float* max_radii, void* stream) {
+  const char* fn = "gsr_densify_stats";
+  if (B < 0 || P < 0 || P > DENS_MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: B=%d P=%lld (B >= 0, 0..2^28 rows)", fn, B, (long long)P);
+  if ((long long)B * (long long)P > 0x7fffffffll) return set_err(GSR_ERR_INVALID, "%s: B * P = %lld beyond 2^31 - 1", fn, (long long)B * (long long)P);
+  if (B == 0 || P == 0) return GSR_OK;
+  if (!grad || !accum || !denom) return set_err(GSR_ERR_INVALID, "%s: null argument", fn);
+  if (!radii && !filter) return set_err(GSR_ERR_INVALID, "%s: neither radii nor a filter: nothing says which Gaussians a view saw", fn);
+  if (max_radii && !radii) return set_err(GSR_ERR_INVALID, "%s: max_radii2D needs the radii", fn);
+  if (int rc = check_aligned4(fn, grad, radii, accum, denom, max_radii)) return rc;
+  hipLaunchKernelGGL(k_densify_stats, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), grad, radii,
+                     filter, B, (unsigned)P, accum, denom, max_radii);
+  LAUNCH_CHECK(fn);
+  return GSR_OK;
+}
+
+// the three 0/1 counts scanned in place into exclusive offsets, and the totals read back: the plan's one wait for the device
+static int dens_scan_counts(const char* fn, const DensWs& w, uint32_t n, int64_t* counts, hipStream_t st) {
+  uint32_t* offs[3] = {w.off_keep, w.off_clone, w.off_split};
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 3 && e == hipSuccess; ++k) {
+    scan_exclusive_u32(offs[k], offs[k], n, nullptr, w.sums, st);         // in place; offs[k][n] = the total
+    e = hipMemcpyAsync(w.totals + k, offs[k] + n, sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+  }
+  uint32_t host[3] = {0, 0, 0};
+  if (e == hipSuccess) e = hipMemcpyAsync(host, w.totals, sizeof(host), hipMemcpyDeviceToHost, st);   // the call's one read-back
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return set_err(GSR_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+  for (int k = 0; k < 3; ++k) counts[k] = (int64_t)host[k];
+  return GSR_OK;
+}
+
+static int dens_params(const char* fn, double max_grad, double min_opacity, double extent, double percent_dense, double max_screen_size,
+                       int32_t N, uint32_t flags, DensParams* p) {
+  if (flags & ~(DENS_WORLD_PRUNE | DENS_SCREEN_PRUNE)) return set_err(GSR_ERR_INVALID, "%s: unknown flags 0x%x", fn, flags);
+  switch (dens_thresholds(max_grad, min_opacity, extent, percent_dense, max_screen_size, N, flags, p)) {
+    case 0: return GSR_OK;
+    case 1: return set_err(GSR_ERR_INVALID, "%s: max_grad=%g is not a finite float32", fn, max_grad);
+    case 2: return set_err(GSR_ERR_INVALID, "%s: extent=%g with percent_dense=%g: log(percent_dense extent) or log(0.1 extent) is not finite", fn,
+                           extent, percent_dense);
+    case 3: return set_err(GSR_ERR_INVALID, "%s: min_opacity=%g: logit(min_opacity) is not finite (0 < min_opacity < 1)", fn, min_opacity);
+    case 4: return set_err(GSR_ERR_INVALID, "%s: N=%d (1..%d children)", fn, N, DENS_MAX_N);
+    default: return set_err(GSR_ERR_INVALID, "%s: max_screen_size=%g is not a finite float32", fn, max_screen_size);
+  }
+}
+
+int gsr_densify_plan(const float* accum, const float* denom, const float* scaling, const float* opacity, const float* max_radii,
+                     int64_t P, double max_grad, double min_opacity, double extent, double percent_dense, double max_screen_size,
+                     int32_t N, uint32_t flags, void* ws, int64_t ws_bytes, int64_t* counts, void* stream) {
+  const char* fn = "gsr_densify_plan";
+  if (P < 0 || P > DENS_MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: P=%lld (0..2^28 rows)", fn, (long long)P);
+  if (!counts) return set_err(GSR_ERR_INVALID, "%s: null counts", fn);
+  DensParams p;
+  if (int rc = dens_params(fn, max_grad, min_opacity, extent, percent_dense, max_screen_size, N, flags, &p)) return rc;
+  counts[0] = counts[1] = counts[2] = 0;
+  if (P == 0) return GSR_OK;
+  if (!accum || !denom || !scaling || !opacity) return set_err(GSR_ERR_INVALID, "%s: null argument", fn);
+  if ((flags & DENS_SCREEN_PRUNE) && !max_radii) return set_err(GSR_ERR_INVALID, "%s: screen_prune needs max_radii2D", fn);
+  if (int rc = check_aligned4(fn, accum, denom, scaling, opacity, max_radii)) return rc;
+  Carve c(ws);
+  DensWs w = dens_regions(c, P);
+  if (!ws) return set_err(GSR_ERR_INVALID, "%s: null workspace", fn);
+  if (int rc = check_workspace(fn, ws, ws_bytes, c.off, 16, "gsr_densify_plan_bytes")) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t n = (uint32_t)P;
+  hipLaunchKernelGGL(k_densify_classify, dim3((n + 255) / 256), dim3(256), 0, st, accum, denom, scaling, opacity, max_radii, n, p, w.code,
+                     w.off_keep, w.off_clone, w.off_split);
+  return dens_scan_counts(fn, w, n, counts, st);
+}
+
+int gsr_densify_plan_prune(const uint8_t* prune_mask, int64_t P, void* ws, int64_t ws_bytes, int64_t* counts, void* stream) {
+  const char* fn = "gsr_densify_plan_prune";
+  if (P < 0 || P > DENS_MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: P=%lld (0..2^28 rows)", fn, (long long)P);
+  if (!counts) return set_err(GSR_ERR_INVALID, "%s: null counts", fn);
+  counts[0] = counts[1] = counts[2] = 0;
+  if (P == 0) return GSR_OK;
+  if (!prune_mask) return set_err(GSR_ERR_INVALID, "%s: null mask", fn);
+  Carve c(ws);
+  DensWs w = dens_regions(c, P);
+  if (!ws) return set_err(GSR_ERR_INVALID, "%s: null workspace", fn);
+  if (int rc = check_workspace(fn, ws, ws_bytes, c.off, 16, "gsr_densify_plan_bytes")) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t n = (uint32_t)P;
+  hipLaunchKernelGGL(k_densify_classify_mask, dim3((n + 255) / 256), dim3(256), 0, st, prune_mask, n, w.code, w.off_keep, w.off_clone, w.off_split);
+  return dens_scan_counts(fn, w, n, counts, st);
+}
+
+static bool dens_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+
+int gsr_densify_apply(const void* ws, int64_t ws_bytes, int64_t P, const int64_t* counts, int32_t n, const void* const* src,
+                      void* const* dst, const void* const* m_src, const void* const* v_src, void* const* m_dst, void* const* v_dst,
+                      const int32_t* cols, const int32_t* roles, const float* rotation, int32_t N, uint32_t seed, const float* normals,
+                      const uint8_t* mask_in, uint8_t* mask_out, int32_t* origin, int32_t* kind, void* stream) {
+  const char* fn = "gsr_densify_apply";
+  if (N < 1 || N > DENS_MAX_N) return set_err(GSR_ERR_INVALID, "%s: N=%d (1..%d children)", fn, N, DENS_MAX_N);
+  if (n < 0 || n > DENS_MAX_TENSORS) return set_err(GSR_ERR_INVALID, "%s: n=%d (0..%d tensors)", fn, n, DENS_MAX_TENSORS);
+  if (P < 0 || P > DENS_MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: P=%lld (0..2^28 rows)", fn, (long long)P);
+  if (!counts || (n > 0 && (!src || !dst || !cols || !roles))) return set_err(GSR_ERR_INVALID, "%s: null argument", fn);
+  if ((m_src || v_src || m_dst || v_dst) && !(m_src && v_src && m_dst && v_dst))
+    return set_err(GSR_ERR_INVALID, "%s: the four moment tables come together", fn);
+  if ((origin != nullptr) != (kind != nullptr)) return set_err(GSR_ERR_INVALID, "%s: origin and kind come together", fn);
+  if (mask_in && !mask_out) return set_err(GSR_ERR_INVALID, "%s: a row mask in needs a row mask out", fn);
+  for (int k = 0; k < 3; ++k)
+    if (counts[k] < 0 || counts[k] > P) return set_err(GSR_ERR_INVALID, "%s: counts[%d]=%lld of P=%lld rows", fn, k, (long long)counts[k], (long long)P);
+  const long long Pn = (long long)counts[0] + (long long)counts[1] + (long long)N * (long long)counts[2];
+  if (Pn > DENS_MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: P'=%lld rows (at most 2^28)", fn, Pn);
+  DensMove a;
+  memset(&a, 0, sizeof(a));
+  unsigned long long blocks = 0;
+  int t_xyz = -1, t_scale = -1;
+  for (int t = 0; t < n; ++t) {
+    if (cols[t] < 1 || cols[t] > DENS_MAX_COLS) return set_err(GSR_ERR_INVALID, "%s: tensor %d: cols=%d (1..%d columns)", fn, t, cols[t], DENS_MAX_COLS);
+    if (roles[t] != DENS_COPY && roles[t] != DENS_XYZ && roles[t] != DENS_SCALE) return set_err(GSR_ERR_INVALID, "%s: tensor %d: role %d", fn, t, roles[t]);
+    if ((roles[t] == DENS_XYZ || roles[t] == DENS_SCALE) && cols[t] != 3)
+      return set_err(GSR_ERR_INVALID, "%s: tensor %d: the XYZ and SCALE tensors have 3 columns, not %d", fn, t, cols[t]);
+    if (roles[t] == DENS_XYZ) { if (t_xyz >= 0) return set_err(GSR_ERR_INVALID, "%s: two XYZ tensors", fn); t_xyz = t; }
+    if (roles[t] == DENS_SCALE) { if (t_scale >= 0) return set_err(GSR_ERR_INVALID, "%s: two SCALE tensors", fn); t_scale = t; }
+    if ((P > 0 && !src[t]) || (Pn > 0 && !dst[t])) return set_err(GSR_ERR_INVALID, "%s: tensor %d: null pointer", fn, t);
+    const bool state = m_src && m_src[t];
+    if (m_src && (state != (v_src[t] != nullptr) || (Pn > 0 && state != (m_dst[t] != nullptr)) || (Pn > 0 && state != (v_dst[t] != nullptr))))
+      return set_err(GSR_ERR_INVALID, "%s: tensor %d: a moment pair needs all of m, v in and out", fn, t);
+    a.src[t] = static_cast<const float*>(src[t]); a.dst[t] = static_cast<float*>(dst[t]);
+    if (state) {
+      a.m_src[t] = static_cast<const float*>(m_src[t]); a.v_src[t] = static_cast<const float*>(v_src[t]);
+      a.m_dst[t] = static_cast<float*>(m_dst[t]); a.v_dst[t] = static_cast<float*>(v_dst[t]);
+    }
+    if (((uintptr_t)a.src[t] | (uintptr_t)a.dst[t] | (uintptr_t)a.m_src[t] | (uintptr_t)a.v_src[t] | (uintptr_t)a.m_dst[t] | (uintptr_t)a.v_dst[t]) & 3)
+      return set_err(GSR_ERR_INVALID, "%s: tensor %d: every tensor must be 4-byte aligned", fn, t);
+    a.cols[t] = cols[t]; a.role[t] = roles[t];
+    a.first[t] = (unsigned)blocks;
+    blocks += dens_blocks((unsigned long long)P * (unsigned long long)cols[t]);
+  }
+  if (counts[2] > 0 && t_xyz >= 0 && (t_scale < 0 || !rotation))
+    return set_err(GSR_ERR_INVALID, "%s: the XYZ tensor's children need the SCALE tensor and the rotation", fn);
+  if (int rc = check_aligned4(fn, rotation, normals, origin, kind)) return rc;
+  // nothing that is written may overlap anything that is read (the move is not in place): every source, moment, the rotation,
+  // the normals, the row mask and the plan's workspace against every destination, moment, mask_out, origin and kind
+  {
+    struct Span { const void* p; size_t n; const char* what; };
+    std::vector<Span> rd, wr;
+    for (int t = 0; t < n; ++t) {
+      const size_t sb = (size_t)P * cols[t] * 4, db = (size_t)Pn * cols[t] * 4;
+      rd.push_back({a.src[t], sb, "a source tensor"}); rd.push_back({a.m_src[t], sb, "a source moment"}); rd.push_back({a.v_src[t], sb, "a source moment"});
+      wr.push_back({a.dst[t], db, "a destination tensor"}); wr.push_back({a.m_dst[t], db, "a destination moment"});
+      wr.push_back({a.v_dst[t], db, "a destination moment"});
+    }
+    rd.push_back({rotation, (size_t)P * 16, "the rotation"});
+    rd.push_back({normals, (size_t)P * (size_t)N * 12, "the normals"});
+    rd.push_back({mask_in, (size_t)P, "the row mask"});
+    if (ws && ws_bytes > 0) rd.push_back({ws, (size_t)ws_bytes, "the workspace"});
+    wr.push_back({mask_out, (size_t)Pn, "the row mask out"});
+    wr.push_back({origin, (size_t)Pn * 4, "origin"});
+    wr.push_back({kind, (size_t)Pn * 4, "kind"});
+    for (const Span& w : wr)
+      for (const Span& r : rd)
+        if (dens_overlap(r.p, r.n, w.p, w.n))
+          return set_err(GSR_ERR_INVALID, "%s: %s overlaps %s: the move is not in place", fn, w.what, r.what);
+    for (size_t i = 0; i < wr.size(); ++i)
+      for (size_t j = i + 1; j < wr.size(); ++j)
+        if (dens_overlap(wr[i].p, wr[i].n, wr[j].p, wr[j].n))
+          return set_err(GSR_ERR_INVALID, "%s: %s overlaps %s: two outputs share memory", fn, wr[i].what, wr[j].what);
+  }
+  if (Pn == 0 || P == 0) return GSR_OK;
+  Carve c(const_cast<void*>(ws));
+  DensWs w = dens_regions(c, P);
+  if (!ws) return set_err(GSR_ERR_INVALID, "%s: null workspace", fn);
+  if (int rc = check_workspace(fn, ws, ws_bytes, c.off, 16, "gsr_densify_plan_bytes")) return rc;
+  const bool table = mask_out || origin;
+  const unsigned long long grid = blocks + (table ? ((unsigned long long)P + DENS_SPAN - 1) / DENS_SPAN : 0ull);
+  if (grid > 0x7fffffffull) return set_err(GSR_ERR_INVALID, "%s: too many elements for one launch", fn);
+  for (int t = n; t <= DENS_MAX_TENSORS; ++t) a.first[t] = (unsigned)blocks;
+  a.n = n; a.P = (unsigned)P;
+  a.n_keep = (unsigned)counts[0]; a.n_clone = (unsigned)counts[1]; a.n_split = (unsigned)counts[2];
+  a.code = w.code; a.off_keep = w.off_keep; a.off_clone = w.off_clone; a.off_split = w.off_split;
+  a.xyz = t_xyz >= 0 ? a.src[t_xyz] : nullptr; a.scale = t_scale >= 0 ? a.src[t_scale] : nullptr; a.rot = rotation;
+  a.normals = normals; a.seed = seed; a.N = N;
+  a.c = (float)log(0.8 * (double)N);
+  a.mask_in = mask_in; a.mask_out = mask_out; a.origin = origin; a.kind = kind;
+  if (grid == 0) return GSR_OK;
+  hipLaunchKernelGGL(k_densify_move, dim3((unsigned)grid), dim3(DENS_BLOCK), 0, static_cast<hipStream_t>(stream), a);
+  LAUNCH_CHECK(fn);
   return GSR_OK;
 }
 

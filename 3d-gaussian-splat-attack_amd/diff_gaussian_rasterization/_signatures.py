@@ -59,6 +59,11 @@ SIGNATURES = {
     "gsr_pgd_step_normed": (INT, _p(3) + (I64, I32, F32, F32, PTR, PTR)),
     "gsr_pgd_step_multi": (INT, (I32,) + _p(7) + (I32, PTR, PTR)),
     "gsr_adam_step_multi": (INT, (I32,) + _p(10) + (I64, PTR, I64, I64, PTR)),
+    "gsr_densify_stats": (INT, _p(3) + (I32, I64) + _p(4)),
+    "gsr_densify_plan_bytes": (INT, (I64, PTR)),
+    "gsr_densify_plan": (INT, _p(5) + (I64, F64, F64, F64, F64, F64, I32, U32, PTR, I64, PTR, PTR)),
+    "gsr_densify_plan_prune": (INT, (PTR, I64, PTR, I64, PTR, PTR)),
+    "gsr_densify_apply": (INT, (PTR, I64, I64, PTR, I32) + _p(9) + (I32, U32) + _p(6)),
     "gsr_knn_dist2": (INT, (PTR, I32, PTR, PTR)),
     "gsr_knn_query": (INT, (PTR, I32, PTR, I32, I32, U32) + _p(3)),
     "gsr_knn_gather_mean": (INT, (PTR, I32, I32, I32, I32) + _p(4)),

@@ -4,10 +4,13 @@ the PGD step functions read.
 Counterpart of the getters of the reference's ``scene/gaussian_model.py:24-39,97-124``
 (seven parameter tensors + exp / sigmoid / normalize / cat activations).  The fitting set-ups
 (training_setup, finetune_setup, the tail of inpaint_setup, update_learning_rate: :160-214,350-375) put a
-gsplat_attack.optim.GaussianAdam on the model; densification (:652-711) is not here.
+gsplat_attack.optim.GaussianAdam on the model; adaptive density control (:413-416, :591-712: add_densification_stats,
+densify_and_prune, prune_points, reset_opacity, oneupSHdegree) runs through diff_gaussian_rasterization.densify_ops on a
+device and through the tensor ops of gsplat_attack.densify on the host.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -31,6 +34,11 @@ class GaussianModel:
         self._rotation = e
         self._opacity = e
         self._objects_dc = e
+        # the densification statistics (reference :57-59,176-177): created by the set-ups, reset by a densify
+        self.xyz_gradient_accum = e
+        self.denom = e
+        self.max_radii2D = e
+        self.densify_count = 0                 # the default seed of densify_and_prune's keyed normals: a fit repeats
 
     # ---- construction -------------------------------------------------
     @classmethod
@@ -115,6 +123,13 @@ class GaussianModel:
                                                     lr_final=opt.position_lr_final * self.spatial_lr_scale,
                                                     lr_delay_mult=opt.position_lr_delay_mult,
                                                     max_steps=opt.position_lr_max_steps)
+        self._reset_densification_stats()
+
+    def _reset_densification_stats(self) -> None:
+        P, dev = int(self._xyz.shape[0]), self._xyz.device
+        self.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
+        self.denom = torch.zeros((P, 1), device=dev)
+        self.max_radii2D = torch.zeros((P,), device=dev)
 
     def training_setup(self, opt) -> None:
         """The optimiser of a full fit (reference :160-179): Adam(lr=0, eps=1e-15) over the seven groups xyz, f_dc, f_rest,
@@ -184,6 +199,174 @@ class GaussianModel:
         if opt is not None:
             self._setup_optimizer(opt, rows=(self._xyz.shape[0] - n_new, self._xyz.shape[0]))
         return new_mask
+
+    # ---- adaptive density control (scene/gaussian_model.py:413-416,591-712) ------------------------------------------------
+    def oneupSHdegree(self) -> None:
+        """reference :126-128"""
+        if self.active_sh_degree < self.max_sh_degree:
+            self.active_sh_degree += 1
+
+    def reset_opacity(self) -> None:
+        """Clamp every opacity at 0.01 and reset the opacity group's moments (reference :413-416, tensor ops as written
+        there, through GaussianAdam.replace)."""
+        op = self.get_opacity.detach()
+        x = torch.min(op, torch.ones_like(op) * 0.01)
+        new = torch.log(x / (1 - x))                                         # inverse_sigmoid, utils/general_utils.py:18-19
+        if self.optimizer is not None:
+            self.optimizer.replace("opacity", new)
+        else:
+            self._opacity = nn.Parameter(new, requires_grad=self._opacity.requires_grad)
+
+    def _stats_ready(self) -> None:
+        if self.xyz_gradient_accum.shape[0] != self._xyz.shape[0] or self.xyz_gradient_accum.device != self._xyz.device:
+            self._reset_densification_stats()
+
+    def add_densification_stats(self, viewspace_point_tensor, update_filter, radii=None) -> None:
+        """xyz_gradient_accum[f] += |grad[f, :2]|, denom[f] += 1 (reference :710-712) and, with radii, max_radii2D[f] =
+        max(max_radii2D[f], radii[f]) (the line of the reference's training loop), f = update_filter.  viewspace_point_tensor:
+        the render's `viewspace_points` leaf after the backward ([P,3], or a batch's [B,P,3] with update_filter and radii
+        [B,P]: the views are taken in order) or the gradient itself.  update_filter None: radii > 0.  One launch on a device."""
+        g = viewspace_point_tensor.grad if getattr(viewspace_point_tensor, "grad", None) is not None else viewspace_point_tensor
+        g = g.detach()
+        if update_filter is None and radii is None:
+            raise ValueError("add_densification_stats: neither update_filter nor radii")
+        self._stats_ready()
+        if g.is_cuda:
+            from diff_gaussian_rasterization import densify_ops
+            densify_ops.stats_(g.to(torch.float32).contiguous(), self.xyz_gradient_accum, self.denom, radii, update_filter,
+                               self.max_radii2D if radii is not None else None)
+            return
+        if g.dim() == 2:
+            g = g[None]
+        B = g.shape[0]
+        rad = None if radii is None else radii.reshape(B, -1)
+        flt = (rad > 0) if update_filter is None else (update_filter.reshape(B, -1) != 0)
+        for b in range(B):                              # csrc/gsr_densify.h: sqrt(gx gx + gy gy), every operation rounded once
+            f = flt[b]
+            gx, gy = g[b, :, 0].to(torch.float32), g[b, :, 1].to(torch.float32)
+            norm = torch.from_numpy(np.sqrt((gx * gx + gy * gy).numpy()))      # numpy's root rounds once; torch's vectorised one need not
+            self.xyz_gradient_accum[f] += norm[f][:, None]
+            self.denom[f] += 1
+            if rad is not None:
+                self.max_radii2D[f] = torch.max(self.max_radii2D[f], rad[b][f].to(torch.float32))
+
+    def _groups(self):
+        """[(group name, attribute)] in the optimiser's order, or the reference's when there is none"""
+        from .optim import GROUP_ATTRS
+        if self.optimizer is None:
+            return list(GROUP_ATTRS)
+        attrs = dict(GROUP_ATTRS)
+        named = [(g["name"], attrs[g["name"]]) for g in self.optimizer.param_groups]
+        return named + [(n, a) for n, a in GROUP_ATTRS if n not in dict(named)]
+
+    def _install(self, new: dict, moments: dict, mask_out) -> None:
+        if self.optimizer is not None:
+            rest = self.optimizer.install(new, moments, mask_out)
+        else:
+            rest = new
+        attrs = dict(self._groups())
+        for name, data in rest.items():                 # tensors outside the optimiser's groups
+            old = getattr(self, attrs[name])
+            setattr(self, attrs[name], nn.Parameter(data.contiguous(), requires_grad=old.requires_grad))
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, *, N: int = 2, seed=None, normals=None,
+                          screen_prune: bool = False):
+        """Clone, split and prune in one pass (reference :694-708 with :652-692; the contract, its stated deviations and the
+        non-finite rules are in csrc/gsr_densify.h).  As in the reference the screen-size test is inert and a truthy
+        max_screen_size only switches on the world-size prune (max scale > 0.1 extent); screen_prune=True (an extension)
+        also prunes original rows whose max_radii2D, accumulated before the call, exceeds max_screen_size.  normals: None
+        (keyed by seed; seed None: the model's densify_count, so a fit repeats) or [P,N,3] standard normals.  Parameters,
+        Adam moments and the optimiser's row selection follow their rows; new rows have zero moments and move.  The
+        statistics are reset.  -> (origin, kind) int32 [P']: the source row, and 0 keep, 1 clone, 2 + j child j."""
+        from . import densify as DZ
+        if self.optimizer is None and self.percent_dense == 0.0:
+            raise ValueError("densify_and_prune: percent_dense is not set; call a set-up with an OptimizationParams first")
+        self._stats_ready()
+        if seed is None:
+            seed = self.densify_count
+        self.densify_count += 1
+        groups = self._groups()
+        opt = self.optimizer
+        state = {} if opt is None else opt.state
+        live = None if opt is None else opt._live(int(self._xyz.shape[0]), self._xyz.device)
+        with torch.no_grad():
+            if self._xyz.is_cuda:
+                from diff_gaussian_rasterization import densify_ops as DO
+                pl = DO.plan(self.xyz_gradient_accum, self.denom, self._scaling, self._opacity, max_grad=max_grad, min_opacity=min_opacity,
+                             extent=extent, percent_dense=self.percent_dense, max_screen_size=max_screen_size, N=N,
+                             screen_prune=screen_prune, max_radii=self.max_radii2D)
+                role = dict(xyz=DO.XYZ, scaling=DO.SCALE)
+                items = []
+                for name, attr in groups:
+                    st = state.get(name)
+                    items.append((getattr(self, attr).detach(), None if st is None else st["exp_avg"], None if st is None else st["exp_avg_sq"],
+                                  role.get(name, DO.COPY)))
+                outs, mask_out, origin, kind = DO.apply(pl, items, self._rotation.detach(), seed=seed, normals=normals, row_mask=live)
+                new = {name: o[0] for (name, _), o in zip(groups, outs)}
+                moments = {name: (o[1], o[2]) for (name, _), o in zip(groups, outs) if o[1] is not None}
+            else:
+                thr = DZ.thresholds(max_grad, min_opacity, extent, self.percent_dense, N, max_screen_size, screen_prune)
+                keep, clone, kids = DZ.classify(self.xyz_gradient_accum, self.denom, self._scaling.detach(), self._opacity.detach(),
+                                                self.max_radii2D, thr, max_screen_size, screen_prune)
+                P = int(self._xyz.shape[0])
+                if normals is None:
+                    z = torch.zeros(P, N, 3)
+                    rows = kids.nonzero().reshape(-1)
+                    z[rows] = torch.from_numpy(DZ.keyed_normals(seed, rows.numpy(), N))
+                else:
+                    z = normals.to(torch.float32)
+                tensors = {name: getattr(self, attr).detach() for name, attr in groups}
+                moms = {name: (state[name]["exp_avg"], state[name]["exp_avg_sq"]) for name, _ in groups if state.get(name) is not None}
+                new, moments, origin, kind = DZ.move_host(tensors, moms, keep, clone, kids, N, thr["c"], z)
+                mask_out = None
+                if live is not None:
+                    mask_out = torch.ones(origin.numel(), dtype=torch.uint8)
+                    nk = int(keep.sum())
+                    mask_out[:nk] = live[keep].to(torch.uint8)
+            self._install(new, moments, mask_out)
+        self._reset_densification_stats()
+        return origin, kind
+
+    def prune_points(self, mask: torch.Tensor) -> None:
+        """Remove the rows mask selects (reference :591-606): parameters, moments, the row selection and the three
+        statistics follow their rows.  On a device: the fused prune of gsr_densify_apply (no clone, no split)."""
+        mask = mask.detach().reshape(-1).bool().to(self._xyz.device)
+        P = int(self._xyz.shape[0])
+        if mask.numel() != P:
+            raise ValueError(f"prune_points: mask of {mask.numel()} entries for {P} Gaussians")
+        self._stats_ready()
+        stats = dict(xyz_gradient_accum=self.xyz_gradient_accum, denom=self.denom, max_radii2D=self.max_radii2D)
+        with torch.no_grad():
+            if not self._xyz.is_cuda:
+                keep = ~mask
+                if self.optimizer is not None:
+                    self.optimizer.prune(keep)
+                    rest = [a for n, a in self._groups() if n not in {g["name"] for g in self.optimizer.param_groups}]
+                else:
+                    rest = [a for _, a in self._groups()]
+                for a in rest:
+                    old = getattr(self, a)
+                    setattr(self, a, nn.Parameter(old.detach()[keep].clone(), requires_grad=old.requires_grad))
+                for n, t in stats.items():
+                    setattr(self, n, t[keep])
+                return
+            from diff_gaussian_rasterization import densify_ops as DO
+            pl = DO.plan_prune(mask)
+            groups = self._groups()
+            opt = self.optimizer
+            state = {} if opt is None else opt.state
+            live = None if opt is None else opt._live(P, self._xyz.device)
+            items = []
+            for name, attr in groups:
+                st = state.get(name)
+                items.append((getattr(self, attr).detach(), None if st is None else st["exp_avg"], None if st is None else st["exp_avg_sq"], DO.COPY))
+            items += [(t, None, None, DO.COPY) for t in stats.values()]
+            outs, mask_out, _, _ = DO.apply(pl, items, self._rotation.detach(), row_mask=live, want_origin=False)
+            new = {name: o[0] for (name, _), o in zip(groups, outs)}
+            moments = {name: (o[1], o[2]) for (name, _), o in zip(groups, outs) if o[1] is not None}
+            self._install(new, moments, mask_out)
+            for n, o in zip(stats, outs[len(groups):]):
+                setattr(self, n, o[0])
 
     def concat_setup(self, feature_name: str, tensor_to_concat: torch.Tensor, requires_grad: bool) -> None:
         """Append rows to one attribute and re-wrap it (reference :243-262)."""

@@ -9,7 +9,8 @@ of inpaint_setup, update_learning_rate, _prune_optimizer / cat_tensors_to_optimi
   GaussianAdam         torch.optim.Adam(l, lr=0.0, eps=1e-15) over the model's seven named groups, as ONE fused launch per
                        step (diff_gaussian_rasterization.adam_ops.adam_step_: gsr_adam_step_multi), with an optional row
                        mask or row range: rows left out are neither read nor written
-  refit                update_learning_rate, render, photometric_loss, backward, step, zero_grad
+  refit                update_learning_rate, render, photometric_loss, backward, step, zero_grad; with densify= the original
+                       densification schedule (gsplat_attack.densify)
 
 The arithmetic of a step is csrc/gsr_adam.h's: m' = m + (1 - b1)(g - m); v' = b2 v + (1 - b2)(g g);
 den = sqrt(v') / sqrt_bc2 + eps; x' = x - step_size (m' / den), every operation rounded once in float32, with
@@ -286,6 +287,29 @@ class GaussianAdam:
             self.rows = (self.rows[0], P + n_new)
         return out
 
+    def install(self, tensors: Dict[str, torch.Tensor], moments: Dict[str, Tuple[torch.Tensor, torch.Tensor]],
+                row_mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Install what a densify or a fused prune moved (GaussianModel.densify_and_prune / prune_points): every group takes
+        its new tensor as a new nn.Parameter (so a render cache sees new geometry) and, where it has state, its moved moments.
+        row_mask: the moved row selection (kept rows their byte, new rows 1), given iff the optimiser selects rows; a row
+        range becomes that mask -- append's rule for a range that does not end at the last row, applied to every range, so
+        that no count has to come back from the device.  -> the entries of `tensors` that belong to no group."""
+        names = {g["name"] for g in self.param_groups}
+        if (self.row_mask is not None or self.rows is not None) != (row_mask is not None):
+            raise ValueError("GaussianAdam.install: a moved row mask is needed iff the optimiser selects rows")
+        with torch.no_grad():
+            for g in self.param_groups:
+                n = g["name"]
+                new = self._rewrap(g, tensors[n].detach())
+                if n in self.state:
+                    m, v = moments[n]
+                    if m.shape != new.shape or v.shape != new.shape:
+                        raise ValueError(f"GaussianAdam.install: {n}: moments of shape {tuple(m.shape)} for {tuple(new.shape)}")
+                    self.state[n] = dict(exp_avg=m, exp_avg_sq=v)
+        if row_mask is not None:
+            self.row_mask, self.rows = row_mask.to(torch.uint8).contiguous(), None
+        return {n: t for n, t in tensors.items() if n not in names}
+
     def replace(self, name: str, tensor: torch.Tensor) -> nn.Parameter:
         """A new tensor for one group with its moments reset to zero (reference replace_tensor_to_optimizer)."""
         for g in self.param_groups:
@@ -301,11 +325,16 @@ class GaussianAdam:
 
 
 def refit(model, cameras, targets, *, iters: int, lambda_dssim: float = 0.2, pipe=None, background=None,
-          views_per_step: int = 1) -> torch.Tensor:
+          views_per_step: int = 1, densify=None) -> torch.Tensor:
     """The plain fit loop of a model whose optimiser is set up (training_setup, finetune_setup or inpaint_setup(opt=...)):
     per step update_learning_rate, render the next `views_per_step` cameras (round robin; render_batch for more than one),
     photometric_loss against their targets, backward, optimizer.step(), zero_grad.  targets: [V,3,H,W] or a sequence of
-    [3,H,W], one per camera.  No densification.  -> the per-step losses [iters] on the device (one read-back for the caller)."""
+    [3,H,W], one per camera.  -> the per-step losses [iters] on the device (one read-back for the caller).
+    densify: None (no densification: the loop above and nothing else) or a gsplat_attack.densify.DensifyParams: the reference's
+    schedule (that of the original 3D Gaussian Splatting training loop) -- oneupSHdegree every sh_degree_interval iterations at the top of the loop; after the backward, while
+    iteration < densify_until_iter, add_densification_stats (with the radii) every iteration, densify_and_prune every
+    densification_interval iterations past densify_from_iter (max_screen_size once past opacity_reset_interval), reset_opacity
+    every opacity_reset_interval; then the step.  Iterations count from 1."""
     from .image_loss import photometric_loss
     from .renderer import PipelineParams, render, render_batch
     if getattr(model, "optimizer", None) is None:
@@ -322,13 +351,28 @@ def refit(model, cameras, targets, *, iters: int, lambda_dssim: float = 0.2, pip
         model.update_learning_rate(it + 1)
         ids = [(it * k + j) % V for j in range(k)]
         gt = torch.stack([targets[i] for i in ids]).to(dev)
+        if densify is not None:
+            sh_up, dens, reset, size = densify.actions(it + 1)
+            if sh_up:
+                model.oneupSHdegree()
         if k == 1:
-            img = render(cameras[ids[0]], model, pipe, bg)["render"][None]
+            out = render(cameras[ids[0]], model, pipe, bg)
+            img = out["render"][None]
         else:
-            img = render_batch([cameras[i] for i in ids], model, pipe, bg)["render"]
+            out = render_batch([cameras[i] for i in ids], model, pipe, bg)
+            img = out["render"]
         loss = photometric_loss(img, gt, lambda_dssim)
         loss.backward()
         losses[it] = loss.detach()
+        if densify is not None and it + 1 < densify.densify_until_iter:
+            with torch.no_grad():
+                model.add_densification_stats(out["viewspace_points"], None, radii=out["radii"])
+                if dens:
+                    model.densify_and_prune(densify.densify_grad_threshold, densify.min_opacity,
+                                            densify.extent if densify.extent is not None else model.spatial_lr_scale, size,
+                                            N=densify.N, seed=densify.seed, screen_prune=densify.screen_prune)
+                if reset:
+                    model.reset_opacity()
         model.optimizer.step()
         model.optimizer.zero_grad()
     return losses

@@ -518,6 +518,56 @@ int gsr_adam_step_multi(int32_t n, void* const* x, const void* const* g, void* c
                         int64_t step, const uint8_t* row_mask /* or null */, int64_t row_begin, int64_t row_end /* -1: rows */,
                         void* stream);
 
+/*
+ * Adaptive density control (reference scene/gaussian_model.py:591-712: add_densification_stats, densify_and_prune with its
+ * clone, split and prune passes, prune_points) as one launch chain with ONE read-back; the scalar contract, its deviations
+ * from the reference and the non-finite rules are in csrc/gsr_densify.h.  No change of GSR_VERSION, no capability bit: the
+ * stage is present iff the library exports these symbols.  All tensors are contiguous float32 on the device unless said.
+ *
+ * gsr_densify_stats: for the B views of grad [B, P, 3] in view order, where filter [B, P] (uint8) is non-zero -- or, with
+ *   filter NULL, where radii [B, P] (int32) > 0 --: accum[i] += sqrtf(gx gx + gy gy), denom[i] += 1 and, with radii and
+ *   max_radii given, max_radii[i] = max(max_radii[i], radii).  One lane per Gaussian; bit for bit B single-view calls.
+ *
+ * gsr_densify_plan: classifies the P rows from accum / denom (NaN -> 0) >= max_grad, the row's largest raw scale against
+ *   log(percent_dense extent) and, with GSR_DENSIFY_WORLD_PRUNE, log(0.1 extent), the raw opacity against logit(min_opacity),
+ *   a child's scale (raw - log(0.8 N)), and with GSR_DENSIFY_SCREEN_PRUNE max_radii [P] > max_screen_size; scans the three
+ *   counts into `ws` (device, 16-byte aligned, gsr_densify_plan_bytes(P) bytes) and returns counts[3] (HOST) = {kept originals,
+ *   kept clones, split parents whose children stay}: P' = counts[0] + counts[1] + N counts[2].  Waits for the stream once.
+ *
+ * gsr_densify_plan_prune: the plan of a plain prune (reference prune_points :591-606) from a byte mask [P] (non-zero = the row
+ *   goes): counts = {kept rows, 0, 0}, the same workspace, the same one wait.
+ *
+ * gsr_densify_apply: moves n <= 8 tensors src[t] [P, cols[t] <= 48] to dst[t] [P', cols[t]] in ONE launch, in the reference's
+ *   order: kept originals in row order, clones in parent order, children j-major (child j of the k-th split parent at
+ *   counts[0] + counts[1] + j counts[2] + k).  roles[t]: 0 copy; 1 xyz (a child is xyz + R(q) (z * exp(scale)), q = `rotation`
+ *   [P, 4], scale = the source of the role-2 tensor, z = normals [P, N, 3] or, with normals NULL, the keyed normal of (seed,
+ *   row, child, axis)); 2 scale (a child gets raw - log(0.8 N)).  m_src / v_src / m_dst / v_dst (all four NULL, or per tensor a
+ *   pair in and out or NULL): kept rows carry their moments, new rows get zeros.  mask_in [P] / mask_out [P'] (uint8): the
+ *   optimiser's row mask follows its rows, new rows get 1 (mask_in NULL: kept rows get 1).  origin / kind [P'] (int32, both or
+ *   neither): the source row, and 0 keep, 1 clone, 2 + j child j.  Every element of every destination is written exactly once;
+ *   the sources are not written.  ws, P, N and counts must be those of the plan.  counts[1] = counts[2] = 0 is a fused prune.
+ *
+ * GSR_ERR_INVALID before any launch: N outside 1..8, more than 8 tensors, cols outside 1..48, P or P' above 2^28, anything
+ * written (a destination, a moment out, mask_out, origin, kind) that overlaps anything read (a source, a moment in, the rotation,
+ * the normals, mask_in, the workspace) or another output, a max_grad / extent (with percent_dense) / min_opacity / max_screen_size whose
+ * threshold is not a finite float32 (the message names which), unknown flags, a workspace too small or misaligned.
+ */
+#define GSR_DENSIFY_WORLD_PRUNE 1u
+#define GSR_DENSIFY_SCREEN_PRUNE 2u
+int gsr_densify_stats(const float* grad, const int32_t* radii /* or null */, const uint8_t* filter /* or null */, int32_t B,
+                      int64_t P, float* accum, float* denom, float* max_radii /* or null */, void* stream);
+int gsr_densify_plan_bytes(int64_t P, int64_t* bytes);
+int gsr_densify_plan(const float* accum, const float* denom, const float* scaling, const float* opacity,
+                     const float* max_radii /* or null */, int64_t P, double max_grad, double min_opacity, double extent,
+                     double percent_dense, double max_screen_size, int32_t N, uint32_t flags, void* ws, int64_t ws_bytes,
+                     int64_t* counts, void* stream);
+int gsr_densify_plan_prune(const uint8_t* prune_mask, int64_t P, void* ws, int64_t ws_bytes, int64_t* counts, void* stream);
+int gsr_densify_apply(const void* ws, int64_t ws_bytes, int64_t P, const int64_t* counts, int32_t n, const void* const* src,
+                      void* const* dst, const void* const* m_src, const void* const* v_src, void* const* m_dst,
+                      void* const* v_dst, const int32_t* cols, const int32_t* roles, const float* rotation, int32_t N,
+                      uint32_t seed, const float* normals /* or null */, const uint8_t* mask_in /* or null */,
+                      uint8_t* mask_out /* or null */, int32_t* origin /* or null */, int32_t* kind /* or null */, void* stream);
+
 /* Mean squared distance of every point to its 3 nearest other points (exact): replaces the reference's second native
  * import, simple_knn._C.distCUDA2 (reference scene/gaussian_model.py:17, called at :144 to seed the initial scales).
  * points [P,3] float32 device, mean_dist2 [P] float32 device.  Synchronises the stream once (scene set-up routine, not
