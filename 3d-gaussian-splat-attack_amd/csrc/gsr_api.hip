@@ -28,6 +28,7 @@
 #include "gsr_pgd.hip.h"
 #include "gsr_adam.hip.h"
 #include "gsr_densify.hip.h"
+#include "gsr_deteval.hip.h"
 #include "gsr_groups.hip.h"
 #include "gsr_hull.h"
 #include "gsr_image.hip.h"
@@ -2426,6 +2427,129 @@ int gsr_densify_apply(const void* ws, int64_t ws_bytes, int64_t P, const int64_t
   a.mask_in = mask_in; a.mask_out = mask_out; a.origin = origin; a.kind = kind;
   if (grid == 0) return GSR_OK;
   hipLaunchKernelGGL(k_densify_move, dim3((unsigned)grid), dim3(DENS_BLOCK), 0, static_cast<hipStream_t>(stream), a);
+  LAUNCH_CHECK(fn);
+  return GSR_OK;
+}
+
+// ---- detection metrics (gsr_deteval.h / gsr_deteval.hip.h): no allocation, no copy, no host wait; every check is made on
+// the host before the first device call.
+static int deteval_spec(const char* fn, const GsrDetEvalSpec* spec, gsr_de::Spec* s) {
+  static_assert(sizeof(GsrDetEvalSpec) == sizeof(gsr_de::Spec), "GsrDetEvalSpec and gsr_de::Spec are one layout");
+  if (!spec) return set_err(GSR_ERR_INVALID, "%s: null spec", fn);
+  memcpy(s, spec, sizeof(*s));
+  if (const char* why = gsr_de::spec_error(*s)) return set_err(GSR_ERR_INVALID, "%s: bad spec: %s", fn, why);
+  return GSR_OK;
+}
+
+struct DeWs {
+  uint32_t *k0, *v0, *k1, *v1, *cls, *table, *sums, *count, *off, *scan_sums;
+};
+
+static DeWs deteval_regions(Carve& c, const gsr_de::Spec& s, long long N) {
+  const size_t n = (size_t)N * (size_t)s.D;
+  DeWs w;
+  w.k0 = c.take<uint32_t>(n);
+  w.v0 = c.take<uint32_t>(n);
+  w.k1 = c.take<uint32_t>(n);
+  w.v1 = c.take<uint32_t>(n);
+  w.cls = c.take<uint32_t>(n);
+  w.table = c.take<uint32_t>(radix_table_words((uint32_t)n));
+  w.sums = c.take<uint32_t>(RS_BINS);
+  w.count = c.take<uint32_t>((size_t)s.K + 2);
+  w.off = c.take<uint32_t>((size_t)s.K + 2);
+  w.scan_sums = c.take<uint32_t>((size_t)(s.K + 1) / 2048 + 2);
+  return w;
+}
+
+static int deteval_rows(const char* fn, const gsr_de::Spec& s, int64_t N) {
+  if (N < 1 || N * (int64_t)s.D > gsr_de::MAX_ROWS)
+    return set_err(GSR_ERR_INVALID, "%s: N=%lld images of D=%d detections (N >= 1, N * D <= 2^20)", fn, (long long)N, s.D);
+  return GSR_OK;
+}
+
+int gsr_deteval_workspace_bytes(const GsrDetEvalSpec* spec, int64_t N, int64_t* bytes) {
+  const char* fn = "gsr_deteval_workspace_bytes";
+  gsr_de::Spec s;
+  if (int rc = deteval_spec(fn, spec, &s)) return rc;
+  if (int rc = deteval_rows(fn, s, N)) return rc;
+  if (!bytes) return set_err(GSR_ERR_INVALID, "%s: null bytes", fn);
+  Carve c;
+  deteval_regions(c, s, N);
+  *bytes = (int64_t)c.off;
+  return GSR_OK;
+}
+
+int gsr_deteval_match(const GsrDetEvalSpec* spec, int32_t B, const float* dets, const int32_t* counts, const float* gt_boxes,
+                      const int32_t* gt_cls, int32_t* dt_order, int32_t* dt_rank, int32_t* dt_match, uint8_t* dt_ignore,
+                      uint8_t* gt_ignore, int32_t* gt_match, void* stream) {
+  const char* fn = "gsr_deteval_match";
+  gsr_de::Spec s;
+  if (int rc = deteval_spec(fn, spec, &s)) return rc;
+  if (B < 1 || (long long)B * s.D > gsr_de::MAX_ROWS) return set_err(GSR_ERR_INVALID, "%s: B=%d images of D=%d detections (B >= 1, B * D <= 2^20)", fn, B, s.D);
+  if (!dets || !counts || !dt_order || !dt_rank || !dt_match || !dt_ignore) return set_err(GSR_ERR_INVALID, "%s: null dets / counts / dt_order / dt_rank / dt_match / dt_ignore", fn);
+  if (s.M > 0 && (!gt_boxes || !gt_cls || !gt_ignore || !gt_match)) return set_err(GSR_ERR_INVALID, "%s: null gt_boxes / gt_cls / gt_ignore / gt_match with M=%d", fn, s.M);
+  if (int rc = check_aligned4(fn, dets, counts, gt_boxes, gt_cls, dt_order, dt_rank, dt_match, gt_match)) return rc;
+  int P = 2;                                                // the sort's width: the power of two at or above D
+  while (P < s.D) P <<= 1;
+  hipLaunchKernelGGL(gsr_de::k_de_match, dim3((unsigned)B), dim3(gsr_de::MATCH_THREADS), (size_t)P * 10, static_cast<hipStream_t>(stream), s, P,
+                     dets, counts, gt_boxes, gt_cls, dt_order, dt_rank, dt_match, dt_ignore, gt_ignore, gt_match);
+  LAUNCH_CHECK(fn);
+  return GSR_OK;
+}
+
+int gsr_deteval_accumulate(const GsrDetEvalSpec* spec, int64_t N, const float* dets, const int32_t* dt_order, const int32_t* dt_rank,
+                           const int32_t* dt_match, const uint8_t* dt_ignore, const int32_t* gt_cls, const uint8_t* gt_ignore,
+                           const double* rec_thrs, void* ws, int64_t ws_bytes, double* precision, double* scores, double* recall,
+                           int32_t* npig, void* stream) {
+  const char* fn = "gsr_deteval_accumulate";
+  gsr_de::Spec s;
+  if (int rc = deteval_spec(fn, spec, &s)) return rc;
+  if (int rc = deteval_rows(fn, s, N)) return rc;
+  if (!dets || !dt_order || !dt_rank || !dt_match || !dt_ignore || !rec_thrs || !precision || !scores || !recall || !npig)
+    return set_err(GSR_ERR_INVALID, "%s: null dets / dt_order / dt_rank / dt_match / dt_ignore / rec_thrs / precision / scores / recall / npig", fn);
+  if (s.M > 0 && (!gt_cls || !gt_ignore)) return set_err(GSR_ERR_INVALID, "%s: null gt_cls / gt_ignore with M=%d", fn, s.M);
+  if (int rc = check_aligned4(fn, dets, dt_order, dt_rank, dt_match, gt_cls, npig)) return rc;
+  if ((((uintptr_t)rec_thrs | (uintptr_t)precision | (uintptr_t)scores | (uintptr_t)recall) & 7) != 0)
+    return set_err(GSR_ERR_INVALID, "%s: rec_thrs, precision, scores and recall must be 8-byte aligned", fn);
+  if (!ws) return set_err(GSR_ERR_INVALID, "%s: null workspace", fn);
+  Carve c(ws);
+  DeWs w = deteval_regions(c, s, N);
+  if (int rc = check_workspace(fn, ws, ws_bytes, c.off, 16, "gsr_deteval_workspace_bytes")) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t n = (uint32_t)(N * s.D);
+  HIP_TRY(fn, hipMemsetAsync(w.count, 0, sizeof(uint32_t) * ((size_t)s.K + 2), st));
+  HIP_TRY(fn, hipMemsetAsync(npig, 0, sizeof(int32_t) * (size_t)s.K * (size_t)s.A, st));
+  hipLaunchKernelGGL(gsr_de::k_de_keys, dim3((n + 255) / 256), dim3(256), 0, st, dets, dt_order, n, s.D, s.K, w.k0, w.cls, w.count);
+  // two stable sorts: by score descending (the values start as image * D + position, so equal scores stay in image, then rank
+  // order), then by class
+  const int r1 = radix_sort_pairs(w.k0, w.v0, w.k1, w.v1, n, nullptr, 0, 32, true, w.table, w.sums, st);
+  uint32_t *ka = r1 ? w.k1 : w.k0, *va = r1 ? w.v1 : w.v0, *kb = r1 ? w.k0 : w.k1, *vb = r1 ? w.v0 : w.v1;
+  hipLaunchKernelGGL(gsr_de::k_de_classes, dim3((n + 255) / 256), dim3(256), 0, st, (const uint32_t*)va, (const uint32_t*)w.cls, n, ka);
+  int class_bits = 1;
+  while ((s.K >> class_bits) != 0) ++class_bits;             // the keys are 0 .. K
+  const int r2 = radix_sort_pairs(ka, va, kb, vb, n, nullptr, 0, class_bits, false, w.table, w.sums, st);
+  scan_exclusive_u32(w.count, w.off, (uint32_t)s.K + 1u, nullptr, w.scan_sums, st);
+  if (s.M > 0) {
+    const uint32_t total = (uint32_t)(N * s.A * s.M);
+    hipLaunchKernelGGL(gsr_de::k_de_npig, dim3((total + 255) / 256), dim3(256), 0, st, gt_cls, gt_ignore, total, s.A, s.M, s.K, npig);
+  }
+  gsr_de::CurveArgs a;
+  a.dets = dets; a.dt_order = dt_order; a.dt_rank = dt_rank; a.dt_match = dt_match; a.dt_ignore = dt_ignore;
+  a.vals = r2 ? vb : va; a.off = w.off; a.npig = npig; a.rec_thrs = rec_thrs;
+  a.precision = precision; a.scores = scores; a.recall = recall;
+  hipLaunchKernelGGL(gsr_de::k_de_curve, dim3((unsigned)s.K * (unsigned)(s.A * s.n_caps * s.T)), dim3(gsr_de::ACC_CHUNK), sizeof(double) * 2 * (size_t)s.R, st, s, a);
+  LAUNCH_CHECK(fn);
+  return GSR_OK;
+}
+
+int gsr_deteval_summarize(const GsrDetEvalSpec* spec, const double* precision, const double* recall, double* stats, void* stream) {
+  const char* fn = "gsr_deteval_summarize";
+  gsr_de::Spec s;
+  if (int rc = deteval_spec(fn, spec, &s)) return rc;
+  if (!precision || !recall || !stats) return set_err(GSR_ERR_INVALID, "%s: null precision / recall / stats", fn);
+  if ((((uintptr_t)precision | (uintptr_t)recall | (uintptr_t)stats) & 7) != 0)
+    return set_err(GSR_ERR_INVALID, "%s: precision, recall and stats must be 8-byte aligned", fn);
+  hipLaunchKernelGGL(gsr_de::k_de_summarize, dim3(1), dim3(gsr_de::N_STATS * 64), 0, static_cast<hipStream_t>(stream), s, precision, recall, stats);
   LAUNCH_CHECK(fn);
   return GSR_OK;
 }

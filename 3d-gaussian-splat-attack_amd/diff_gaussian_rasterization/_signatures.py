@@ -75,12 +75,16 @@ SIGNATURES = {
     "gsr_image_resample": (INT, _p(4)),
     "gsr_image_resample_backward": (INT, _p(4) + (I32, PTR)),
     "gsr_image_to_u8": (INT, (PTR, I32, I32, I32, PTR, PTR)),
-    # ---- detector output, detection loss, set-prediction detector
+    # ---- detector output, detection metrics, detection loss, set-prediction detector
     "gsr_det_workspace_bytes": (INT, _p(2)),
     "gsr_det_postprocess": (INT, _p(3) + (I64,) + _p(3)),
     "gsr_det_nms": (INT, (I32, I32) + _p(4) + (F32, I32, PTR, I64) + _p(3)),
     "gsr_det_box_iou": (INT, (PTR, I32, PTR, I32, PTR, PTR)),
     "gsr_det_verdict": (INT, (PTR, PTR, I32, I32, PTR, I32, I32, I32, F32) + _p(3)),
+    "gsr_deteval_workspace_bytes": (INT, (PTR, I64, PTR)),
+    "gsr_deteval_match": (INT, (PTR, I32) + _p(11)),
+    "gsr_deteval_accumulate": (INT, (PTR, I64) + _p(9) + (I64,) + _p(5)),
+    "gsr_deteval_summarize": (INT, _p(5)),
     "gsr_detloss_workspace_bytes": (INT, _p(2)),
     "gsr_detloss": (INT, _p(5) + (I64,) + _p(5)),
     "gsr_setdet_workspace_bytes": (INT, _p(2)),

@@ -57,4 +57,8 @@ def __getattr__(name):
     if name in ("OptimizationParams", "GaussianAdam", "get_expon_lr_func", "refit"):
         from . import optim
         return getattr(optim, name)
+    # scoring an attack: COCO-style AP / AR on the device, the attack success rate, the evaluation sweep
+    if name in ("DetectionEval", "reference_eval", "attack_success_rate", "evaluate_views", "to_coco_json", "from_coco_json"):
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -771,6 +771,76 @@ int gsr_det_box_iou(const float* a, int32_t n, const float* b, int32_t m, float*
 int gsr_det_verdict(const float* dets, const int32_t* counts, int32_t B, int32_t max_det, const float* gt, int32_t target,
                     int32_t untarget, int32_t is_targeted, float iou_match, int32_t* verdict, float* best, void* stream);
 
+/* ---- Detection metrics: COCO-style matching, AP / AR and the summary ----------------------------------------------------
+ * The reference scores an attack on the host (utils/render.py:223-298 dumps COCO JSON, utils/analyze_ap_ar.py runs
+ * pycocotools.COCOeval on it).  These three entries are COCOeval's evaluateImg, accumulate and summarize for boxes, on the
+ * device, from the dets [B,D,6] (x1 y1 x2 y2 score class) and counts [B,2] every detector output stage writes.  No change of
+ * GSR_VERSION, no capability bit, no gsr_query item: the stage is present iff the library exports gsr_deteval_match.
+ *
+ * Arithmetic (csrc/gsr_deteval.h, compiled for kernels and host alike): everything is DOUBLE.  Float32 inputs are widened
+ * once; every operation is rounded on its own, no contraction, no library call -- the same bits on every run and every build.
+ *   live rows    a detection row is live iff its index is below counts[b,0] (clamped to 0..D), none of its six floats is a NaN
+ *                and its class float is an integer in 0..K-1.  A ground-truth row (gt_boxes [B,M,4], gt_cls [B,M] int32) is
+ *                live iff its class is in 0..K-1 and its box holds no NaN.  Dead rows take part in nothing.
+ *   area, IoU    area = (x2-x1)*(y2-y1); iw = min(ax2,bx2) - max(ax1,bx1), ih likewise; inter = (iw <= 0 || ih <= 0) ? 0 : iw*ih;
+ *                iou = inter / ((area_d + area_g) - inter); a NaN IoU counts as 0 (a deviation: COCOeval would match it).
+ *   orders       detections of an image: score descending, then row ascending, -0 == +0 (COCOeval's stable mergesort).
+ *                Ground truth under area range a: rows with area in [lo_a, hi_a] first, ignored rows (area < lo_a ||
+ *                area > hi_a) after them, each part in row order.  No crowd, no `ignore` flag.
+ *   the walk     per area range a, threshold t, detection d in order: best = min(iou_thrs[t], 1 - 1e-10), m = none; through the
+ *                live ground truth of d's class in the order above: a row already matched under (a,t) is skipped; if m is set
+ *                and counted and this row is ignored, stop; iou < best: continue; else best = iou, m = row (a later row of
+ *                equal IoU replaces an earlier one).  A matched d takes dt_ignore = its row's ignore; an unmatched d is ignored
+ *                iff its own area is outside [lo_a, hi_a].
+ *   accumulate   per class k, area a, cap max_dets[m]: the live detections of class k whose dt_rank < max_dets[m], over all
+ *                images, by score descending, then image ascending, then rank ascending.  npig[k,a] = live counted rows of
+ *                class k.  npig == 0: every output of (k,a,m) is -1.  Else tp / fp = cumulative counts over the detections that
+ *                are not ignored (matched / unmatched), rc = tp / npig, pr = tp / ((fp + tp) + 2.220446049250313e-16);
+ *                recall[t,k,a,m] = the last rc (0 with no detections); pr is made non-increasing from the back; for each
+ *                rec_thrs[r] the first index with rc >= rec_thrs[r] gives precision[t,r,k,a,m] = pr and scores[t,r,k,a,m] = the
+ *                score there, both 0 past the end.  The comparison sees the caller's doubles: the library generates no threshold.
+ *   summarize    stats[14]: COCOeval.summarize's twelve -- AP over all thresholds / at the threshold equal to 0.5 / equal to
+ *                0.75 (area 0, last cap), AP for areas 1, 2, 3 (last cap), AR for caps 0, 1, 2 (area 0), AR for areas 1, 2, 3
+ *                (last cap) -- then the reference's AP (all thresholds, area 0, last cap) and AR (area 0, cap 0).  Each is the
+ *                mean of the slice's entries above -1, added in index order ([t,r,k] / [t,k]), or -1 when there are none, when
+ *                no threshold equals 0.5 / 0.75, or when the area range or cap does not exist.  Areas and caps go by POSITION.
+ *
+ * gsr_deteval_match, one batch of B images (B * D <= 2^20), one launch, one workgroup per image.  Writes
+ *   dt_order [B,D] int32    the live rows in order, -1 beyond them          dt_rank [B,D] int32   rank within image and class, -1
+ *   dt_match [B,A,T,D] int32  per POSITION of dt_order: the matched ground-truth row or -1
+ *   dt_ignore [B,A,T,D] uint8 per position: 1 ignored, 0 not (0 beyond the live rows)
+ *   gt_ignore [B,A,M] uint8   0 counted, 1 ignored by area, 2 a dead row    gt_match [B,A,T,M] int32  position in dt_order or -1
+ *   With M == 0 the four ground-truth pointers are not read and may be NULL.
+ * gsr_deteval_accumulate, over the concatenated outputs of N images (N * D <= 2^20; dets as given to the match).  rec_thrs [R]
+ *   doubles on the DEVICE.  Writes precision and scores [T,R,K,A,Mx] double, recall [T,K,A,Mx] double, npig [K,A] int32.  ws:
+ *   device, 16-byte aligned, gsr_deteval_workspace_bytes(spec, N) bytes.  Two stable radix sorts of 32-bit keys (score, then
+ *   class), a scan of the class histogram, then one wave per (k,a,m,t).
+ * gsr_deteval_summarize: one launch; stats [14] double on the device.
+ *
+ * All entries: every tensor argument is a DEVICE pointer, the spec a HOST struct.  A NULL spec or required pointer, K outside
+ * 1..65535, D outside 1..4096, M outside 0..256, T outside 1..10, A outside 1..4, R outside 1..1024, n_caps outside 1..3, caps
+ * that descend or lie outside 1..D, a NaN among iou_thrs / area bounds, B or N < 1, more than 2^20 detection rows, a misaligned
+ * tensor (4 bytes; doubles 8), a workspace too small or misaligned return GSR_ERR_INVALID with a gsr_last_error text before
+ * any device call.  No allocation, no copy, no host synchronisation: everything is enqueued on `stream`; calls are re-entrant
+ * from several host threads (each with its own workspace). */
+typedef struct GsrDetEvalSpec {
+  int32_t K, D, M;           /* classes, detection rows per image, ground-truth rows per image */
+  int32_t T, A, n_caps;      /* IoU thresholds, area ranges, max_dets in use */
+  int32_t max_dets[3];       /* ascending (equal caps are allowed), each 1..D */
+  int32_t R;                 /* recall thresholds */
+  double  iou_thrs[10];
+  double  area_lo[4], area_hi[4];
+} GsrDetEvalSpec;
+int gsr_deteval_workspace_bytes(const GsrDetEvalSpec* spec, int64_t N, int64_t* bytes);
+int gsr_deteval_match(const GsrDetEvalSpec* spec, int32_t B, const float* dets, const int32_t* counts, const float* gt_boxes,
+                      const int32_t* gt_cls, int32_t* dt_order, int32_t* dt_rank, int32_t* dt_match, uint8_t* dt_ignore,
+                      uint8_t* gt_ignore, int32_t* gt_match, void* stream);
+int gsr_deteval_accumulate(const GsrDetEvalSpec* spec, int64_t N, const float* dets, const int32_t* dt_order, const int32_t* dt_rank,
+                           const int32_t* dt_match, const uint8_t* dt_ignore, const int32_t* gt_cls, const uint8_t* gt_ignore,
+                           const double* rec_thrs, void* ws, int64_t ws_bytes, double* precision, double* scores, double* recall,
+                           int32_t* npig, void* stream);
+int gsr_deteval_summarize(const GsrDetEvalSpec* spec, const double* precision, const double* recall, double* stats, void* stream);
+
 /* ---- Detector loss stage: the anchor-free YOLO detection loss and its gradient -----------------------------------------
  * The reference's four YOLO wrappers end infer() by calling the ultralytics DetectionModel in training mode
  * (detectors/yolov8_detector.py:140-156): a task-aligned assigner, BCE on the class logits, CIoU on the decoded boxes
